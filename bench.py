@@ -16,7 +16,9 @@ A "step" is one pass of the hot path over one batch of synthetic input, timed pe
                (the refresh searches 100k-503k queries, in launch chunks of 32,768: that is the step).
     python bench.py --full   measures ONE real refresh end to end instead (caches on disk -> files), per phase.
 Both legs: W untimed warm-up steps, then exactly K steps between barrier + synchronize on both
-sides, MAX over ranks.  Rank 0 prints ONE JSON line.  `roofline` comes from HIP events the library
+sides, MAX over ranks; `ms_per_step` is one timed step of the headline encode leg.  Rank 0 prints ONE JSON line on stdout
+(everything else the run prints goes to stderr).  --dump-outputs DIR writes what the last timed step returned (a seeded
+sample of the rows) as .npy files, so that two builds can be compared output for output.  `roofline` comes from HIP events the library
 records around every kernel launch on the launch stream during the timed steps; `cpu_baseline` is
 the oracle (a port of the reference CPU path) timed on this box's host cores on a bounded sample;
 `power` (and `search.power`) are the board's socket power and shader clock sampled from the amdgpu
@@ -85,7 +87,41 @@ def parse():
     p.add_argument("--slice-dir", type=str, default="/tmp/ance_slice")
     p.add_argument("--encoder-precision", type=str, default=None, choices=["fp16", "split", "fp32"],
                    help="--full only: the encoder arithmetic of the refresh (ance_amd.ann_data_gen --encoder_precision)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write what the last timed step of each leg returned as DIR/<name>.npy (float32 / float64, a fixed seeded "
+                        "sample of rows, at most 64 MB in all): the headline encode leg's embeddings, the search leg's top-k scores "
+                        "and ids (and those of its encoder-like leg); rank 0's arrays")
     return p.parse_args()
+
+
+# --dump-outputs: bytes of rows each leg may write (56 MiB in all, under the 64 MB cap with the .npy headers)
+DUMP_BUDGET = {"encode": 24 << 20, "search": 16 << 20, "search_encoder_like": 16 << 20}
+
+
+def dump_rows(n, row_bytes, budget, seed):
+    """Row indices of a --dump-outputs array: every row when they fit in `budget` bytes, else a fixed seeded sample (ascending);
+    the same for every run with the same arguments, so that two builds can be compared output for output."""
+    m = min(n, budget // row_bytes)
+    if m == n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False))
+
+
+def write_dumps(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+    assert sum(v.nbytes + 128 for v in arrays.values()) <= 64 * 10 ** 6
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
+def result_stream():
+    """The bench prints ONE JSON line on stdout: point file descriptor 1 at stderr for the rest of the run (the refresh job's
+    progress lines, native code, child processes) and return a stream on the original stdout for the result line."""
+    sys.stdout.flush()
+    fd = os.dup(1)
+    os.dup2(2, 1)
+    return os.fdopen(fd, "w")
 
 
 def write_synthetic_cache(path, n, L, median, sigma, lo, seed, block=1 << 20):
@@ -175,6 +211,7 @@ def full_refresh(a):
         torch.distributed.init_process_group(backend=os.environ.get("ANCE_BENCH_BACKEND", "nccl"))
     import logging
     logging.basicConfig(format="%(asctime)s %(name)s %(message)s", level=logging.INFO, stream=sys.stderr)
+    result = result_stream()
     d = a.full_dir
     mode = a.encoder_precision or precision_from_env()
     wall, timings, prep, lines, ndcg = run_refresh(a, d, a.n_passages, a.full_queries, a.full_dev_queries, adg.Dist(), dev, rank, mode)
@@ -191,7 +228,7 @@ def full_refresh(a):
                "passages_per_sec_measured": a.n_passages / enc_s if enc_s > 0 else None,
                "train_queries_per_sec_measured": a.full_queries / timings["search_train"] if timings.get("search_train") else None,
                "lines_written": lines, "dev_ndcg": ndcg}
-        print(json.dumps(out))
+        print(json.dumps(out), file=result, flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
 
@@ -732,10 +769,14 @@ def main():
     if a.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
         sys.exit(2)
+    if a.steps < 1 or a.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1 and --warmup >= 0\n")
+        sys.exit(2)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         return launch_ranks(a)
     if a.full:
         return full_refresh(a)
+    result = result_stream()
     import torch
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -762,6 +803,7 @@ def main():
     dist = adg.Dist()
     eng = adg.HipEngine(dev)
     errors = {}
+    dumps = {}  # --dump-outputs: name -> host array
     out = {"metric": "passages_encoded_per_sec", "value": None, "unit": "passages/s", "n_gpus": world,
            "rccl_ranks": (torch.distributed.get_world_size() if dist_on else 1),
            "backend": (torch.distributed.get_backend() if dist_on else None),
@@ -809,6 +851,9 @@ def main():
                 with PowerSampler(torch, dev.index or 0) as ps:
                     dt = timed_steps(step, steps, 0, dist_on, torch)
                 power = ps.report()
+                if a.dump_outputs and rank == 0 and mode == HEADLINE_MODE:  # `emb` as the last timed step left it
+                    sel = torch.from_numpy(dump_rows(a.encode_block, 768 * 4, DUMP_BUDGET["encode"], 0)).to(dev)
+                    dumps["encode_embeddings"] = emb[sel].cpu().numpy()
                 os.environ["ANCE_ENCODER_STREAMS"] = "1"
                 try:
                     enc1 = Encoder(sd, ARCH_ROBERTA, "roberta.", True, max_seq_len=min(a.seq_len, 512), max_tokens=a.max_tokens,
@@ -936,6 +981,13 @@ def main():
             def step_search():
                 res["DI"] = adg.sharded_search(eng, dist, x, r0, q, a.topk)
 
+            def dump_search(name, seed):  # the merged lists of the last timed step (rank 0 holds them)
+                if a.dump_outputs and rank == 0:
+                    D_, I_ = res["DI"]
+                    sel = torch.from_numpy(dump_rows(D_.shape[0], a.topk * (4 + 8), DUMP_BUDGET[name], seed)).to(D_.device)
+                    dumps[name + "_scores"] = D_[sel].cpu().numpy()
+                    dumps[name + "_ids"] = I_[sel].cpu().numpy().astype(np.float64)  # exact: ids < 2^53
+
             for _ in range(max(a.warmup, 1)):
                 step_search()
             torch.cuda.synchronize()
@@ -946,6 +998,7 @@ def main():
                 dt = timed_steps(step_search, a.steps, 0, dist_on, torch)
             prof = _lib.profile_read()
             _lib.profile_enable(False)
+            dump_search("search", 1)
             comm = dist.comm_ms() if dist_on else {}
             dist.comm = None
             qps = a.query_block * a.steps / dt
@@ -1024,6 +1077,7 @@ def main():
                 dt2 = timed_steps(step_search, a.steps, 0, dist_on, torch)
                 prof2 = _lib.profile_read()
                 _lib.profile_enable(False)
+                dump_search("search_encoder_like", 2)
                 scan2 = prof2["ip_topk_scan"]
                 D2, I2 = res["DI"]
                 exact2 = None
@@ -1089,12 +1143,17 @@ def main():
         pass
     if dist_on and out["rccl_ranks"] != a.gpus:
         errors["ranks"] = "process group has %d ranks, --gpus %d" % (out["rccl_ranks"], a.gpus)
+    if a.dump_outputs and rank == 0:
+        try:
+            write_dumps(a.dump_outputs, dumps)
+        except Exception as e:
+            errors["dump_outputs"] = repr(e)
     if errors:
         out["errors"] = errors
     if dist_on:
         torch.distributed.barrier()
     if rank == 0:
-        print(json.dumps(out))
+        print(json.dumps(out), file=result, flush=True)
     if dist_on:
         torch.distributed.destroy_process_group()
 

@@ -1,9 +1,11 @@
 """bench.py's own data tools (CPU): the synthetic tokenised cache `bench.py --full` writes is the reference's cache format
-(utils/util.py:257-307) as `ance_amd.cache.TokenCache` reads it, block boundaries included, and deterministic."""
+(utils/util.py:257-307) as `ance_amd.cache.TokenCache` reads it, block boundaries included, and deterministic.  One GPU test
+runs the bench itself at a small size."""
 import hashlib
 import os
 
 import numpy as np
+import pytest
 
 
 def test_synthetic_cache_round_trip(tmp_path):
@@ -103,3 +105,83 @@ def test_power_sampler_reads_hwmon_files(tmp_path):
     empty.mkdir()
     ps2 = bench.PowerSampler(None, 0, hwmon_dirs=[str(empty)])
     assert ps2.files is None or ps2.report() is None
+
+
+def test_dump_rows_are_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: every row when the leg's budget holds them, else the same seeded, ascending sample on every run; the
+    files are float32 / float64 and the legs' budgets stay under the 64 MB the option promises."""
+    import bench
+    assert np.array_equal(bench.dump_rows(100, 3072, 1 << 20, 0), np.arange(100))
+    a = bench.dump_rows(16384, 3072, 24 << 20, 0)
+    assert len(a) == 8192 and np.array_equal(a, np.unique(a)) and a[-1] < 16384
+    assert np.array_equal(a, bench.dump_rows(16384, 3072, 24 << 20, 0))
+    assert not np.array_equal(a, bench.dump_rows(16384, 3072, 24 << 20, 1))
+    assert sum(bench.DUMP_BUDGET.values()) + 128 * 5 <= 64 * 10 ** 6
+    bench.write_dumps(str(tmp_path / "d"), {"x": np.ones((4, 3), np.float32), "y": np.arange(3.0)})
+    assert np.load(str(tmp_path / "d" / "x.npy")).dtype == np.float32 and np.load(str(tmp_path / "d" / "y.npy")).dtype == np.float64
+    with pytest.raises(AssertionError):
+        bench.write_dumps(str(tmp_path / "e"), {"ids": np.arange(3)})
+    with pytest.raises(AssertionError):
+        bench.write_dumps(str(tmp_path / "e"), {"big": np.zeros(8 * 10 ** 6 + 1)})
+
+
+def test_result_stream_keeps_stdout_to_the_json_line():
+    """The bench's stdout is its one JSON line: what the run prints otherwise (the refresh job's progress line, a child
+    process) goes to stderr."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, subprocess, bench\n"
+            "r = bench.result_stream()\n"
+            "print('Rank:0 --- ANN NDCG@10:0.0')\n"
+            "subprocess.run(['echo', 'child'])\n"
+            "print(json.dumps({'ms_per_step': 1.0}), file=r, flush=True)\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout == '{"ms_per_step": 1.0}\n'
+    assert "ANN NDCG" in r.stderr and "child" in r.stderr
+
+
+def _bench_line(root, tmp_path, steps, dump):
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--layers", "2",
+           "--n-passages", "200000", "--encode-block", "2048", "--query-block", "2048", "--exact-check-queries", "8",
+           "--skip-precise", "--skip-mfma-probe", "--skip-other-configs", "--no-cpu-baseline",
+           "--slice-passages", "20000", "--slice-queries", "2048", "--slice-dev-queries", "256",
+           "--slice-dir", str(tmp_path / ("slice%d" % steps)), "--dump-outputs", dump]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout[-3000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_line_and_dumped_outputs(tmp_path):
+    """bench.py on a small corpus, twice with different --steps: stdout is exactly the JSON line (the whole-refresh slice,
+    which prints the job's NDCG line, included), `steps` / `ms_per_step` describe the timed steps, and --dump-outputs writes
+    the same float arrays on both runs -- the inputs are seeded, the outputs of a step do not depend on how many ran."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d1, d2 = str(tmp_path / "d1"), str(tmp_path / "d2")
+    o1 = _bench_line(root, tmp_path, 3, d1)
+    o2 = _bench_line(root, tmp_path, 2, d2)
+    for o, k in ((o1, 3), (o2, 2)):
+        assert "errors" not in o, o.get("errors")
+        assert o["steps"] == k and o["ms_per_step"] > 0 and o["search"]["ms_per_step"] > 0
+        assert abs(o["value"] - 2048 * 1e3 / o["ms_per_step"]) <= 1e-6 * o["value"]
+        assert o["full_refresh_slice"]["lines_written"] == 2048
+    shapes = {"encode_embeddings": (2048, 768), "search_scores": (2048, 200), "search_ids": (2048, 200),
+              "search_encoder_like_scores": (2048, 200), "search_encoder_like_ids": (2048, 200)}
+    assert sorted(os.listdir(d1)) == sorted(n + ".npy" for n in shapes)
+    assert sum(os.path.getsize(os.path.join(d1, f)) for f in os.listdir(d1)) <= 64 * 10 ** 6
+    for n, shape in shapes.items():
+        a, b = np.load(os.path.join(d1, n + ".npy")), np.load(os.path.join(d2, n + ".npy"))
+        assert a.shape == shape and a.dtype == (np.float64 if n.endswith("_ids") else np.float32) and np.isfinite(a).all()
+        assert np.array_equal(a, b), n
+    ids = np.load(os.path.join(d1, "search_ids.npy"))
+    assert ids.min() >= 0 and ids.max() < 200000 and np.array_equal(ids, np.rint(ids))
+    assert (np.diff(np.load(os.path.join(d1, "search_scores.npy")), axis=1) <= 0).all()
