@@ -13,7 +13,6 @@ struct AttnArgs {
     int n_heads;
     int cls_only;          // 1: only query 0 of every sequence is computed; its row goes to ctx[s] (compact)
     int q_compact;         // with cls_only: that query is row s of the Q columns of qk (the encoder's compact [CLS] projection)
-    int coalesced;         // 1 (default): Q rows and output rows through the wave-private LDS slabs; 0: per-lane loads / stores (A/B)
 };
 
 size_t attention_lds_bytes(int max_seq_len, int n_waves);

@@ -42,11 +42,10 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// COAL: the block's output goes through the wave's private 4 KiB slab ([32 queries][64 dims], chunk-swizzled like the K
+// The block's output goes through the wave's private 4 KiB slab ([32 queries][64 dims], chunk-swizzled like the K
 // tile) and leaves as whole 128-byte rows.  Straight from the accumulators a store instruction writes 8 bytes into each of
 // 32 different rows: 64 cache-line accesses per instruction, and it is the L1's tag rate -- one lookup per cycle -- that
 // bounds this kernel (rocprofv3: 83 k lookups per CU and launch, 7 x what the bytes need).
-template <bool COAL>
 __device__ __forceinline__ void attend_qblock(const AttnArgs &A, const _Float16 *Ks, const _Float16 *Vs, const f16x8 (&qf)[4], int s,
                                               int h, int tok0, int T, int Tk, int vld, int qb0, int q_end, int g, int i,
                                               _Float16 *slab) {
@@ -111,7 +110,7 @@ __device__ __forceinline__ void attend_qblock(const AttnArgs &A, const _Float16 
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
     // O^T[d][query]: d = db*32 + (r&3) + 8 (r>>2) + 4 g  ->  4 consecutive d per (db, r>>2)
-    if constexpr (COAL) {
+    {
         const int l = g * 32 + i;
 #pragma unroll
         for (int db = 0; db < 2; ++db) {
@@ -134,25 +133,12 @@ __device__ __forceinline__ void attend_qblock(const AttnArgs &A, const _Float16 
             }
         }
         wave_lds_sync();  // the slab is this wave's next Q block
-    } else if (qb0 + i < q_end) {
-        const size_t orow = A.cls_only ? (size_t)s : (size_t)(tok0 + qb0 + i);
-        _Float16 *op = A.ctx + orow * A.ld_ctx + h * HD + 4 * g;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-            const f32x16 &o = db == 0 ? o0 : o1;
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const f16x4 v = {(_Float16)(o[4 * rq + 0] * inv), (_Float16)(o[4 * rq + 1] * inv),
-                                 (_Float16)(o[4 * rq + 2] * inv), (_Float16)(o[4 * rq + 3] * inv)};
-                *reinterpret_cast<f16x4 *>(op + db * 32 + 8 * rq) = v;
-            }
-        }
     }
 }
 
 // NW waves per workgroup (4 in the product; 32 NW queries per round).  Three workgroups per CU: at 128 tokens the 49 KB
 // of LDS allow no more.
-template <bool COAL, int NW>
+template <int NW>
 __global__ void __launch_bounds__(64 * NW, 3) attention_kernel(const AttnArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     constexpr int NT = 64 * NW;
@@ -171,41 +157,33 @@ __global__ void __launch_bounds__(64 * NW, 3) attention_kernel(const AttnArgs A)
     const int tid = threadIdx.x;
     const int w = tid >> 6, l = tid & 63, g = l >> 5, i = l & 31;
     const int H = A.n_heads * HD;
-    _Float16 *slab = Vs + (size_t)HD * vld + w * (32 * HD);  // COAL: this wave's [32][64] Q / O slab
+    _Float16 *slab = Vs + (size_t)HD * vld + w * (32 * HD);  // this wave's [32][64] Q / O slab
 
     // Q of this wave's first query block: requested before the staging so that its latency overlaps the K / V^T loads.
-    // COAL: whole 128-byte rows (8 lanes per row, 8 rows per instruction) that go through the slab; otherwise each lane
-    // loads its own fragment pieces (B operand: lane (query i, group g) holds head dims 32 g + 8 s .. + 8) -- 64 cache-line
-    // accesses per instruction instead of 8.
+    // Whole 128-byte rows (8 lanes per row, 8 rows per instruction) that go through the slab: loading its own fragment pieces
+    // (B operand: lane (query i, group g) holds head dims 32 g + 8 s .. + 8) a lane would make 64 cache-line accesses per
+    // instruction instead of 8.
     const int q_end = A.cls_only ? 1 : T;  // last layer: only the [CLS] query feeds the head
     f16x8 qf[4];
     // (q_compact: the one query of sequence s is row s of the Q columns -- encoder.hip projects the [CLS] rows compactly)
     auto q_row = [&](int r) { return A.q_compact ? (size_t)s : (size_t)(tok0 + min(r, T - 1)); };
     auto q_request = [&](int qb0) {
-        if constexpr (COAL) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = j * 8 + (l >> 3);
-                qf[j] = *reinterpret_cast<const f16x8 *>(A.qk + q_row(qb0 + row) * A.ld_qk + h * HD + (l & 7) * 8);
-            }
-        } else {
-            const _Float16 *qp = A.qk + q_row(qb0 + i) * A.ld_qk + h * HD + 32 * g;
-#pragma unroll
-            for (int sx = 0; sx < 4; ++sx) qf[sx] = *reinterpret_cast<const f16x8 *>(qp + sx * 8);
+        for (int j = 0; j < 4; ++j) {
+            const int row = j * 8 + (l >> 3);
+            qf[j] = *reinterpret_cast<const f16x8 *>(A.qk + q_row(qb0 + row) * A.ld_qk + h * HD + (l & 7) * 8);
         }
     };
-    auto q_to_fragments = [&]() {  // COAL: rows -> slab -> B-operand fragments (wave-private, no workgroup barrier)
-        if constexpr (COAL) {
+    auto q_to_fragments = [&]() {  // rows -> slab -> B-operand fragments (wave-private, no workgroup barrier)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = j * 8 + (l >> 3);
-                *reinterpret_cast<f16x8 *>(slab + row * HD + kswz(row, l & 7) * 8) = qf[j];
-            }
-            wave_lds_sync();
-#pragma unroll
-            for (int sx = 0; sx < 4; ++sx) qf[sx] = *reinterpret_cast<const f16x8 *>(slab + i * HD + kswz(i, 4 * g + sx) * 8);
-            wave_lds_sync();  // the slab takes the block's output next
+        for (int j = 0; j < 4; ++j) {
+            const int row = j * 8 + (l >> 3);
+            *reinterpret_cast<f16x8 *>(slab + row * HD + kswz(row, l & 7) * 8) = qf[j];
         }
+        wave_lds_sync();
+#pragma unroll
+        for (int sx = 0; sx < 4; ++sx) qf[sx] = *reinterpret_cast<const f16x8 *>(slab + i * HD + kswz(i, 4 * g + sx) * 8);
+        wave_lds_sync();  // the slab takes the block's output next
     };
     if (w * 32 < q_end) q_request(w * 32);
 
@@ -258,7 +236,7 @@ __global__ void __launch_bounds__(64 * NW, 3) attention_kernel(const AttnArgs A)
             q_request(qb0);
             q_to_fragments();
         }
-        attend_qblock<COAL>(A, Ks, Vs, qf, s, h, tok0, T, Tk, vld, qb0, q_end, g, i, slab);
+        attend_qblock(A, Ks, Vs, qf, s, h, tok0, T, Tk, vld, qb0, q_end, g, i, slab);
     }
 }
 
@@ -274,7 +252,7 @@ __global__ void __launch_bounds__(64 * NW, 3) attention_kernel(const AttnArgs A)
 //     O^T = 2^-11 (V_hi P_lo'^T + V_lo' P_hi^T) + V_hi P_hi^T          (two accumulator sets, combined once at the end)
 // LDS: 4 x keys x 64 halves = 64 KB at 128 keys, 128 KB at 256; longer sequences stage their keys 256 at a time (the
 // online softmax iterates key blocks anyway) and re-stage them for every pass of 128 queries.  Replaces the vector-unit kernel of
-// precise32.h (launch_attention32, kept behind ANCE_SPLIT_ATTN=0) at 8 x the speed for the lengths of config 2.
+// precise32.h (launch_attention32, now the fp32 mode's only) at 8 x the speed for the lengths of config 2.
 // V in LDS (round 6, TR): ROW-major like K -- [key][64 dims + 8 pad] halves, staged by 16-byte writes -- and read as V^T fragments
 // with gfx950's LDS transpose read (ds_read_b64_tr_b16: every lane gives the address of 4 contiguous halves, within each group of
 // 16 lanes the 16 x 4 block arrives transposed: out[l][j] = in[16 (l / 16) + 4 j + (l % 16) / 4][l % 4], tools/tr16_probe.cpp).  The
@@ -332,12 +310,6 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
     // one per round (4 rounds at 128 keys).  The chunked path (T > 256) stages under live accumulators and keeps UNR = 1.
     auto stage = [&](int k0, auto unr_tag) {
         constexpr int UNR = decltype(unr_tag)::value;
-#if defined(ATTN_DIAG_NO_STAGE)  // measurement builds only (scripts/gpu_r6_attn_phases.sh): what the kernel costs without one of its phases
-        if (n_heads > 0) {  // no panel loads, no split: the LDS writes only (zeros)
-            for (int e = tid; e < kc * 32; e += NT) *reinterpret_cast<f16x8 *>(Kh + e * 8) = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            return;
-        }
-#endif
         for (int e0 = tid; e0 < kc * 8; e0 += UNR * NT) {
             f32x4 kv[UNR][4];
 #pragma unroll
@@ -346,11 +318,6 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
                 const int kl_ = e >> 3, ch = e & 7, key = k0 + kl_;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) kv[it][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if defined(ATTN_DIAG_NO_LOAD)  // the split and the LDS writes, without the panel's global loads
-                if (n_heads > 0) {
-                    for (int q = 0; q < 4; ++q) kv[it][q] = f32x4{0.01f * ch, 0.02f, -0.01f * kl_, 0.005f};
-                } else
-#endif
                 if (e < kc * 8 && key < T) {
                     const float *kp = qkv + (size_t)(tok0 + key) * ld + n_heads * HD + h * HD + ch * 8;
                     kv[it][0] = *reinterpret_cast<const f32x4 *>(kp);
@@ -428,11 +395,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
                 __syncthreads();
             }
             if (!active) continue;
-#if defined(ATTN_DIAG_NO_COMPUTE)
-            const int nkb = n_heads > 0 ? 0 : 1;
-#else
             const int nkb = min(kc, Tk - k0) >> 5;
-#endif
             for (int kb = 0; kb < nkb; ++kb) {
                 const int krow = kb * 32 + i;
                 const int ksw = (krow >> 1) & 7;
@@ -501,9 +464,6 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
             }
         }
         if (!active) continue;
-#if defined(ATTN_DIAG_NO_COMPUTE)
-        l_run = 1.0f;
-#endif
         const float l_tot = l_run + __shfl_xor(l_run, 32);
         const float inv = 1.0f / l_tot;
         {
@@ -587,7 +547,6 @@ size_t attention_lds_bytes(int max_seq_len, int n_waves) {
 // ramp and tail of four launches (112 us).
 int launch_attention(const AttnArgs &A, int n_seq, int max_seq_len, hipStream_t st) {
     if (n_seq <= 0) return ANCE_OK;
-    const bool coal = A.coalesced != 0;
     const size_t lds = attention_lds_bytes(max_seq_len, 4);
     if (lds > 160 * 1024) {
         set_last_error("attention: sequence too long for LDS");
@@ -598,15 +557,12 @@ int launch_attention(const AttnArgs &A, int n_seq, int max_seq_len, hipStream_t 
     static size_t attr_set[64] = {0};  // the attribute is per device (ordinals >= 64: set on every call)
     const bool tracked = dev >= 0 && dev < 64;
     if (!tracked || lds > __atomic_load_n(&attr_set[dev], __ATOMIC_ACQUIRE)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(attention_kernel<true, 4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(attention_kernel<false, 4>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(attention_kernel<4>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return check_launch("attention attr");
         if (tracked) __atomic_store_n(&attr_set[dev], lds, __ATOMIC_RELEASE);
     }
-    if (coal) hipLaunchKernelGGL((attention_kernel<true, 4>), dim3((unsigned)n_seq * A.n_heads), dim3(256), lds, st, A);
-    else hipLaunchKernelGGL((attention_kernel<false, 4>), dim3((unsigned)n_seq * A.n_heads), dim3(256), lds, st, A);
+    hipLaunchKernelGGL((attention_kernel<4>), dim3((unsigned)n_seq * A.n_heads), dim3(256), lds, st, A);
     return ANCE_OK;
 }
 

@@ -4,40 +4,43 @@
 //   = transformers RobertaModel/BertModel forward + embeddingHead + norm (model/models.py:149-157,
 //     165-199, 235-259).
 //
-// Per micro-batch (<= max_tokens real tokens), per layer:
-//   QK   = h16 Wqk^T + b          (gemm EPI_QK, Q pre-scaled by 1/8)        [T, 1536] f16
-//   V^T  = Wv h16^T + b           (gemm EPI_VT, key-contiguous)             [768, cols] f16
-//   ctx  = softmax(Q K^T) V       (attention.hip)                           [T, 768] f16
-//   preA = ctx Wo^T + b + LN(preB)  (gemm EPI_RES32)                        [T, 768] f32
-//   LayerNorm(preA)               -> h16 (next MFMA operand) and per-row (mean, rstd)
-//   f    = gelu(h16 W1^T + b)     (gemm EPI_GELU)                           [T, 3072] f16
-//   preB = f W2^T + b + LN(preA) ; LayerNorm(preB) -> h16, (mean, rstd)
-// then  emb = LayerNorm(Wh LN(preB)[cls] + bh)  (fp32)  or raw LN(preB)[cls] for DPR's BERT.
-// The fp32 residual stream h = LN(pre) is never stored: its consumers (the next RES32 epilogue, the
-// [CLS] gather, the head) recompute it from the pre-LN row and the two row statistics with the one
-// expression ln_apply4 -- 6 KB per token and layer less HBM traffic (LayerNorm kernel 72 -> ~46 us).
-// Precision: fp16 MFMA operands, fp32 accumulation, fp32 residual stream / LayerNorm / softmax.
+// Three arithmetic modes (AnceEncoderDesc.precision), one forward each: forward_fp16, forward_split, forward_fp32.  encode_impl
+// plans the micro-batches (<= max_tokens real tokens), packs their tokens and hands each one to the forward of the handle's mode
+// on one of two lanes (activation sets) and streams.
 //
-// "LayerNorm without a kernel" (default; ANCE_LN_FOLD=0 selects the form above): the two LayerNorm passes of a layer
-// read 3 KB and write 1.5 KB per token at the HBM roofline for arithmetic every consumer can do on the fly.  Instead
+// fp16 mode: fp16 MFMA operands, fp32 accumulation, fp32 LayerNorm statistics and softmax.  The residual stream of a layer is
+// never normalised by a kernel of its own ("LayerNorm without a kernel"): a LayerNorm pass would read 3 KB and write 1.5 KB per
+// token at the HBM roofline for arithmetic every consumer can do on the fly.  Instead
 //   * the RES GEMM epilogue (EPI_RESLN) writes its output row v as an fp16 pair (hi = fp16(v), lo = fp16(v - hi): the same
 //     3 KB the fp32 row took, 22 mantissa bits) and the (mean, M2) of every 64-column slice (96 bytes per row);
 //   * the consumer GEMMs take hi AS IT IS for their token operand and finish the normalisation algebraically:
 //       LN(v) W^T + b = r (v (gamma (.) W)^T - mu c) + (b + W beta),   c[n] = sum_k fp16(gamma_k W[n][k])
-//     with gamma folded into the fp16 weight when it is loaded, c summed over the ROUNDED weights (so that the identity is
-//     exact for the products the MFMA actually forms) and b' in fp32;
+//     with gamma folded into the fp16 weight when it is loaded (fold_weight_kernel), c summed over the ROUNDED weights (so that
+//     the identity is exact for the products the MFMA actually forms) and b' in fp32;
 //   * every consumer combines the 12 slices of a row into (mean, rstd) itself (Chan): a GEMM tile gets the partials of
 //     its 256 tokens, with its bias / csum / gamma / beta vectors, by LDS-DMA ahead of its main loop and combines them
 //     when its epilogue starts -- there is no LayerNorm kernel and no statistics kernel at all;
 //   * the consumers of the fp32 value (next RES epilogue, [CLS] gather, head) recompute LN(hi + lo) from the pair.
-// Rounding points that move: the token operand is fp16(v) instead of fp16(LN(v)) -- the same relative rounding of every
-// element, taken before the mean is removed -- and gamma (.) W is rounded once instead of W.  Measured parity: DESIGN.md 4.
+// Per layer, x_b = the (hi, lo) pair of the previous layer's pre-LayerNorm output (or of the embeddings, embed_fold_kernel):
+//   QK   = LN(x_b) Wqk^T + b          (gemm EPI_QK_F, Q pre-scaled by log2(e) / 8)   [T, 1536] f16
+//   V^T  = Wv LN(x_b)^T + b           (gemm EPI_VT_F, key-contiguous)                 [768, cols] f16
+//   ctx  = softmax(Q K^T) V           (attention.hip)                                 [T, 768] f16
+//   x_a  = ctx Wo^T + b + LN(x_b)     (gemm EPI_RESLN: pair + slice statistics)       [T, 768] (hi, lo)
+//   f    = gelu(LN(x_a) W1^T + b)     (gemm EPI_GELU_F)                               [T, 3072] f16
+//   x_b  = f W2^T + b + LN(x_a)       (gemm EPI_RESLN)                                [T, 768] (hi, lo)
+// then  emb = LayerNorm(Wh LN(x_b)[cls] + bh)  (fp32: head_gemm_kernel, head_ln_kernel)  or LN(x_b)[cls] for DPR's BERT
+// (head_kernel).  The last layer runs its Q projection and everything after the attention on the [CLS] rows only (the CLS-only
+// tail; ANCE_CLS_TAIL=0 runs it in full, bit-identically).  Rounding points against the fp32 forward: the token operand is
+// fp16(v) instead of fp16(LN(v)) -- the same relative rounding of every element, taken before the mean is removed -- and
+// gamma (.) W is rounded once instead of W.  Measured parity: DESIGN.md 4.
 //
-// SPLIT mode (ANCE_ENCODER_SPLIT=1; round 4): an fp32-GRADE result at a third of the fp16 MFMA rate instead of the sixteenth the
-// fp32-input matrix cores run at (precise32.h).  Every GEMM operand is an fp16 pair  v = hi + lo' 2^-11  (rows [hi | lo']),
-// a product is three fp16 MFMA passes on the pipeline of the default mode (gemm256_f16.hip: gemm256_split_kernel), the
-// LayerNorm fold, the fp32 softmax (precise32.h attention, fp32 Q | K | V from the QKV epilogue), the exact-erf GELU and the
-// fp32 head are the reference's arithmetic.  Stated tolerance 2e-5 (tests/test_split_model.py: 3.3e-6 on the CPU model).
+// SPLIT mode (the default; round 4-5): an fp32-GRADE result on the fp16 matrix cores instead of the sixteenth of their rate the
+// fp32-input ones run at (precise32.h).  Every GEMM operand is an fp16 pair row (common.h), a product is three fp16 MFMAs per
+// k-step on the pipeline of the fp16 mode (gemm256_f16.hip: gemm256_split_kernel), with the same LayerNorm fold; the attention
+// runs on fp32 Q | K | V (attention.hip: attention_split_kernel), the GELU is the exact erf form and the head is fp32 -- the
+// reference's arithmetic.  Stated tolerance 2e-5 (tests/test_split_model.py: 3.3e-6 on the CPU model).
+//
+// fp32 mode: fp32 operands throughout (precise32.h), the audit path.
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -212,103 +215,13 @@ __global__ void __launch_bounds__(256) pack_kernel(const PlanArgs P) {
     }
 }
 
-// LayerNorm of one 768-wide row held as 12 floats per lane (3 x float4, lane-contiguous)
-// LayerNorm of one 768-wide row held by one wave (3 float4 per lane): fp16 output for the next GEMM and the
-// row statistics for the consumers of the fp32 value (see the file header).
-__device__ __forceinline__ void ln_row_store(f32x4 v0, f32x4 v1, f32x4 v2, const float *gamma, const float *beta,
-                                             float eps, _Float16 *out16, float *stats, int l) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += v0[j] + v1[j] + v2[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    const float mean = s * (1.0f / H);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float a = v0[j] - mean, b = v1[j] - mean, c = v2[j] - mean;
-        q += a * a + b * b + c * c;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
-    const float rstd = rsqrtf(q * (1.0f / H) + eps);
-    const f32x4 *g4 = reinterpret_cast<const f32x4 *>(gamma);
-    const f32x4 *b4 = reinterpret_cast<const f32x4 *>(beta);
-    f32x4 vin[3] = {v0, v1, v2};
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-        const int c4 = p * 64 + l;  // float4 index within the row
-        const f32x4 y = ln_apply4(vin[p], mean, rstd, g4[c4], b4[c4]);
-        reinterpret_cast<f16x4 *>(out16)[c4] = f16x4{(_Float16)y[0], (_Float16)y[1], (_Float16)y[2], (_Float16)y[3]};
-    }
-    if (l == 0) {
-        stats[0] = mean;
-        stats[1] = rstd;
-    }
-}
-
-__global__ void __launch_bounds__(256) embed_ln_kernel(const int *tok_id, const int *tok_pos, int Tpad, const float *word,
-                                                       const float *pos, const float *type0, int vocab, int max_pos,
-                                                       const float *gamma, const float *beta, float eps, float *pre,
-                                                       _Float16 *h16, float *stats) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (t >= Tpad) return;
-    int id = tok_id[t], p = tok_pos[t];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(word + (size_t)id * H);
-    const f32x4 *p4 = reinterpret_cast<const f32x4 *>(pos + (size_t)p * H);
-    const f32x4 *t4 = reinterpret_cast<const f32x4 *>(type0);
-    f32x4 v[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int c4 = k * 64 + l;
-        v[k] = (w4[c4] + t4[c4]) + p4[c4];  // same association as the reference: (word + type) + pos
-        reinterpret_cast<f32x4 *>(pre + (size_t)t * H)[c4] = v[k];
-    }
-    ln_row_store(v[0], v[1], v[2], gamma, beta, eps, h16 + (size_t)t * H, stats + 2 * (size_t)t, l);
-}
-
-__global__ void __launch_bounds__(256) ln_kernel(const float *pre, int Tpad, const float *gamma, const float *beta, float eps,
-                                                 _Float16 *h16, float *stats) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (t >= Tpad) return;
-    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(pre + (size_t)t * H);
-    ln_row_store(x4[l], x4[64 + l], x4[128 + l], gamma, beta, eps, h16 + (size_t)t * H, stats + 2 * (size_t)t, l);
-}
-
-// last layer, CLS-only tail: compact residual rows  dst[s] = LN(pre[seq_off[s]])  (rows S..S_pad zeroed)
-__global__ void __launch_bounds__(256) gather_cls_kernel(const float *pre, const float *stats, const float *gamma,
-                                                         const float *beta, const int *seq_off, int S, int S_pad, float *dst) {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (s >= S_pad) return;
-    f32x4 *d4 = reinterpret_cast<f32x4 *>(dst + (size_t)s * H);
-    if (s < S) {
-        const size_t row = (size_t)seq_off[s];
-        const f32x4 *s4 = reinterpret_cast<const f32x4 *>(pre + row * H);
-        const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            d4[k * 64 + l] = ln_apply4(s4[k * 64 + l], mean, rstd, reinterpret_cast<const f32x4 *>(gamma)[k * 64 + l],
-                                       reinterpret_cast<const f32x4 *>(beta)[k * 64 + l]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) d4[k * 64 + l] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
-
-// hi / lo / ldp: the fp16 pair of the pre-LayerNorm row -- pair_w = 0: two planes (default mode, lo = fp16(v - hi)); pair_w = W: lo is
-// null and hi points to pair rows of the split mode (common.h: pair_hi_col / pair_lo_col)
+// Output of a tower without embeddingHead (DPR's BERT): the last layer's LayerNorm of the [CLS] row, one block per sequence.
+// pre / stats: fp32 rows and their (mean, rstd) (fp32 mode); or hi / lo / ldp: the fp16 pair of the pre-LayerNorm row with the slice
+// partials part -- pair_w = 0: two planes (fp16 mode, lo = fp16(v - hi)); pair_w = W: lo is null and hi points to pair rows of the
+// split mode (common.h: pair_hi_col / pair_lo_col)
 __global__ void __launch_bounds__(256) head_kernel(const float *pre, const _Float16 *hi, const _Float16 *lo, int ldp, int pair_w,
                                                    const float *stats, const float *part, float eps, const float *lng, const float *lnb,
-                                                   const int *seq_off, int compact, const float *W, const float *b,
-                                                   const float *gamma, const float *beta, int has_head, float *out, unsigned *faults) {
-    __shared__ float cls[H];
-    __shared__ float z[HEAD_OUT];
-    __shared__ float red[8];
+                                                   const int *seq_off, int compact, float *out, unsigned *faults) {
     const int s = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)(compact ? s : seq_off[s]);  // compact: row s already is the [CLS] row
     float mean_h, rstd_h;  // h = LN(pre), recomputed (file header)
@@ -320,49 +233,12 @@ __global__ void __launch_bounds__(256) head_kernel(const float *pre, const _Floa
         if (pair_w) return (float)hi[row * ldp + pair_hi_col(j, pair_w)] + (float)hi[row * ldp + pair_lo_col(j, pair_w)] * PAIR_LO_INV;
         return (float)hi[row * ldp + j] + (float)lo[row * ldp + j];
     };
-    if (!has_head) {
-        for (int j = tid; j < H; j += 256) dst[j] = (src(j) - mean_h) * rstd_h * lng[j] + lnb[j];
-        // a NaN anywhere in the row (or an infinity: rstd 0) shows in its statistics: count the row (ance_encoder_range_faults [1])
-        if (tid == 0 && faults && (!(fabsf(mean_h) < INFINITY) || !(rstd_h > 0.f && rstd_h < INFINITY))) atomicAdd(faults + 1, 1u);
-        return;
-    }
-    for (int j = tid; j < H; j += 256) cls[j] = (src(j) - mean_h) * rstd_h * lng[j] + lnb[j];
-    __syncthreads();
-    // each wave computes output features n = w, w+4, ...: lanes split k, reduce by shuffle
-    const int w = tid >> 6, l = tid & 63;
-    for (int n = w; n < HEAD_OUT; n += 4) {
-        const float *wr = W + (size_t)n * H;
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < H / 64; ++k) acc = fmaf(wr[k * 64 + l], cls[k * 64 + l], acc);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-        if (l == 0) z[n] = acc + b[n];
-    }
-    __syncthreads();
-    float sm = 0.f;
-    for (int j = tid; j < HEAD_OUT; j += 256) sm += z[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off);
-    if (l == 0) red[w] = sm;
-    __syncthreads();
-    const float mean = (red[0] + red[1] + red[2] + red[3]) * (1.0f / HEAD_OUT);
-    float q = 0.f;
-    for (int j = tid; j < HEAD_OUT; j += 256) {
-        const float a = z[j] - mean;
-        q += a * a;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
-    if (l == 0) red[4 + w] = q;
-    __syncthreads();
-    const float rstd = rsqrtf((red[4] + red[5] + red[6] + red[7]) * (1.0f / HEAD_OUT) + 1e-5f);
-    for (int j = tid; j < HEAD_OUT; j += 256) dst[j] = (z[j] - mean) * rstd * gamma[j] + beta[j];
-    if (tid == 0 && faults && (!(fabsf(mean) < INFINITY) || !(rstd > 0.f && rstd < INFINITY))) atomicAdd(faults + 1, 1u);
+    for (int j = tid; j < H; j += 256) dst[j] = (src(j) - mean_h) * rstd_h * lng[j] + lnb[j];
+    // a NaN anywhere in the row (or an infinity: rstd 0) shows in its statistics: count the row (ance_encoder_range_faults [1])
+    if (tid == 0 && faults && (!(fabsf(mean_h) < INFINITY) || !(rstd_h > 0.f && rstd_h < INFINITY))) atomicAdd(faults + 1, 1u);
 }
 
-
-// ---- folded-LayerNorm path ---------------------------------------------------------------------
+// ---- fp16 mode: folded LayerNorm (file header) ------------------------------------------------------
 __device__ __forceinline__ void split_store(const f32x4 v, _Float16 *hi, _Float16 *lo, int c4) {
     const f16x4 h = cvt_f16x4_pinned(v);
     const f16x4 r = f16x4{(_Float16)(v[0] - (float)h[0]), (_Float16)(v[1] - (float)h[1]), (_Float16)(v[2] - (float)h[2]),
@@ -717,8 +593,11 @@ int resolve_precision(const AnceEncoderDesc *d) {
     return split_env() ? ANCE_PRECISION_SPLIT : ANCE_PRECISION_FP16;
 }
 
+// Per-layer weights.  Every mode's buffers have a place in the arena (layout_weights), but ance_encoder_create fills only those the
+// handle's forward reads: fp16 mode the fp16 / folded ones, split mode the *_s ones, fp32 mode the *32 ones and b1; all modes bo,
+// b2 and the LayerNorm parameters.
 struct LayerW {
-    _Float16 *wqk, *wv, *wo, *w1, *w2;
+    _Float16 *wqk, *wv, *wo, *w1, *w2;  // fp16 path
     _Float16 *wqkv_s, *wo_s, *w1_s, *w2_s;  // split path: pair rows [hi (K) | lo' (K)]
     float *bqkv_s, *cqkv_s, *b1_s, *c1_s;   // split path: folded biases and row sums
     float *sc_s;  // split path: [0..3] max |g (.) W| of Wqkv, Wo, W1, W2 as float bits (weight load), [4..7] the inverse of their power-of-two scales
@@ -758,12 +637,13 @@ struct AnceEncoder {
     struct Lane {
         int *seq_off, *seq_vtcol, *seq_len, *tok_id, *tok_pos, *tok_vtcol;
         float *preA, *preB;      // pre-LayerNorm rows: attention block output / FFN block output (or embeddings)
-        float *statsA, *statsB;  // (mean, rstd) per row of preA / preB
-        _Float16 *h16, *qk16, *vt16, *ctx16, *ffn16;
+        float *statsA, *statsB;  // (mean, rstd) per row of preA / preB (fp32 path: statsB of the last layer)
+        _Float16 *h16;           // (read by no mode: kept so that the workspace layout does not change)
+        _Float16 *qk16, *vt16, *ctx16, *ffn16;
         int4 *desc;              // attention descriptors in length-bucket order
         float *x32, *xa32, *qkv32, *ctx32, *ffn32;  // fp32 path only: hidden states, Q|K|V, attention output, FFN activation
         float *partA, *partB;    // folded LayerNorm: (mean, M2) of the twelve 64-column slices of every row of the two streams
-        // folded LayerNorm: preA / preB hold the (hi, lo) fp16 pairs of the stream instead of fp32 rows
+        // fp16 / split paths: preA / preB hold the fp16 pairs of the stream instead of fp32 rows
         _Float16 *xa_hi() const { return reinterpret_cast<_Float16 *>(preA); }
         _Float16 *xb_hi() const { return reinterpret_cast<_Float16 *>(preB); }
     } lane[MAX_LANES];
@@ -772,13 +652,7 @@ struct AnceEncoder {
     hipEvent_t ev_fork, ev_join[MAX_LANES];
     std::vector<int32_t> host_lens;
     bool cls_tail;  // run the last layer's post-attention part on the [CLS] rows only (ANCE_CLS_TAIL=0 disables)
-    bool ln_fold;   // LayerNorm folded into the GEMMs (file header; ANCE_LN_FOLD=0 disables)
-    bool head_mfma; // embeddingHead as one fp32 MFMA GEMM (ANCE_HEAD_MFMA=0: one block per sequence)
-    bool precise;   // fp32 path (precise32.h)
-    bool split;     // split (fp32-grade) path
-    bool n_split;   // FFN1 with the N-split tile order (ANCE_GEMM_NSPLIT=0 disables)
-    bool split_attn; // split mode: attention on the matrix cores (ANCE_SPLIT_ATTN=0: fp32 vector-unit kernel)
-    bool attn_coal; // attention Q / output rows through LDS slabs (ANCE_ATTN_COAL=0: per-lane accesses)
+    int mode;       // ANCE_PRECISION_FP16 / SPLIT / FP32 (resolve_precision)
 };
 
 namespace {
@@ -899,6 +773,305 @@ void cpy32(const void *src, float *dst, size_t n, hipStream_t st) {
     (void)hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
 }
 
+// Geometry of one micro-batch (encode_impl plans it; the forwards run it on one lane and one stream).
+struct MicroBatch {
+    int S, T;       // sequences, real tokens
+    int Tpad;       // tokens padded to the GEMM tile (256)
+    int ldvt;       // row stride of V^T (fp16 mode)
+    int maxlen;     // longest sequence
+    float *out;     // [S, HEAD_OUT] rows of the output
+};
+
+// The output of the encoder from the last layer's LayerNorm of the [CLS] rows: the embeddingHead as one MFMA GEMM + its
+// LayerNorm (has_head), or those rows as they are (DPR's BERT).  pre / stats: fp32 rows and their (mean, rstd); hi / lo / ldp /
+// pair_w / part: the fp16 pair form (head_kernel); compact: row s already is the [CLS] row of sequence s.
+void encoder_output(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb, const float *pre,
+                    const _Float16 *hi, const _Float16 *lo, int ldp, int pair_w, const float *stats, const float *part, int compact) {
+    const AnceEncoderDesc &D = e->d;
+    const LayerW &WL = e->layers[D.n_layers - 1];
+    ProfScope ps(PC_HEAD, st);
+    if (D.has_head) {
+        hipLaunchKernelGGL(head_gemm_kernel, dim3((mb.S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES, st, pre, hi, lo, ldp,
+                           pair_w, stats, part, D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off, compact, mb.S, e->head_w, e->head_b, mb.out);
+        hipLaunchKernelGGL(head_ln_kernel, dim3((mb.S + 3) / 4), dim3(256), 0, st, mb.out, mb.S, e->norm_w, e->norm_b, e->faults);
+    } else {
+        hipLaunchKernelGGL(head_kernel, dim3(mb.S), dim3(256), 0, st, pre, hi, lo, ldp, pair_w, stats, part, D.ln_eps, WL.ln2w, WL.ln2b,
+                           LN.seq_off, compact, mb.out, e->faults);
+    }
+}
+
+// ---- fp32 mode (precise32.h): plain sequence of fp32 kernels, every layer on every token ----
+int forward_fp32(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
+    const AnceEncoderDesc &D = e->d;
+    const int I = D.intermediate, T = mb.T, Tpad = mb.Tpad;
+    {
+        ProfScope pe(PC_EMBED, st);
+        hipLaunchKernelGGL(embed32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
+                           e->type0, D.vocab_size, D.max_position, LN.preB);
+        hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, e->eln_w, e->eln_b, D.ln_eps,
+                           LN.x32, (float *)nullptr);
+    }
+    int rc = ANCE_OK;
+    for (int li = 0; li < D.n_layers && !rc; ++li) {
+        const LayerW &W = e->layers[li];
+        const bool last = li == D.n_layers - 1;
+        {
+            ProfScope ps(PC_GEMM_QK, st, 2.0 * T * (3.0 * H) * H);
+            rc = launch_gemm32(P_EPI_BIAS, LN.x32, H, W.wqkv32, H, W.bqkv32, nullptr, 0, LN.qkv32, 3 * H, Tpad, 3 * H, H, st);
+        }
+        if (rc) break;
+        {
+            ProfScope ps(PC_ATTN, st);
+            rc = launch_attention32(LN.qkv32, LN.ctx32, LN.seq_off, mb.S, D.n_heads, st);
+        }
+        if (rc) break;
+        {
+            ProfScope ps(PC_GEMM_OUT, st, 2.0 * T * (double)H * H);
+            rc = launch_gemm32(P_EPI_RES, LN.ctx32, H, W.wo32, H, W.bo, LN.x32, H, LN.preA, H, Tpad, H, H, st);
+        }
+        if (rc) break;
+        {
+            ProfScope ps(PC_LN, st);
+            hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preA, Tpad, W.ln1w, W.ln1b, D.ln_eps, LN.xa32,
+                               (float *)nullptr);
+        }
+        {
+            ProfScope ps(PC_GEMM_FFN1, st, 2.0 * T * (double)I * H);
+            rc = launch_gemm32(P_EPI_GELU, LN.xa32, H, W.w132, H, W.b1, nullptr, 0, LN.ffn32, I, Tpad, I, H, st);
+        }
+        if (rc) break;
+        {
+            ProfScope ps(PC_GEMM_FFN2, st, 2.0 * T * (double)I * H);
+            rc = launch_gemm32(P_EPI_RES, LN.ffn32, I, W.w232, I, W.b2, LN.xa32, H, LN.preB, H, Tpad, H, I, st);
+        }
+        if (rc) break;
+        {
+            ProfScope ps(PC_LN, st);
+            hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, W.ln2w, W.ln2b, D.ln_eps, LN.x32,
+                               last ? LN.statsB : (float *)nullptr);
+        }
+    }
+    if (rc) return rc;
+    encoder_output(e, LN, st, mb, LN.preB, nullptr, nullptr, H, 0, LN.statsB, nullptr, 0);
+    return ANCE_OK;
+}
+
+// ---- split (fp32-grade) mode: the fp16 mode's schedule with pair operands and the fp32 attention ----
+int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
+    const AnceEncoderDesc &D = e->d;
+    const int I = D.intermediate, S = mb.S, T = mb.T, Tpad = mb.Tpad;
+    _Float16 *const xa = reinterpret_cast<_Float16 *>(LN.preA), *const xb = reinterpret_cast<_Float16 *>(LN.preB);
+    _Float16 *const ctxp = reinterpret_cast<_Float16 *>(LN.ctx32), *const ffnp = reinterpret_cast<_Float16 *>(LN.ffn32);
+    {
+        ProfScope pe(PC_EMBED, st);
+        hipLaunchKernelGGL(embed_split_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word,
+                           e->pos, e->type0, D.vocab_size, D.max_position, xb, LN.partB, e->faults);
+    }
+    const bool cls_tail = e->cls_tail;
+    const int S_pad = (int)align_up((size_t)S, 256);
+    const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_f16.hip: tile_of_block)
+    int rc = ANCE_OK;
+    for (int li = 0; li < D.n_layers && !rc; ++li) {
+        const LayerW &W = e->layers[li];
+        const bool tail = cls_tail && li == D.n_layers - 1;
+        const int Mrows = tail ? S_pad : Tpad;
+        const double Mwork = tail ? (double)S : (double)T;
+        // layer 0 reads the embedding stream, stored times EMB_SCALE: its LayerNorm runs with eps EMB_SCALE^2 (embed_split_kernel)
+        const float eps_b = li == 0 ? D.ln_eps * (EMB_SCALE * EMB_SCALE) : D.ln_eps;
+        GemmArgs G;
+        memset(&G, 0, sizeof(G));
+        // Q | K | V projection -> fp32 (the LayerNorm that produces this layer's input is folded in)
+        G.A = xb; G.lda = HP; G.B = W.wqkv_s; G.ldb = HP; G.M = Tpad; G.N = 3 * H; G.K = H;
+        G.bias = W.bqkv_s; G.csum = W.cqkv_s; G.part_in = LN.partB; G.ln_eps = eps_b;
+        G.out32 = LN.qkv32; G.ldc = 3 * H; G.wscale_inv = W.sc_s + 4; G.range_faults = e->faults;
+        // CLS-only tail: the last layer's attention has ONE query per sequence.  K | V of every token, but Q of the [CLS]
+        // rows only: their pair rows and slice partials are compacted first (they are also the residual of the
+        // attention-output GEMM below) and projected by a second, small launch into the Q columns of rows 0 .. S_pad of
+        // qkv32 -- row s = the query of sequence s (attention_split_kernel, cls_only).  A third of this GEMM's work in one
+        // layer of twelve; every element is the same arithmetic as in the full launch.
+        float *const cpt = reinterpret_cast<float *>(ffnp + (size_t)S_pad * HP);  // (the FFN buffer is dead here)
+        if (tail) {
+            ProfScope ps(PC_LN, st);
+            hipLaunchKernelGGL(gather_cls_split_kernel, dim3(S_pad / 4), dim3(256), 0, st, xb, LN.partB, LN.seq_off, S, S_pad,
+                               ffnp, cpt);
+        }
+        {
+            ProfScope ps(PC_GEMM_QK, st, tail ? 2.0 * T * (2.0 * H) * H + 2.0 * S * (double)H * H : 2.0 * T * (3.0 * H) * H);
+            if (tail) {
+                G.B = W.wqkv_s + (size_t)H * HP; G.N = 2 * H; G.bias = W.bqkv_s + H; G.csum = W.cqkv_s + H;
+                G.out32 = LN.qkv32 + H;
+                rc = launch_gemm_f16(EPI_S_QKV, G, st);
+                G.A = ffnp; G.part_in = cpt; G.M = S_pad;
+                G.B = W.wqkv_s; G.N = H; G.bias = W.bqkv_s; G.csum = W.cqkv_s; G.out32 = LN.qkv32;
+                if (!rc) rc = launch_gemm_f16(EPI_S_QKV, G, st);
+            } else {
+                rc = launch_gemm_f16(EPI_S_QKV, G, st);
+            }
+        }
+        if (rc) break;
+        {
+            ProfScope ps(PC_ATTN, st);
+            if (tail && S_pad > S)  // rows S..S_pad of the compact attention output feed the GEMM tile: keep them finite
+                (void)hipMemsetAsync(ctxp + (size_t)S * HP, 0, (size_t)(S_pad - S) * HP * sizeof(_Float16), st);
+            // (cls_only: one query per sequence, read from row s of the Q columns -- the tail's compact Q projection above)
+            rc = launch_attention_split(LN.qkv32, ctxp, LN.desc, S, D.n_heads, mb.maxlen, tail ? 1 : 0, st);
+        }
+        if (rc) break;
+        // attention.output.dense + residual LayerNorm(x_b), x_b = the previous layer's output (or the embeddings)
+        memset(&G, 0, sizeof(G));
+        G.res_gamma = li == 0 ? e->eln_w : e->layers[li - 1].ln2w;
+        G.res_beta = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
+        G.res_hi = xb; G.ldr = HP; G.part_in = LN.partB; G.ln_eps = eps_b; G.range_faults = e->faults;
+        if (tail) {  // the compact pair rows + partials of the [CLS] tokens (gathered in front of the QKV GEMM)
+            G.res_hi = ffnp; G.part_in = cpt;
+        }
+        G.A = ctxp; G.lda = HP; G.B = W.wo_s; G.ldb = HP; G.M = Mrows; G.N = H; G.K = H;
+        G.bias = W.bo; G.out16 = xa; G.ldc = HP; G.part_out = LN.partA; G.wscale_inv = W.sc_s + 5;
+        {
+            ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
+            rc = launch_gemm_f16(EPI_S_RESLN, G, st);
+        }
+        if (rc) break;
+        // intermediate.dense + exact GELU (attention.output.LayerNorm folded in)
+        memset(&G, 0, sizeof(G));
+        G.A = xa; G.lda = HP; G.B = W.w1_s; G.ldb = HP; G.M = Mrows; G.N = I; G.K = H;
+        G.bias = W.b1_s; G.csum = W.c1_s; G.part_in = LN.partA; G.ln_eps = D.ln_eps;
+        G.out16 = ffnp; G.ldc = 2 * I; G.n_split = n_split; G.wscale_inv = W.sc_s + 6;
+        G.range_faults = e->faults;
+        {
+            ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
+            rc = launch_gemm_f16(EPI_S_GELU, G, st);
+        }
+        if (rc) break;
+        // output.dense + residual LayerNorm(x_a)
+        memset(&G, 0, sizeof(G));
+        G.A = ffnp; G.lda = 2 * I; G.B = W.w2_s; G.ldb = 2 * I; G.M = Mrows; G.N = H; G.K = I;
+        G.bias = W.b2; G.res_gamma = W.ln1w; G.res_beta = W.ln1b; G.res_hi = xa; G.ldr = HP;
+        G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.out16 = xb; G.ldc = HP; G.part_out = LN.partB; G.wscale_inv = W.sc_s + 7;
+        G.range_faults = e->faults;
+        {
+            ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
+            rc = launch_gemm_f16(EPI_S_RESLN, G, st);
+        }
+    }
+    if (rc) return rc;
+    encoder_output(e, LN, st, mb, nullptr, xb, nullptr, HP, H, nullptr, LN.partB, cls_tail ? 1 : 0);
+    return ANCE_OK;
+}
+
+// ---- fp16 mode: the folded-LayerNorm forward of the file header ----
+int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
+    const AnceEncoderDesc &D = e->d;
+    const int I = D.intermediate, S = mb.S, T = mb.T, Tpad = mb.Tpad;
+    // the two halves of the fp16 pair of a stream share the fp32 row's 3 KB
+    _Float16 *const xa_hi = LN.xa_hi(), *const xa_lo = xa_hi + (size_t)e->tcap * H;
+    _Float16 *const xb_hi = LN.xb_hi(), *const xb_lo = xb_hi + (size_t)e->tcap * H;
+    {
+        ProfScope pe(PC_EMBED, st);
+        hipLaunchKernelGGL(embed_fold_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
+                           e->type0, D.vocab_size, D.max_position, xb_hi, xb_lo, LN.partB);
+    }
+    // Only the [CLS] row of the last layer reaches the head (model/models.py:49,152): after the
+    // last layer's K / V projections everything runs on the S compact [CLS] rows.
+    const bool cls_tail = e->cls_tail;
+    const int S_pad = (int)align_up((size_t)S, 256);
+    const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_f16.hip: tile_of_block)
+    for (int li = 0; li < D.n_layers; ++li) {
+        const LayerW &W = e->layers[li];
+        const bool tail = cls_tail && li == D.n_layers - 1;
+        const int Mrows = tail ? S_pad : Tpad;   // rows of the post-attention GEMMs
+        const double Mwork = tail ? (double)S : (double)T;
+        GemmArgs G;
+        memset(&G, 0, sizeof(G));
+        // Q | K projection
+        G.A = xb_hi; G.lda = H; G.B = W.wqk; G.ldb = H; G.M = Tpad; G.N = 2 * H; G.K = H;
+        G.bias = W.bqk; G.out16 = LN.qk16; G.ldc = 2 * H; G.scale_cols = H;
+        G.scale = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) and log2(e): the softmax runs on exp2
+        G.part_in = LN.partB; G.ln_eps = D.ln_eps; G.csum = W.cqk; G.tok_lo = xb_lo;
+        // CLS-only tail: K of every token, Q of the compact [CLS] rows only -- row s of the Q columns is the query of sequence s
+        // (attention_kernel, q_compact); the same arithmetic per element as the full launch (split mode: above)
+        _Float16 *const chi = LN.ffn16, *const clo = chi + (size_t)S_pad * H;  // (the FFN buffer is dead here)
+        float *const cpt = reinterpret_cast<float *>(clo + (size_t)S_pad * H);
+        if (tail) {
+            ProfScope ps(PC_LN, st);
+            hipLaunchKernelGGL(gather_cls_fold_kernel, dim3(S_pad / 4), dim3(256), 0, st, xb_hi, xb_lo, LN.partB, LN.seq_off,
+                               S, S_pad, chi, clo, cpt);
+        }
+        int rc;
+        {
+            ProfScope ps(PC_GEMM_QK, st, tail ? 2.0 * T * (double)H * H + 2.0 * S * (double)H * H : 2.0 * T * (2.0 * H) * H);
+            if (tail) {
+                G.B = W.wqk + (size_t)H * H; G.N = H; G.bias = W.bqk + H; G.csum = W.cqk + H; G.out16 = LN.qk16 + H; G.scale_cols = 0;
+                rc = launch_gemm_f16(EPI_QK_F, G, st);
+                G.A = chi; G.tok_lo = clo; G.part_in = cpt; G.M = S_pad;
+                G.B = W.wqk; G.bias = W.bqk; G.csum = W.cqk; G.out16 = LN.qk16; G.scale_cols = H;
+                if (!rc) rc = launch_gemm_f16(EPI_QK_F, G, st);
+            } else {
+                rc = launch_gemm_f16(EPI_QK_F, G, st);
+            }
+        }
+        if (rc) return rc;
+        // V^T = Wv h^T
+        memset(&G, 0, sizeof(G));
+        G.A = W.wv; G.lda = H; G.B = xb_hi; G.ldb = H; G.M = H; G.N = Tpad; G.K = H;
+        G.bias = W.bv; G.out16 = LN.vt16; G.ldc = mb.ldvt; G.col_map = LN.tok_vtcol; G.n_valid = T;
+        G.part_in = LN.partB; G.ln_eps = D.ln_eps; G.csum = W.cv; G.tok_lo = xb_lo;
+        {
+            ProfScope ps(PC_GEMM_VT, st, 2.0 * T * (double)H * H);
+            rc = launch_gemm_f16(EPI_VT_F, G, st);
+        }
+        if (rc) return rc;
+        AttnArgs A;
+        A.qk = LN.qk16; A.vt = LN.vt16; A.ctx = LN.ctx16; A.desc = LN.desc;
+        A.ld_qk = 2 * H; A.ld_vt = mb.ldvt; A.ld_ctx = H; A.n_heads = D.n_heads; A.cls_only = tail ? 1 : 0; A.q_compact = tail ? 1 : 0;
+        {
+            ProfScope ps(PC_ATTN, st, 0.0);
+            rc = launch_attention(A, S, mb.maxlen, st);
+        }
+        if (rc) return rc;
+        // attention.output.dense + residual.  The residual is LN(x_b) with the LayerNorm that produced this layer's input: the
+        // previous layer's output.LayerNorm, or the embedding LayerNorm.
+        memset(&G, 0, sizeof(G));
+        G.res_gamma = li == 0 ? e->eln_w : e->layers[li - 1].ln2w;
+        G.res_beta = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
+        G.res_hi = xb_hi; G.res_lo = xb_lo; G.part_in = LN.partB; G.ln_eps = D.ln_eps;
+        if (tail) {  // the compact (hi, lo, partials) rows of the [CLS] tokens (gathered in front of the Q | K GEMM)
+            G.res_hi = chi; G.res_lo = clo; G.part_in = cpt;
+        }
+        G.out16 = xa_hi; G.out_lo = xa_lo; G.part_out = LN.partA;
+        G.A = LN.ctx16; G.lda = H; G.B = W.wo; G.ldb = H; G.M = Mrows; G.N = H; G.K = H;
+        G.bias = W.bo; G.ldc = H;
+        {
+            ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
+            rc = launch_gemm_f16(EPI_RESLN, G, st);
+        }
+        if (rc) return rc;
+        // intermediate.dense + GELU
+        memset(&G, 0, sizeof(G));
+        G.A = xa_hi; G.lda = H; G.B = W.w1; G.ldb = H; G.M = Mrows; G.N = I; G.K = H;
+        G.bias = W.b1; G.out16 = LN.ffn16; G.ldc = I;
+        G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.csum = W.c1; G.tok_lo = xa_lo; G.n_split = n_split;
+        {
+            ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
+            rc = launch_gemm_f16(EPI_GELU_F, G, st);
+        }
+        if (rc) return rc;
+        // output.dense + residual
+        memset(&G, 0, sizeof(G));
+        G.A = LN.ffn16; G.lda = I; G.B = W.w2; G.ldb = I; G.M = Mrows; G.N = H; G.K = I;
+        G.bias = W.b2; G.ldc = H;
+        G.res_gamma = W.ln1w; G.res_beta = W.ln1b; G.res_hi = xa_hi; G.res_lo = xa_lo; G.out16 = xb_hi; G.out_lo = xb_lo;
+        G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.part_out = LN.partB;
+        {
+            ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
+            rc = launch_gemm_f16(EPI_RESLN, G, st);
+        }
+        if (rc) return rc;
+    }
+    encoder_output(e, LN, st, mb, nullptr, xb_hi, xb_lo, H, 0, nullptr, LN.partB, cls_tail ? 1 : 0);
+    return ANCE_OK;
+}
+
 int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *d_lens, const int32_t *h_lens, int hdr,
                 int64_t n, int L, int n_chunks, float *d_out, hipStream_t caller_st) {
     hipStream_t st = caller_st;
@@ -912,7 +1085,6 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
         return ANCE_E_INVALID;
     }
     const AnceEncoderDesc &D = e->d;
-    const int I = D.intermediate;
     int mb_index = 0;
     bool forked = false;
 
@@ -983,349 +1155,13 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
                 const int nb_seq = (S + 3) / 4, nb_pad = (Tpad - T + 255) / 256;
                 hipLaunchKernelGGL(pack_kernel, dim3(nb_seq > nb_pad ? nb_seq : nb_pad), dim3(256), 0, st, P);
             }
-            if (e->precise) {
-                // ---- fp32 path (precise32.h): plain sequence of fp32 kernels, every layer on every token ----
-                int rc = ANCE_OK;
-                {
-                    ProfScope pe(PC_EMBED, st);
-                    hipLaunchKernelGGL(embed32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
-                                       e->type0, D.vocab_size, D.max_position, LN.preB);
-                    hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, e->eln_w, e->eln_b, D.ln_eps,
-                                       LN.x32, (float *)nullptr);
-                }
-                for (int li = 0; li < D.n_layers && !rc; ++li) {
-                    const LayerW &W = e->layers[li];
-                    const bool last = li == D.n_layers - 1;
-                    {
-                        ProfScope ps(PC_GEMM_QK, st, 2.0 * T * (3.0 * H) * H);
-                        rc = launch_gemm32(P_EPI_BIAS, LN.x32, H, W.wqkv32, H, W.bqkv32, nullptr, 0, LN.qkv32, 3 * H, Tpad, 3 * H, H, st);
-                    }
-                    if (rc) break;
-                    {
-                        ProfScope ps(PC_ATTN, st);
-                        rc = launch_attention32(LN.qkv32, LN.ctx32, LN.seq_off, S, D.n_heads, st);
-                    }
-                    if (rc) break;
-                    {
-                        ProfScope ps(PC_GEMM_OUT, st, 2.0 * T * (double)H * H);
-                        rc = launch_gemm32(P_EPI_RES, LN.ctx32, H, W.wo32, H, W.bo, LN.x32, H, LN.preA, H, Tpad, H, H, st);
-                    }
-                    if (rc) break;
-                    {
-                        ProfScope ps(PC_LN, st);
-                        hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preA, Tpad, W.ln1w, W.ln1b, D.ln_eps, LN.xa32,
-                                           (float *)nullptr);
-                    }
-                    {
-                        ProfScope ps(PC_GEMM_FFN1, st, 2.0 * T * (double)I * H);
-                        rc = launch_gemm32(P_EPI_GELU, LN.xa32, H, W.w132, H, W.b1, nullptr, 0, LN.ffn32, I, Tpad, I, H, st);
-                    }
-                    if (rc) break;
-                    {
-                        ProfScope ps(PC_GEMM_FFN2, st, 2.0 * T * (double)I * H);
-                        rc = launch_gemm32(P_EPI_RES, LN.ffn32, I, W.w232, I, W.b2, LN.xa32, H, LN.preB, H, Tpad, H, I, st);
-                    }
-                    if (rc) break;
-                    {
-                        ProfScope ps(PC_LN, st);
-                        hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, W.ln2w, W.ln2b, D.ln_eps, LN.x32,
-                                           last ? LN.statsB : (float *)nullptr);
-                    }
-                }
-                if (rc) return rc;
-                {
-                    ProfScope ps(PC_HEAD, st);
-                    const LayerW &WL = e->layers[D.n_layers - 1];
-                    float *dst = d_out + (size_t)(r0 * n_chunks + gs) * HEAD_OUT;
-                    if (D.has_head) {
-                        hipLaunchKernelGGL(head_gemm_kernel, dim3((S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES, st, LN.preB,
-                                           (const _Float16 *)nullptr, (const _Float16 *)nullptr, H, 0, LN.statsB, (const float *)nullptr,
-                                           D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off, 0, S, e->head_w, e->head_b, dst);
-                        hipLaunchKernelGGL(head_ln_kernel, dim3((S + 3) / 4), dim3(256), 0, st, dst, S, e->norm_w, e->norm_b, e->faults);
-                    } else {
-                        hipLaunchKernelGGL(head_kernel, dim3(S), dim3(256), 0, st, LN.preB, (const _Float16 *)nullptr,
-                                           (const _Float16 *)nullptr, H, 0, LN.statsB, (const float *)nullptr, D.ln_eps, WL.ln2w, WL.ln2b,
-                                           LN.seq_off, 0, e->head_w, e->head_b, e->norm_w, e->norm_b, 0, dst, e->faults);
-                    }
-                }
-                gs = g;
-                continue;
-            }
-            if (e->split) {
-                // ---- split (fp32-grade) path: the default mode's schedule with pair operands and the fp32 attention ----
-                _Float16 *const xa = reinterpret_cast<_Float16 *>(LN.preA), *const xb = reinterpret_cast<_Float16 *>(LN.preB);
-                _Float16 *const ctxp = reinterpret_cast<_Float16 *>(LN.ctx32), *const ffnp = reinterpret_cast<_Float16 *>(LN.ffn32);
-                {
-                    ProfScope pe(PC_EMBED, st);
-                    hipLaunchKernelGGL(embed_split_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word,
-                                       e->pos, e->type0, D.vocab_size, D.max_position, xb, LN.partB, e->faults);
-                }
-                const bool cls_tail = e->cls_tail;
-                const int S_pad = (int)align_up((size_t)S, 256);
-                int rc = ANCE_OK;
-                for (int li = 0; li < D.n_layers && !rc; ++li) {
-                    const LayerW &W = e->layers[li];
-                    const bool tail = cls_tail && li == D.n_layers - 1;
-                    const int Mrows = tail ? S_pad : Tpad;
-                    const double Mwork = tail ? (double)S : (double)T;
-                    // layer 0 reads the embedding stream, stored times EMB_SCALE: its LayerNorm runs with eps EMB_SCALE^2 (embed_split_kernel)
-                    const float eps_b = li == 0 ? D.ln_eps * (EMB_SCALE * EMB_SCALE) : D.ln_eps;
-                    GemmArgs G;
-                    memset(&G, 0, sizeof(G));
-                    // Q | K | V projection -> fp32 (the LayerNorm that produces this layer's input is folded in)
-                    G.A = xb; G.lda = HP; G.B = W.wqkv_s; G.ldb = HP; G.M = Tpad; G.N = 3 * H; G.K = H;
-                    G.bias = W.bqkv_s; G.csum = W.cqkv_s; G.part_in = LN.partB; G.ln_eps = eps_b;
-                    G.out32 = LN.qkv32; G.ldc = 3 * H; G.wscale_inv = W.sc_s + 4; G.range_faults = e->faults;
-                    // CLS-only tail: the last layer's attention has ONE query per sequence.  K | V of every token, but Q of the [CLS]
-                    // rows only: their pair rows and slice partials are compacted first (they are also the residual of the
-                    // attention-output GEMM below) and projected by a second, small launch into the Q columns of rows 0 .. S_pad of
-                    // qkv32 -- row s = the query of sequence s (attention_split_kernel, cls_only).  A third of this GEMM's work in one
-                    // layer of twelve; every element is the same arithmetic as in the full launch.
-                    const bool tail_q = tail && e->split_attn;
-                    float *const cpt = reinterpret_cast<float *>(ffnp + (size_t)S_pad * HP);  // (the FFN buffer is dead here)
-                    if (tail) {
-                        ProfScope ps(PC_LN, st);
-                        hipLaunchKernelGGL(gather_cls_split_kernel, dim3(S_pad / 4), dim3(256), 0, st, xb, LN.partB, LN.seq_off, S, S_pad,
-                                           ffnp, cpt);
-                    }
-                    {
-                        ProfScope ps(PC_GEMM_QK, st, tail_q ? 2.0 * T * (2.0 * H) * H + 2.0 * S * (double)H * H : 2.0 * T * (3.0 * H) * H);
-                        if (tail_q) {
-                            G.B = W.wqkv_s + (size_t)H * HP; G.N = 2 * H; G.bias = W.bqkv_s + H; G.csum = W.cqkv_s + H;
-                            G.out32 = LN.qkv32 + H;
-                            rc = launch_gemm_f16(EPI_S_QKV, G, st);
-                            G.A = ffnp; G.part_in = cpt; G.M = S_pad;
-                            G.B = W.wqkv_s; G.N = H; G.bias = W.bqkv_s; G.csum = W.cqkv_s; G.out32 = LN.qkv32;
-                            if (!rc) rc = launch_gemm_f16(EPI_S_QKV, G, st);
-                        } else {
-                            rc = launch_gemm_f16(EPI_S_QKV, G, st);
-                        }
-                    }
-                    if (rc) break;
-                    {
-                        ProfScope ps(PC_ATTN, st);
-                        if (tail && S_pad > S)  // rows S..S_pad of the compact attention output feed the GEMM tile: keep them finite
-                            (void)hipMemsetAsync(ctxp + (size_t)S * HP, 0, (size_t)(S_pad - S) * HP * sizeof(_Float16), st);
-                        // (cls_only: one query per sequence, read from row s of the Q columns -- the tail's compact Q projection above)
-                        rc = e->split_attn ? launch_attention_split(LN.qkv32, ctxp, LN.desc, S, D.n_heads, maxlen, tail ? 1 : 0, st)
-                                           : ANCE_E_INVALID;
-                        if (rc == ANCE_E_INVALID)  // ANCE_SPLIT_ATTN=0: the fp32 vector-unit kernel (A/B)
-                            rc = launch_attention32(LN.qkv32, nullptr, LN.seq_off, S, D.n_heads, st, ctxp, tail ? 1 : 0);
-                    }
-                    if (rc) break;
-                    // attention.output.dense + residual LayerNorm(x_b), x_b = the previous layer's output (or the embeddings)
-                    memset(&G, 0, sizeof(G));
-                    G.res_gamma = li == 0 ? e->eln_w : e->layers[li - 1].ln2w;
-                    G.res_beta = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
-                    G.res_hi = xb; G.ldr = HP; G.part_in = LN.partB; G.ln_eps = eps_b; G.range_faults = e->faults;
-                    if (tail) {  // the compact pair rows + partials of the [CLS] tokens (gathered in front of the QKV GEMM)
-                        G.res_hi = ffnp; G.part_in = cpt;
-                    }
-                    G.A = ctxp; G.lda = HP; G.B = W.wo_s; G.ldb = HP; G.M = Mrows; G.N = H; G.K = H;
-                    G.bias = W.bo; G.out16 = xa; G.ldc = HP; G.part_out = LN.partA; G.wscale_inv = W.sc_s + 5;
-                    {
-                        ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
-                        rc = launch_gemm_f16(EPI_S_RESLN, G, st);
-                    }
-                    if (rc) break;
-                    // intermediate.dense + exact GELU (attention.output.LayerNorm folded in)
-                    memset(&G, 0, sizeof(G));
-                    G.A = xa; G.lda = HP; G.B = W.w1_s; G.ldb = HP; G.M = Mrows; G.N = I; G.K = H;
-                    G.bias = W.b1_s; G.csum = W.c1_s; G.part_in = LN.partA; G.ln_eps = D.ln_eps;
-                    G.out16 = ffnp; G.ldc = 2 * I; G.n_split = (e->n_split && (I / 256) % 2 == 0) ? 2 : 0; G.wscale_inv = W.sc_s + 6;
-                    G.range_faults = e->faults;
-                    {
-                        ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
-                        rc = launch_gemm_f16(EPI_S_GELU, G, st);
-                    }
-                    if (rc) break;
-                    // output.dense + residual LayerNorm(x_a)
-                    memset(&G, 0, sizeof(G));
-                    G.A = ffnp; G.lda = 2 * I; G.B = W.w2_s; G.ldb = 2 * I; G.M = Mrows; G.N = H; G.K = I;
-                    G.bias = W.b2; G.res_gamma = W.ln1w; G.res_beta = W.ln1b; G.res_hi = xa; G.ldr = HP;
-                    G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.out16 = xb; G.ldc = HP; G.part_out = LN.partB; G.wscale_inv = W.sc_s + 7;
-                    G.range_faults = e->faults;
-                    {
-                        ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
-                        rc = launch_gemm_f16(EPI_S_RESLN, G, st);
-                    }
-                }
-                if (rc) return rc;
-                {
-                    ProfScope ps(PC_HEAD, st);
-                    const LayerW &WL = e->layers[D.n_layers - 1];
-                    float *dst = d_out + (size_t)(r0 * n_chunks + gs) * HEAD_OUT;
-                    if (D.has_head) {
-                        hipLaunchKernelGGL(head_gemm_kernel, dim3((S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES, st,
-                                           (const float *)nullptr, (const _Float16 *)xb, (const _Float16 *)nullptr, HP, H,
-                                           (const float *)nullptr, (const float *)LN.partB, D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off,
-                                           cls_tail ? 1 : 0, S, e->head_w, e->head_b, dst);
-                        hipLaunchKernelGGL(head_ln_kernel, dim3((S + 3) / 4), dim3(256), 0, st, dst, S, e->norm_w, e->norm_b, e->faults);
-                    } else {
-                        hipLaunchKernelGGL(head_kernel, dim3(S), dim3(256), 0, st, (const float *)nullptr, (const _Float16 *)xb,
-                                           (const _Float16 *)nullptr, HP, H, (const float *)nullptr, (const float *)LN.partB,
-                                           D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off, cls_tail ? 1 : 0, e->head_w, e->head_b, e->norm_w,
-                                           e->norm_b, 0, dst, e->faults);
-                    }
-                }
-                gs = g;
-                continue;
-            }
-            const bool fold = e->ln_fold;
-            // folded LayerNorm: the two halves of the fp16 pair of a stream share the fp32 row's 3 KB
-            _Float16 *const xa_hi = LN.xa_hi(), *const xa_lo = xa_hi + (size_t)e->tcap * H;
-            _Float16 *const xb_hi = LN.xb_hi(), *const xb_lo = xb_hi + (size_t)e->tcap * H;
-            {
-            ProfScope pe(PC_EMBED, st);
-            if (fold)
-                hipLaunchKernelGGL(embed_fold_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
-                                   e->type0, D.vocab_size, D.max_position, xb_hi, xb_lo, LN.partB);
-            else
-                hipLaunchKernelGGL(embed_ln_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
-                                   e->type0, D.vocab_size, D.max_position, e->eln_w, e->eln_b, D.ln_eps, LN.preB, LN.h16, LN.statsB);
-            }
-            // Only the [CLS] row of the last layer reaches the head (model/models.py:49,152): after the
-            // last layer's K / V projections everything runs on the S compact [CLS] rows.
-            const bool cls_tail = e->cls_tail;
-            const int S_pad = (int)align_up((size_t)S, 256);
-            for (int li = 0; li < D.n_layers; ++li) {
-                const LayerW &W = e->layers[li];
-                const bool tail = cls_tail && li == D.n_layers - 1;
-                const int Mrows = tail ? S_pad : Tpad;   // rows of the post-attention GEMMs / LayerNorms
-                const double Mwork = tail ? (double)S : (double)T;
-                GemmArgs G;
-                memset(&G, 0, sizeof(G));
-                // Q | K projection
-                G.A = fold ? xb_hi : LN.h16; G.lda = H; G.B = W.wqk; G.ldb = H; G.M = Tpad; G.N = 2 * H; G.K = H;
-                G.bias = W.bqk; G.out16 = LN.qk16; G.ldc = 2 * H; G.scale_cols = H;
-                G.scale = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) and log2(e): the softmax runs on exp2
-                G.part_in = LN.partB; G.ln_eps = D.ln_eps; G.csum = W.cqk; G.tok_lo = fold ? xb_lo : nullptr;
-                // CLS-only tail (folded form): K of every token, Q of the compact [CLS] rows only -- row s of the Q columns is the query
-                // of sequence s (attention_kernel, cls_only); the same arithmetic per element as the full launch (split mode: above)
-                const bool tail_q = tail && fold;
-                _Float16 *const chi = LN.ffn16, *const clo = chi + (size_t)S_pad * H;  // (the FFN buffer is dead here)
-                float *const cpt = reinterpret_cast<float *>(clo + (size_t)S_pad * H);
-                if (tail_q) {
-                    ProfScope ps(PC_LN, st);
-                    hipLaunchKernelGGL(gather_cls_fold_kernel, dim3(S_pad / 4), dim3(256), 0, st, xb_hi, xb_lo, LN.partB, LN.seq_off,
-                                       S, S_pad, chi, clo, cpt);
-                }
-                int rc;
-                {
-                    ProfScope ps(PC_GEMM_QK, st, tail_q ? 2.0 * T * (double)H * H + 2.0 * S * (double)H * H : 2.0 * T * (2.0 * H) * H);
-                    if (tail_q) {
-                        G.B = W.wqk + (size_t)H * H; G.N = H; G.bias = W.bqk + H; G.csum = W.cqk + H; G.out16 = LN.qk16 + H; G.scale_cols = 0;
-                        rc = launch_gemm_f16(EPI_QK_F, G, st);
-                        G.A = chi; G.tok_lo = clo; G.part_in = cpt; G.M = S_pad;
-                        G.B = W.wqk; G.bias = W.bqk; G.csum = W.cqk; G.out16 = LN.qk16; G.scale_cols = H;
-                        if (!rc) rc = launch_gemm_f16(EPI_QK_F, G, st);
-                    } else {
-                        rc = launch_gemm_f16(fold ? EPI_QK_F : EPI_QK, G, st);
-                    }
-                }
-                if (rc) return rc;
-                // V^T = Wv h^T
-                memset(&G, 0, sizeof(G));
-                G.A = W.wv; G.lda = H; G.B = fold ? xb_hi : LN.h16; G.ldb = H; G.M = H; G.N = Tpad; G.K = H;
-                G.bias = W.bv; G.out16 = LN.vt16; G.ldc = ldvt; G.col_map = LN.tok_vtcol; G.n_valid = T;
-                G.part_in = LN.partB; G.ln_eps = D.ln_eps; G.csum = W.cv; G.tok_lo = fold ? xb_lo : nullptr;
-                {
-                    ProfScope ps(PC_GEMM_VT, st, 2.0 * T * (double)H * H);
-                    rc = launch_gemm_f16(fold ? EPI_VT_F : EPI_VT, G, st);
-                }
-                if (rc) return rc;
-                AttnArgs A;
-                A.qk = LN.qk16; A.vt = LN.vt16; A.ctx = LN.ctx16; A.desc = LN.desc;
-                A.ld_qk = 2 * H; A.ld_vt = ldvt; A.ld_ctx = H; A.n_heads = D.n_heads; A.cls_only = tail ? 1 : 0; A.q_compact = tail_q ? 1 : 0; A.coalesced = e->attn_coal ? 1 : 0;
-                {
-                    ProfScope ps(PC_ATTN, st, 0.0);
-                    rc = launch_attention(A, S, maxlen, st);
-                }
-                if (rc) return rc;
-                // attention.output.dense + residual.  The residual is LN(preB) with the LayerNorm that produced
-                // this layer's input: the previous layer's output.LayerNorm, or the embedding LayerNorm.
-                const float *rg = li == 0 ? e->eln_w : e->layers[li - 1].ln2w;
-                const float *rb = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
-                memset(&G, 0, sizeof(G));
-                G.res_stats = LN.statsB; G.res_gamma = rg; G.res_beta = rb;
-                if (fold) {
-                    G.res_hi = xb_hi; G.res_lo = xb_lo; G.part_in = LN.partB; G.ln_eps = D.ln_eps;
-                    if (tail) {  // the compact (hi, lo, partials) rows of the [CLS] tokens (gathered in front of the Q | K GEMM)
-                        G.res_hi = chi; G.res_lo = clo; G.part_in = cpt;
-                    }
-                    G.out16 = xa_hi; G.out_lo = xa_lo; G.part_out = LN.partA;
-                } else {
-                    G.res32 = LN.preB;
-                    if (tail) {  // compact residual rows (already normalised), parked in the (currently dead) FFN buffer
-                        float *rc = reinterpret_cast<float *>(LN.ffn16);
-                        ProfScope ps(PC_LN, st);
-                        hipLaunchKernelGGL(gather_cls_kernel, dim3(S_pad / 4), dim3(256), 0, st, LN.preB, LN.statsB, rg, rb, LN.seq_off,
-                                           S, S_pad, rc);
-                        G.res32 = rc; G.res_stats = nullptr;
-                    }
-                    G.out32 = LN.preA;
-                }
-                G.A = LN.ctx16; G.lda = H; G.B = W.wo; G.ldb = H; G.M = Mrows; G.N = H; G.K = H;
-                G.bias = W.bo; G.ldc = H;
-                {
-                    ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
-                    rc = launch_gemm_f16(fold ? EPI_RESLN : EPI_RES32, G, st);
-                }
-                if (rc) return rc;
-                if (!fold) {
-                    ProfScope ps(PC_LN, st);
-                    hipLaunchKernelGGL(ln_kernel, dim3(Mrows / 4), dim3(256), 0, st, LN.preA, Mrows, W.ln1w, W.ln1b, D.ln_eps,
-                                       LN.h16, LN.statsA);
-                }
-                // intermediate.dense + GELU
-                memset(&G, 0, sizeof(G));
-                G.A = fold ? xa_hi : LN.h16; G.lda = H; G.B = W.w1; G.ldb = H; G.M = Mrows; G.N = I; G.K = H;
-                G.bias = W.b1; G.out16 = LN.ffn16; G.ldc = I;
-                G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.csum = W.c1; G.tok_lo = fold ? xa_lo : nullptr;
-                G.n_split = (fold && e->n_split && (I / 256) % 2 == 0) ? 2 : 0;
-                {
-                    ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
-                    rc = launch_gemm_f16(fold ? EPI_GELU_F : EPI_GELU, G, st);
-                }
-                if (rc) return rc;
-                // output.dense + residual
-                memset(&G, 0, sizeof(G));
-                G.A = LN.ffn16; G.lda = I; G.B = W.w2; G.ldb = I; G.M = Mrows; G.N = H; G.K = I;
-                G.bias = W.b2; G.ldc = H;
-                G.res_stats = LN.statsA; G.res_gamma = W.ln1w; G.res_beta = W.ln1b;
-                if (fold) {
-                    G.res_hi = xa_hi; G.res_lo = xa_lo; G.out16 = xb_hi; G.out_lo = xb_lo;
-                    G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.part_out = LN.partB;
-                } else {
-                    G.res32 = LN.preA; G.out32 = LN.preB;
-                }
-                {
-                    ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
-                    rc = launch_gemm_f16(fold ? EPI_RESLN : EPI_RES32, G, st);
-                }
-                if (rc) return rc;
-                if (!fold) {
-                    ProfScope ps(PC_LN, st);
-                    hipLaunchKernelGGL(ln_kernel, dim3(Mrows / 4), dim3(256), 0, st, LN.preB, Mrows, W.ln2w, W.ln2b, D.ln_eps,
-                                       LN.h16, LN.statsB);
-                }
-            }
-            {
-                ProfScope ps(PC_HEAD, st);
-                const LayerW &WL = e->layers[D.n_layers - 1];
-                float *dst = d_out + (size_t)(r0 * n_chunks + gs) * HEAD_OUT;
-                const _Float16 *hh = fold ? xb_hi : nullptr, *hl = fold ? xb_lo : nullptr;
-                if (D.has_head && e->head_mfma) {
-                    hipLaunchKernelGGL(head_gemm_kernel, dim3((S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES, st, LN.preB, hh,
-                                       hl, H, 0, LN.statsB, fold ? LN.partB : (const float *)nullptr, D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off,
-                                       cls_tail ? 1 : 0, S, e->head_w, e->head_b, dst);
-                    hipLaunchKernelGGL(head_ln_kernel, dim3((S + 3) / 4), dim3(256), 0, st, dst, S, e->norm_w, e->norm_b, e->faults);
-                } else {
-                    hipLaunchKernelGGL(head_kernel, dim3(S), dim3(256), 0, st, LN.preB, hh, hl, H, 0, LN.statsB,
-                                       fold ? LN.partB : (const float *)nullptr, D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off,
-                                       cls_tail ? 1 : 0, e->head_w, e->head_b, e->norm_w, e->norm_b, D.has_head, dst, e->faults);
-                }
-            }
+            MicroBatch mb;
+            mb.S = S; mb.T = T; mb.Tpad = Tpad; mb.ldvt = ldvt; mb.maxlen = maxlen;
+            mb.out = d_out + (size_t)(r0 * n_chunks + gs) * HEAD_OUT;
+            const int rc = e->mode == ANCE_PRECISION_FP32    ? forward_fp32(e, LN, st, mb)
+                           : e->mode == ANCE_PRECISION_SPLIT ? forward_split(e, LN, st, mb)
+                                                             : forward_fp16(e, LN, st, mb);
+            if (rc) return rc;
             gs = g;
         }
         if (forked && r0 + FETCH_CHUNK < n && !h_lens) {
@@ -1385,20 +1221,7 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
     {
         const char *ct = getenv("ANCE_CLS_TAIL");
         e->cls_tail = !(ct && ct[0] == '0');
-        const char *lf = getenv("ANCE_LN_FOLD");
-        e->ln_fold = !(lf && lf[0] == '0');
-        const char *hm = getenv("ANCE_HEAD_MFMA");
-        e->head_mfma = !(hm && hm[0] == '0');
-        const char *ac = getenv("ANCE_ATTN_COAL");
-        e->attn_coal = !(ac && ac[0] == '0');
-        const int mode = resolve_precision(desc);
-        e->precise = mode == ANCE_PRECISION_FP32;
-        e->split = mode == ANCE_PRECISION_SPLIT;
-        if (e->precise || e->split) e->ln_fold = false;  // these paths take the plain biases and LayerNorm parameters
-        const char *nsp = getenv("ANCE_GEMM_NSPLIT");
-        e->n_split = !(nsp && nsp[0] == '0');
-        const char *sa = getenv("ANCE_SPLIT_ATTN");
-        e->split_attn = !(sa && sa[0] == '0');
+        e->mode = resolve_precision(desc);
         const char *ns = getenv("ANCE_ENCODER_STREAMS");
         e->n_lanes = (ns && ns[0] >= '1' && ns[0] <= '0' + MAX_LANES) ? ns[0] - '0' : 2;
     }
@@ -1436,13 +1259,20 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
     cpy32(w[2], e->type0, H, st);
     cpy32(w[3], e->eln_w, H, st);
     cpy32(w[4], e->eln_b, H, st);
+    // each mode prepares only the weights its forward reads (the arena layout is the same for all three: layout_weights)
     for (int i = 0; i < desc->n_layers; ++i) {
         const void *const *p = w + 5 + 16 * i;
         LayerW &L = e->layers[i];
-        if (e->ln_fold) {
-            // the LayerNorm that produces this layer's input: embeddings.LayerNorm or the previous output.LayerNorm
-            const float *gin = (const float *)(i == 0 ? w[3] : w[5 + 16 * (i - 1) + 14]);
-            const float *bin = (const float *)(i == 0 ? w[4] : w[5 + 16 * (i - 1) + 15]);
+        // the LayerNorm that produces this layer's input: embeddings.LayerNorm or the previous output.LayerNorm
+        const float *gin = (const float *)(i == 0 ? w[3] : w[5 + 16 * (i - 1) + 14]);
+        const float *bin = (const float *)(i == 0 ? w[4] : w[5 + 16 * (i - 1) + 15]);
+        cpy32(p[7], L.bo, H, st);
+        cpy32(p[8], L.ln1w, H, st);
+        cpy32(p[9], L.ln1b, H, st);
+        cpy32(p[13], L.b2, H, st);
+        cpy32(p[14], L.ln2w, H, st);
+        cpy32(p[15], L.ln2b, H, st);
+        if (e->mode == ANCE_PRECISION_FP16) {
             auto foldw = [&](const void *W, const void *b, const float *g, const float *be, int N, _Float16 *W16, float *cs,
                              float *bo) {
                 hipLaunchKernelGGL(fold_weight_kernel, dim3((N + 3) / 4), dim3(256), 0, st, (const float *)W, (const float *)b, g,
@@ -1452,23 +1282,9 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
             foldw(p[2], p[3], gin, bin, H, L.wqk + (size_t)H * H, L.cqk + H, L.bqk + H);            // key
             foldw(p[4], p[5], gin, bin, H, L.wv, L.cv, L.bv);                                        // value
             foldw(p[10], p[11], (const float *)p[8], (const float *)p[9], (int)I, L.w1, L.c1, L.b1);  // intermediate.dense
-        } else {
-            cvt16(p[0], L.wqk, (size_t)H * H, st);                 // query
-            cvt16(p[2], L.wqk + (size_t)H * H, (size_t)H * H, st);  // key
-            cpy32(p[1], L.bqk, H, st);
-            cpy32(p[3], L.bqk + H, H, st);
-            cvt16(p[4], L.wv, (size_t)H * H, st);
-            cpy32(p[5], L.bv, H, st);
-            cvt16(p[10], L.w1, I * H, st);
-            cpy32(p[11], L.b1, I, st);
-        }
-        cvt16(p[6], L.wo, (size_t)H * H, st);
-        cpy32(p[7], L.bo, H, st);
-        cpy32(p[8], L.ln1w, H, st);
-        cpy32(p[9], L.ln1b, H, st);
-        if (e->split) {
-            const float *gin = (const float *)(i == 0 ? w[3] : w[5 + 16 * (i - 1) + 14]);
-            const float *bin = (const float *)(i == 0 ? w[4] : w[5 + 16 * (i - 1) + 15]);
+            cvt16(p[6], L.wo, (size_t)H * H, st);
+            cvt16(p[12], L.w2, (size_t)H * I, st);
+        } else if (e->mode == ANCE_PRECISION_SPLIT) {
             unsigned *slots = reinterpret_cast<unsigned *>(L.sc_s);
             (void)hipMemsetAsync(L.sc_s, 0, 4 * sizeof(float), st);
             auto mx = [&](const void *W, const float *g, int N, int K, int slot) {
@@ -1491,8 +1307,7 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
             sw(p[6], nullptr, nullptr, nullptr, H, H, 1, L.wo_s, nullptr, nullptr);                                      // attention.output.dense
             sw(p[10], p[11], (const float *)p[8], (const float *)p[9], (int)I, H, 2, L.w1_s, L.c1_s, L.b1_s);            // intermediate.dense
             sw(p[12], nullptr, nullptr, nullptr, H, (int)I, 3, L.w2_s, nullptr, nullptr);                                // output.dense
-        }
-        if (e->precise) {
+        } else {
             cpy32(p[0], L.wqkv32, (size_t)H * H, st);
             cpy32(p[2], L.wqkv32 + (size_t)H * H, (size_t)H * H, st);
             cpy32(p[4], L.wqkv32 + (size_t)2 * H * H, (size_t)H * H, st);
@@ -1501,12 +1316,9 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
             cpy32(p[5], L.bqkv32 + 2 * H, H, st);
             cpy32(p[6], L.wo32, (size_t)H * H, st);
             cpy32(p[10], L.w132, I * H, st);
+            cpy32(p[11], L.b1, I, st);
             cpy32(p[12], L.w232, (size_t)H * I, st);
         }
-        cvt16(p[12], L.w2, (size_t)H * I, st);
-        cpy32(p[13], L.b2, H, st);
-        cpy32(p[14], L.ln2w, H, st);
-        cpy32(p[15], L.ln2b, H, st);
     }
     if (desc->has_head) {
         const void *const *p = w + 5 + 16 * desc->n_layers;
@@ -1539,7 +1351,7 @@ extern "C" void ance_encoder_destroy(AnceEncoder *enc) {
 
 extern "C" int ance_encoder_precision(const AnceEncoder *enc) {
     if (!enc) return ANCE_E_INVALID;
-    return enc->precise ? ANCE_PRECISION_FP32 : enc->split ? ANCE_PRECISION_SPLIT : ANCE_PRECISION_FP16;
+    return enc->mode;
 }
 
 extern "C" int ance_encoder_range_faults(AnceEncoder *enc, uint32_t *h_out, int reset, void *stream) {

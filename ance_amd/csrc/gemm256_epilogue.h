@@ -101,12 +101,6 @@ __device__ __forceinline__ bool epb_stats(const GemmArgs &G, float *smem_f, int 
     return __builtin_amdgcn_readfirstlane(__syncthreads_or(wide)) != 0;  // (readfirstlane: the compiler must know it is uniform)
 }
 
-#ifdef ANCE_MEASURE
-// measurement library only (WRONG results): bit 0 -- the RESLN epilogue reads its residual rows from rows 0..31 of the tile's
-// slice (cache-resident), bit 1 -- it writes its output rows there: how much of the epilogue is its HBM traffic
-__device__ int g_res_ablate = 0;
-#endif
-
 template <int EPI_, bool WAVE_SYNC = false>
 __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc)[2][4], float *smem_f, int m0, int n0,
                                                  int w, int l, unsigned long long *pass_stamps = nullptr) {
@@ -117,7 +111,7 @@ __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc
     const int mw0 = m0 + wm * 128, nw0 = n0 + wn * 64;
     constexpr bool FOLD = EPI_ == EPI_QK_F || EPI_ == EPI_GELU_F || EPI_ == EPI_VT_F;
     constexpr int EPI = EPI_ == EPI_QK_F ? EPI_QK : EPI_ == EPI_GELU_F ? EPI_GELU : EPI_ == EPI_VT_F ? EPI_VT : EPI_;
-    if constexpr (EPI == EPI_VT) {
+    if constexpr (EPI == EPI_VT) {  // (EPI_VT_F only)
         // Output rows are A-matrix rows m (features, bias per row); columns are tokens n scattered
         // through col_map (per-sequence 8-aligned key columns, so 16-byte stores are impossible in
         // general).  Slab [64 m][64 n] halves per pass; on read-back a lane owns ONE token column and
@@ -131,36 +125,28 @@ __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             epi_sync<WAVE_SYNC>();
-            float bias[2], cs[2] = {0.f, 0.f};  // per-lane row (feature) constants of the two 32-row blocks of this pass
+            float bias[2], cs[2];  // per-lane row (feature) constants of the two 32-row blocks of this pass
 #pragma unroll
             for (int yy = 0; yy < 2; ++yy) {
-                if constexpr (FOLD) {
-                    bias[yy] = smem_f[EPB_OFF + EPB_VEC + wm * 128 + (2 * p + yy) * 32 + i];
-                    cs[yy] = smem_f[EPB_OFF + EPB_VEC + 256 + wm * 128 + (2 * p + yy) * 32 + i];
-                } else {
-                    bias[yy] = G.bias[mw0 + (2 * p + yy) * 32 + i];
-                }
+                bias[yy] = smem_f[EPB_OFF + EPB_VEC + wm * 128 + (2 * p + yy) * 32 + i];
+                cs[yy] = smem_f[EPB_OFF + EPB_VEC + 256 + wm * 128 + (2 * p + yy) * 32 + i];
             }
 #pragma unroll
             for (int x = 0; x < 2; ++x)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    // FOLD: tokens are the columns -- (mean, rstd) of 4 consecutive tokens = 32 bytes of LDS, read once per
-                    // pass and column quad; r (acc - mu c) + b = acc r + (b - (mu r) c)
-                    f32x4 r4 = {1.f, 1.f, 1.f, 1.f}, mr4 = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (FOLD) {
-                        const float *sp = smem_f + EPB_OFF + EPB_STATS + 2 * (wn * 64 + x * 32 + 8 * rq + 4 * g);
-                        const f32x4 s01 = *reinterpret_cast<const f32x4 *>(sp);
-                        const f32x4 s23 = *reinterpret_cast<const f32x4 *>(sp + 4);
-                        r4 = f32x4{s01[1], s01[3], s23[1], s23[3]};
-                        mr4 = f32x4{s01[0] * s01[1], s01[2] * s01[3], s23[0] * s23[1], s23[2] * s23[3]};
-                    }
+                    // tokens are the columns -- (mean, rstd) of 4 consecutive tokens = 32 bytes of LDS, read once per pass and
+                    // column quad; r (acc - mu c) + b = acc r + (b - (mu r) c)
+                    const float *sp = smem_f + EPB_OFF + EPB_STATS + 2 * (wn * 64 + x * 32 + 8 * rq + 4 * g);
+                    const f32x4 s01 = *reinterpret_cast<const f32x4 *>(sp);
+                    const f32x4 s23 = *reinterpret_cast<const f32x4 *>(sp + 4);
+                    const f32x4 r4 = f32x4{s01[1], s01[3], s23[1], s23[3]};
+                    const f32x4 mr4 = f32x4{s01[0] * s01[1], s01[2] * s01[3], s23[0] * s23[1], s23[2] * s23[3]};
 #pragma unroll
                     for (int yy = 0; yy < 2; ++yy) {
                         const f32x16 &a = acc[x][2 * p + yy];
                         f32x4 t = f32x4{a[4 * rq], a[4 * rq + 1], a[4 * rq + 2], a[4 * rq + 3]};
-                        if constexpr (FOLD) t = t * r4 + (bias[yy] - mr4 * cs[yy]);
-                        else t = t + bias[yy];
+                        t = t * r4 + (bias[yy] - mr4 * cs[yy]);
                         *reinterpret_cast<f16x4 *>(slab + (yy * 32 + i) * LS + x * 32 + 8 * rq + 4 * g) =
                             f16x4{(_Float16)t[0], (_Float16)t[1], (_Float16)t[2], (_Float16)t[3]};
                     }
@@ -178,30 +164,14 @@ __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc
         constexpr int LS = 68;
         const int c4 = l & 15;
         const f32x4 bias = *reinterpret_cast<const f32x4 *>(G.bias + nw0 + c4 * 4);
-        const bool lazy_ln = G.res_stats != nullptr;  // uniform: residual = LayerNorm(res32 row) recomputed here
-        f32x4 lng = {0, 0, 0, 0}, lnb = {0, 0, 0, 0};
-        if (lazy_ln) {
-            lng = *reinterpret_cast<const f32x4 *>(G.res_gamma + nw0 + c4 * 4);
-            lnb = *reinterpret_cast<const f32x4 *>(G.res_beta + nw0 + c4 * 4);
-        }
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
             // residual rows of this pass: issued first so their latency hides behind the LDS round trip
             f32x4 res[8];
-            float mean[8], rstd[8];
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
                 const int rr = it * 4 + (l >> 4);
-                const size_t row = (size_t)(mw0 + y * 32 + rr);
-                res[it] = *reinterpret_cast<const f32x4 *>(G.res32 + row * G.ldc + nw0 + c4 * 4);
-                if (lazy_ln) {
-                    mean[it] = G.res_stats[2 * row];
-                    rstd[it] = G.res_stats[2 * row + 1];
-                }
-            }
-            if (lazy_ln) {
-#pragma unroll
-                for (int it = 0; it < 8; ++it) res[it] = ln_apply4(res[it], mean[it], rstd[it], lng, lnb);
+                res[it] = *reinterpret_cast<const f32x4 *>(G.res32 + (size_t)(mw0 + y * 32 + rr) * G.ldc + nw0 + c4 * 4);
             }
             epi_sync<WAVE_SYNC>();
 #pragma unroll
@@ -241,11 +211,7 @@ __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
                 const int rr = it * 4 + (l >> 4);
-#ifdef ANCE_MEASURE
-                const size_t row = (g_res_ablate & 1) ? (size_t)rr : (size_t)(mw0 + y * 32 + rr);
-#else
                 const size_t row = (size_t)(mw0 + y * 32 + rr);
-#endif
                 rh[it] = *reinterpret_cast<const f16x4 *>(G.res_hi + row * G.ldc + nw0 + c4 * 4);
                 rl[it] = *reinterpret_cast<const f16x4 *>(G.res_lo + row * G.ldc + nw0 + c4 * 4);
                 mean[it] = pb[EPB_STATS + 2 * (wm * 128 + y * 32 + rr)];
@@ -263,13 +229,8 @@ __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc
             epi_sync<WAVE_SYNC>();
             // running pointers (a row step is 4 rows): 64-bit address arithmetic per store was a fifth of this loop
             const size_t row0 = (size_t)(mw0 + y * 32 + (l >> 4));
-#ifdef ANCE_MEASURE
-            const size_t orow0 = (g_res_ablate & 2) ? (size_t)(l >> 4) : row0;
-#else
-            const size_t orow0 = row0;
-#endif
-            _Float16 *ph = G.out16 + orow0 * G.ldc + nw0 + c4 * 4;
-            _Float16 *pl = G.out_lo + orow0 * G.ldc + nw0 + c4 * 4;
+            _Float16 *ph = G.out16 + row0 * G.ldc + nw0 + c4 * 4;
+            _Float16 *pl = G.out_lo + row0 * G.ldc + nw0 + c4 * 4;
             const size_t rstep = (size_t)4 * G.ldc;
             f32x4 vv[8];
 #pragma unroll
@@ -409,9 +370,6 @@ constexpr float GELU_Q[10] = {-1.0f, -1.627907395362854f, -0.918441653251648f, -
                               1.1468856428109575e-05f};
 __device__ __forceinline__ float gelu_exact(float x) {
 #pragma clang fp contract(off)
-#ifdef ANCE_GELU_ERFF  // A/B builds only (make variant NAME=erff DEFS=-DANCE_GELU_ERFF): round 4's library erff
-    return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
-#endif
     const float z = __builtin_fminf(__builtin_fabsf(x) * 0.70710678118654752440f, 6.6f);
     float q = GELU_Q[9];
 #pragma unroll
@@ -427,9 +385,6 @@ __device__ __forceinline__ float gelu_exact(float x) {
 __constant__ float kGeluExactQ[10] = {GELU_Q[0], GELU_Q[1], GELU_Q[2], GELU_Q[3], GELU_Q[4], GELU_Q[5], GELU_Q[6], GELU_Q[7], GELU_Q[8], GELU_Q[9]};
 __device__ __forceinline__ f32x4 gelu_exact4(const f32x4 x) {
 #pragma clang fp contract(off)
-#ifdef ANCE_GELU_ERFF
-    return f32x4{gelu_exact(x[0]), gelu_exact(x[1]), gelu_exact(x[2]), gelu_exact(x[3])};
-#endif
     f32x4 out;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -448,19 +403,11 @@ __device__ __forceinline__ f32x4 gelu_exact4(const f32x4 x) {
 // Output stores of the split epilogues are NON-TEMPORAL: the outputs of a launch (0.6-1.6 GB) are consumed by the next kernel and
 // only pass through the 4 MB L2s on their way out, where they evict the operand panels the main loops re-read.  Same-box A/B
 // (profiles/r05_ab_nt_store.jsonl, three alternations): FFN1 -0.7 %, the attention that follows the QKV GEMM -2.5 %, step +0.3 %.
-// (ANCE_EPI_PLAIN_STORE: A/B builds with ordinary stores.)
 // The pair-row epilogues move 8 columns per lane (16-byte hi and 16-byte lo accesses): an epilogue is bound by the NUMBER of
 // vector-memory instructions its eight waves push through the CU's one address unit (~16 cycles each whatever their width) -- the
 // fp32 store epilogue of QKV (32 dwordx4 stores per wave and tile) measured 4 us, the GELU pair epilogue with 8-byte accesses (64
 // stores) 8.4 us, RESLN (64 loads + 64 stores + 32 statistics stores) 13.5 us.  Round 6: half as many, twice as wide.
 __device__ __forceinline__ f16x8 cat_f16x4(const f16x4 a, const f16x4 b) { return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
-#ifndef ANCE_EPI_PLAIN_STORE
-__device__ __forceinline__ void epi_pair_store_nt(const f32x4 v, _Float16 *row, int W, int n) {
-    f16x4 h, r;
-    pair_split4(v, &h, &r);
-    __builtin_nontemporal_store(h, reinterpret_cast<f16x4 *>(row + pair_hi_col(n, W)));
-    __builtin_nontemporal_store(r, reinterpret_cast<f16x4 *>(row + pair_lo_col(n, W)));
-}
 // columns n .. n + 7 (n a multiple of 8: inside one 32-column block)
 __device__ __forceinline__ void epi_pair_store8_nt(const f32x4 va, const f32x4 vb, _Float16 *row, int W, int n) {
     f16x4 ha, ra, hb, rb;
@@ -469,21 +416,6 @@ __device__ __forceinline__ void epi_pair_store8_nt(const f32x4 va, const f32x4 v
     __builtin_nontemporal_store(cat_f16x4(ha, hb), reinterpret_cast<f16x8 *>(row + pair_hi_col(n, W)));
     __builtin_nontemporal_store(cat_f16x4(ra, rb), reinterpret_cast<f16x8 *>(row + pair_lo_col(n, W)));
 }
-#define EPI_PAIR_STORE(v, row, W, n) epi_pair_store_nt(v, row, W, n)
-#define EPI_PAIR_STORE8(va, vb, row, W, n) epi_pair_store8_nt(va, vb, row, W, n)
-#define EPI_F32_STORE(p, v) __builtin_nontemporal_store(v, p)
-#else
-__device__ __forceinline__ void epi_pair_store8(const f32x4 va, const f32x4 vb, _Float16 *row, int W, int n) {
-    f16x4 ha, ra, hb, rb;
-    pair_split4(va, &ha, &ra);
-    pair_split4(vb, &hb, &rb);
-    *reinterpret_cast<f16x8 *>(row + pair_hi_col(n, W)) = cat_f16x4(ha, hb);
-    *reinterpret_cast<f16x8 *>(row + pair_lo_col(n, W)) = cat_f16x4(ra, rb);
-}
-#define EPI_PAIR_STORE(v, row, W, n) pair_store4(v, row, W, n)
-#define EPI_PAIR_STORE8(va, vb, row, W, n) epi_pair_store8(va, vb, row, W, n)
-#define EPI_F32_STORE(p, v) (*(p) = (v))
-#endif
 
 // slice statistics of the pair epilogues: a lane holds 8 columns of a row, 4 lanes a 32-column block, 8 lanes the 64-column slice
 __device__ __forceinline__ float quad_sum(float x) {  // every lane of the quad ends with the same bits
@@ -583,8 +515,8 @@ __device__ __forceinline__ void gemm256_epilogue_split(const GemmArgs &G, f32x16
                 range_track4(a, &vmax);  // (QKV: the attention splits K and V into pairs while it stages them)
                 vv[it][h] = a;
             }
-            if constexpr (EPI == EPI_S_QKV) EPI_F32_STORE(reinterpret_cast<f32x4 *>(G.out32 + row * G.ldc + nc), vv[it][0]);
-            else EPI_PAIR_STORE8(vv[it][0], vv[it][NV - 1], G.out16 + row * G.ldc, G.N, nc);
+            if constexpr (EPI == EPI_S_QKV) __builtin_nontemporal_store(vv[it][0], reinterpret_cast<f32x4 *>(G.out32 + row * G.ldc + nc));
+            else epi_pair_store8_nt(vv[it][0], vv[it][NV - 1], G.out16 + row * G.ldc, G.N, nc);
         }
         if constexpr (EPI == EPI_S_RESLN) {
             // (mean, M2) of the 64 columns of every row: lane sums of 8 columns, quad sums (32 columns), the two quads of the row
@@ -670,8 +602,8 @@ __device__ __forceinline__ void gemm256_epilogue_split32(const GemmArgs &G, f32x
                 range_track4(a, &vmax);
                 vv[h] = a;
             }
-            if constexpr (EPI == EPI_S_QKV) EPI_F32_STORE(reinterpret_cast<f32x4 *>(G.out32 + row * G.ldc + n), vv[0]);
-            else EPI_PAIR_STORE8(vv[0], vv[NV - 1], G.out16 + row * G.ldc, G.N, n);
+            if constexpr (EPI == EPI_S_QKV) __builtin_nontemporal_store(vv[0], reinterpret_cast<f32x4 *>(G.out32 + row * G.ldc + n));
+            else epi_pair_store8_nt(vv[0], vv[NV - 1], G.out16 + row * G.ldc, G.N, n);
         }
     }
     range_report(vmax, G.range_faults);

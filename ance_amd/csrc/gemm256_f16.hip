@@ -5,7 +5,8 @@
 //   EPI_QK     out16 = (acc + bias[n]) * (n < scale_cols ? scale : 1)      Q | K projection, Q/8
 //   EPI_GELU   out16 = gelu_erf(acc + bias[n])                            intermediate.dense
 //   EPI_RES32  out32 = acc + bias[n] + res32[m][n]                        attention.output.dense / output.dense
-//   EPI_VT     out16[m][col[n]] = acc + bias[m]   (n < n_valid)           V^T = Wv . h^T, key-contiguous
+//   (ance_debug_gemm reaches the main loop through these three; the encoder runs the folded-LayerNorm forms EPI_*_F /
+//   EPI_RESLN of gemm_f16.h and the split GEMM below)
 //
 // Why this tile: a 128 x 128 tile has 64 FLOP per staged byte, i.e. 39 TB/s of L2 traffic at the
 // 2.5 PFLOP/s MFMA rate -- more than the 34.5 TB/s the eight L2s deliver -- so it is L2-bound by
@@ -22,9 +23,6 @@
 // Staging is direct-to-LDS (global_load_lds_dwordx4): the LDS image is lane-linear, so the XOR
 // swizzle is applied to the per-lane SOURCE address.  Measured alternatives on MI355X are listed in
 // DESIGN.md section 9 (register staging, a BK=32 ring, LDS-DMA placements, staggered starts, ...).
-// Template ABLATE compiles the measurement switches of ance_debug_gemm in (the two-phase loop the
-// pipeline replaced, with or without loads / MFMA; the pipeline's own ablations); the product
-// instance has none of them.
 #include "common.h"
 #include "gemm_f16.h"
 #include "gemm256_epilogue.h"
@@ -41,103 +39,8 @@ constexpr int STAGE_HALVES = 2 * OPER_HALVES;   // A-rows tile + B-rows tile (64
 constexpr int G256_THREADS = 512;
 constexpr size_t G256_LDS_BYTES = (size_t)2 * STAGE_HALVES * sizeof(_Float16);  // 128 KiB
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
-
-// Two-phase loop (one barrier + full vmcnt drain per K-tile): the structure the ping-pong pipeline
-// replaced.  Kept only behind ance_debug_gemm's ablation switches (1: no loads after the first tile,
-// 2: no MFMA, 4: every block loads tile (0,0), 8: none -- plain A/B reference).
-__device__ __forceinline__ void two_phase_loop(const GemmArgs &G, f32x16 (&acc)[2][4], _Float16 *smem, int m0, int n0, int w,
-                                               int l) {
-    const int g = l >> 5, i = l & 31, wm = w >> 2, wn = w & 3;
-    // ---- staging ------------------------------------------------------------------------------
-    // LDS image of an operand tile: row r (128 B), 16-byte chunk c stored in slot c ^ ((r >> 1) & 7).
-    // One wave-instruction covers 8 rows x 8 chunks = 1 KiB; wave w handles row groups w, w+8, ...
-    // lane L: row-in-group L >> 3, LDS slot L & 7  ->  source chunk = slot ^ swizzle(row).
-    const int rg = l >> 3, slot = l & 7;
-    const _Float16 *srcA[4], *srcB[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (j * 8 + w) * 8 + rg;
-        const int ch = slot ^ ((row >> 1) & 7);
-        const int ml = ((G.debug_mode & 4)) ? 0 : m0, nl = ((G.debug_mode & 4)) ? 0 : n0;  // ablation: L2-resident operands
-        srcA[j] = G.A + (size_t)(ml + row) * G.lda + ch * 8;
-        srcB[j] = G.B + (size_t)(nl + row) * G.ldb + ch * 8;
-    }
-    auto stage_issue = [&](int kt, int buf) {
-        const int k0 = kt * TK;
-        _Float16 *sa = smem + buf * STAGE_HALVES;
-        _Float16 *sb = sa + OPER_HALVES;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int piece = ((j * 8 + w) * 8) * TK;  // wave-uniform LDS base of this 1 KiB piece
-            __builtin_amdgcn_global_load_lds((glb_void_t *)(srcA[j] + k0), (lds_void_t *)(sa + piece), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_void_t *)(srcB[j] + k0), (lds_void_t *)(sb + piece), 16, 0, 0);
-        }
-    };
-
-    // ---- fragment rows: MFMA rows <- B-matrix rows (n), MFMA cols <- A-matrix rows (m) -----------
-    int nrow[2], nsw[2], mrow[4], msw[4];
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-        nrow[x] = wn * 64 + x * 32 + i;
-        nsw[x] = (nrow[x] >> 1) & 7;
-    }
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-        mrow[x] = wm * 128 + x * 32 + i;
-        msw[x] = (mrow[x] >> 1) & 7;
-    }
-
-    const int NK = G.K / TK;
-    stage_issue(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < NK; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < NK && !((G.debug_mode & 1))) stage_issue(kt + 1, buf ^ 1);
-        const _Float16 *sa = smem + buf * STAGE_HALVES;  // A-matrix rows (m)
-        const _Float16 *sb = sa + OPER_HALVES;           // B-matrix rows (n)
-        // fragments of k-step s+1 are requested before the MFMAs of k-step s are issued
-        f16x8 fn[2][2], fm[2][4];
-        auto load_frags = [&](int s, int set) {
-            const int ch = 2 * s + g;
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-                fn[set][x] = *reinterpret_cast<const f16x8 *>(sb + nrow[x] * TK + ((ch ^ nsw[x]) * 8));
-#pragma unroll
-            for (int y = 0; y < 4; ++y)
-                fm[set][y] = *reinterpret_cast<const f16x8 *>(sa + mrow[y] * TK + ((ch ^ msw[y]) * 8));
-        };
-        auto mfma_step = [&](int set) {
-            if ((G.debug_mode & 2)) {  // ablation: keep the LDS reads alive, skip the matrix pipe
-#pragma unroll
-                for (int x = 0; x < 2; ++x) asm volatile("" ::"v"(fn[set][x]));
-#pragma unroll
-                for (int y = 0; y < 4; ++y) asm volatile("" ::"v"(fm[set][y]));
-                return;
-            }
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < 4; ++y)
-                    acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fn[set][x], fm[set][y], acc[x][y], 0, 0, 0);
-        };
-        load_frags(0, 0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (s + 1 < 4) load_frags(s + 1, (s + 1) & 1);
-            mfma_step(s & 1);
-        }
-        // an LDS-DMA is a pending LDS write on the VM counter: retire it before the barrier publishes it
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-
-}
-
-// Product kernel, second form (ANCE_GEMM_DESC=0 selects the first one below for A/B): operands through buffer
-// descriptors (PipeSrcDesc), epilogue passes ordered inside the wave instead of by workgroup barriers.
+// fp16 GEMM: operands through buffer descriptors (PipeSrcDesc), epilogue passes ordered inside the wave instead of by workgroup
+// barriers.
 #ifdef ANCE_MEASURE
 // measurement library: per-workgroup 100 MHz stamps of the folded kernels (ance_debug_gemm_stamps): [block][8] =
 // start, main loop done, statistics ready, epilogue done, and for EPI_RESLN the end of each of its four passes
@@ -189,7 +92,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
     for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int y = 0; y < 4; ++y) acc[x][y] = f32x16{0};
-    Pipe256T<PipeSrcDesc, false, true, true> P;
+    Pipe256T<PipeSrcDesc> P;
     P.init(smem, w, l);
     // descriptors of this tile's 256 rows of each operand (bases are wave-uniform: kernel arguments and blockIdx)
     P.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.A + (size_t)m0 * G.lda), 0, (int)(256u * (uint32_t)G.lda * 2u), 0x00020000);
@@ -204,7 +107,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
         }
     constexpr bool EPB = EPI >= EPI_RESLN;  // folded-LayerNorm epilogues: parameter block by LDS-DMA, ahead of the pipeline's own
 #ifdef ANCE_MEASURE
-    unsigned long long *stamps_ = (EPI == EPI_RESLN && G.debug_mode == 64) ? g_gemm_stamps : nullptr;
+    unsigned long long *stamps_ = (EPI == EPI_RESLN && G.stamp) ? g_gemm_stamps : nullptr;
 #endif
     GSTAMP(0);
     if constexpr (EPB) epb_issue<EPI>(G, smem_f, m0, n0, w, l);
@@ -220,7 +123,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
         GSTAMP(1);
         const bool wide = epb_stats(G, smem_f, tid);
         if (wide && G.tok_lo) {
-            Pipe256T<PipeSrcDesc, false, true, true, false, true> P2;
+            Pipe256T<PipeSrcDesc, false, true> P2;
             P2.init(smem, w, l);
             P2.S = P.S;
             const float *st = smem_f + EPB_OFF + EPB_STATS;
@@ -281,7 +184,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const Ge
     for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int y = 0; y < 4; ++y) acc[x][y] = f32x16{0};
-    Pipe256T<PipeSrcDesc, false, true, true, true> P;
+    Pipe256T<PipeSrcDesc, true> P;
     P.init(smem, w, l);
     P.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.A + (size_t)m0 * G.lda), 0, (int)(256u * (uint32_t)G.lda * 2u), 0x00020000);
     P.S.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.B + (size_t)n0 * G.ldb), 0, (int)(256u * (uint32_t)G.ldb * 2u), 0x00020000);
@@ -295,7 +198,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const Ge
         }
     const float winv = G.wscale_inv ? *G.wscale_inv : 1.0f;  // wave-uniform: a scalar load, long back when the epilogue starts
 #ifdef ANCE_MEASURE
-    unsigned long long *stamps_ = G.debug_mode == 64 ? g_gemm_stamps : nullptr;  // [block][8]: start, main loop done, statistics, end
+    unsigned long long *stamps_ = G.stamp ? g_gemm_stamps : nullptr;  // [block][8]: start, main loop done, statistics, end
 #endif
     GSTAMP(0);
     epb_issue<EPI>(G, smem_f, m0, n0, w, l);
@@ -396,7 +299,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(c
     };
     int mt, nt;
     if (!next_tile(&mt, &nt)) return;
-    Pipe256T<PipeSrcStream, false, true, true, true> P;
+    Pipe256T<PipeSrcStream, true> P;
     P.init(smem, w, l);
     P.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.A), 0, (int)((uint32_t)G.M * (uint32_t)G.lda * 2u), 0x00020000);
     P.S.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.B), 0, (int)((uint32_t)G.N * (uint32_t)G.ldb * 2u), 0x00020000);
@@ -465,80 +368,6 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(c
     }
 }
 
-template <int EPI, bool ABLATE>
-__global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_kernel(const GemmArgs G) {
-    extern __shared__ __attribute__((aligned(16))) float smem_f[];
-    _Float16 *smem = reinterpret_cast<_Float16 *>(smem_f);
-
-    const int NT = G.N / TN, MT = G.M / TM;
-    // XCD-aware tile order (speed only): blocks b, b+8, ... share an XCD.  The dimension with more
-    // tiles is dealt round-robin to the XCDs, the other one is swept fastest, so the panel of the
-    // outer dimension stays in that XCD's L2 while the inner panels stream through it.
-    const int b = blockIdx.x, xcd = b & 7, jx = b >> 3;
-    int mt, nt;
-    if (MT >= NT) {
-        mt = (jx / NT) * 8 + xcd;
-        nt = jx % NT;
-    } else {
-        nt = (jx / MT) * 8 + xcd;
-        mt = jx % MT;
-    }
-    if (mt >= MT || nt >= NT) return;
-    const int m0_ = mt * TM, n0_ = nt * TN;
-
-    const int tid = threadIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l = tid & 63;  // wave w: output rows m wm*128.. (wm = w >> 2), columns n wn*64.. (wn = w & 3)
-
-    f32x16 acc[2][4];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) acc[x][y] = f32x16{0};
-
-    if (!ABLATE || (G.debug_mode & (16 | 32))) {
-        // product path: ping-pong pipeline of pipe256.h (debug_mode 16 + bits: its ablations)
-        Pipe256T<PipeSrcFixed, ABLATE, true, !ABLATE> P;  // product: coarse (2-phase) schedule; ablation build: the 4-phase one
-        P.init(smem, w, l);
-        P.dbg = G.debug_mode;
-        P.S.dbg = ABLATE ? G.debug_mode : 0;
-        const int m0 = (ABLATE && (G.debug_mode & 4)) ? 0 : m0_, n0 = (ABLATE && (G.debug_mode & 4)) ? 0 : n0_;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int r = pipe_stage_row(w, l, j), ch = pipe_stage_chunk(r, l);
-                P.S.src[h][j] = G.A + (size_t)(m0 + pipe_a_tile_row(h, r)) * G.lda + ch;
-                P.S.src[2 + h][j] = G.B + (size_t)(n0 + pipe_b_tile_row(h, r)) * G.ldb + ch;
-            }
-        if (ABLATE && (G.debug_mode & 32)) {
-            // timeline mode (epi 0 / 1 only): 100 MHz real-time stamps of this workgroup's phases go to the
-            // otherwise unused res32 buffer as uint64[workgroup][5]: start, prologue done, main loop done,
-            // epilogue issued, stores drained
-            unsigned long long *ts = reinterpret_cast<unsigned long long *>(const_cast<float *>(G.res32)) + (size_t)b * 5;
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            P.prologue();
-            const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-            P.enter();
-            P.tiles_final(G.K / TK, acc);
-            P.leave();
-            const unsigned long long t2 = __builtin_amdgcn_s_memrealtime();
-            gemm256_epilogue<EPI>(G, acc, smem_f, m0_, n0_, w, l);
-            const unsigned long long t3 = __builtin_amdgcn_s_memrealtime();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            const unsigned long long t4 = __builtin_amdgcn_s_memrealtime();
-            if (tid == 0) { ts[0] = t0; ts[1] = t1; ts[2] = t2; ts[3] = t3; ts[4] = t4; }
-            return;
-        }
-        P.run(G.K / TK, acc);
-    } else {
-        two_phase_loop(G, acc, smem, m0_, n0_, w, l);
-    }
-
-    gemm256_epilogue<EPI>(G, acc, smem_f, m0_, n0_, w, l);
-}
-
 #ifdef ANCE_MEASURE
 unsigned long long *g_gemm_stamps_host = nullptr;
 int g_gemm_stamps_epi = EPI_RESLN;  // which epilogue's launches are stamped (ance_debug_gemm_stamps_epi)
@@ -568,10 +397,9 @@ int device_cu_count() {
     return cus[dev];
 }
 
-template <bool ABLATE>
 int launch256(int epi, const GemmArgs &G, hipStream_t st) {
     const int MT = G.M / TM, NT = G.N / TN;
-    if (G.n_split != 0 && (G.n_split != 2 || (NT & 1) || ABLATE || epi < EPI_RESLN)) {
+    if (G.n_split != 0 && (G.n_split != 2 || (NT & 1) || epi < EPI_RESLN)) {
         set_last_error("gemm256: n_split needs an even number of N tiles and a descriptor-form kernel");
         return ANCE_E_INVALID;
     }
@@ -579,17 +407,10 @@ int launch256(int epi, const GemmArgs &G, hipStream_t st) {
                             : MT >= NT     ? (unsigned)((MT + 7) / 8 * 8) * (unsigned)NT
                                            : (unsigned)((NT + 7) / 8 * 8) * (unsigned)MT;
     void (*k)(const GemmArgs) = nullptr;
-    static int use_desc = -1;
-    if (use_desc < 0) {
-        const char *e = getenv("ANCE_GEMM_DESC");
-        use_desc = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    const bool desc = !ABLATE && use_desc;
     switch (epi) {
-        case EPI_QK: k = desc ? gemm256_f16_desc_kernel<EPI_QK> : gemm256_f16_kernel<EPI_QK, ABLATE>; break;
-        case EPI_GELU: k = desc ? gemm256_f16_desc_kernel<EPI_GELU> : gemm256_f16_kernel<EPI_GELU, ABLATE>; break;
-        case EPI_RES32: k = desc ? gemm256_f16_desc_kernel<EPI_RES32> : gemm256_f16_kernel<EPI_RES32, ABLATE>; break;
-        case EPI_VT: k = desc ? gemm256_f16_desc_kernel<EPI_VT> : gemm256_f16_kernel<EPI_VT, ABLATE>; break;
+        case EPI_QK: k = gemm256_f16_desc_kernel<EPI_QK>; break;
+        case EPI_GELU: k = gemm256_f16_desc_kernel<EPI_GELU>; break;
+        case EPI_RES32: k = gemm256_f16_desc_kernel<EPI_RES32>; break;
         case EPI_RESLN: k = gemm256_f16_desc_kernel<EPI_RESLN>; break;
         case EPI_QK_F: k = gemm256_f16_desc_kernel<EPI_QK_F>; break;
         case EPI_GELU_F: k = gemm256_f16_desc_kernel<EPI_GELU_F>; break;
@@ -600,15 +421,15 @@ int launch256(int epi, const GemmArgs &G, hipStream_t st) {
         default: set_last_error("gemm256: bad epilogue"); return ANCE_E_INVALID;
     }
     // the dynamic-LDS attribute is per template instance AND per device
-    static unsigned long long attr_done[2 * EPI_COUNT] = {0};
-    const int ai = epi + ((desc || epi >= EPI_RESLN) ? EPI_COUNT : 0);
+    static unsigned long long attr_done[EPI_COUNT] = {0};
+    const int ai = epi;
     if (attr_needed(&attr_done[ai])) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(G256_LDS_BYTES + (size_t)EPB_FLOATS * sizeof(float))) != hipSuccess)
             return check_launch("gemm256 attr");
         attr_mark(&attr_done[ai]);
     }
-    if (!ABLATE && (epi == EPI_S_QKV || epi == EPI_S_GELU) && gemm_stream_mode() == 1 && G.K >= 96 && (uint64_t)G.M * (uint64_t)G.lda * 2u < (1ull << 31) &&
+    if ((epi == EPI_S_QKV || epi == EPI_S_GELU) && gemm_stream_mode() == 1 && G.K >= 96 && (uint64_t)G.M * (uint64_t)G.lda * 2u < (1ull << 31) &&
         (uint64_t)G.N * (uint64_t)G.ldb * 2u < (1ull << 31)
 #ifdef ANCE_MEASURE
         && !(epi == g_gemm_stamps_epi && g_gemm_stamps_host)
@@ -630,7 +451,7 @@ int launch256(int epi, const GemmArgs &G, hipStream_t st) {
 #ifdef ANCE_MEASURE
     if (epi == g_gemm_stamps_epi && g_gemm_stamps_host) {
         GemmArgs G2 = G;
-        G2.debug_mode = 64;
+        G2.stamp = 1;
         hipLaunchKernelGGL(k, dim3(blocks), dim3(G256_THREADS), lds, st, G2);
         return ANCE_OK;
     }
@@ -652,15 +473,7 @@ int launch_gemm_f16(int epi, const GemmArgs &G, hipStream_t st) {
         set_last_error("gemm_f16: M,N must be multiples of 256 and K a multiple of 64, >= 128");
         return ANCE_E_INVALID;
     }
-#ifdef ANCE_MEASURE  // the ablation / timeline builds of the kernel exist in the measurement library only
-    if (G.debug_mode) return launch256<true>(epi, G, st);
-#else
-    if (G.debug_mode) {
-        set_last_error("gemm_f16: ablation and timeline modes need the measurement library (make -C ance_amd/csrc measure)");
-        return ANCE_E_INVALID;
-    }
-#endif
-    return launch256<false>(epi, G, st);
+    return launch256(epi, G, st);
 }
 
 }  // namespace ance
@@ -675,17 +488,13 @@ extern "C" void ance_debug_gemm_stamps(void *d_stamps) {
 // measurement library only: the epilogue (gemm_f16.h: EPI_*) whose launches leave stamps; default EPI_RESLN.  The split kernels
 // (EPI_S_QKV 8, EPI_S_GELU 9, EPI_S_RESLN 10) fill slots 0..3: start, main loop done, statistics ready, stores drained
 extern "C" void ance_debug_gemm_stamps_epi(int epi) { ance::g_gemm_stamps_epi = epi; }
-// measurement library only (WRONG results): see g_res_ablate in gemm256_epilogue.h
-extern "C" void ance_debug_gemm_res_ablate(int bits) {
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ance::g_res_ablate), &bits, sizeof(bits));
-}
 #endif
 
-// Test / measurement hook (include/ance_amd.h): the encoder's GEMM kernel on caller-provided data.
+// Test hook (include/ance_amd.h): the fp16 GEMM kernel on caller-provided data.  ablate is kept for the ABI and must be 0.
 extern "C" int ance_debug_gemm(int ablate, int epi, const void *d_a_f16, const void *d_b_f16, int M, int N, int K,
                                const float *d_bias, void *d_out, const float *d_res32, void *stream) {
     using namespace ance;
-    if (!d_a_f16 || !d_b_f16 || !d_bias || !d_out || epi < 0 || epi > 2 || (epi == EPI_RES32 && !d_res32)) {
+    if (ablate != 0 || !d_a_f16 || !d_b_f16 || !d_bias || !d_out || epi < 0 || epi > 2 || (epi == EPI_RES32 && !d_res32)) {
         set_last_error("ance_debug_gemm: invalid argument");
         return ANCE_E_INVALID;
     }
@@ -693,16 +502,8 @@ extern "C" int ance_debug_gemm(int ablate, int epi, const void *d_a_f16, const v
     memset(&G, 0, sizeof(G));
     G.A = (const _Float16 *)d_a_f16; G.lda = K; G.B = (const _Float16 *)d_b_f16; G.ldb = K;
     G.M = M; G.N = N; G.K = K; G.bias = d_bias; G.ldc = N; G.scale = 1.0f; G.scale_cols = 0;
-    G.debug_mode = ablate;
     if (epi == EPI_RES32) { G.out32 = (float *)d_out; G.res32 = d_res32; }
     else G.out16 = (_Float16 *)d_out;
-    if (epi != EPI_RES32 && (ablate & 32)) {  // timeline buffer
-        if (!d_res32) {
-            set_last_error("ance_debug_gemm: timeline mode needs d_res32 (uint64[M/256 * N/256][5])");
-            return ANCE_E_INVALID;
-        }
-        G.res32 = d_res32;
-    }
     ProfScope ps(PC_GEMM_FFN1, (hipStream_t)stream, 2.0 * M * (double)N * K);
     int rc = launch_gemm_f16(epi, G, (hipStream_t)stream);
     return rc ? rc : check_launch("ance_debug_gemm");

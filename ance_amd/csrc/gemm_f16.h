@@ -13,6 +13,8 @@ namespace ance {
 // no LayerNorm kernel, no statistics kernel, no parameter load left on the epilogue's critical path.
 // EPI_S_*: the SPLIT (fp32-grade) GEMM of gemm256_f16.hip -- operands are fp16 (hi, lo) pair rows, three MFMAs per k-step from four
 // staged operand tiles (pipe256.h: PAIR3); epilogues in gemm256_epilogue.h.
+// EPI_QK / GELU / RES32: the plain epilogues, reached through ance_debug_gemm.  EPI_VT has no launch of its own: it names the
+// epilogue form EPI_VT_F runs.
 enum { EPI_QK = 0, EPI_GELU = 1, EPI_RES32 = 2, EPI_VT = 3, EPI_RESLN = 4, EPI_QK_F = 5, EPI_GELU_F = 6, EPI_VT_F = 7,
        EPI_S_QKV = 8, EPI_S_GELU = 9, EPI_S_RESLN = 10, EPI_COUNT = 11 };
 
@@ -21,19 +23,16 @@ struct GemmArgs {
     const _Float16 *B;  // [N, K], row stride ldb
     int lda, ldb;
     int M, N, K;        // M, N multiples of 256; K multiple of 64
-    const float *bias;  // per column n (EPI_QK / GELU / RES32) or per row m (EPI_VT)
+    const float *bias;  // per column n, or per row m (EPI_VT_F)
     _Float16 *out16;
     float *out32;
     const float *res32;  // EPI_RES32: residual, same layout as out32
-    // EPI_RES32, optional: the residual is LayerNorm(res32) and is recomputed here from the pre-LN rows and the
-    // per-row (mean, rstd) the LayerNorm kernel left -- the normalised fp32 rows are never written to HBM.
-    const float *res_stats;  // [M][2] or null (res32 is then used as it is)
-    const float *res_gamma, *res_beta;  // [N]
+    const float *res_gamma, *res_beta;  // [N] (EPI_RESLN, EPI_S_RESLN)
     int ldc;             // row stride of out16 / out32 / res32 (elements)
     float scale;         // EPI_QK: applied to columns n < scale_cols
     int scale_cols;
-    const int *col_map;  // EPI_VT: token n -> destination column
-    int n_valid;         // EPI_VT: columns n >= n_valid are not stored
+    const int *col_map;  // EPI_VT_F: token n -> destination column
+    int n_valid;         // EPI_VT_F: columns n >= n_valid are not stored
     // folded LayerNorm: part_in[token][12][2] = (mean, M2) of the twelve 64-column slices of the token's pre-LayerNorm row
     // (tokens are the rows m for QK_F / GELU_F / RESLN's residual, the columns n for VT_F), ln_eps, and for EPI_*_F the
     // per-feature sum of the folded fp16 weight row
@@ -55,11 +54,12 @@ struct GemmArgs {
     const float *wscale_inv;
     unsigned *range_faults;  // split epilogues: sticky counter of threads that stored a value outside the fp16 range (common.h: range_report), or null
     int n_split;         // 2: N-split tile order (gemm256_f16.hip: tile_of_block; desc / split kernels only, N / 256 even); else 0
-    int debug_mode;      // ance_debug_gemm ablations: 1 = no loads after tile 0, 2 = no MFMA, 4 = all blocks load tile (0,0)
+#ifdef ANCE_MEASURE
+    int stamp;           // measurement library: this launch leaves per-workgroup stamps (ance_debug_gemm_stamps)
+#endif
 };
 
-// y = (x - mean) * rstd * gamma + beta -- the ONE expression every LayerNorm consumer uses, so that the fp32
-// residual recomputed in a GEMM epilogue is bitwise the value the LayerNorm kernel rounded to fp16.
+// y = (x - mean) * rstd * gamma + beta -- the ONE expression every consumer of a normalised row uses.
 __device__ __forceinline__ f32x4 ln_apply4(f32x4 x, float mean, float rstd, f32x4 g, f32x4 b) {
     f32x4 y;
 #pragma unroll

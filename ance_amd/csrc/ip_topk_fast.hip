@@ -517,8 +517,6 @@ struct FastParams {
     int *ovf_list;  // [OVF_CAP]
     int prune_at;           // first scheduled prune once every list has this many rows (<= F_C - FP)
     int prune_growth;       // percent: the tile count between scheduled prunes grows by this factor (150 = 1.5x)
-    int dbg;                     // STAMPS kernel only, timing experiments (results WRONG): 1 = no insertions after window 4,
-                                 // 2 = no filter at all after window 4, 3 = as 2 and no prune check either
     unsigned long long *stamps;  // measurement: [workgroup][8] accumulated 100 MHz ticks (STAMPS kernel only)
 };
 
@@ -544,11 +542,7 @@ struct FastSrc {
     // computed ONCE per K-tile, in the read half-phase -- the compare / select / shift chains (and the four s_cselect of the descriptor)
     // used to sit in front of each DMA, between the MFMAs, fenced there by the schedule's sched_barriers: ~25 scalar instructions per
     // K-tile in the matrix pipe's shadow.
-#ifdef ANCE_FAST_NO_PRECOMPUTE  // A/B builds only (make variant NAME=noprep DEFS=-DANCE_FAST_NO_PRECOMPUTE): the form of rounds 2-5
-    static constexpr bool PRECOMPUTE = false;
-#else
     static constexpr bool PRECOMPUTE = true;
-#endif
     int so_1, so_2;                // K offset (bytes) of K-tile t + 1 (A-half1) and of K-tile t + 2 (A-half0, B-half0, B-half1)
     __amdgpu_buffer_rsrc_t rx_2;   // corpus descriptor of K-tile t + 2
     __device__ __forceinline__ void prepare(int t) {
@@ -673,7 +667,7 @@ __global__ void __launch_bounds__(F_THREADS, 2) ip_topk_fast_kernel(const FastPa
     // Tile sequence: window by window, inside a window the Ws tiles of this split.  K-tile index t of the tile
     // being computed; t >= NK addresses the next tile of the sequence, so the LDS-DMA prefetch (5-6 phases
     // ahead) runs through the filter step into the next tile.
-    Pipe256T<FastSrc, false, true, true> pipe;  // coarse schedule (two phases per K-tile, B-half0 fragments kept in registers)
+    Pipe256T<FastSrc> pipe;
     pipe.init(smem, w, l);
     {
         FastSrc &S = pipe.S;
@@ -787,9 +781,6 @@ __global__ void __launch_bounds__(F_THREADS, 2) ip_topk_fast_kernel(const FastPa
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
-            if constexpr (STAMPS) {
-                if (P.dbg >= 2 && win > 4) continue;
-            }
             const int ql = qf + y * 32;
             const bool qv = (q0 + ql) < P.nq;
             const float thr = thr_s[ql];  // -inf until the first prune
@@ -810,9 +801,6 @@ __global__ void __launch_bounds__(F_THREADS, 2) ip_topk_fast_kernel(const FastPa
             if (!ragged) {
                 const float mx = max3_f32(max3_f32(mq[0], mq[1], mq[2]), mq[3], mq[3]);
                 if (__ballot(qv && !(mx < thr)) == 0ull) continue;
-            }
-            if constexpr (STAMPS) {
-                if (P.dbg == 1 && win > 4) continue;
             }
             u64 *cq = cand + (size_t)ql * F_C;
 #pragma unroll
@@ -1128,7 +1116,7 @@ int env_int(const char *name, int dflt) {
 // Tuning knobs of the fast path (include/ance_amd.h lists them): read from the environment ONCE, when the library first
 // needs them; ance_reload_env() re-reads (tests and sweeps that change a knob inside one process call it).
 struct FastKnobs {
-    int splits, window_tiles, dedup, center, share, wait_us, prune_at, prune_growth, debug;
+    int splits, window_tiles, dedup, center, share, wait_us, prune_at, prune_growth;
     void load() {
         splits = env_int("ANCE_FAST_SPLITS", 0);
         window_tiles = env_int("ANCE_FAST_WINDOW_TILES", 256);
@@ -1139,7 +1127,6 @@ struct FastKnobs {
         prune_at = env_int("ANCE_FAST_PRUNE_AT", 512);
         prune_growth = env_int("ANCE_FAST_PRUNE_GROWTH", 150);
         if (prune_growth < 105) prune_growth = 105;
-        debug = env_int("ANCE_FAST_DEBUG", 0);
     }
 };
 FastKnobs &fast_knobs() {
@@ -1369,16 +1356,16 @@ int ip_topk_fast(const float *d_x, int64_t n, int64_t row_base, const void *d_in
         if (P.prune_at > F_C - FP) P.prune_at = F_C - FP;
         P.prune_growth = prune_growth;
 #ifdef ANCE_MEASURE
-        P.stamps = stamps; P.dbg = kn.debug;
+        P.stamps = stamps;
 #else
-        P.stamps = nullptr; P.dbg = 0;
+        P.stamps = nullptr;
 #endif
         const int gq = 32 / pl.S;
         const int groups = (P.n_qt + gq - 1) / gq;
         const unsigned blocks = (unsigned)((groups + 7) / 8 * 8) * 32u;
         {
             ProfScope ps(PC_SCAN, st, 2.0 * (double)nqc * (double)n * (double)d);
-#ifdef ANCE_MEASURE  // the instrumented builds (per-workgroup time stamps, timing experiments) exist in the measurement library only
+#ifdef ANCE_MEASURE  // the instrumented builds (per-workgroup time stamps) exist in the measurement library only
             if (stamps) {
                 hipLaunchKernelGGL((ip_topk_fast_kernel<true, false>), dim3(blocks), dim3(F_THREADS), F_LDS_BYTES, st, P);
                 hipLaunchKernelGGL((ip_topk_fast_kernel<true, true>), dim3(blocks), dim3(F_THREADS), F_LDS_BYTES, st, P);

@@ -10,7 +10,7 @@
 // never 0 in steady state; the four waves with wm = 1 run one barrier behind the four with wm = 0, so on every SIMD one wave is
 // in its MFMA half-phase while the other one reads LDS.
 //
-// THE SCHEDULE OF THE PRODUCT KERNELS IS THE COARSE ONE (COARSE: two phases per K-tile, both B halves of a K-tile in registers):
+// THE SCHEDULE (two phases per K-tile, both B halves of a K-tile in registers):
 //   phase P0: read A-half0, B-half0, B-half1   MFMAs on acc[0][0..1], acc[1][0..1]   + stage A-half1 of tile t+1
 //   phase P1: read A-half1                     MFMAs on acc[1][2..3], acc[0][2..3]   + stage A0, B0, B1 of tile t+2
 // with 16 MFMAs per phase on plain fp16 operands and -- PAIR3, the split GEMM of the DEFAULT arithmetic -- 24: both operands are
@@ -31,22 +31,14 @@
 // prefetched by the last two K-tiles of the current one, in the steady-state rhythm; the epilogue / filter step runs with those
 // LDS-DMAs in flight and the next K loop starts without a pipeline fill.
 //
-// The original FOUR-phase schedule (one 64 x 32 output quadrant of every wave per phase, 8 MFMAs each, B-half0 read twice or
-// kept in 16 registers: KEEP_B0) is what the measurement builds of the fp16 GEMM and the search filter still instantiate:
-//   phase c0: read A-half0 + B-half0   MFMA acc[0][0..1]  + stage B-half0 of tile t+1
-//   phase c1: read B-half1             MFMA acc[1][0..1]  + stage A-half0 of tile t+2
-//   phase c2: read A-half1             MFMA acc[1][2..3]  + stage B-half1 of tile t+2
-//   phase c3: read B-half0 (again)     MFMA acc[0][2..3]  + stage A-half1 of tile t+2
 // Every phase is  { ds_reads }  s_barrier  { MFMAs with the LDS-DMAs issued between them }  s_barrier.  Where the LDS-DMAs are
-// issued was chosen by cycle counts (profiles/attic/r01_gemm_schedule_variants_cycles.txt): between the MFMAs 1.36 M cycles per
-// XCD on 8192^3, in the read half-phase 1.57-1.96 M, at the start / end of the MFMA half-phase 1.48-1.50 M; the wm stagger itself
-// is worth 1.36 vs 1.78 M and the two-phase loop this replaced took 1.88 M.  Its hazards (slot = interval between two barriers;
-// wm = 0 reads phase p in slot 2p and computes it in slot 2p+1, wm = 1 one slot later): RAW -- the wait at the end of the c3 reads
-// of tile t-1 leaves at most two half-tiles in flight (A-half0 and B-half1 of tile t+1), so every wave has retired its pieces of
-// all four half-tiles of tile t and the barrier that follows publishes them; WAR -- as above.
+// issued was chosen by cycle counts on the four-phase schedule this one replaced (profiles/attic/r01_gemm_schedule_variants_cycles.txt):
+// between the MFMAs 1.36 M cycles per XCD on 8192^3, in the read half-phase 1.57-1.96 M, at the start / end of the MFMA half-phase
+// 1.48-1.50 M; the wm stagger itself is worth 1.36 vs 1.78 M.
 // Needs NK >= 2 K-tiles.  The last two tiles are peeled (nothing left to stage, smaller counts).
 // tests/test_pipe_schedule_model.py replays these tables (prologue, steady state, peeled tiles, streaming hand-over, both wave
-// groups, every form) on a slot timeline and asserts the RAW / WAR conditions for every K-tile count.
+// groups, every form -- the retired four-phase one included) on a slot timeline and asserts the RAW / WAR conditions for every
+// K-tile count.
 #pragma once
 #include "common.h"
 
@@ -85,20 +77,6 @@ __device__ __forceinline__ int pipe_b_tile_row(int h, int r) { return (((r >> 5)
 // source address because the LDS image of an LDS-DMA is lane-linear).
 __device__ __forceinline__ int pipe_stage_row(int w, int l, int j) { return (w + 8 * j) * 8 + (l >> 3); }
 __device__ __forceinline__ int pipe_stage_chunk(int row, int l) { return ((l & 7) ^ ((row >> 1) & 7)) * 8; }
-
-// Source policy of a plain GEMM: fixed per-lane pointers at k = 0, K-tile t at +64 t halves.
-struct PipeSrcFixed {
-    const _Float16 *src[4][2];  // [A0 A1 B0 B1][piece]
-    int dbg = 0;                // measurement ablation bit 0: always re-read K-tiles 0/1
-    template <int TYPE, int J>
-    __device__ __forceinline__ const _Float16 *addr(int t) const {
-        return src[TYPE][J] + ((dbg & 1) ? (t & 1) * 64 : t * 64);
-    }
-    template <int TYPE, int J>
-    __device__ __forceinline__ void issue(int t, pipe_lds_t *dst) const {
-        __builtin_amdgcn_global_load_lds((pipe_glb_t *)addr<TYPE, J>(t), dst, 16, 0, 0);
-    }
-};
 
 // Source policy of a plain GEMM through buffer descriptors: one descriptor per operand matrix (wave-uniform SGPRs), one
 // 32-bit per-lane byte offset per staged piece that never changes, the K offset in an SGPR -- no 64-bit address
@@ -151,38 +129,25 @@ struct pipe_src_precomputes<S, decltype((void)S::PRECOMPUTE)> { static constexpr
 
 // SRC provides  template <int TYPE, int J> void issue(int t, pipe_lds_t *dst)  : the LDS-DMA (16 bytes per lane, 1 KiB per
 // wave, lane-linear at dst) of piece J of half-tile TYPE (0 A-half0, 1 A-half1, 2 B-half0, 3 B-half1) of K-tile t.
-// DBG compiles measurement ablations in (dbg bit 1: no MFMA, bit 3: no staging); product code uses DBG = false.
-// KEEP_B0: hold the B-half0 fragments of a K-tile in 16 more VGPRs from phase c0 to c3 instead of reading
-// them from LDS a second time (the GEMM has the registers, the search filter does not).
-// COARSE (needs KEEP_B0): two phases per K-tile instead of four -- half as many barriers.
-//   phase P0: read A-half0, B-half0, B-half1   16 MFMA acc[0][0..1], acc[1][0..1]   + stage A-half1 of tile t+1
-//   phase P1: read A-half1                     16 MFMA acc[1][2..3], acc[0][2..3]   + stage A0, B0, B1 of tile t+2
-//   RAW  the wait at the end of the P1 reads of tile t-1 (vmcnt(2)) leaves only A-half1 of tile t in flight, so
-//        A0 / B0 / B1 of tile t are retired and the following barrier publishes them; the wait at the end of the
-//        P0 reads of tile t (vmcnt(6)) leaves only A0 / B0 / B1 of tile t+1 in flight, so A-half1 of tile t is
-//        retired before the barrier that precedes its read.
-//   WAR  as above: a half-tile last read in phase p is restaged in the MFMA half-phase of phase p+1 at the earliest
-//        (A0 / B0 / B1 read in P0 of tile t, restaged in P1 of tile t; A1 read in P1 of tile t, restaged in P0 of t+1).
-// PAIR3 (needs COARSE; the split GEMM, round 5): both operands are BLOCKED pair rows (common.h), so the 64 halves of an LDS row are
+// The B-half0 fragments of a K-tile are held in fbk, the B-half1 ones in fb: both B halves are read in P0 (schedule above).
+// PAIR3 (the split GEMM, round 5): both operands are BLOCKED pair rows (common.h), so the 64 halves of an LDS row are
 //   [hi k 0..15 | hi k 16..31 | lo k 0..15 | lo k 16..31]  (fragment index s = 0..3)
 // and a K-tile is a 32-deep k-slice of hi AND lo of both operands.  Staging, LDS reads, barriers and waits are those of the
-// coarse schedule; only the products change: per output quadrant and k-step j the three MFMAs  hi_j x hi_j,  lo_j x hi_j,
+// plain fp16 form; only the products change: per output quadrant and k-step j the three MFMAs  hi_j x hi_j,  lo_j x hi_j,
 // hi_j x lo_j  (fragment pairs (j, j), (j + 2, j), (j, j + 2)) into the same accumulator -- 24 MFMAs per phase instead of 16,
 // i.e. per MFMA two thirds of the LDS-DMAs, ds_reads and barriers of three passes over [hi | lo'] rows (round 4).
 // MASKED: per-lane row masks on the fragments -- a lane whose keep_a bit y (A-tile row block y = 0..3 of its wave) / keep_b bit x
 // (B-tile row block x = 0, 1) is clear feeds zeros for that row, so the pass adds nothing to it.  Used by the folded GEMMs' second
 // pass over the lo halves of the token operand, which must touch the rows with a wide mean and ONLY those (a row's bits must not
 // depend on which other rows share its tile: gemm256_f16.hip).
-template <class SRC, bool DBG = false, bool KEEP_B0 = false, bool COARSE = false, bool PAIR3 = false, bool MASKED = false>
+template <class SRC, bool PAIR3 = false, bool MASKED = false>
 struct Pipe256T {
-    static_assert(!COARSE || KEEP_B0, "the coarse schedule keeps both B halves in registers");
-    static_assert(!PAIR3 || COARSE, "the pair products are built on the coarse schedule");
     SRC S;
     _Float16 *smem;
-    int w, dbg = 0;
+    int w;
     int ra[2], rb, kx[4];  // per-lane read offsets (halves)
     unsigned keep_a = 0xFu, keep_b = 0x3u;  // MASKED only
-    f16x8 fa[2][4], fb[4], fbk[KEEP_B0 ? 4 : 1];
+    f16x8 fa[2][4], fb[4], fbk[4];
 
     __device__ __forceinline__ void init(_Float16 *smem_, int w_, int l) {
         smem = smem_;
@@ -198,7 +163,6 @@ struct Pipe256T {
 
     template <int TYPE, int J, bool PRE = false>
     __device__ __forceinline__ void stage_piece(int t) {
-        if (DBG && (dbg & 8)) return;            // ablation: stage nothing (prologue included)
         _Float16 *dst = smem + (t & 1) * PIPE_BUF_HALVES + TYPE * PIPE_HALF_HALVES + (w + 8 * J) * 512;
         if constexpr (PRE && pipe_src_precomputes<SRC>::value) S.template issue_pre<TYPE, J>((pipe_lds_t *)dst);  // offsets of S.prepare(t)
         else S.template issue<TYPE, J>(t, (pipe_lds_t *)dst);
@@ -228,67 +192,11 @@ struct Pipe256T {
             f16x8 v = *reinterpret_cast<const f16x8 *>(base + rb + kx[s]);
             if constexpr (MASKED)
                 if (!((keep_b >> H) & 1u)) v = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            if constexpr (KEEP_B0 && H == 0) fbk[s] = v;
+            if constexpr (H == 0) fbk[s] = v;
             else fb[s] = v;
         }
     }
-    // MFMA half-phase: barrier, 8 MFMAs with the two LDS-DMA pieces of half-tile STAGE (of K-tile ts)
-    // issued in the shadow of the matrix pipe (an LDS-DMA costs 60-185 issue cycles in a read
-    // half-phase, which is the one with no slack), barrier.  STAGE < 0: nothing to stage.
-    template <int X, int YH, int STAGE>
-    __device__ __forceinline__ void mfma(f32x16 (&acc)[2][4], int ts) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // (no s_setprio around the MFMAs: 1.31-1.34 M cycles per XCD on 8192^3 without it, 1.36-1.38 M with it)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                const f16x8 &bf = (KEEP_B0 && X == 0) ? fbk[s] : fb[s];
-                if (DBG && (dbg & 2)) {  // ablation: keep the LDS reads alive, skip the matrix pipe
-                    asm volatile("" ::"v"(bf), "v"(fa[yy][s]));
-                } else {
-                    acc[X][2 * YH + yy] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, fa[yy][s], acc[X][2 * YH + yy], 0, 0, 0);
-                }
-            }
-            if constexpr (STAGE >= 0) {
-                if (s == 0 || s == 2) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (s == 0) stage_piece<(STAGE >= 0 ? STAGE : 0), 0>(ts);
-                    else stage_piece<(STAGE >= 0 ? STAGE : 0), 1>(ts);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-
-    // MODE 0: steady state (tiles t+1, t+2 exist); 1: t = NK-2; 2: t = NK-1
-    template <int MODE>
-    __device__ __forceinline__ void tile(int t, f32x16 (&acc)[2][4]) {
-        // c0
-        read_a<0>(t);
-        read_b<0>(t);
-        mfma<0, 0, (MODE <= 1 ? 2 : -1)>(acc, t + 1);
-        // c1
-        read_b<1>(t);
-        mfma<1, 0, (MODE == 0 ? 0 : -1)>(acc, t + 2);
-        // c2
-        read_a<1>(t);
-        mfma<1, 1, (MODE == 0 ? 3 : -1)>(acc, t + 2);
-        // c3: the wait retires every half-tile of tile t+1 (see RAW above)
-        if constexpr (!KEEP_B0) read_b<0>(t);
-        if constexpr (MODE == 0) PIPE_WAIT_VM(4);
-        if constexpr (MODE == 1) PIPE_WAIT_VM(0);
-        mfma<0, 1, (MODE == 0 ? 1 : -1)>(acc, t + 2);
-    }
-
-    // ---- coarse schedule ------------------------------------------------------------------------------
-    // MFMA half-phase of the coarse schedule: 16 MFMAs on A fragments fa (A-half YH) against both B halves, with
+    // MFMA half-phase: 16 MFMAs on A fragments fa (A-half YH) against both B halves, with
     // N_STAGE LDS-DMA pieces (two per listed half-tile of K-tile ts) issued after every second MFMA.
     template <int YH, int ST0, int ST1, int ST2>
     __device__ __forceinline__ void mfma16(f32x16 (&acc)[2][4], int ts) {
@@ -312,11 +220,7 @@ struct Pipe256T {
 #pragma unroll
             for (int yy = 0; yy < 2; ++yy) {
                 const f16x8 &bf = xx == 0 ? fbk[sb] : fb[sb];
-                if (DBG && (dbg & 2)) {
-                    asm volatile("" ::"v"(bf), "v"(fa[yy][sa]));
-                } else {
-                    acc[xx][2 * YH + yy] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, fa[yy][sa], acc[xx][2 * YH + yy], 0, 0, 0);
-                }
+                acc[xx][2 * YH + yy] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, fa[yy][sa], acc[xx][2 * YH + yy], 0, 0, 0);
             }
             // one LDS-DMA piece after each of the first 2 * n_stage MFMA pairs (PAIR3, STAGE_GAP = 2: after every second pair --
             // the phase is half as long again, the pieces keep their distance in MFMA time)
@@ -399,26 +303,17 @@ struct Pipe256T {
     // prologue: stage K-tile 0 and A0 B1 A1 of K-tile 1 (what the steady state has issued when a tile
     // starts), publish tile 0
     __device__ __forceinline__ void prologue() {
-        if constexpr (COARSE) {
-            // tile 0 complete except its A-half1 (retired by the first P0 wait), then A0 B0 B1 of tile 1
-            stage<0>(0); stage<2>(0); stage<3>(0); stage<1>(0);
-            PIPE_WAIT_VM(2);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            stage<0>(1); stage<2>(1); stage<3>(1);
-        } else {
-            stage<0>(0); stage<2>(0); stage<3>(0); stage<1>(0); stage<0>(1); stage<3>(1); stage<1>(1);
-            PIPE_WAIT_VM(6);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        // tile 0 complete except its A-half1 (retired by the first P0 wait), then A0 B0 B1 of tile 1
+        stage<0>(0); stage<2>(0); stage<3>(0); stage<1>(0);
+        PIPE_WAIT_VM(2);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        stage<0>(1); stage<2>(1); stage<3>(1);
     }
-    // coarse schedule: the prologue's half-tiles (K-tile 0, A0 B0 B1 of K-tile 1) with ALL of them retired and published -- what a
+    // the prologue's half-tiles (K-tile 0, A0 B0 B1 of K-tile 1) with ALL of them retired and published -- what a
     // K-tile 0 with loose waits (tile2: VM0 / VM1) needs when no epilogue preceded it
     __device__ __forceinline__ void prologue_landed() {
-        static_assert(COARSE, "coarse schedule only");
         stage<0>(0); stage<2>(0); stage<3>(0); stage<1>(0);
         stage<0>(1); stage<2>(1); stage<3>(1);
         PIPE_WAIT_VM(0);
@@ -439,19 +334,17 @@ struct Pipe256T {
     }
     // K-tiles 0..NK-1 of a stream that CONTINUES (the source policy maps t >= NK onto what follows):
     // on return K-tiles NK and NK+1 are staged exactly as the prologue leaves tiles 0 and 1 (the wait
-    // of the last c3 has retired tile NK).
-    // VM0L / VM1L (coarse schedule, != 6 / 2): K-tile 0 was prefetched under an epilogue and waits with these counts (tile2).  The
+    // of the last P1 has retired tile NK).
+    // VM0L / VM1L (!= 6 / 2): K-tile 0 was prefetched under an epilogue and waits with these counts (tile2).  The
     // FIRST output tile of a persistent workgroup then starts from prologue_landed (every LDS-DMA of the prologue retired: a loose
     // wait has nothing to wait for), so that K-tile 0 is the same code for every output tile.
     template <int VM0L = 6, int VM1L = 2>
     __device__ __forceinline__ void tiles_streaming(int NK, f32x16 (&acc)[2][4]) {
-        if constexpr (COARSE && (VM0L != 6 || VM1L != 2)) {
+        if constexpr (VM0L != 6 || VM1L != 2) {
             tile2<0, VM0L, VM1L>(0, acc);
             for (int t = 1; t < NK; ++t) tile2<0>(t, acc);
         } else {
-            for (int t = 0; t < NK; ++t) {
-                if constexpr (COARSE) tile2<0>(t, acc); else tile<0>(t, acc);
-            }
+            for (int t = 0; t < NK; ++t) tile2<0>(t, acc);
         }
     }
     // K-tiles T0..NK-1 of a stream that ENDS (T0 even: the buffer parity of a tile is t & 1; NK - T0 >= 2): nothing beyond
@@ -459,20 +352,14 @@ struct Pipe256T {
     // (VM0L / VM1L as tiles_streaming; they need NK - T0 >= 3: K-tile T0 is then a steady-state tile)
     template <int VM0L = 6, int VM1L = 2>
     __device__ __forceinline__ void tiles_final(int NK, f32x16 (&acc)[2][4], int T0 = 0) {
-        if constexpr (COARSE && (VM0L != 6 || VM1L != 2)) {
+        if constexpr (VM0L != 6 || VM1L != 2) {
             tile2<0, VM0L, VM1L>(T0, acc);
             for (int t = T0 + 1; t < NK - 2; ++t) tile2<0>(t, acc);
-            tile2<1>(NK - 2, acc);
-            tile2<2>(NK - 1, acc);
-        } else if constexpr (COARSE) {
-            for (int t = T0; t < NK - 2; ++t) tile2<0>(t, acc);
-            tile2<1>(NK - 2, acc);
-            tile2<2>(NK - 1, acc);
         } else {
-            for (int t = T0; t < NK - 2; ++t) tile<0>(t, acc);
-            tile<1>(NK - 2, acc);
-            tile<2>(NK - 1, acc);
+            for (int t = T0; t < NK - 2; ++t) tile2<0>(t, acc);
         }
+        tile2<1>(NK - 2, acc);
+        tile2<2>(NK - 1, acc);
     }
 
     // Whole K loop of one output tile.  On return every wave has passed the same number of barriers.

@@ -181,21 +181,16 @@ __global__ void __launch_bounds__(256) embed32_kernel(const int *tok_id, const i
 constexpr int P_KC = 128;
 constexpr size_t P_ATT_LDS = (size_t)2 * P_KC * 64 * sizeof(float);
 
-// ctx_pair != null (split mode, encoder.hip): the output row is written as an fp16 pair row (common.h), the token operand of the
-// split attention-output GEMM; cls_only: only query 0 of every sequence is
-// computed and its row goes to row s (compact), as in attention.hip.
-__global__ void __launch_bounds__(256) attention32_kernel(const float *qkv, float *ctx, _Float16 *ctx_pair, int cls_only,
-                                                          const int *seq_off, int n_heads) {
+__global__ void __launch_bounds__(256) attention32_kernel(const float *qkv, float *ctx, const int *seq_off, int n_heads) {
     extern __shared__ __attribute__((aligned(16))) float smem_p[];
     float *Ks = smem_p, *Vs = smem_p + P_KC * 64;
     const int s = blockIdx.x / n_heads, h = blockIdx.x - s * n_heads;
     const int tok0 = seq_off[s], T = seq_off[s + 1] - tok0;
     const int tid = threadIdx.x;
     const int ld = 3 * 768;
-    const int q_end = cls_only ? 1 : T;
-    for (int q0 = 0; q0 < q_end; q0 += 256) {
+    for (int q0 = 0; q0 < T; q0 += 256) {
         const int qi = q0 + tid;
-        const bool qv = qi < q_end;
+        const bool qv = qi < T;
         float q[64], acc[64];
         float m = -INFINITY, lsum = 0.f;
         {
@@ -233,25 +228,14 @@ __global__ void __launch_bounds__(256) attention32_kernel(const float *qkv, floa
         }
         if (qv) {
             const float inv = 1.0f / lsum;
-            const size_t orow = cls_only ? (size_t)s : (size_t)(tok0 + qi);
-            if (ctx_pair) {
-                _Float16 *ph = ctx_pair + orow * 1536;
+            float *op = ctx + (size_t)(tok0 + qi) * 768 + h * 64;
 #pragma unroll
-                for (int d = 0; d < 64; d += 4) {
-                    const f32x4 v = {acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv};
-                    pair_store4(v, ph, 768, h * 64 + d);  // the stored hi and the hi of (v - hi) are the same bits (common.h)
-                }
-            } else {
-                float *op = ctx + orow * 768 + h * 64;
-#pragma unroll
-                for (int d = 0; d < 64; ++d) op[d] = acc[d] * inv;
-            }
+            for (int d = 0; d < 64; ++d) op[d] = acc[d] * inv;
         }
     }
 }
 
-int launch_attention32(const float *qkv, float *ctx, const int *seq_off, int n_seq, int n_heads, hipStream_t st,
-                       _Float16 *ctx_pair = nullptr, int cls_only = 0) {
+int launch_attention32(const float *qkv, float *ctx, const int *seq_off, int n_seq, int n_heads, hipStream_t st) {
     static unsigned long long attr_done = 0;
     if (attr_needed(&attr_done)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(attention32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -259,7 +243,7 @@ int launch_attention32(const float *qkv, float *ctx, const int *seq_off, int n_s
             return check_launch("attention32 attr");
         attr_mark(&attr_done);
     }
-    hipLaunchKernelGGL(attention32_kernel, dim3((unsigned)n_seq * n_heads), dim3(256), P_ATT_LDS, st, qkv, ctx, ctx_pair, cls_only, seq_off, n_heads);
+    hipLaunchKernelGGL(attention32_kernel, dim3((unsigned)n_seq * n_heads), dim3(256), P_ATT_LDS, st, qkv, ctx, seq_off, n_heads);
     return ANCE_OK;
 }
 

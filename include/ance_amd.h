@@ -218,12 +218,10 @@ typedef struct AnceEncoder AnceEncoder;
  *   ANCE_ENCODER_PRECISE=1   fp32 mode: fp32 operands on the fp32-input matrix cores, exact erf GELU, fp32 softmax -- the
  *                            reference's arithmetic (model/models.py:149-157); max |delta| 1e-5, 4.4 x slower than the default (the audit
  *                            path); wins over the other two switches
- *   ANCE_GEMM_NSPLIT=0       FFN1 without the N-split tile order (A/B switch)
  *   ANCE_ENCODER_STREAMS=n   internal streams / activation sets (1 or 2, default 2)
- *   ANCE_LN_FOLD=0 ANCE_HEAD_MFMA=0 ANCE_CLS_TAIL=0 ANCE_ATTN_COAL=0 ANCE_GEMM_DESC=0   A/B switches back to the previous
- *                            form of one piece each (LayerNorm kernels, per-sequence head, full last layer, per-lane
- *                            attention loads / stores, flat-pointer GEMM staging; ANCE_GEMM_DESC is read at the first GEMM
- *                            launch of the process, the others per handle) */
+ *   ANCE_CLS_TAIL=0          the full last layer instead of the CLS-only tail (bit-identical: the tail's reference; per handle)
+ *   ANCE_GEMM_STREAM=0       the launch-per-tile split GEMM for QKV and FFN1 instead of the persistent streaming one
+ *                            (bit-identical: the streaming kernel's reference; read once per process, ance_reload_env re-reads) */
 size_t ance_encoder_weight_bytes(const AnceEncoderDesc *desc);
 size_t ance_encoder_workspace_bytes(const AnceEncoderDesc *desc);
 
@@ -270,17 +268,10 @@ int ance_encode_ids(AnceEncoder *enc, const int32_t *d_ids, int64_t ld_ids, cons
                     const int32_t *h_lens, int64_t n, int L, int n_chunks, float *d_out, void *stream);
 
 /*
- * Test / measurement hook: C = A . B^T (+ epilogue) with the encoder's GEMM kernel on caller data.
+ * Test hook: C = A . B^T (+ epilogue) with the encoder's fp16 GEMM kernel (ping-pong main loop) on caller data.
  *   epi 0: out f16 = acc + bias[n]; 1: out f16 = gelu(acc + bias[n]); 2: out f32 = acc + bias[n] + res32
  *   d_a_f16 [M,K], d_b_f16 [N,K] fp16 row-major; M, N multiples of 256, K a multiple of 64, >= 128.
- *   ablate 0: the product kernel (ping-pong main loop).  Non-zero values are accepted by the MEASUREMENT library only
- *   (`make -C ance_amd/csrc measure`; the product library returns ANCE_E_INVALID) and select the two-phase loop it
- *   replaced, with measurement ablations by bit (results are then WRONG on purpose): 1 = no global
- *   loads after the first K-tile, 2 = no MFMA, 4 = every block loads tile (0,0); 8 = no ablation
- *   (correct results; the A/B reference for the main loop).  16 + bits: the ping-pong loop with
- *   ablations 1 = every K-tile re-reads tiles 0/1, 2 = no MFMA, 4 = tile (0,0), 8 = no staging at all.
- *   32 (epi 0 / 1): timeline -- correct results, and d_res32 receives uint64[M/256 * N/256][5] stamps of the
- *   100 MHz real-time counter per workgroup: start, prologue done, main loop done, epilogue issued, stores drained.
+ *   ablate must be 0 (kept for the ABI; any other value returns ANCE_E_INVALID, in every build of the library).
  */
 int ance_debug_gemm(int ablate, int epi, const void *d_a_f16, const void *d_b_f16, int M, int N, int K,
                     const float *d_bias, void *d_out, const float *d_res32, void *stream);

@@ -28,7 +28,7 @@ for n_layers in (1, 4):
             sd64 = {k: v.double() for k, v in sd.items()}
             want = encoder_ref.rdot_nll_ln_emb(sd64, torch.from_numpy(ids), encoder_ref.mask_from_lengths(lens, 128), n_layers=n_layers).float().numpy()
         row = dict(n_layers=n_layers, offset=offset, emb_offset=emb)
-        for mode, env in (("default", {}), ("ln_fold0", {"ANCE_LN_FOLD": "0"}), ("no_tail", {"ANCE_CLS_TAIL": "0"}),
+        for mode, env in (("default", {}), ("no_tail", {"ANCE_CLS_TAIL": "0"}),
                           ("split", {"ANCE_ENCODER_SPLIT": "1"}), ("fp32", {"ANCE_ENCODER_PRECISE": "1"})):
             for k, v in env.items():
                 os.environ[k] = v
