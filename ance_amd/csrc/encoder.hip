@@ -91,16 +91,40 @@ struct PlanArgs {
     int S;                // sequences in this micro-batch
     int L, n_chunks, Lc;
     int pad_id, arch;
-    int T, Tpad;          // real tokens / padded to 128 (host computed, same arithmetic)
+    int T, Tpad;          // real tokens / padded to 256 (host computed, same arithmetic; SEED: T is an upper bound, the device
+                          // total is seq_off[S])
+    int vt_spare;         // SEED: V^T column the pad rows below T write to (no sequence reads it)
     int *seq_off, *seq_vtcol, *seq_len;
     int *tok_id, *tok_pos, *tok_vtcol;
     int4 *desc;           // attention descriptors (first token, length, V^T column, sequence), longest length bucket first
-    int bstart[4];        // first descriptor of each bucket (host computed: the host knows every length)
+    unsigned *faults;     // ance_encoder_range_faults; SEED: [1] counts sequences that are empty or start with the pad id
 };
 
 __device__ __forceinline__ int len_bucket(int eff) {  // ceil(eff / 32) - 1, everything above 96 tokens in bucket 3
     const int b = (eff + 31) >> 5;
     return b > 4 ? 3 : b - 1;
+}
+
+// SEED (ANCE_ARCH_SEED): the encoder masks every key whose id is the pad id, inside the record's length too.  Positions skip pad
+// ids already, so dropping those tokens leaves every other token's output unchanged: seq_len[s] = the number of non-pad ids in
+// [0, len), which plan_kernel / pack_kernel then treat as the sequence's length.  One wave per sequence (no MaxP: n_chunks = 1).
+// A record that is empty or starts with the pad id has no defined output in the reference (a pad row or NaN): counted in faults[1].
+__global__ void __launch_bounds__(256) seed_count_kernel(const PlanArgs P) {
+    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int l = threadIdx.x & 63;
+    if (s >= P.S) return;
+    const int64_t rec = P.g0 + s;
+    const int full = record_len(P.base, P.ld, P.lens, rec, P.L);
+    const int32_t *src = P.base + rec * P.ld + P.hdr;
+    int cnt = 0;
+    for (int j0 = 0; j0 < full; j0 += 64) {
+        const int j = j0 + l;
+        cnt += __popcll(__ballot(j < full && src[j] != P.pad_id));
+    }
+    if (l == 0) {
+        P.seq_len[s] = cnt;
+        if (full == 0 || src[0] == P.pad_id) atomicAdd(P.faults + 1, 1u);
+    }
 }
 
 // effective lengths + exclusive scans (token offsets; 8-aligned V^T columns; rank inside the length bucket).  One block.
@@ -115,13 +139,18 @@ __global__ void __launch_bounds__(1024) plan_kernel(const PlanArgs P) {
     for (int j = 0; j < per; ++j) {
         const int s = b0 + j;
         if (s < P.S) {
-            const int64_t gs = P.g0 + s;
-            const int64_t rec = gs / P.n_chunks;
-            const int c = (int)(gs - rec * P.n_chunks);
-            const int full = record_len(P.base, P.ld, P.lens, rec, P.L);
-            int lc = full - c * P.Lc;
-            lc = lc < 0 ? 0 : (lc > P.Lc ? P.Lc : lc);
-            P.seq_len[s] = lc;
+            int lc;
+            if (P.arch == ANCE_ARCH_SEED) {
+                lc = P.seq_len[s];  // seed_count_kernel
+            } else {
+                const int64_t gs = P.g0 + s;
+                const int64_t rec = gs / P.n_chunks;
+                const int c = (int)(gs - rec * P.n_chunks);
+                const int full = record_len(P.base, P.ld, P.lens, rec, P.L);
+                lc = full - c * P.Lc;
+                lc = lc < 0 ? 0 : (lc > P.Lc ? P.Lc : lc);
+                P.seq_len[s] = lc;
+            }
             const int eff = lc > 0 ? lc : 1;
             sum += eff;
             sum8 += (eff + 7) & ~7;
@@ -149,6 +178,8 @@ __global__ void __launch_bounds__(1024) plan_kernel(const PlanArgs P) {
     }
     int run = s_tot[tid] - sum, run8 = s_tot8[tid] - sum8;
     unsigned long long rbk = s_bk[tid] - bk;  // sequences of each bucket before this thread's
+    // first descriptor of each bucket, longest sequences first, from the totals (SEED's lengths are known on the device only)
+    const unsigned long long tbk = s_bk[1023];
     for (int j = 0; j < per; ++j) {
         const int s = b0 + j;
         if (s < P.S) {
@@ -157,7 +188,9 @@ __global__ void __launch_bounds__(1024) plan_kernel(const PlanArgs P) {
             P.seq_off[s] = run;
             P.seq_vtcol[s] = run8;
             const int b = len_bucket(eff);
-            P.desc[P.bstart[b] + (int)((rbk >> (16 * b)) & 0xFFFF)] = make_int4(run, eff, run8, s);
+            int bstart = 0;
+            for (int bb = 3; bb > b; --bb) bstart += (int)((tbk >> (16 * bb)) & 0xFFFF);
+            P.desc[bstart + (int)((rbk >> (16 * b)) & 0xFFFF)] = make_int4(run, eff, run8, s);
             rbk += 1ull << (16 * b);
             run += eff;
             run8 += (eff + 7) & ~7;
@@ -180,8 +213,26 @@ __global__ void __launch_bounds__(256) pack_kernel(const PlanArgs P) {
             // all-pad chunk == one pad token attending to itself
             if (l == 0) {
                 P.tok_id[t0] = P.pad_id;
-                P.tok_pos[t0] = P.arch == ANCE_ARCH_ROBERTA ? P.pad_id : 0;
+                P.tok_pos[t0] = P.arch == ANCE_ARCH_BERT ? 0 : P.pad_id;
                 P.tok_vtcol[t0] = v0;
+            }
+        } else if (P.arch == ANCE_ARCH_SEED) {
+            // the non-pad ids of [0, len) back to back: rank r gets position pad + 1 + r (RoBERTa's rule on the kept tokens)
+            const int32_t *src = P.base + rec * P.ld + P.hdr;
+            const int full = record_len(P.base, P.ld, P.lens, rec, P.L);
+            int before = 0;
+            for (int j0 = 0; j0 < full; j0 += 64) {
+                const int j = j0 + l;
+                const int id = j < full ? src[j] : P.pad_id;
+                const bool keep = j < full && id != P.pad_id;
+                const u64 m = __ballot(keep);
+                const int r = before + __popcll(m & ((1ull << l) - 1ull));
+                if (keep) {
+                    P.tok_id[t0 + r] = id;
+                    P.tok_pos[t0 + r] = P.pad_id + 1 + r;
+                    P.tok_vtcol[t0 + r] = v0 + r;
+                }
+                before += __popcll(m);
             }
         } else {
             const int32_t *src = P.base + rec * P.ld + P.hdr + c * P.Lc;
@@ -206,12 +257,15 @@ __global__ void __launch_bounds__(256) pack_kernel(const PlanArgs P) {
             }
         }
     }
-    // rows T..Tpad exist only to fill the last GEMM tile
+    // rows T..Tpad exist only to fill the last GEMM tile.  SEED: from the device total on; the V^T GEMM stores rows below the host's
+    // T, so those write the spare column
+    const bool seed = P.arch == ANCE_ARCH_SEED;
+    const int T = seed ? P.seq_off[P.S] : P.T;
     const int gt = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gt < P.Tpad - P.T) {
-        P.tok_id[P.T + gt] = P.pad_id;
-        P.tok_pos[P.T + gt] = P.arch == ANCE_ARCH_ROBERTA ? P.pad_id : 0;
-        P.tok_vtcol[P.T + gt] = 0;
+    if (gt < P.Tpad - T) {
+        P.tok_id[T + gt] = P.pad_id;
+        P.tok_pos[T + gt] = P.arch == ANCE_ARCH_BERT ? 0 : P.pad_id;
+        P.tok_vtcol[T + gt] = seed ? P.vt_spare : 0;
     }
 }
 
@@ -661,7 +715,7 @@ bool desc_ok(const AnceEncoderDesc *d) {
     return d && d->hidden == H && d->n_heads == 12 && d->intermediate > 0 && d->intermediate % 128 == 0 &&
            d->n_layers >= 1 && d->vocab_size > 0 && d->max_position > 0 && d->max_seq_len >= 1 &&
            d->max_seq_len <= 512 && d->max_tokens >= 512 && d->max_tokens % 256 == 0 && d->precision >= 0 && d->precision <= 3 &&
-           (d->arch == ANCE_ARCH_ROBERTA || d->arch == ANCE_ARCH_BERT);
+           (d->arch == ANCE_ARCH_ROBERTA || d->arch == ANCE_ARCH_BERT || d->arch == ANCE_ARCH_SEED);
 }
 
 void layout_weights(const AnceEncoderDesc *d, Arena &a, AnceEncoder *e) {
@@ -1085,6 +1139,11 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
         return ANCE_E_INVALID;
     }
     const AnceEncoderDesc &D = e->d;
+    const bool seed = D.arch == ANCE_ARCH_SEED;
+    if (seed && n_chunks != 1) {
+        set_last_error("ance_encode: ANCE_ARCH_SEED encodes whole records (n_chunks must be 1)");
+        return ANCE_E_INVALID;
+    }
     int mb_index = 0;
     bool forked = false;
 
@@ -1103,6 +1162,14 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
                 return check_launch("ance_encode: length read-back");
             hl = e->host_lens.data();
         }
+        if (seed)
+            for (int i = 0; i < nr; ++i)
+                if (hl[i] <= 0) {
+                    // no [CLS]: the reference reads a pad row or NaN there (a record that starts with the pad id is caught on the
+                    // device: seed_count_kernel)
+                    set_last_error("ance_encode: empty record under ANCE_ARCH_SEED (the reference defines no output for it)");
+                    return ANCE_E_INVALID;
+                }
         if (e->n_lanes > 1 && !forked) {  // side streams start after everything already queued by the caller
             (void)hipEventRecord(e->ev_fork, caller_st);
             for (int ln = 0; ln < e->n_lanes; ++ln) (void)hipStreamWaitEvent(e->side[ln], e->ev_fork, 0);
@@ -1115,8 +1182,8 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
             const AnceEncoder::Lane &LN = e->lane[mb_index % e->n_lanes];
             hipStream_t st = e->n_lanes > 1 ? e->side[mb_index % e->n_lanes] : caller_st;
             ++mb_index;
+            // SEED: the lengths here are upper bounds of the compacted ones (they size grids, LDS and buffers only)
             int S = 0, T = 0, V = 0, maxlen = 1;
-            int n_bucket[4] = {0, 0, 0, 0};
             int64_t g = gs;
             while (g < gs_end && S < e->scap) {
                 const int64_t rec = g / n_chunks;
@@ -1130,29 +1197,27 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
                 if (T + eff > e->tcap || V + v8 > e->vcap - 256) break;
                 T += eff; V += v8; ++S; ++g;
                 if (eff > maxlen) maxlen = eff;
-                const int nb = (eff + 31) >> 5;
-                ++n_bucket[nb > 4 ? 3 : nb - 1];  // = len_bucket(eff) of plan_kernel
             }
             if (S == 0) {
                 set_last_error("ance_encode: max_tokens too small for one sequence");
                 return ANCE_E_INVALID;
             }
             const int Tpad = (int)align_up((size_t)T, 256);
-            const int ldvt = (int)align_up((size_t)V, 256);
+            // SEED: column V (never part of a sequence) takes the V^T stores of the pad rows below T; V + 8 <= vcap - 256
+            const int ldvt = (int)align_up((size_t)V + (seed ? 8 : 0), 256);
 
             PlanArgs P;
             P.base = base; P.ld = ld; P.lens = d_lens; P.hdr = hdr;
             P.g0 = r0 * n_chunks + gs; P.S = S; P.L = L; P.n_chunks = n_chunks; P.Lc = Lc;
-            P.pad_id = D.pad_token_id; P.arch = D.arch; P.T = T; P.Tpad = Tpad;
+            P.pad_id = D.pad_token_id; P.arch = D.arch; P.T = T; P.Tpad = Tpad; P.vt_spare = V;
             P.seq_off = LN.seq_off; P.seq_vtcol = LN.seq_vtcol; P.seq_len = LN.seq_len;
             P.tok_id = LN.tok_id; P.tok_pos = LN.tok_pos; P.tok_vtcol = LN.tok_vtcol;
-            P.desc = LN.desc;
-            P.bstart[3] = 0;  // longest sequences first
-            for (int b = 2; b >= 0; --b) P.bstart[b] = P.bstart[b + 1] + n_bucket[b + 1];
+            P.desc = LN.desc; P.faults = e->faults;
             {
                 ProfScope ps(PC_PLAN, st);
+                if (seed) hipLaunchKernelGGL(seed_count_kernel, dim3((S + 3) / 4), dim3(256), 0, st, P);
                 hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(1024), 0, st, P);
-                const int nb_seq = (S + 3) / 4, nb_pad = (Tpad - T + 255) / 256;
+                const int nb_seq = (S + 3) / 4, nb_pad = ((seed ? Tpad : Tpad - T) + 255) / 256;
                 hipLaunchKernelGGL(pack_kernel, dim3(nb_seq > nb_pad ? nb_seq : nb_pad), dim3(256), 0, st, P);
             }
             MicroBatch mb;

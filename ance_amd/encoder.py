@@ -4,11 +4,13 @@ Reference interface mirrored (same names, argument meaning, output shapes):
   model/models.py:149-157   RobertaDot_NLL_LN.query_emb / body_emb      -> [B, 768]
   model/models.py:165-199   RobertaDot_CLF_ANN_NLL_MultiChunk.body_emb  -> [B, C, 768]
   model/models.py:254-259   BiEncoder.query_emb / body_emb (DPR, BERT)  -> [B, 768]
+  model/models.py:201-221   SEEDEncoderDot_NLL_LN.query_emb / body_emb  -> [B, 768]
 called as ``model.module.query_emb(input_ids=..., attention_mask=...)`` by
 drivers/run_ann_data_gen.py:171-180 (seam B4).  Weights are read from a HF checkpoint directory
 (``checkpoint-N/``: pytorch_model.bin or model.safetensors, keys ``roberta.*``, ``embeddingHead.*``,
 ``norm.*``; ``classifier.*`` / pooler ignored) or from a DPR ``model_dict`` (``question_model.*``,
-``ctx_model.*``; utils/dpr_utils.py:74-78).
+``ctx_model.*``; utils/dpr_utils.py:74-78), or from a SEED-Encoder checkpoint directory (fairseq names under
+``seed_encoder.encoder.sentence_encoder.``, ``embeddingHead.*``, ``norm.*``; ``seed_state_dict``).
 
 All arithmetic happens in csrc/ (C ABI ``ance_encoder_create`` / ``ance_encode_*``); this file is
 plumbing: weight gathering, buffer ownership, call-shape adaptation.  No CPU fallback.
@@ -21,7 +23,7 @@ import numpy as np
 
 from . import _lib
 
-ARCH_ROBERTA, ARCH_BERT = 0, 1
+ARCH_ROBERTA, ARCH_BERT, ARCH_SEED = 0, 1, 2  # include/ance_amd.h: ANCE_ARCH_*
 
 _LAYER_KEYS = (
     "attention.self.query.weight", "attention.self.query.bias",
@@ -117,8 +119,8 @@ class Encoder:
         self.desc = _lib.AnceEncoderDesc(
             arch=arch, n_layers=n_layers, hidden=int(word.shape[1]), n_heads=12, intermediate=int(inter),
             vocab_size=int(word.shape[0]), max_position=int(pos.shape[0]),
-            pad_token_id=(1 if arch == ARCH_ROBERTA else 0) if pad_token_id is None else int(pad_token_id),
-            ln_eps=(1e-5 if arch == ARCH_ROBERTA else 1e-12) if ln_eps is None else float(ln_eps),
+            pad_token_id=(0 if arch == ARCH_BERT else 1) if pad_token_id is None else int(pad_token_id),
+            ln_eps=(1e-12 if arch == ARCH_BERT else 1e-5) if ln_eps is None else float(ln_eps),
             has_head=1 if has_head else 0, max_seq_len=int(max_seq_len),
             max_tokens=max(512, int(max_tokens) // 256 * 256), precision=precision_code)
         wbytes = L.ance_encoder_weight_bytes(ctypes.byref(self.desc))
@@ -177,6 +179,10 @@ class Encoder:
         elif not ev.query():
             return
         over, nan_rows = int(self._faults[0]), int(self._faults[1])
+        if nan_rows and self.arch == ARCH_SEED and not over:
+            raise _lib.AnceRangeError(
+                "encoder (SEED): %d records start with the pad id or produced NaN rows -- the reference defines no embedding for a "
+                "record without its leading [CLS] (it reads a pad row or NaN there)" % nan_rows)
         if over or nan_rows:
             raise _lib.AnceRangeError(
                 "encoder range guard (%s mode): %d threads stored values above 65,504 in magnitude (the hi half of an fp16 pair "
@@ -323,6 +329,61 @@ def load_hf_state_dict(ckpt_dir):
     raise FileNotFoundError("no model.safetensors / pytorch_model.bin in %s" % ckpt_dir)
 
 
+SEED_PREFIX = "seed_encoder.encoder.sentence_encoder."
+_SEED_LAYER_KEYS = (  # fairseq name under layers.N. -> HF name under encoder.layer.N. (same [out, in] Linear layout)
+    ("self_attn.q_proj", "attention.self.query"), ("self_attn.k_proj", "attention.self.key"),
+    ("self_attn.v_proj", "attention.self.value"), ("self_attn.out_proj", "attention.output.dense"),
+    ("self_attn_layer_norm", "attention.output.LayerNorm"), ("fc1", "intermediate.dense"), ("fc2", "output.dense"),
+    ("final_layer_norm", "output.LayerNorm"),
+)
+
+
+def seed_state_dict(sd, prefix="seed."):
+    """SEEDEncoderDot_NLL_LN weights (model/models.py:201-221: a fairseq TransformerSentenceEncoder under
+    ``seed_encoder.encoder.sentence_encoder.`` + ``embeddingHead`` / ``norm``) under the names ``Encoder`` reads (``weight_names``
+    with ``prefix``), for ``ARCH_SEED``.  Pure: tensors are shared, not copied.  The encoder has no segment embedding
+    (num_segments=0), so the token-type row is zeros -- adding it is exact.  ``classification_heads.*``, ``decoder.*`` and
+    anything else outside the encoder and the head are ignored.  Raises KeyError on a missing weight, ValueError on a bad shape."""
+    import torch
+    src = SEED_PREFIX
+    if src + "embed_tokens.weight" not in sd:
+        raise KeyError("no '%sembed_tokens.weight' in state dict (not a SEED-Encoder checkpoint)" % src)
+    word = sd[src + "embed_tokens.weight"]
+    H = int(word.shape[-1])
+    if src + "layers.0.fc1.weight" not in sd:
+        raise KeyError("no '%slayers.*' weights in state dict" % src)
+    inter = int(sd[src + "layers.0.fc1.weight"].shape[0])
+    e = prefix + "embeddings."
+    out, want = {}, {}
+
+    def put(name, tensor, shape):
+        out[name], want[name] = tensor, shape
+
+    put(e + "word_embeddings.weight", word, (int(word.shape[0]), H))
+    pos = sd[src + "embed_positions.weight"]
+    put(e + "position_embeddings.weight", pos, (int(pos.shape[0]), H))
+    put(e + "token_type_embeddings.weight", torch.zeros(1, H, dtype=word.dtype), (1, H))
+    put(e + "LayerNorm.weight", sd[src + "emb_layer_norm.weight"], (H,))
+    put(e + "LayerNorm.bias", sd[src + "emb_layer_norm.bias"], (H,))
+    n = 0
+    while ("%slayers.%d.fc1.weight" % (src, n)) in sd:
+        for fs, hf in _SEED_LAYER_KEYS:
+            o = inter if fs == "fc1" else H
+            i = inter if fs == "fc2" else H
+            w_shape = (H,) if fs.endswith("layer_norm") else (o, i)
+            put("%sencoder.layer.%d.%s.weight" % (prefix, n, hf), sd["%slayers.%d.%s.weight" % (src, n, fs)], w_shape)
+            put("%sencoder.layer.%d.%s.bias" % (prefix, n, hf), sd["%slayers.%d.%s.bias" % (src, n, fs)], (o,))
+        n += 1
+    put("embeddingHead.weight", sd["embeddingHead.weight"], (768, H))
+    put("embeddingHead.bias", sd["embeddingHead.bias"], (768,))
+    put("norm.weight", sd["norm.weight"], (768,))
+    put("norm.bias", sd["norm.bias"], (768,))
+    for k, v in out.items():
+        if tuple(v.shape) != want[k]:
+            raise ValueError("SEED weight for %s has shape %s, expected %s" % (k, tuple(v.shape), want[k]))
+    return out
+
+
 def load_model(model_type, checkpoint_path, max_seq_length=128, max_tokens=65536, device=None, precision=None):
     """Registry of model/models.py:299-322 restricted to the encoders on the path.  precision: see ``Encoder``."""
     model_type = model_type.lower()
@@ -345,7 +406,25 @@ def load_model(model_type, checkpoint_path, max_seq_length=128, max_tokens=65536
         c = Encoder(sd, ARCH_BERT, "ctx_model.", False, max_seq_len=min(max_seq_length, 512), max_tokens=max_tokens,
                     device=device, precision=precision)
         return AnceModel(model_type, q, c)
-    raise ValueError("model_type %r is not on the MI355X path (supported: rdot_nll, rdot_nll_multi_chunk, dpr)" % model_type)
+    if model_type == "seeddot_nll":
+        # SEEDEncoderDot_NLL_LN: body_emb IS query_emb -- one tower, attention mask ignored (pad ids are masked by id)
+        sd = load_hf_state_dict(checkpoint_path)
+        cfg = read_config(checkpoint_path)
+        mapped = seed_state_dict(sd)
+        n_cfg = cfg.get("encoder_layers")
+        if n_cfg is not None and count_layers(mapped, "seed.") != int(n_cfg):
+            raise ValueError("config.json says encoder_layers=%d, the checkpoint has %d layers"
+                             % (int(n_cfg), count_layers(mapped, "seed.")))
+        pad = int(cfg.get("pad_token_id", 1))
+        max_pos, rows = cfg.get("max_positions"), int(mapped["seed.embeddings.position_embeddings.weight"].shape[0])
+        if max_pos is not None and rows != int(max_pos) + pad + 1:  # learned positions: max_positions + padding_idx + 1 rows
+            raise ValueError("config.json says max_positions=%d, the position table has %d rows (expected %d)"
+                             % (int(max_pos), rows, int(max_pos) + pad + 1))
+        enc = Encoder(mapped, ARCH_SEED, "seed.", True, pad_token_id=pad,
+                      max_seq_len=min(max_seq_length, 512), max_tokens=max_tokens, device=device, precision=precision)
+        return AnceModel(model_type, enc)
+    raise ValueError("model_type %r is not on the MI355X path (supported: rdot_nll, rdot_nll_multi_chunk, dpr, seeddot_nll)"
+                     % model_type)
 
 
 def read_config(ckpt_dir):

@@ -83,6 +83,11 @@ def load_tokenizer(args):
     factory = getattr(args, "tokenizer_factory", None)
     if factory is not None:
         return factory()
+    if args.model_type.startswith("seed"):
+        # the cache format is model-agnostic: caches written by the reference's own preprocess are consumed unchanged
+        raise ValueError("model_type %r: this project has no SEED-Encoder tokenizer -- produce the SEED caches with the "
+                         "reference's preprocess (data/msmarco_data.py with --model_type seeddot_nll) and point --data_dir at "
+                         "them" % args.model_type)
     import transformers
     cls = transformers.BertTokenizer if args.model_type.startswith("dpr") else transformers.RobertaTokenizer
     return cls.from_pretrained(args.model_name_or_path, do_lower_case=True, cache_dir=None)

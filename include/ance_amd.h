@@ -151,6 +151,11 @@ int ance_ip_score_rows(const float *d_x, int64_t n, const float *d_q, int64_t nq
 
 #define ANCE_ARCH_ROBERTA 0 /* positions = cumsum(id != pad) * (id != pad) + pad, type 0     */
 #define ANCE_ARCH_BERT 1    /* positions = 0..len-1, token type 0                              */
+#define ANCE_ARCH_SEED 2    /* SEED-Encoder (model/models.py:201-221): RoBERTa's tower, but every key whose id is the pad id is
+                               masked, inside the record's length too -- those tokens are dropped before the tower (exact: positions
+                               skip them); token-type row 0 must be zero (there is no segment embedding); n_chunks must be 1.  A
+                               record that is empty (ANCE_E_INVALID) or starts with the pad id (range-guard counter [1]) has no
+                               defined output */
 
 typedef struct AnceEncoderDesc {
     int32_t arch;         /* ANCE_ARCH_*                                                     */
@@ -239,7 +244,8 @@ int ance_encoder_precision(const AnceEncoder *enc);
  *   [0] threads of the split mode's pair-forming stages (embedding sum, Q | K | V, GELU output, residual stream) that saw a
  *       value above 65,504 in magnitude or a non-finite one -- the split mode's precondition is violated, the embeddings of
  *       that call are NOT fp32-grade (the fp16 hi half overflowed);
- *   [1] output rows (any mode) whose statistics are NaN or infinite.
+ *   [1] output rows (any mode) whose statistics are NaN or infinite; under ANCE_ARCH_SEED also the records that start with the
+ *       pad id (the reference's output for them is a pad row or NaN).
  * Enqueues on `stream` a copy of both to h_out (HOST pointer, uint32[2]; pinned memory keeps the copy asynchronous) and, if
  * reset != 0, zeroes them behind it.  Never synchronises: h_out is valid once `stream` has passed this point.
  */
