@@ -53,8 +53,9 @@
 namespace ance {
 namespace {
 
-constexpr int H = 768;          // hidden size this build is specialised for
-constexpr int HEAD_OUT = 768;   // embeddingHead output (model/models.py:145)
+// The hidden width H is a template parameter of every kernel and forward that depends on it: 768 (RoBERTa-base, BERT-base, SEED)
+// or 1024 (RoBERTa-large: ANCE_ARCH_ROBERTA with the head only, desc_ok).  Head dimension 64 at both.
+constexpr int HEAD_OUT = 768;   // embeddingHead output (model/models.py:145), at either width
 constexpr int S_CAP_MAX = 8192; // sequences per micro-batch
 constexpr int FETCH_CHUNK = 262144;
 constexpr int MAX_LANES = 2;     // activation sets / internal streams (3 and 4 lanes measured no gain: DESIGN.md 9)
@@ -273,13 +274,14 @@ __global__ void __launch_bounds__(256) pack_kernel(const PlanArgs P) {
 // pre / stats: fp32 rows and their (mean, rstd) (fp32 mode); or hi / lo / ldp: the fp16 pair of the pre-LayerNorm row with the slice
 // partials part -- pair_w = 0: two planes (fp16 mode, lo = fp16(v - hi)); pair_w = W: lo is null and hi points to pair rows of the
 // split mode (common.h: pair_hi_col / pair_lo_col)
+template <int H>
 __global__ void __launch_bounds__(256) head_kernel(const float *pre, const _Float16 *hi, const _Float16 *lo, int ldp, int pair_w,
                                                    const float *stats, const float *part, float eps, const float *lng, const float *lnb,
                                                    const int *seq_off, int compact, float *out, unsigned *faults) {
     const int s = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)(compact ? s : seq_off[s]);  // compact: row s already is the [CLS] row
     float mean_h, rstd_h;  // h = LN(pre), recomputed (file header)
-    if (part) stats_from_parts(part + row * 24, eps, &mean_h, &rstd_h);
+    if (part) stats_from_parts<H>(part + row * PART_FLOATS, eps, &mean_h, &rstd_h);
     else { mean_h = stats[2 * row]; rstd_h = stats[2 * row + 1]; }
     float *dst = out + (size_t)s * HEAD_OUT;
     auto src = [&](int j) {
@@ -290,6 +292,24 @@ __global__ void __launch_bounds__(256) head_kernel(const float *pre, const _Floa
     for (int j = tid; j < H; j += 256) dst[j] = (src(j) - mean_h) * rstd_h * lng[j] + lnb[j];
     // a NaN anywhere in the row (or an infinity: rstd 0) shows in its statistics: count the row (ance_encoder_range_faults [1])
     if (tid == 0 && faults && (!(fabsf(mean_h) < INFINITY) || !(rstd_h > 0.f && rstd_h < INFINITY))) atomicAdd(faults + 1, 1u);
+}
+
+// slice statistics of an embedding row (PartFormat): lanes 16 j .. 16 j + 15 hold the (mean, M2) of columns 256 k + 64 j .. + 63.
+// 768: one slice per 16 lanes; 1024: two adjacent 64-column halves merged into one 128-column slice (part_merge)
+template <int H>
+__device__ __forceinline__ void store_embed_part(float *part, int t, int k, int l, float m64, float q64) {
+    if constexpr (H == 1024) {
+        const float mo = __shfl_xor(m64, 16), qo = __shfl_xor(q64, 16);
+        if ((l & 31) == 0) {
+            float m, q;
+            part_merge(m64, q64, mo, qo, &m, &q);
+            *reinterpret_cast<float2 *>(part + (size_t)t * PART_FLOATS + (2 * k + (l >> 5)) * 2) = make_float2(m, q);
+        }
+    } else if ((l & 15) == 0) {
+        float *pp = part + ((size_t)t * 12 + 4 * k + (l >> 4)) * 2;  // (12 slices x 2 = PART_FLOATS)
+        pp[0] = m64;
+        pp[1] = q64;
+    }
 }
 
 // ---- fp16 mode: folded LayerNorm (file header) ------------------------------------------------------
@@ -305,8 +325,9 @@ __device__ __forceinline__ f32x4 pair_load(const _Float16 *hi, const _Float16 *l
     return f32x4{(float)h[0] + (float)r[0], (float)h[1] + (float)r[1], (float)h[2] + (float)r[2], (float)h[3] + (float)r[3]};
 }
 
-// embeddings -> (hi, lo) pair of the pre-LayerNorm row + the (mean, M2) of its twelve 64-column slices (the format the
-// RES epilogue leaves: gemm_f16.h); one wave per token, 16 lanes per slice
+// embeddings -> (hi, lo) pair of the pre-LayerNorm row + its slice statistics (the format the RES epilogue leaves: gemm_f16.h,
+// PartFormat); one wave per token, 16 lanes per 64 columns
+template <int H>
 __global__ void __launch_bounds__(256) embed_fold_kernel(const int *tok_id, const int *tok_pos, int Tpad, const float *word,
                                                          const float *pos, const float *type0, int vocab, int max_pos,
                                                          _Float16 *hi, _Float16 *lo, float *part) {
@@ -320,22 +341,19 @@ __global__ void __launch_bounds__(256) embed_fold_kernel(const int *tok_id, cons
     const f32x4 *p4 = reinterpret_cast<const f32x4 *>(pos + (size_t)p * H);
     const f32x4 *t4 = reinterpret_cast<const f32x4 *>(type0);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int c4 = k * 64 + l;  // columns 4 c4 .. 4 c4 + 3: slice 4 k + l / 16
+    for (int k = 0; k < H / 256; ++k) {
+        const int c4 = k * 64 + l;  // columns 4 c4 .. 4 c4 + 3
         const f32x4 v = (w4[c4] + t4[c4]) + p4[c4];  // same association as the reference: (word + type) + pos
         split_store(v, hi + (size_t)t * H, lo + (size_t)t * H, c4);
         const float m64 = row16_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
         const float d0 = v[0] - m64, d1 = v[1] - m64, d2 = v[2] - m64, d3 = v[3] - m64;
         const float q64 = row16_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-        if ((l & 15) == 0) {
-            float *pp = part + ((size_t)t * 12 + 4 * k + (l >> 4)) * 2;
-            pp[0] = m64;
-            pp[1] = q64;
-        }
+        store_embed_part<H>(part, t, k, l, m64, q64);
     }
 }
 
 // last layer, CLS-only tail: compact (hi, lo, slice partials) rows of the [CLS] tokens; rows S..S_pad zeroed
+template <int H>
 __global__ void __launch_bounds__(256) gather_cls_fold_kernel(const _Float16 *hi, const _Float16 *lo, const float *part,
                                                               const int *seq_off, int S, int S_pad, _Float16 *chi, _Float16 *clo,
                                                               float *cpart) {
@@ -347,24 +365,26 @@ __global__ void __launch_bounds__(256) gather_cls_fold_kernel(const _Float16 *hi
         const size_t row = (size_t)seq_off[s];
         const f16x4 *sh = reinterpret_cast<const f16x4 *>(hi + row * H), *sl = reinterpret_cast<const f16x4 *>(lo + row * H);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < H / 256; ++k) {
             dh[k * 64 + l] = sh[k * 64 + l];
             dl[k * 64 + l] = sl[k * 64 + l];
         }
-        if (l < 24) cpart[(size_t)s * 24 + l] = part[row * 24 + l];
+        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = part[row * PART_FLOATS + l];
     } else {
         const f16x4 z = {0, 0, 0, 0};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < H / 256; ++k) {
             dh[k * 64 + l] = z;
             dl[k * 64 + l] = z;
         }
-        if (l < 24) cpart[(size_t)s * 24 + l] = (l & 1) ? 64.0f : 0.f;  // mean 0, variance 1: a finite rstd
+        // mean 0, variance 1: a finite rstd
+        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = (l & 1) ? (float)PartFormat<H>::COLS : 0.f;
     }
 }
 
-// weight load with the LayerNorm folded in (K = 768 columns): W16[n][k] = fp16(gamma[k] W[n][k]),
+// weight load with the LayerNorm folded in (K = H columns): W16[n][k] = fp16(gamma[k] W[n][k]),
 // csum[n] = sum_k W16[n][k] (over the ROUNDED values), bout[n] = b[n] + sum_k beta[k] W[n][k].  One wave per row.
+template <int H>
 __global__ void __launch_bounds__(256) fold_weight_kernel(const float *W, const float *b, const float *gamma, const float *beta,
                                                           int N, _Float16 *W16, float *csum, float *bout) {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -373,7 +393,7 @@ __global__ void __launch_bounds__(256) fold_weight_kernel(const float *W, const 
     const f32x4 *w4 = reinterpret_cast<const f32x4 *>(W + (size_t)n * H);
     float cs = 0.f, bs = 0.f;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < H / 256; ++k) {
         const int c4 = k * 64 + l;
         const f32x4 w = w4[c4], g = reinterpret_cast<const f32x4 *>(gamma)[c4], be = reinterpret_cast<const f32x4 *>(beta)[c4];
         const f16x4 h = f16x4{(_Float16)(g[0] * w[0]), (_Float16)(g[1] * w[1]), (_Float16)(g[2] * w[2]), (_Float16)(g[3] * w[3])};
@@ -393,7 +413,7 @@ __global__ void __launch_bounds__(256) fold_weight_kernel(const float *W, const 
 }
 
 // ---- split mode ---------------------------------------------------------------------------------
-constexpr int HP = 2 * H;  // halves per pair row of a 768-wide stream (common.h: blocked [hi (32) | lo (32)] column blocks)
+// (a pair row of an H-wide stream has 2 H halves: common.h, blocked [hi (32) | lo (32)] column blocks)
 
 // embeddings -> pair rows of the pre-LayerNorm stream + the slice statistics (format of EPI_S_RESLN); one wave per token.
 // The row is stored times EMB_SCALE: the lo half of a pair is unscaled (common.h), i.e. good to 2^-25 ABSOLUTE, which is fp32-grade for
@@ -402,6 +422,7 @@ constexpr int HP = 2 * H;  // halves per pair row of a 768-wide stream (common.h
 // 0's Q | K | V GEMM and the residual of its attention-output GEMM) run with eps EMB_SCALE^2 -- powers of two, so (v s - mean s) and
 // rstd / s are the unscaled values' bits.
 constexpr float EMB_SCALE = 16.0f;
+template <int H>
 __global__ void __launch_bounds__(256) embed_split_kernel(const int *tok_id, const int *tok_pos, int Tpad, const float *word,
                                                           const float *pos, const float *type0, int vocab, int max_pos,
                                                           _Float16 *xp, float *part, unsigned *faults) {
@@ -416,19 +437,15 @@ __global__ void __launch_bounds__(256) embed_split_kernel(const int *tok_id, con
     const f32x4 *t4 = reinterpret_cast<const f32x4 *>(type0);
     float mx = 0.f;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < H / 256; ++k) {
         const int c4 = k * 64 + l;
         const f32x4 v = ((w4[c4] + t4[c4]) + p4[c4]) * EMB_SCALE;  // same association as the reference: (word + type) + pos
         range_track4(v, &mx);
-        pair_store4(v, xp + (size_t)t * HP, H, c4 * 4);
+        pair_store4(v, xp + (size_t)t * 2 * H, H, c4 * 4);
         const float m64 = row16_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
         const float d0 = v[0] - m64, d1 = v[1] - m64, d2 = v[2] - m64, d3 = v[3] - m64;
         const float q64 = row16_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-        if ((l & 15) == 0) {
-            float *pp = part + ((size_t)t * 12 + 4 * k + (l >> 4)) * 2;
-            pp[0] = m64;
-            pp[1] = q64;
-        }
+        store_embed_part<H>(part, t, k, l, m64, q64);
     }
     range_report(mx, faults);
 }
@@ -497,34 +514,41 @@ __global__ void __launch_bounds__(256) split_weight_kernel(const float *W, const
 }
 
 // last layer, CLS-only tail in split mode: compact pair rows + slice partials of the [CLS] tokens; rows S..S_pad zeroed
+template <int H>
 __global__ void __launch_bounds__(256) gather_cls_split_kernel(const _Float16 *xp, const float *part, const int *seq_off, int S,
                                                                int S_pad, _Float16 *cxp, float *cpart) {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int l = threadIdx.x & 63;
     if (s >= S_pad) return;
+    constexpr int HP = 2 * H;
     f16x8 *d = reinterpret_cast<f16x8 *>(cxp + (size_t)s * HP);
     if (s < S) {
         const size_t row = (size_t)seq_off[s];
         const f16x8 *sp = reinterpret_cast<const f16x8 *>(xp + row * HP);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) d[k * 64 + l] = sp[k * 64 + l];
-        if (l < 24) cpart[(size_t)s * 24 + l] = part[row * 24 + l];
+        for (int k = 0; k < H / 256; ++k) d[k * 64 + l] = sp[k * 64 + l];
+        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = part[row * PART_FLOATS + l];
     } else {
         const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) d[k * 64 + l] = z;
-        if (l < 24) cpart[(size_t)s * 24 + l] = (l & 1) ? 64.0f : 0.f;  // mean 0, variance 1: a finite rstd
+        for (int k = 0; k < H / 256; ++k) d[k * 64 + l] = z;
+        // mean 0, variance 1: a finite rstd
+        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = (l & 1) ? (float)PartFormat<H>::COLS : 0.f;
     }
 }
 
 // ---- embeddingHead as one fp32 MFMA GEMM over the [CLS] rows (model/models.py:145-152) ----------
 // z[s][n] = sum_k LN(cls_s)[k] W[n][k] + b[n]; 32 sequences x 128 features per workgroup, one 32 x 32 tile per wave
 // (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation in k order).  The 32 normalised [CLS] rows are staged
-// once in LDS (96.5 KiB); W rows stream from L2 as 16-byte pieces per lane.  A block per sequence re-read the whole
-// 2.36 MB W (2 GB of L2 reads per 883 rows, 166 us); this reads it 28 times.
+// once in LDS (96.5 KiB at H = 768, 128.5 KiB at 1024); W rows stream from L2 as 16-byte pieces per lane.  A block per sequence
+// re-read the whole 2.36 MB W (2 GB of L2 reads per 883 rows, 166 us); this reads it 28 times.
+template <int H>
 constexpr int HEAD_LDA = H + 4;  // floats; 16 lanes x stride 4 banks: conflict-free ds_read_b128
-constexpr size_t HEAD_LDS_BYTES = (size_t)32 * HEAD_LDA * sizeof(float);
+template <int H>
+constexpr size_t HEAD_LDS_BYTES = (size_t)32 * HEAD_LDA<H> * sizeof(float);
+static_assert(HEAD_LDS_BYTES<1024> <= 160 * 1024, "head GEMM LDS at hidden 1024");
 
+template <int H>
 __global__ void __launch_bounds__(256) head_gemm_kernel(const float *pre32, const _Float16 *hi, const _Float16 *lo, int ldp,
                                                         int pair_w, const float *stats, const float *part, float eps, const float *lng,
                                                         const float *lnb, const int *seq_off, int compact, int S, const float *W,
@@ -535,14 +559,14 @@ __global__ void __launch_bounds__(256) head_gemm_kernel(const float *pre32, cons
     // stage LN(pre)[cls] of 32 sequences: wave w takes rows w, w + 4, ...
     for (int r = w; r < 32; r += 4) {
         const int s = s0 + r;
-        f32x4 *dst = reinterpret_cast<f32x4 *>(cls + r * HEAD_LDA);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(cls + r * HEAD_LDA<H>);
         if (s < S) {
             const size_t row = (size_t)(compact ? s : seq_off[s]);
             float mean, rstd;
-            if (part) stats_from_parts(part + row * 24, eps, &mean, &rstd);  // (every lane: 24 cached floats)
+            if (part) stats_from_parts<H>(part + row * PART_FLOATS, eps, &mean, &rstd);  // (every lane: 24 cached floats)
             else { mean = stats[2 * row]; rstd = stats[2 * row + 1]; }
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
+            for (int k = 0; k < H / 256; ++k) {
                 const int c4 = k * 64 + l;
                 const f32x4 x = !hi      ? reinterpret_cast<const f32x4 *>(pre32 + row * H)[c4]
                                 : pair_w ? pair_load4(hi + row * ldp, pair_w, c4 * 4)   // split mode: pair rows (see head_kernel)
@@ -552,13 +576,13 @@ __global__ void __launch_bounds__(256) head_gemm_kernel(const float *pre32, cons
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) dst[k * 64 + l] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < H / 256; ++k) dst[k * 64 + l] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
     __syncthreads();
     // MFMA rows (A operand) = sequences, columns (B operand) = features n0 + 32 w + i; k-step j of a 16-byte piece uses
     // k = 8 s' + 4 g + j on both sides
-    const float *ap = cls + i * HEAD_LDA + 4 * g;
+    const float *ap = cls + i * HEAD_LDA<H> + 4 * g;
     const float *wp = W + (size_t)(n0 + 32 * w + i) * H + 4 * g;
     f32x16 acc = {0};
 #pragma unroll 4
@@ -696,7 +720,7 @@ struct AnceEncoder {
         _Float16 *qk16, *vt16, *ctx16, *ffn16;
         int4 *desc;              // attention descriptors in length-bucket order
         float *x32, *xa32, *qkv32, *ctx32, *ffn32;  // fp32 path only: hidden states, Q|K|V, attention output, FFN activation
-        float *partA, *partB;    // folded LayerNorm: (mean, M2) of the twelve 64-column slices of every row of the two streams
+        float *partA, *partB;    // folded LayerNorm: slice statistics of every row of the two streams (gemm_f16.h: PartFormat)
         // fp16 / split paths: preA / preB hold the fp16 pairs of the stream instead of fp32 rows
         _Float16 *xa_hi() const { return reinterpret_cast<_Float16 *>(preA); }
         _Float16 *xb_hi() const { return reinterpret_cast<_Float16 *>(preB); }
@@ -711,8 +735,13 @@ struct AnceEncoder {
 
 namespace {
 
+// Shapes (include/ance_amd.h): head dimension 64 and hidden 768 (every arch), or hidden 1024 for RoBERTa with the ANCE head only --
+// DPR's BiEncoder is BERT-base and SEED's config is base width; a head-less large tower would change the output width.  At 1024 the
+// FFN GEMMs also need intermediate % 256 (N of FFN1 is a whole number of 256-column tiles).
 bool desc_ok(const AnceEncoderDesc *d) {
-    return d && d->hidden == H && d->n_heads == 12 && d->intermediate > 0 && d->intermediate % 128 == 0 &&
+    if (!d || d->n_heads <= 0 || d->hidden != 64 * d->n_heads || (d->hidden != 768 && d->hidden != 1024)) return false;
+    if (d->hidden == 1024 && (d->arch != ANCE_ARCH_ROBERTA || d->has_head != 1 || d->intermediate % 256 != 0)) return false;
+    return d->intermediate > 0 && d->intermediate % 128 == 0 &&
            d->n_layers >= 1 && d->vocab_size > 0 && d->max_position > 0 && d->max_seq_len >= 1 &&
            d->max_seq_len <= 512 && d->max_tokens >= 512 && d->max_tokens % 256 == 0 && d->precision >= 0 && d->precision <= 3 &&
            (d->arch == ANCE_ARCH_ROBERTA || d->arch == ANCE_ARCH_BERT || d->arch == ANCE_ARCH_SEED);
@@ -720,6 +749,7 @@ bool desc_ok(const AnceEncoderDesc *d) {
 
 void layout_weights(const AnceEncoderDesc *d, Arena &a, AnceEncoder *e) {
     const size_t I = d->intermediate;
+    const int H = d->hidden, HP = 2 * H;
     const int mode = resolve_precision(d);
     float *word = a.take<float>((size_t)d->vocab_size * H);
     float *pos = a.take<float>((size_t)d->max_position * H);
@@ -783,6 +813,7 @@ void layout_workspace(const AnceEncoderDesc *d, Arena &a, AnceEncoder *e) {
     const int scap = tcap < S_CAP_MAX ? tcap : S_CAP_MAX;
     const int vcap = (int)align_up((size_t)tcap + tcap / 4 + 256, 256);
     const int mode = resolve_precision(d);
+    const int H = d->hidden;
     unsigned *faults = a.take<unsigned>(64);  // [0] out-of-range stores of the split mode, [1] NaN output rows (ance_encoder_range_faults)
     int *lens_fetch = a.take<int>(FETCH_CHUNK);
     if (e) {
@@ -800,8 +831,8 @@ void layout_workspace(const AnceEncoderDesc *d, Arena &a, AnceEncoder *e) {
         L.vt16 = a.take<_Float16>((size_t)H * vcap);
         L.ctx16 = a.take<_Float16>((size_t)tcap * H);
         L.ffn16 = a.take<_Float16>((size_t)tcap * d->intermediate);
-        L.partA = a.take<float>((size_t)tcap * (H / 64) * 2);
-        L.partB = a.take<float>((size_t)tcap * (H / 64) * 2);
+        L.partA = a.take<float>((size_t)tcap * PART_FLOATS);
+        L.partB = a.take<float>((size_t)tcap * PART_FLOATS);
         L.x32 = L.xa32 = L.qkv32 = L.ctx32 = L.ffn32 = nullptr;
         if (mode == ANCE_PRECISION_FP32) {
             L.x32 = a.take<float>((size_t)tcap * H);
@@ -839,30 +870,32 @@ struct MicroBatch {
 // The output of the encoder from the last layer's LayerNorm of the [CLS] rows: the embeddingHead as one MFMA GEMM + its
 // LayerNorm (has_head), or those rows as they are (DPR's BERT).  pre / stats: fp32 rows and their (mean, rstd); hi / lo / ldp /
 // pair_w / part: the fp16 pair form (head_kernel); compact: row s already is the [CLS] row of sequence s.
+template <int H>
 void encoder_output(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb, const float *pre,
                     const _Float16 *hi, const _Float16 *lo, int ldp, int pair_w, const float *stats, const float *part, int compact) {
     const AnceEncoderDesc &D = e->d;
     const LayerW &WL = e->layers[D.n_layers - 1];
     ProfScope ps(PC_HEAD, st);
     if (D.has_head) {
-        hipLaunchKernelGGL(head_gemm_kernel, dim3((mb.S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES, st, pre, hi, lo, ldp,
+        hipLaunchKernelGGL(head_gemm_kernel<H>, dim3((mb.S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES<H>, st, pre, hi, lo, ldp,
                            pair_w, stats, part, D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off, compact, mb.S, e->head_w, e->head_b, mb.out);
         hipLaunchKernelGGL(head_ln_kernel, dim3((mb.S + 3) / 4), dim3(256), 0, st, mb.out, mb.S, e->norm_w, e->norm_b, e->faults);
     } else {
-        hipLaunchKernelGGL(head_kernel, dim3(mb.S), dim3(256), 0, st, pre, hi, lo, ldp, pair_w, stats, part, D.ln_eps, WL.ln2w, WL.ln2b,
+        hipLaunchKernelGGL(head_kernel<H>, dim3(mb.S), dim3(256), 0, st, pre, hi, lo, ldp, pair_w, stats, part, D.ln_eps, WL.ln2w, WL.ln2b,
                            LN.seq_off, compact, mb.out, e->faults);
     }
 }
 
 // ---- fp32 mode (precise32.h): plain sequence of fp32 kernels, every layer on every token ----
+template <int H>
 int forward_fp32(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
     const AnceEncoderDesc &D = e->d;
     const int I = D.intermediate, T = mb.T, Tpad = mb.Tpad;
     {
         ProfScope pe(PC_EMBED, st);
-        hipLaunchKernelGGL(embed32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
+        hipLaunchKernelGGL(embed32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
                            e->type0, D.vocab_size, D.max_position, LN.preB);
-        hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, e->eln_w, e->eln_b, D.ln_eps,
+        hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, e->eln_w, e->eln_b, D.ln_eps,
                            LN.x32, (float *)nullptr);
     }
     int rc = ANCE_OK;
@@ -886,7 +919,7 @@ int forward_fp32(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
         if (rc) break;
         {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preA, Tpad, W.ln1w, W.ln1b, D.ln_eps, LN.xa32,
+            hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.preA, Tpad, W.ln1w, W.ln1b, D.ln_eps, LN.xa32,
                                (float *)nullptr);
         }
         {
@@ -901,24 +934,26 @@ int forward_fp32(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
         if (rc) break;
         {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(ln32_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, W.ln2w, W.ln2b, D.ln_eps, LN.x32,
+            hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, W.ln2w, W.ln2b, D.ln_eps, LN.x32,
                                last ? LN.statsB : (float *)nullptr);
         }
     }
     if (rc) return rc;
-    encoder_output(e, LN, st, mb, LN.preB, nullptr, nullptr, H, 0, LN.statsB, nullptr, 0);
+    encoder_output<H>(e, LN, st, mb, LN.preB, nullptr, nullptr, H, 0, LN.statsB, nullptr, 0);
     return ANCE_OK;
 }
 
 // ---- split (fp32-grade) mode: the fp16 mode's schedule with pair operands and the fp32 attention ----
+template <int H>
 int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
+    constexpr int HP = 2 * H;
     const AnceEncoderDesc &D = e->d;
     const int I = D.intermediate, S = mb.S, T = mb.T, Tpad = mb.Tpad;
     _Float16 *const xa = reinterpret_cast<_Float16 *>(LN.preA), *const xb = reinterpret_cast<_Float16 *>(LN.preB);
     _Float16 *const ctxp = reinterpret_cast<_Float16 *>(LN.ctx32), *const ffnp = reinterpret_cast<_Float16 *>(LN.ffn32);
     {
         ProfScope pe(PC_EMBED, st);
-        hipLaunchKernelGGL(embed_split_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word,
+        hipLaunchKernelGGL(embed_split_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word,
                            e->pos, e->type0, D.vocab_size, D.max_position, xb, LN.partB, e->faults);
     }
     const bool cls_tail = e->cls_tail;
@@ -946,7 +981,7 @@ int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, c
         float *const cpt = reinterpret_cast<float *>(ffnp + (size_t)S_pad * HP);  // (the FFN buffer is dead here)
         if (tail) {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(gather_cls_split_kernel, dim3(S_pad / 4), dim3(256), 0, st, xb, LN.partB, LN.seq_off, S, S_pad,
+            hipLaunchKernelGGL(gather_cls_split_kernel<H>, dim3(S_pad / 4), dim3(256), 0, st, xb, LN.partB, LN.seq_off, S, S_pad,
                                ffnp, cpt);
         }
         {
@@ -954,12 +989,12 @@ int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, c
             if (tail) {
                 G.B = W.wqkv_s + (size_t)H * HP; G.N = 2 * H; G.bias = W.bqkv_s + H; G.csum = W.cqkv_s + H;
                 G.out32 = LN.qkv32 + H;
-                rc = launch_gemm_f16(EPI_S_QKV, G, st);
+                rc = launch_gemm_f16(EPI_S_QKV, G, st, H);
                 G.A = ffnp; G.part_in = cpt; G.M = S_pad;
                 G.B = W.wqkv_s; G.N = H; G.bias = W.bqkv_s; G.csum = W.cqkv_s; G.out32 = LN.qkv32;
-                if (!rc) rc = launch_gemm_f16(EPI_S_QKV, G, st);
+                if (!rc) rc = launch_gemm_f16(EPI_S_QKV, G, st, H);
             } else {
-                rc = launch_gemm_f16(EPI_S_QKV, G, st);
+                rc = launch_gemm_f16(EPI_S_QKV, G, st, H);
             }
         }
         if (rc) break;
@@ -983,7 +1018,7 @@ int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, c
         G.bias = W.bo; G.out16 = xa; G.ldc = HP; G.part_out = LN.partA; G.wscale_inv = W.sc_s + 5;
         {
             ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
-            rc = launch_gemm_f16(EPI_S_RESLN, G, st);
+            rc = launch_gemm_f16(EPI_S_RESLN, G, st, H);
         }
         if (rc) break;
         // intermediate.dense + exact GELU (attention.output.LayerNorm folded in)
@@ -994,7 +1029,7 @@ int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, c
         G.range_faults = e->faults;
         {
             ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_S_GELU, G, st);
+            rc = launch_gemm_f16(EPI_S_GELU, G, st, H);
         }
         if (rc) break;
         // output.dense + residual LayerNorm(x_a)
@@ -1005,15 +1040,16 @@ int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, c
         G.range_faults = e->faults;
         {
             ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_S_RESLN, G, st);
+            rc = launch_gemm_f16(EPI_S_RESLN, G, st, H);
         }
     }
     if (rc) return rc;
-    encoder_output(e, LN, st, mb, nullptr, xb, nullptr, HP, H, nullptr, LN.partB, cls_tail ? 1 : 0);
+    encoder_output<H>(e, LN, st, mb, nullptr, xb, nullptr, HP, H, nullptr, LN.partB, cls_tail ? 1 : 0);
     return ANCE_OK;
 }
 
 // ---- fp16 mode: the folded-LayerNorm forward of the file header ----
+template <int H>
 int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
     const AnceEncoderDesc &D = e->d;
     const int I = D.intermediate, S = mb.S, T = mb.T, Tpad = mb.Tpad;
@@ -1022,7 +1058,7 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
     _Float16 *const xb_hi = LN.xb_hi(), *const xb_lo = xb_hi + (size_t)e->tcap * H;
     {
         ProfScope pe(PC_EMBED, st);
-        hipLaunchKernelGGL(embed_fold_kernel, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
+        hipLaunchKernelGGL(embed_fold_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
                            e->type0, D.vocab_size, D.max_position, xb_hi, xb_lo, LN.partB);
     }
     // Only the [CLS] row of the last layer reaches the head (model/models.py:49,152): after the
@@ -1048,7 +1084,7 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
         float *const cpt = reinterpret_cast<float *>(clo + (size_t)S_pad * H);
         if (tail) {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(gather_cls_fold_kernel, dim3(S_pad / 4), dim3(256), 0, st, xb_hi, xb_lo, LN.partB, LN.seq_off,
+            hipLaunchKernelGGL(gather_cls_fold_kernel<H>, dim3(S_pad / 4), dim3(256), 0, st, xb_hi, xb_lo, LN.partB, LN.seq_off,
                                S, S_pad, chi, clo, cpt);
         }
         int rc;
@@ -1056,12 +1092,12 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
             ProfScope ps(PC_GEMM_QK, st, tail ? 2.0 * T * (double)H * H + 2.0 * S * (double)H * H : 2.0 * T * (2.0 * H) * H);
             if (tail) {
                 G.B = W.wqk + (size_t)H * H; G.N = H; G.bias = W.bqk + H; G.csum = W.cqk + H; G.out16 = LN.qk16 + H; G.scale_cols = 0;
-                rc = launch_gemm_f16(EPI_QK_F, G, st);
+                rc = launch_gemm_f16(EPI_QK_F, G, st, H);
                 G.A = chi; G.tok_lo = clo; G.part_in = cpt; G.M = S_pad;
                 G.B = W.wqk; G.bias = W.bqk; G.csum = W.cqk; G.out16 = LN.qk16; G.scale_cols = H;
-                if (!rc) rc = launch_gemm_f16(EPI_QK_F, G, st);
+                if (!rc) rc = launch_gemm_f16(EPI_QK_F, G, st, H);
             } else {
-                rc = launch_gemm_f16(EPI_QK_F, G, st);
+                rc = launch_gemm_f16(EPI_QK_F, G, st, H);
             }
         }
         if (rc) return rc;
@@ -1072,7 +1108,7 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
         G.part_in = LN.partB; G.ln_eps = D.ln_eps; G.csum = W.cv; G.tok_lo = xb_lo;
         {
             ProfScope ps(PC_GEMM_VT, st, 2.0 * T * (double)H * H);
-            rc = launch_gemm_f16(EPI_VT_F, G, st);
+            rc = launch_gemm_f16(EPI_VT_F, G, st, H);
         }
         if (rc) return rc;
         AttnArgs A;
@@ -1097,7 +1133,7 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
         G.bias = W.bo; G.ldc = H;
         {
             ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
-            rc = launch_gemm_f16(EPI_RESLN, G, st);
+            rc = launch_gemm_f16(EPI_RESLN, G, st, H);
         }
         if (rc) return rc;
         // intermediate.dense + GELU
@@ -1107,7 +1143,7 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
         G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.csum = W.c1; G.tok_lo = xa_lo; G.n_split = n_split;
         {
             ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_GELU_F, G, st);
+            rc = launch_gemm_f16(EPI_GELU_F, G, st, H);
         }
         if (rc) return rc;
         // output.dense + residual
@@ -1118,11 +1154,11 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
         G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.part_out = LN.partB;
         {
             ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_RESLN, G, st);
+            rc = launch_gemm_f16(EPI_RESLN, G, st, H);
         }
         if (rc) return rc;
     }
-    encoder_output(e, LN, st, mb, nullptr, xb_hi, xb_lo, H, 0, nullptr, LN.partB, cls_tail ? 1 : 0);
+    encoder_output<H>(e, LN, st, mb, nullptr, xb_hi, xb_lo, H, 0, nullptr, LN.partB, cls_tail ? 1 : 0);
     return ANCE_OK;
 }
 
@@ -1223,9 +1259,10 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
             MicroBatch mb;
             mb.S = S; mb.T = T; mb.Tpad = Tpad; mb.ldvt = ldvt; mb.maxlen = maxlen;
             mb.out = d_out + (size_t)(r0 * n_chunks + gs) * HEAD_OUT;
-            const int rc = e->mode == ANCE_PRECISION_FP32    ? forward_fp32(e, LN, st, mb)
-                           : e->mode == ANCE_PRECISION_SPLIT ? forward_split(e, LN, st, mb)
-                                                             : forward_fp16(e, LN, st, mb);
+            const bool large = D.hidden == 1024;  // desc_ok: 768 or 1024
+            const int rc = e->mode == ANCE_PRECISION_FP32    ? (large ? forward_fp32<1024>(e, LN, st, mb) : forward_fp32<768>(e, LN, st, mb))
+                           : e->mode == ANCE_PRECISION_SPLIT ? (large ? forward_split<1024>(e, LN, st, mb) : forward_split<768>(e, LN, st, mb))
+                                                             : (large ? forward_fp16<1024>(e, LN, st, mb) : forward_fp16<768>(e, LN, st, mb));
             if (rc) return rc;
             gs = g;
         }
@@ -1305,8 +1342,11 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
             return check_launch("ance_encoder_create: streams");
         }
     }
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(head_gemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)HEAD_LDS_BYTES) != hipSuccess) {  // per device: set for the device this handle lives on
+    const int H = desc->hidden, HP = 2 * H;
+    if ((H == 1024 ? hipFuncSetAttribute(reinterpret_cast<const void *>(head_gemm_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)HEAD_LDS_BYTES<1024>)
+                   : hipFuncSetAttribute(reinterpret_cast<const void *>(head_gemm_kernel<768>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)HEAD_LDS_BYTES<768>)) != hipSuccess) {  // per device: set for the device this handle lives on
         delete e;
         return check_launch("ance_encoder_create: head attr");
     }
@@ -1340,7 +1380,7 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
         if (e->mode == ANCE_PRECISION_FP16) {
             auto foldw = [&](const void *W, const void *b, const float *g, const float *be, int N, _Float16 *W16, float *cs,
                              float *bo) {
-                hipLaunchKernelGGL(fold_weight_kernel, dim3((N + 3) / 4), dim3(256), 0, st, (const float *)W, (const float *)b, g,
+                hipLaunchKernelGGL(H == 1024 ? fold_weight_kernel<1024> : fold_weight_kernel<768>, dim3((N + 3) / 4), dim3(256), 0, st, (const float *)W, (const float *)b, g,
                                    be, N, W16, cs, bo);
             };
             foldw(p[0], p[1], gin, bin, H, L.wqk, L.cqk, L.bqk);                                     // query

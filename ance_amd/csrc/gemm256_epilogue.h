@@ -88,12 +88,13 @@ __device__ __forceinline__ void epb_issue(const GemmArgs &G, float *smem_f, int 
 // |mean| rstd > FOLD_WIDE_MEAN: the single-fp16 token operand of the folded GEMMs rounds v, not v - mean, so its error grows
 // with |mean| / std (20-80 x at an offset of 5-30 std); such a tile adds a second pass over the lo halves.
 constexpr float FOLD_WIDE_MEAN = 2.0f;
+template <int HW>
 __device__ __forceinline__ bool epb_stats(const GemmArgs &G, float *smem_f, int tid) {
     float *pb = smem_f + EPB_OFF;
     int wide = 0;
     if (tid < 256) {
         float mean, rstd;
-        stats_from_parts(pb + EPB_PART + tid * 24, G.ln_eps, &mean, &rstd);
+        stats_from_parts<HW>(pb + EPB_PART + tid * PART_FLOATS, G.ln_eps, &mean, &rstd);
         pb[EPB_STATS + 2 * tid] = mean;
         pb[EPB_STATS + 2 * tid + 1] = rstd;
         wide = __builtin_fabsf(mean) * rstd > FOLD_WIDE_MEAN;
@@ -101,7 +102,22 @@ __device__ __forceinline__ bool epb_stats(const GemmArgs &G, float *smem_f, int 
     return __builtin_amdgcn_readfirstlane(__syncthreads_or(wide)) != 0;  // (readfirstlane: the compiler must know it is uniform)
 }
 
-template <int EPI_, bool WAVE_SYNC = false>
+// Hidden 1024 (PartFormat<1024>): the RES epilogues leave 128-column slice statistics, but a wave owns 64 columns.  Each wave parks
+// the (mean, M2) of its 64 columns of every row in the parameter block's partial area (dead once epb_stats has run: its barrier
+// comes after the last read), and after one workgroup barrier thread t merges the two halves of slice t & 1 of tile row t >> 1.
+__device__ __forceinline__ void epb_park_part(float *smem_f, int row_local, int wn, float mean, float m2) {
+    *reinterpret_cast<float2 *>(smem_f + EPB_OFF + EPB_PART + (row_local * 4 + wn) * 2) = make_float2(mean, m2);
+}
+__device__ __forceinline__ void epb_merge_parts(const GemmArgs &G, const float *smem_f, int m0, int n0, int tid) {
+    __syncthreads();
+    const int r = tid >> 1, hf = tid & 1;
+    const f32x4 ab = *reinterpret_cast<const f32x4 *>(smem_f + EPB_OFF + EPB_PART + (r * 4 + 2 * hf) * 2);
+    float m, q;
+    part_merge(ab[0], ab[1], ab[2], ab[3], &m, &q);
+    *reinterpret_cast<float2 *>(G.part_out + (size_t)(m0 + r) * PART_FLOATS + ((n0 >> 7) + hf) * 2) = make_float2(m, q);
+}
+
+template <int EPI_, bool WAVE_SYNC = false, int HW = 768>
 __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc)[2][4], float *smem_f, int m0, int n0,
                                                  int w, int l, unsigned long long *pass_stamps = nullptr) {
     _Float16 *smem = reinterpret_cast<_Float16 *>(smem_f);
@@ -279,7 +295,12 @@ __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc
             for (int it = 0; it < 8; ++it) q8[it] += __builtin_amdgcn_update_dpp(0.f, q8[it], 0x124, 0xF, 0xF, true);
 #pragma unroll
             for (int it = 0; it < 8; ++it) q8[it] += __builtin_amdgcn_update_dpp(0.f, q8[it], 0x128, 0xF, 0xF, true);
-            if (c4 == 0) {
+            if constexpr (HW == 1024) {
+                if (c4 == 0) {
+#pragma unroll
+                    for (int it = 0; it < 8; ++it) epb_park_part(smem_f, wm * 128 + y * 32 + it * 4 + (l >> 4), wn, s8[it], q8[it]);
+                }
+            } else if (c4 == 0) {
                 float *pp = G.part_out + (row0 * n_parts + slice) * 2;
                 const size_t pstep = (size_t)4 * n_parts * 2;
 #pragma unroll
@@ -289,6 +310,7 @@ __device__ __forceinline__ void gemm256_epilogue(const GemmArgs &G, f32x16 (&acc
             if (pass_stamps && w == 0 && l == 0) pass_stamps[y] = __builtin_amdgcn_s_memrealtime();
 #endif
         }
+        if constexpr (HW == 1024) epb_merge_parts(G, smem_f, m0, n0, w * 64 + l);
     } else {
         // fp16 outputs: slab [64 m][64 n] halves, row stride 72 halves (144 B); 2 passes
         _Float16 *slab = smem + w * 8192;  // 16 KiB per wave
@@ -441,7 +463,7 @@ __device__ __forceinline__ float sumsq8(const f32x4 a, const f32x4 b, float m) {
 // Columns per lane on read-back: 8 for the pair-row outputs (16-byte hi and 16-byte lo accesses: 4 lanes write the 64 + 64 bytes of a
 // pair block), 4 for the fp32 rows of QKV (16 lanes write 256 contiguous bytes; with 8 columns a lane's two 16-byte stores would
 // interleave with its neighbours' -- measured +3.5 % on that GEMM).
-template <int EPI>
+template <int EPI, int HW = 768>
 __device__ __forceinline__ void gemm256_epilogue_split(const GemmArgs &G, f32x16 (&acc)[2][4], float *smem_f, int m0, int n0,
                                                        int w, int l, float winv) {
 #pragma clang fp contract(off)
@@ -536,10 +558,14 @@ __device__ __forceinline__ void gemm256_epilogue_split(const GemmArgs &G, f32x16
             static_assert(ITS == 4 && LPR >= 4, "one lane per row group");
             const float ss = cl == 0 ? s4[0] : cl == 1 ? s4[1] : cl == 2 ? s4[2] : s4[3];
             const float qq = cl == 0 ? q4[0] : cl == 1 ? q4[1] : cl == 2 ? q4[2] : q4[3];
-            if (cl < ITS)
+            if constexpr (HW == 1024) {
+                if (cl < ITS) epb_park_part(smem_f, wm * 128 + y * 32 + cl * RPI + rl_, wn, ss, qq);
+            } else if (cl < ITS) {
                 *reinterpret_cast<float2 *>(G.part_out + ((size_t)(mw0 + y * 32 + cl * RPI + rl_) * n_parts + slice) * 2) = make_float2(ss, qq);
+            }
         }
     }
+    if constexpr (EPI == EPI_S_RESLN && HW == 1024) epb_merge_parts(G, smem_f, m0, n0, w * 64 + l);
     range_report(vmax, G.range_faults);
 }
 

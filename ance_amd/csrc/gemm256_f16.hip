@@ -77,7 +77,8 @@ __device__ __forceinline__ bool tile_of_block(const GemmArgs &G, int b, int *mt_
     return mt < MT && nt < NT;
 }
 
-template <int EPI>
+// HW: the hidden width of the slice partials the folded epilogues read and write (gemm_f16.h: PartFormat)
+template <int EPI, int HW = 768>
 __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const GemmArgs G) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     _Float16 *smem = reinterpret_cast<_Float16 *>(smem_f);
@@ -121,7 +122,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
         // test_fp16_rows_do_not_depend_on_their_tile_mates.
         P.run(G.K / TK, acc);
         GSTAMP(1);
-        const bool wide = epb_stats(G, smem_f, tid);
+        const bool wide = epb_stats<HW>(G, smem_f, tid);
         if (wide && G.tok_lo) {
             Pipe256T<PipeSrcDesc, false, true> P2;
             P2.init(smem, w, l);
@@ -144,14 +145,14 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
     } else {
         P.run(G.K / TK, acc);
         GSTAMP(1);
-        if constexpr (EPB) (void)epb_stats(G, smem_f, tid);
+        if constexpr (EPB) (void)epb_stats<HW>(G, smem_f, tid);
     }
     GSTAMP(2);
 #ifdef ANCE_MEASURE
-    gemm256_epilogue<EPI, true>(G, acc, smem_f, m0, n0, w, l, stamps_ ? stamps_ + (size_t)blockIdx.x * 8 + 4 : nullptr);
+    gemm256_epilogue<EPI, true, HW>(G, acc, smem_f, m0, n0, w, l, stamps_ ? stamps_ + (size_t)blockIdx.x * 8 + 4 : nullptr);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
-    gemm256_epilogue<EPI, true>(G, acc, smem_f, m0, n0, w, l);
+    gemm256_epilogue<EPI, true, HW>(G, acc, smem_f, m0, n0, w, l);
 #endif
     GSTAMP(3);
 }
@@ -169,7 +170,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
 // (G.wscale_inv undoes it in the epilogue).  Every partial product is exact in fp32 (11 x 11 bits); fp32 accumulation is what
 // is left.  tests/test_split_model.py restates the rounding points on the CPU (3.0e-6 against the fp64 oracle at 12 layers;
 // plain fp32: 2.8e-6).
-template <int EPI>
+template <int EPI, int HW = 768>
 __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const GemmArgs G) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     _Float16 *smem = reinterpret_cast<_Float16 *>(smem_f);
@@ -204,9 +205,9 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const Ge
     epb_issue<EPI>(G, smem_f, m0, n0, w, l);
     P.run(G.K / 32, acc);  // K-tile = 64 halves of a blocked pair row = 32 k of hi and lo
     GSTAMP(1);
-    (void)epb_stats(G, smem_f, tid);
+    (void)epb_stats<HW>(G, smem_f, tid);
     GSTAMP(2);
-    gemm256_epilogue_split<EPI>(G, acc, smem_f, m0, n0, w, l, winv);
+    gemm256_epilogue_split<EPI, HW>(G, acc, smem_f, m0, n0, w, l, winv);
 #ifdef ANCE_MEASURE
     if (stamps_) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -223,7 +224,8 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const Ge
 //   [0, 128 KiB)          stage buffers; the A-half1 slot of buffer 1 is free between two tiles (K-tile 1's A-half1 is staged by
 //                         P0 of K-tile 0): slabs of waves 0-2
 //   STATS 2 KiB, VEC 3 KiB   (mean, rstd) of the tile's 256 tokens; bias | csum or gamma | beta of its 256 features
-//   R 27 KiB              during the K loop the slice partials of the tile's tokens (24 KiB, LDS-DMA issued after the previous
+//   R 27 KiB              during the K loop the slice partials of the tile's tokens (24 KiB at either hidden width: PART_FLOATS
+//                         floats per token; LDS-DMA issued after the previous
 //                         epilogue, retired by the pipeline's counted waits); during the epilogue the slabs of waves 3-7
 // = 160 KiB exactly.  Tile order: workgroup b is on XCD b & 7 (round-robin dispatch) and takes the virtual blocks
 // ((i * slots + (b >> 3)) << 3) | xcd, i = 0, 1, ... of tile_of_block's order -- at any time the 32 CUs of an XCD work on the 32
@@ -234,6 +236,8 @@ constexpr int EPS_VEC = EPS_STATS + 512;
 constexpr int EPS_R = EPS_VEC + 768;             // 27,648 bytes: slice partials (24 KiB) | slabs of waves 3-7 (5 x 4,608 B)
 constexpr size_t GS_LDS_BYTES = (size_t)(EPS_R + 256 * 24 + 768) * sizeof(float);  // 163,840
 static_assert(GS_LDS_BYTES == 160 * 1024, "the streaming kernel uses the whole LDS of a CU");
+static_assert(256 * PART_FLOATS == 256 * 24 && 2 * PartFormat<768>::N <= PART_FLOATS && 2 * PartFormat<1024>::N <= PART_FLOATS,
+              "the slice partials of 256 tokens fill R at hidden 768 and fit it at hidden 1024");
 static_assert(5 * EPS_SLAB_FLOATS <= 256 * 24 + 768 && 3 * EPS_SLAB_FLOATS * 4 <= 16384, "slab layout");
 #ifndef ANCE_STREAM_LOOSE_FIRST
 #define ANCE_STREAM_LOOSE_FIRST 1  // 1: K-tile 0 of a prefetched tile does not wait for the previous epilogue's stores (pipe256.h: tile2); 0: steady-state waits
@@ -248,7 +252,7 @@ template <int EPI_>
 __device__ __forceinline__ void eps_issue(const GemmArgs &G, float *smem_f, int m0, int n0, int w, int l) {
     typedef __attribute__((address_space(3))) void lds_t;
     typedef const __attribute__((address_space(1))) void glb_t;
-    const float *psrc = G.part_in + (size_t)m0 * 24;
+    const float *psrc = G.part_in + (size_t)m0 * PART_FLOATS;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int piece = w + 8 * j;  // 24 pieces of 1 KiB
@@ -279,7 +283,7 @@ __device__ __forceinline__ void eps_barrier() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int EPI>
+template <int EPI, int HW = 768>
 __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(const GemmArgs G, const int n_blocks) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     _Float16 *smem = reinterpret_cast<_Float16 *>(smem_f);
@@ -350,7 +354,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(c
         // after it R belongs to the slabs
         if (tf < 256) {
             float mean, rstd;
-            stats_from_parts(smem_f + EPS_R + tf * 24, Ge.ln_eps, &mean, &rstd);
+            stats_from_parts<HW>(smem_f + EPS_R + tf * PART_FLOATS, Ge.ln_eps, &mean, &rstd);
             smem_f[EPS_STATS + 2 * tf] = mean;
             smem_f[EPS_STATS + 2 * tf + 1] = rstd;
         }
@@ -397,7 +401,25 @@ int device_cu_count() {
     return cus[dev];
 }
 
-int launch256(int epi, const GemmArgs &G, hipStream_t st) {
+// the kernels of one hidden width (gemm_f16.h: PartFormat); the plain epilogues (ance_debug_gemm) read no partials: 768 only
+template <int HW>
+void (*gemm_kernel_of(int epi))(const GemmArgs) {
+    switch (epi) {
+        case EPI_QK: return HW == 768 ? gemm256_f16_desc_kernel<EPI_QK> : nullptr;
+        case EPI_GELU: return HW == 768 ? gemm256_f16_desc_kernel<EPI_GELU> : nullptr;
+        case EPI_RES32: return HW == 768 ? gemm256_f16_desc_kernel<EPI_RES32> : nullptr;
+        case EPI_RESLN: return gemm256_f16_desc_kernel<EPI_RESLN, HW>;
+        case EPI_QK_F: return gemm256_f16_desc_kernel<EPI_QK_F, HW>;
+        case EPI_GELU_F: return gemm256_f16_desc_kernel<EPI_GELU_F, HW>;
+        case EPI_VT_F: return gemm256_f16_desc_kernel<EPI_VT_F, HW>;
+        case EPI_S_QKV: return gemm256_split_kernel<EPI_S_QKV, HW>;
+        case EPI_S_GELU: return gemm256_split_kernel<EPI_S_GELU, HW>;
+        case EPI_S_RESLN: return gemm256_split_kernel<EPI_S_RESLN, HW>;
+        default: return nullptr;
+    }
+}
+
+int launch256(int epi, const GemmArgs &G, hipStream_t st, int hw) {
     const int MT = G.M / TM, NT = G.N / TN;
     if (G.n_split != 0 && (G.n_split != 2 || (NT & 1) || epi < EPI_RESLN)) {
         set_last_error("gemm256: n_split needs an even number of N tiles and a descriptor-form kernel");
@@ -406,28 +428,20 @@ int launch256(int epi, const GemmArgs &G, hipStream_t st) {
     const unsigned blocks = G.n_split == 2 ? (unsigned)((MT + 3) / 4 * 4) * (unsigned)NT
                             : MT >= NT     ? (unsigned)((MT + 7) / 8 * 8) * (unsigned)NT
                                            : (unsigned)((NT + 7) / 8 * 8) * (unsigned)MT;
+    const int wi = hw == 1024 ? 1 : 0;  // instance set
     void (*k)(const GemmArgs) = nullptr;
-    switch (epi) {
-        case EPI_QK: k = gemm256_f16_desc_kernel<EPI_QK>; break;
-        case EPI_GELU: k = gemm256_f16_desc_kernel<EPI_GELU>; break;
-        case EPI_RES32: k = gemm256_f16_desc_kernel<EPI_RES32>; break;
-        case EPI_RESLN: k = gemm256_f16_desc_kernel<EPI_RESLN>; break;
-        case EPI_QK_F: k = gemm256_f16_desc_kernel<EPI_QK_F>; break;
-        case EPI_GELU_F: k = gemm256_f16_desc_kernel<EPI_GELU_F>; break;
-        case EPI_VT_F: k = gemm256_f16_desc_kernel<EPI_VT_F>; break;
-        case EPI_S_QKV: k = gemm256_split_kernel<EPI_S_QKV>; break;
-        case EPI_S_GELU: k = gemm256_split_kernel<EPI_S_GELU>; break;
-        case EPI_S_RESLN: k = gemm256_split_kernel<EPI_S_RESLN>; break;
-        default: set_last_error("gemm256: bad epilogue"); return ANCE_E_INVALID;
+    if (epi >= 0 && epi < EPI_COUNT && (hw == 768 || hw == 1024)) k = wi ? gemm_kernel_of<1024>(epi) : gemm_kernel_of<768>(epi);
+    if (!k) {
+        set_last_error("gemm256: bad epilogue or hidden width");
+        return ANCE_E_INVALID;
     }
     // the dynamic-LDS attribute is per template instance AND per device
-    static unsigned long long attr_done[EPI_COUNT] = {0};
-    const int ai = epi;
-    if (attr_needed(&attr_done[ai])) {
+    static unsigned long long attr_done[2][EPI_COUNT] = {{0}};
+    if (attr_needed(&attr_done[wi][epi])) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(G256_LDS_BYTES + (size_t)EPB_FLOATS * sizeof(float))) != hipSuccess)
             return check_launch("gemm256 attr");
-        attr_mark(&attr_done[ai]);
+        attr_mark(&attr_done[wi][epi]);
     }
     if ((epi == EPI_S_QKV || epi == EPI_S_GELU) && gemm_stream_mode() == 1 && G.K >= 96 && (uint64_t)G.M * (uint64_t)G.lda * 2u < (1ull << 31) &&
         (uint64_t)G.N * (uint64_t)G.ldb * 2u < (1ull << 31)
@@ -435,12 +449,14 @@ int launch256(int epi, const GemmArgs &G, hipStream_t st) {
         && !(epi == g_gemm_stamps_epi && g_gemm_stamps_host)
 #endif
     ) {
-        void (*ks)(const GemmArgs, int) = epi == EPI_S_QKV ? gemm256_split_stream_kernel<EPI_S_QKV> : gemm256_split_stream_kernel<EPI_S_GELU>;
-        static unsigned long long sattr_done[2] = {0, 0};
-        if (attr_needed(&sattr_done[epi - EPI_S_QKV])) {
+        void (*ks)(const GemmArgs, int) =
+            wi ? (epi == EPI_S_QKV ? gemm256_split_stream_kernel<EPI_S_QKV, 1024> : gemm256_split_stream_kernel<EPI_S_GELU, 1024>)
+               : (epi == EPI_S_QKV ? gemm256_split_stream_kernel<EPI_S_QKV> : gemm256_split_stream_kernel<EPI_S_GELU>);
+        static unsigned long long sattr_done[2][2] = {{0, 0}, {0, 0}};
+        if (attr_needed(&sattr_done[wi][epi - EPI_S_QKV])) {
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS_LDS_BYTES) != hipSuccess)
                 return check_launch("gemm256 stream attr");
-            attr_mark(&sattr_done[epi - EPI_S_QKV]);
+            attr_mark(&sattr_done[wi][epi - EPI_S_QKV]);
         }
         const unsigned cus = (unsigned)device_cu_count() & ~7u;  // one workgroup per CU (160 KiB of LDS each), a multiple of the 8 XCDs
         const unsigned grid = blocks < cus ? blocks : cus;
@@ -468,12 +484,12 @@ bool gemm256_applicable(const GemmArgs &G) {
     return G.M > 0 && G.N > 0 && G.K >= 2 * TK && G.M % TM == 0 && G.N % TN == 0 && G.K % TK == 0;
 }
 
-int launch_gemm_f16(int epi, const GemmArgs &G, hipStream_t st) {
+int launch_gemm_f16(int epi, const GemmArgs &G, hipStream_t st, int hw) {
     if (!gemm256_applicable(G)) {
         set_last_error("gemm_f16: M,N must be multiples of 256 and K a multiple of 64, >= 128");
         return ANCE_E_INVALID;
     }
-    return launch256(epi, G, st);
+    return launch256(epi, G, st, hw);
 }
 
 }  // namespace ance
@@ -517,7 +533,7 @@ extern "C" int ance_debug_gemm_split(int epi, const void *d_a_pair, const void *
                                      const void *d_res_pair, void *d_out, float *d_part_out, const float *d_wscale_inv, void *stream) {
     using namespace ance;
     if (!d_a_pair || !d_b_pair || !d_bias || !d_vec1 || !d_part || !d_out || epi < EPI_S_QKV || epi > EPI_S_RESLN ||
-        (epi == EPI_S_RESLN && (!d_vec2 || !d_res_pair || !d_part_out || N != 768)) || K % 64 != 0) {
+        (epi == EPI_S_RESLN && (!d_vec2 || !d_res_pair || !d_part_out || (N != 768 && N != 1024))) || K % 64 != 0) {
         set_last_error("ance_debug_gemm_split: invalid argument");
         return ANCE_E_INVALID;
     }
@@ -533,7 +549,8 @@ extern "C" int ance_debug_gemm_split(int epi, const void *d_a_pair, const void *
         G.res_gamma = d_vec1; G.res_beta = d_vec2; G.res_hi = (const _Float16 *)d_res_pair; G.ldr = 2 * N;
         G.out16 = (_Float16 *)d_out; G.ldc = 2 * N; G.part_out = d_part_out;
     }
-    int rc = launch_gemm_f16(epi, G, (hipStream_t)stream);
+    // EPI_S_RESLN at N = 1024: the partials (in and out) are the hidden-1024 format (gemm_f16.h: PartFormat)
+    int rc = launch_gemm_f16(epi, G, (hipStream_t)stream, epi == EPI_S_RESLN && N == 1024 ? 1024 : 768);
     return rc ? rc : check_launch("ance_debug_gemm_split");
 }
 

@@ -33,14 +33,14 @@ struct GemmArgs {
     int scale_cols;
     const int *col_map;  // EPI_VT_F: token n -> destination column
     int n_valid;         // EPI_VT_F: columns n >= n_valid are not stored
-    // folded LayerNorm: part_in[token][12][2] = (mean, M2) of the twelve 64-column slices of the token's pre-LayerNorm row
+    // folded LayerNorm: part_in[token][PART_FLOATS] = (mean, M2) of the slices of the token's pre-LayerNorm row (PartFormat)
     // (tokens are the rows m for QK_F / GELU_F / RESLN's residual, the columns n for VT_F), ln_eps, and for EPI_*_F the
     // per-feature sum of the folded fp16 weight row
     const float *part_in;
     float ln_eps;
     const float *csum;
     // EPI_RESLN: residual = LayerNorm(res_hi + res_lo) with the statistics of part_in and res_gamma / res_beta; outputs
-    // out16 (hi), out_lo and part_out[m][N / 64][2] = (mean, M2) of the 64 output columns each wave owns
+    // out16 (hi), out_lo and part_out[m][PART_FLOATS] = the (mean, M2) of the output row's slices (PartFormat)
     const _Float16 *res_hi, *res_lo;
     _Float16 *out_lo;
     float *part_out;
@@ -76,19 +76,42 @@ __device__ __forceinline__ float row16_sum(float x) {
     return x;
 }
 
-// (mean, rstd) of a 768-wide row from the (mean, M2) of its twelve 64-column slices: Chan's combination with equal counts
+// Row statistics of the folded LayerNorm: every stream row carries PART_FLOATS floats of partial (mean, M2) pairs.  Hidden 768:
+// twelve 64-column slices (24 floats).  Hidden 1024: eight 128-column slices (16 of the 24 floats; sixteen 64-column slices
+// would need 32 floats per token, which the LDS of the GEMM kernels has no room for: DESIGN.md) -- the producers combine two
+// 64-column halves with part_merge before they store.
+constexpr int PART_FLOATS = 24;
+template <int HW>
+struct PartFormat {
+    static_assert(HW == 768 || HW == 1024, "hidden 768 or 1024");
+    static constexpr int N = HW == 768 ? 12 : 8;      // slices per row
+    static constexpr int COLS = HW == 768 ? 64 : 128; // columns per slice
+    static_assert(2 * N <= PART_FLOATS && N * COLS == HW, "partial layout");
+};
+
+// (mean, M2) of 128 columns from the (mean, M2) of its two 64-column halves a (lower columns) and b: Chan with equal counts
+__device__ __forceinline__ void part_merge(float ma, float qa, float mb, float qb, float *m, float *q) {
+#pragma clang fp contract(off)
+    const float d = ma - mb;
+    *m = (ma + mb) * 0.5f;
+    *q = (qa + qb) + 32.0f * (d * d);
+}
+
+// (mean, rstd) of a HW-wide row from the (mean, M2) of its slices (PartFormat): Chan's combination with equal counts
+template <int HW = 768>
 __device__ __forceinline__ void stats_from_parts(const float *pp, float eps, float *mean, float *rstd) {
+    constexpr int NP = PartFormat<HW>::N;
     float m = 0.f, q = 0.f;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) m += pp[2 * j];
-    m *= 1.0f / 12.0f;
+    for (int j = 0; j < NP; ++j) m += pp[2 * j];
+    m *= 1.0f / (float)NP;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
+    for (int j = 0; j < NP; ++j) {
         const float d = pp[2 * j] - m;
-        q += pp[2 * j + 1] + 64.0f * d * d;
+        q += pp[2 * j + 1] + (float)PartFormat<HW>::COLS * d * d;
     }
     *mean = m;
-    *rstd = rsqrtf(q * (1.0f / 768.0f) + eps);
+    *rstd = rsqrtf(q * (1.0f / (float)HW) + eps);
 }
 
 // epilogue parameter block in LDS, above the 128 KiB of stage buffers (floats)
@@ -99,7 +122,8 @@ constexpr int EPB_VEC = EPB_STATS + 512; // three vectors of 256 floats: bias, c
 constexpr int EPB_FLOATS = EPB_VEC + 768;
 
 // 256 x 256 x 64 tile kernel of gemm256_f16.hip (M, N multiples of 256, K of 64).
-int launch_gemm_f16(int epi, const GemmArgs &args, hipStream_t stream);
+// hw: the hidden width whose slice partials part_in / part_out hold (PartFormat): 768 or 1024.
+int launch_gemm_f16(int epi, const GemmArgs &args, hipStream_t stream, int hw = 768);
 bool gemm256_applicable(const GemmArgs &args);
 void reload_gemm_knobs();  // re-read ANCE_GEMM_STREAM (ance_reload_env)
 

@@ -113,26 +113,27 @@ int launch_gemm32(int epi, const float *A, int lda, const float *B, int ldb, con
     return ANCE_OK;
 }
 
-// LayerNorm of 768-wide fp32 rows -> fp32 rows (+ the row statistics when stats != null); one wave per row, two passes
+// LayerNorm of HW-wide fp32 rows (768 or 1024) -> fp32 rows (+ the row statistics when stats != null); one wave per row, two passes
+template <int HW>
 __global__ void __launch_bounds__(256) ln32_kernel(const float *pre, int rows, const float *gamma, const float *beta, float eps,
                                                    float *out, float *stats) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int l = threadIdx.x & 63;
     if (t >= rows) return;
-    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(pre + (size_t)t * 768);
-    f32x4 v[3];
+    const f32x4 *x4 = reinterpret_cast<const f32x4 *>(pre + (size_t)t * HW);
+    f32x4 v[HW / 256];
     float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < HW / 256; ++k) {
         v[k] = x4[k * 64 + l];
         s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    const float mean = s * (1.0f / 768.0f);
+    const float mean = s * (1.0f / (float)HW);
     float q = 0.f;
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < HW / 256; ++k)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float a = v[k][j] - mean;
@@ -140,15 +141,15 @@ __global__ void __launch_bounds__(256) ln32_kernel(const float *pre, int rows, c
         }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
-    const float rstd = 1.0f / sqrtf(q * (1.0f / 768.0f) + eps);
+    const float rstd = 1.0f / sqrtf(q * (1.0f / (float)HW) + eps);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < HW / 256; ++k) {
         const int c4 = k * 64 + l;
         const f32x4 gm = reinterpret_cast<const f32x4 *>(gamma)[c4], bt = reinterpret_cast<const f32x4 *>(beta)[c4];
         f32x4 y;
 #pragma unroll
         for (int j = 0; j < 4; ++j) y[j] = (v[k][j] - mean) * rstd * gm[j] + bt[j];
-        reinterpret_cast<f32x4 *>(out + (size_t)t * 768)[c4] = y;
+        reinterpret_cast<f32x4 *>(out + (size_t)t * HW)[c4] = y;
     }
     if (stats && l == 0) {
         stats[2 * (size_t)t] = mean;
@@ -157,6 +158,7 @@ __global__ void __launch_bounds__(256) ln32_kernel(const float *pre, int rows, c
 }
 
 // embeddings: (word + type) + position -> pre (fp32); the embedding LayerNorm is an ln32 launch
+template <int HW>
 __global__ void __launch_bounds__(256) embed32_kernel(const int *tok_id, const int *tok_pos, int rows, const float *word,
                                                       const float *pos, const float *type0, int vocab, int max_pos, float *pre) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -165,29 +167,30 @@ __global__ void __launch_bounds__(256) embed32_kernel(const int *tok_id, const i
     int id = tok_id[t], p = tok_pos[t];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(word + (size_t)id * 768);
-    const f32x4 *p4 = reinterpret_cast<const f32x4 *>(pos + (size_t)p * 768);
+    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(word + (size_t)id * HW);
+    const f32x4 *p4 = reinterpret_cast<const f32x4 *>(pos + (size_t)p * HW);
     const f32x4 *t4 = reinterpret_cast<const f32x4 *>(type0);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < HW / 256; ++k) {
         const int c4 = k * 64 + l;
-        reinterpret_cast<f32x4 *>(pre + (size_t)t * 768)[c4] = (w4[c4] + t4[c4]) + p4[c4];
+        reinterpret_cast<f32x4 *>(pre + (size_t)t * HW)[c4] = (w4[c4] + t4[c4]) + p4[c4];
     }
 }
 
 // Self-attention in fp32 on the vector units: one workgroup per (sequence, head), one thread per query row (two rounds
 // for more than 256 queries), keys and values of the head staged 128 at a time in LDS and read as broadcasts; online
-// softmax in fp32 with the full-precision exp.  qkv: [T, 2304] = Q | K | V rows.  ~2 % of the encoder's FLOPs.
+// softmax in fp32 with the full-precision exp.  qkv: [T, 3 HW] = Q | K | V rows.  ~2 % of the encoder's FLOPs.
 constexpr int P_KC = 128;
 constexpr size_t P_ATT_LDS = (size_t)2 * P_KC * 64 * sizeof(float);
 
+template <int HW>
 __global__ void __launch_bounds__(256) attention32_kernel(const float *qkv, float *ctx, const int *seq_off, int n_heads) {
     extern __shared__ __attribute__((aligned(16))) float smem_p[];
     float *Ks = smem_p, *Vs = smem_p + P_KC * 64;
     const int s = blockIdx.x / n_heads, h = blockIdx.x - s * n_heads;
     const int tok0 = seq_off[s], T = seq_off[s + 1] - tok0;
     const int tid = threadIdx.x;
-    const int ld = 3 * 768;
+    const int ld = 3 * HW;
     for (int q0 = 0; q0 < T; q0 += 256) {
         const int qi = q0 + tid;
         const bool qv = qi < T;
@@ -206,9 +209,9 @@ __global__ void __launch_bounds__(256) attention32_kernel(const float *qkv, floa
             __syncthreads();  // the previous chunk (or round) is no longer read
             for (int e = tid; e < nk * 16; e += 256) {
                 const int key = e >> 4, c4 = e & 15;
-                const float *kp = qkv + (size_t)(tok0 + c0 + key) * ld + 768 + h * 64 + c4 * 4;
+                const float *kp = qkv + (size_t)(tok0 + c0 + key) * ld + HW + h * 64 + c4 * 4;
                 *reinterpret_cast<f32x4 *>(Ks + key * 64 + c4 * 4) = *reinterpret_cast<const f32x4 *>(kp);
-                *reinterpret_cast<f32x4 *>(Vs + key * 64 + c4 * 4) = *reinterpret_cast<const f32x4 *>(kp + 768);
+                *reinterpret_cast<f32x4 *>(Vs + key * 64 + c4 * 4) = *reinterpret_cast<const f32x4 *>(kp + HW);
             }
             __syncthreads();
             if (qv) {
@@ -228,22 +231,29 @@ __global__ void __launch_bounds__(256) attention32_kernel(const float *qkv, floa
         }
         if (qv) {
             const float inv = 1.0f / lsum;
-            float *op = ctx + (size_t)(tok0 + qi) * 768 + h * 64;
+            float *op = ctx + (size_t)(tok0 + qi) * HW + h * 64;
 #pragma unroll
             for (int d = 0; d < 64; ++d) op[d] = acc[d] * inv;
         }
     }
 }
 
+// rows of n_heads x 64 columns: 768 or 1024
 int launch_attention32(const float *qkv, float *ctx, const int *seq_off, int n_seq, int n_heads, hipStream_t st) {
-    static unsigned long long attr_done = 0;
-    if (attr_needed(&attr_done)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(attention32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    const int hw = n_heads * 64;
+    if (hw != 768 && hw != 1024) {
+        set_last_error("attention32: n_heads must be 12 or 16");
+        return ANCE_E_INVALID;
+    }
+    void (*k)(const float *, float *, const int *, int) = hw == 768 ? attention32_kernel<768> : attention32_kernel<1024>;
+    static unsigned long long attr_done[2] = {0, 0};
+    if (attr_needed(&attr_done[hw == 1024])) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)P_ATT_LDS) != hipSuccess)
             return check_launch("attention32 attr");
-        attr_mark(&attr_done);
+        attr_mark(&attr_done[hw == 1024]);
     }
-    hipLaunchKernelGGL(attention32_kernel, dim3((unsigned)n_seq * n_heads), dim3(256), P_ATT_LDS, st, qkv, ctx, seq_off, n_heads);
+    hipLaunchKernelGGL(k, dim3((unsigned)n_seq * n_heads), dim3(256), P_ATT_LDS, st, qkv, ctx, seq_off, n_heads);
     return ANCE_OK;
 }
 

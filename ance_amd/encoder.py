@@ -25,6 +25,10 @@ from . import _lib
 
 ARCH_ROBERTA, ARCH_BERT, ARCH_SEED = 0, 1, 2  # include/ance_amd.h: ANCE_ARCH_*
 
+# include/ance_amd.h: AnceEncoderDesc -- head dimension 64; hidden 768 (every arch) or 1024 (RoBERTa with the ANCE head)
+SUPPORTED_SHAPES = ("hidden 768 / 12 heads (RoBERTa-base, BERT-base, SEED; intermediate a multiple of 128)",
+                    "hidden 1024 / 16 heads (RoBERTa-large with the ANCE head; intermediate a multiple of 256)")
+
 _LAYER_KEYS = (
     "attention.self.query.weight", "attention.self.query.bias",
     "attention.self.key.weight", "attention.self.key.bias",
@@ -88,22 +92,24 @@ class Encoder:
     PRECISIONS = ("split", "fp16", "fp32")
 
     def __init__(self, state_dict, arch=ARCH_ROBERTA, prefix="roberta.", has_head=True, pad_token_id=None,
-                 ln_eps=None, max_seq_len=512, max_tokens=65536, device=None, precision=None):
+                 ln_eps=None, max_seq_len=512, max_tokens=65536, device=None, precision=None, n_heads=None):
         """precision: the arithmetic of the handle (AnceEncoderDesc.precision, include/ance_amd.h).  None = whatever the
         environment says -- with nothing set that is "split", the library's default: fp16-pair operands on the fp16 matrix cores,
         fp32-grade like the reference's own fp32 forward (2e-5; the mode in which the refresh reproduces the reference's negative
         ids).  "fp16" = the fast mode (fp16 MFMA operands, 3e-3 on the embeddings, ~2.2 x the throughput), "fp32" = fp32 operands
         (the audit path, ~4.4 x slower than split).
         max_tokens: token capacity of one micro-batch; the activation workspace scales with it -- split mode: 2.8 GB per 65,536
-        tokens and lane, two lanes (the refresh drivers and bench.py pass 131,072: +1.3 % throughput for 11 GB per tower)."""
+        tokens and lane, two lanes (the refresh drivers and bench.py pass 131,072: +1.3 % throughput for 11 GB per tower).
+        n_heads: attention heads; None = hidden // 64 (the head dimension of every supported shape, ``SUPPORTED_SHAPES``)."""
         import torch
         L = _lib.lib()
         if precision is not None and precision not in self.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(self.PRECISIONS))
         self._create(L, torch, state_dict, arch, prefix, has_head, pad_token_id, ln_eps, max_seq_len, max_tokens, device,
-                     _lib.PRECISION_CODES[precision])
+                     _lib.PRECISION_CODES[precision], n_heads)
 
-    def _create(self, L, torch, state_dict, arch, prefix, has_head, pad_token_id, ln_eps, max_seq_len, max_tokens, device, precision_code):
+    def _create(self, L, torch, state_dict, arch, prefix, has_head, pad_token_id, ln_eps, max_seq_len, max_tokens, device, precision_code,
+                n_heads=None):
         self.device = torch.device(device if device is not None else "cuda")
         n_layers = count_layers(state_dict, prefix)
         if n_layers == 0:
@@ -116,8 +122,10 @@ class Encoder:
         pos = state_dict[names[1]]
         inter = state_dict["%sencoder.layer.0.intermediate.dense.weight" % prefix].shape[0]
         self.arch = arch
+        hidden = int(word.shape[1])
+        n_heads = hidden // 64 if n_heads is None else int(n_heads)
         self.desc = _lib.AnceEncoderDesc(
-            arch=arch, n_layers=n_layers, hidden=int(word.shape[1]), n_heads=12, intermediate=int(inter),
+            arch=arch, n_layers=n_layers, hidden=hidden, n_heads=n_heads, intermediate=int(inter),
             vocab_size=int(word.shape[0]), max_position=int(pos.shape[0]),
             pad_token_id=(0 if arch == ARCH_BERT else 1) if pad_token_id is None else int(pad_token_id),
             ln_eps=(1e-12 if arch == ARCH_BERT else 1e-5) if ln_eps is None else float(ln_eps),
@@ -126,7 +134,9 @@ class Encoder:
         wbytes = L.ance_encoder_weight_bytes(ctypes.byref(self.desc))
         xbytes = L.ance_encoder_workspace_bytes(ctypes.byref(self.desc))
         if wbytes == 0 or xbytes == 0:
-            raise _lib.AnceLibraryError("unsupported encoder shape (hidden must be 768, heads 12)")
+            raise _lib.AnceLibraryError(
+                "unsupported encoder shape (hidden %d, %d heads, intermediate %d, arch %d, head %s); supported: %s"
+                % (hidden, n_heads, int(inter), arch, bool(has_head), "; ".join(SUPPORTED_SHAPES)))
         self._arena = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
         self._ws = torch.empty(xbytes, dtype=torch.uint8, device=self.device)
         staged = [state_dict[k].detach().to(device=self.device, dtype=torch.float32).contiguous() for k in names]
@@ -142,6 +152,7 @@ class Encoder:
         self._h = handle
         self.precision = _lib.PRECISION_NAMES[L.ance_encoder_precision(handle)]
         self.n_layers = n_layers
+        self.hidden, self.n_heads = hidden, n_heads
         self.out_dim = 768
         # range guard (include/ance_amd.h: ance_encoder_range_faults): the counters are copied to pinned memory behind every encode
         # call and looked at without synchronising when the next call starts; check_range(sync=True) is the blocking form
@@ -389,13 +400,14 @@ def load_model(model_type, checkpoint_path, max_seq_length=128, max_tokens=65536
     model_type = model_type.lower()
     if model_type in ("rdot_nll", "rdot_nll_multi_chunk"):
         sd = load_hf_state_dict(checkpoint_path)
+        n_heads = check_roberta_config(read_config(checkpoint_path), sd)
         chunks = 1
         seq = max_seq_length
         if model_type == "rdot_nll_multi_chunk":
             chunks = max(1, max_seq_length // 512)  # base_len = 512 (model/models.py:163)
             seq = 512
         enc = Encoder(sd, ARCH_ROBERTA, "roberta.", True, max_seq_len=min(seq, 512), max_tokens=max_tokens, device=device,
-                      precision=precision)
+                      precision=precision, n_heads=n_heads)
         return AnceModel(model_type, enc, chunks=chunks)
     if model_type == "dpr":
         import torch
@@ -425,6 +437,32 @@ def load_model(model_type, checkpoint_path, max_seq_length=128, max_tokens=65536
         return AnceModel(model_type, enc)
     raise ValueError("model_type %r is not on the MI355X path (supported: rdot_nll, rdot_nll_multi_chunk, dpr, seeddot_nll)"
                      % model_type)
+
+
+def check_roberta_config(cfg, sd, prefix="roberta."):
+    """The tower shape of a RobertaDot_NLL_LN / MultiChunk checkpoint (model/models.py:137-199 build it from the checkpoint's
+    config.json): ``hidden_size``, ``num_attention_heads``, ``intermediate_size`` and ``num_hidden_layers``, each checked against
+    the weights when config.json has it.  Returns the head count (None without a config: hidden // 64).  Raises ValueError naming
+    the first field that disagrees with the weights, or a shape the encoder does not support (``SUPPORTED_SHAPES``)."""
+    if not cfg:
+        return None
+    word = sd.get(prefix + "embeddings.word_embeddings.weight")
+    w1 = sd.get(prefix + "encoder.layer.0.intermediate.dense.weight")
+    have = dict(hidden_size=None if word is None else int(word.shape[1]),
+                intermediate_size=None if w1 is None else int(w1.shape[0]),
+                num_hidden_layers=count_layers(sd, prefix))
+    for k, v in have.items():
+        if k in cfg and v is not None and int(cfg[k]) != v:
+            raise ValueError("config.json says %s=%d, the checkpoint's weights have %d" % (k, int(cfg[k]), v))
+    hidden = have["hidden_size"] if have["hidden_size"] is not None else int(cfg.get("hidden_size", 768))
+    heads = cfg.get("num_attention_heads")
+    if heads is None:
+        return None
+    heads = int(heads)
+    if heads <= 0 or hidden % heads or hidden // heads != 64 or hidden not in (768, 1024):
+        raise ValueError("config.json: hidden_size=%d with num_attention_heads=%d is not a supported encoder shape (supported: %s)"
+                         % (hidden, heads, "; ".join(SUPPORTED_SHAPES)))
+    return heads
 
 
 def read_config(ckpt_dir):

@@ -159,10 +159,10 @@ int ance_ip_score_rows(const float *d_x, int64_t n, const float *d_q, int64_t nq
 
 typedef struct AnceEncoderDesc {
     int32_t arch;         /* ANCE_ARCH_*                                                     */
-    int32_t n_layers;     /* 12                                                              */
-    int32_t hidden;       /* 768 (must be 768 in this build: 12 heads x 64)                  */
-    int32_t n_heads;      /* 12                                                              */
-    int32_t intermediate; /* 3072                                                            */
+    int32_t n_layers;     /* 12 (base) / 24 (large)                                          */
+    int32_t hidden;       /* 768, or 1024 (RoBERTa-large: ANCE_ARCH_ROBERTA with has_head = 1 only); hidden = 64 n_heads */
+    int32_t n_heads;      /* 12 at hidden 768, 16 at hidden 1024 (head dimension 64)         */
+    int32_t intermediate; /* 3072 / 4096; a multiple of 128 (of 256 at hidden 1024)          */
     int32_t vocab_size;
     int32_t max_position; /* rows of the position table (514 RoBERTa / 512 BERT)             */
     int32_t pad_token_id; /* 1 RoBERTa / 0 BERT                                              */
@@ -199,6 +199,12 @@ typedef struct AnceEncoder AnceEncoder;
 
 /* Bytes of the packed weight arena (fp16 GEMM operands + fp32 vectors) and of the activation
  * workspace for desc->max_tokens.  Both are caller-allocated device buffers, 256-byte aligned.
+ *
+ * Shapes.  Both return 0 (and ance_encoder_create ANCE_E_INVALID) unless hidden == 64 n_heads and hidden is 768 or 1024; hidden 1024
+ * also needs arch == ANCE_ARCH_ROBERTA and has_head == 1 (DPR's BiEncoder is BERT-base, SEED's config is base width, and a head-less
+ * large tower would change the output width).  The output rows are [n * n_chunks, 768] at either width.  Large tower (24 layers,
+ * 1024 / 16 / 4096, vocab 50265, 514 positions), max_tokens 131,072: arena 2.03 GB split / 0.82 GB fp16 / 2.03 GB fp32, workspace
+ * 15.8 GB / 7.2 GB / 17.9 GB.
  *
  * Arithmetic.  DEFAULT (nothing in the environment): the SPLIT mode -- an fp32-GRADE result from the fp16 matrix cores: every GEMM
  * operand an fp16 pair v = hi + lo, three MFMAs per k-step (hi hi + lo hi + hi lo) from four operand tiles staged once, fp32
@@ -301,12 +307,13 @@ int ance_nll_forward(const float *d_q, const float *d_a, const float *d_b, const
 /* Test hook: the SPLIT (fp32-grade) GEMM of the encoder with one of its epilogues.  acc[m][n] = sum_k a[m][k] b[n][k] with
  * a = a_hi + a_lo (b likewise; the lo x lo products are left out); d_a_pair [M, 2K] / d_b_pair [N, 2K] fp16 PAIR ROWS -- 32-column
  * blocks [hi (32) | lo (32)], lo = fp16(v - hi) unscaled: ance_pair_layout gives the positions; (mu_m, r_m) = mean and
- * 1 / sqrt(var + ln_eps) of row m combined from d_part [M][12][2], the (mean, M2) of its twelve 64-column slices;
+ * 1 / sqrt(var + ln_eps) of row m combined from d_part [M][12][2], the (mean, M2) of its twelve 64-column slices (EPI_S_RESLN at
+ * N = 1024: [M][24] floats holding the (mean, M2) of eight 128-column slices, in and out -- the hidden-1024 format);
  * w = *d_wscale_inv (device scalar; NULL: 1), the inverse of the power of two b was stored with.
  *   epi 8   d_out fp32 [M, N]      = r_m (w acc - mu_m vec1[n]) + bias[n]                             (vec1 = csum)
  *   epi 9   d_out fp16 pair [M, 2N] = pair(gelu_erf(r_m (w acc - mu_m vec1[n]) + bias[n]))
  *   epi 10  d_out fp16 pair [M, 2N] = pair(w acc + bias[n] + (res[m][n] - mu_m) r_m vec1[n] + vec2[n])   (vec1 = gamma, vec2 = beta,
- *           res = d_res_pair [M, 2N] pair rows; N = 768), d_part_out [M][12][2] = slice statistics of the output rows
+ *           res = d_res_pair [M, 2N] pair rows; N = 768 or 1024), d_part_out [M][24] = slice statistics of the output rows
  * M, N multiples of 256, K of 64, >= 128. */
 int ance_debug_gemm_split(int epi, const void *d_a_pair, const void *d_b_pair, int M, int N, int K, const float *d_bias,
                           const float *d_vec1, const float *d_vec2, const float *d_part, float ln_eps, const void *d_res_pair,

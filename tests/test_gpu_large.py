@@ -1,0 +1,198 @@
+"""The large tower (RoBERTa-large width: hidden 1024, 16 heads, FFN 4096, 24 layers) on the GPU: golden vectors of the reference's own
+RobertaDot_NLL_LN / MultiChunk classes (tests/golden/make_golden_large.py) in the three arithmetic modes, bit-stability under the
+micro-batch split and the A/B switches, the split mode's range guard, and the refresh job on a large-width checkpoint.
+Tolerances: split and fp32 max(2e-5, 4 x the reference's own fp32-vs-fp64 distance, large_manifest.json); fp16 1e-2 (the base
+tower's 5e-3 doubled for twice the depth).  Needs an MI355X."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from golden_util import golden_weights
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LARGE = dict(hidden=1024, inter=4096)
+
+
+def _manifest(golden_dir):
+    with open(os.path.join(golden_dir, "large_manifest.json")) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def large24(golden_dir):
+    """The 24-layer weights of the encoder fixtures, built once for the module (checked against the manifest's sha256)."""
+    return golden_weights(_manifest(golden_dir)["encoder"]["large24"], **LARGE)
+
+
+def _encoder(sd, precision, L, max_tokens):
+    from ance_amd.encoder import ARCH_ROBERTA, Encoder
+    enc = Encoder(sd, ARCH_ROBERTA, "roberta.", True, max_seq_len=L, max_tokens=max_tokens, precision=precision)
+    assert (enc.hidden, enc.n_heads, enc.n_layers) == (1024, 16, sd_layers(sd))
+    return enc
+
+
+def sd_layers(sd):
+    from ance_amd.encoder import count_layers
+    return count_layers(sd, "roberta.")
+
+
+def _encode(enc, ids, lens, n_chunks=1):
+    out = enc.encode_ids(torch.from_numpy(ids).cuda(), torch.from_numpy(lens).cuda(), n_chunks=n_chunks, h_lens=lens)
+    enc.check_range(sync=True)
+    return out
+
+
+def _tol(mode, meta):
+    return 1e-2 if mode == "fp16" else max(2e-5, 4.0 * meta["fp32_vs_fp64"])
+
+
+@pytest.mark.parametrize("mode", ["split", "fp16", "fp32"])
+@pytest.mark.parametrize("fixture,L,chunks", [("large24", 128, 1), ("large24_L512", 512, 1), ("large_maxp", 512, 4)])
+def test_large_goldens_of_reference(golden_dir, large24, mode, fixture, L, chunks):
+    meta = _manifest(golden_dir)["encoder"][fixture]
+    assert meta["checksum"] == _manifest(golden_dir)["encoder"]["large24"]["checksum"]  # one weight set for the three fixtures
+    g = np.load(os.path.join(golden_dir, "encoder_%s.npz" % fixture))
+    enc = _encoder(large24, mode, L, 16384)
+    got = _encode(enc, g["ids"].astype(np.int32), g["lens"].astype(np.int32), chunks).cpu().numpy().reshape(g["emb"].shape)
+    d = float(np.abs(got.astype(np.float64) - g["emb"]).max())
+    print("large golden %s %s: max |delta| %.3e (tolerance %.3e)" % (fixture, mode, d, _tol(mode, meta)))
+    assert np.isfinite(got).all() and d <= _tol(mode, meta), (fixture, mode, d)
+
+
+def _batch(seed, n=300, L=128):
+    from oracle import synth
+    rng = np.random.default_rng(seed)
+    lens = np.concatenate([np.array([1, 2, 31, 32, 33, 64, 65, 96, 97, 128], dtype=np.int32),
+                           rng.integers(3, L + 1, n - 10).astype(np.int32)])
+    return synth.make_records(rng, len(lens), L, lens.astype(np.int64)).astype(np.int32), lens
+
+
+@pytest.mark.parametrize("mode", ["split", "fp16"])
+def test_large_rows_do_not_depend_on_the_micro_batch_split(large24, mode):
+    ids, lens = _batch(91)
+    a = _encode(_encoder(large24, mode, 128, 131072), ids, lens)
+    b = _encode(_encoder(large24, mode, 128, 2048), ids, lens)  # ~20 micro-batches
+    assert torch.isfinite(a).all() and torch.equal(a, b)
+
+
+@pytest.mark.parametrize("switch,value", [("ANCE_CLS_TAIL", "0"), ("ANCE_GEMM_STREAM", "0"), ("ANCE_ENCODER_STREAMS", "1")])
+def test_large_ab_switches_change_no_bit(monkeypatch, large24, switch, value):
+    from ance_amd import _lib
+    ids, lens = _batch(92)
+    want = _encode(_encoder(large24, "split", 128, 8192), ids, lens)
+    monkeypatch.setenv(switch, value)
+    _lib.reload_env()
+    try:
+        got = _encode(_encoder(large24, "split", 128, 8192), ids, lens)
+    finally:
+        monkeypatch.delenv(switch)
+        _lib.reload_env()
+    assert torch.equal(got, want), switch
+
+
+def test_large_split_range_guard_raises_out_of_range():
+    """One FFN channel at 1e5 (layer 0's intermediate.dense bias): fine in fp32, an overflow of the split mode's fp16 hi half."""
+    from ance_amd import _lib
+    from oracle import encoder_ref
+    sd = encoder_ref.det_state_dict(seed=95, n_layers=2, ln_jitter=0.1, **LARGE)
+    sd["roberta.encoder.layer.0.intermediate.dense.bias"][7] = 1.0e5
+    ids, lens = _batch(93, n=40)
+    enc = _encoder(sd, "split", 128, 4096)
+    enc.encode_ids(torch.from_numpy(ids).cuda(), torch.from_numpy(lens).cuda(), h_lens=lens)
+    with pytest.raises(_lib.AnceRangeError, match="encoder_precision fp32"):
+        enc.check_range(sync=True)
+
+
+def test_large_refresh_job_against_the_reference_run(golden_dir, tmp_path):
+    """`python -m ance_amd.ann_data_gen --model_type rdot_nll` on a 4-layer large-width checkpoint directory (with its config.json)
+    against the reference's own generate_new_ann run (tests/golden/e2e_large.json): every differing line a proven near-tie
+    (tests/test_gpu_e2e.py's allowance), the same dev NDCG, and the --inference dumps."""
+    from ance_amd import ann_data_gen as adg
+    from ance_amd.cache import TokenCache
+    from ance_amd.encoder import load_model
+    from oracle import ann_ref, encoder_ref, synth
+    from test_gpu_config1 import chain_score_error, tau_needed
+    with open(os.path.join(golden_dir, "e2e_large.json")) as f:
+        e = json.load(f)
+    w = e["weights"]
+    sd = golden_weights(w, **LARGE)
+    data = str(tmp_path / "data")
+    synth.make_msmarco_like(data, **e["data"])
+    ckpt = tmp_path / "train" / "checkpoint-100"
+    ckpt.mkdir(parents=True)
+    torch.save(sd, str(ckpt / "pytorch_model.bin"))
+    (ckpt / "config.json").write_text(json.dumps({"hidden_size": 1024, "num_attention_heads": 16, "intermediate_size": 4096,
+                                                  "num_hidden_layers": w["n_layers"], "model_type": "roberta"}))
+    (ckpt / "scheduler.pt").write_text("commit marker")
+    a = e["args"]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("ANCE_ENCODER_") and k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+
+    def run(out, *extra):
+        cmd = [sys.executable, "-m", "ance_amd.ann_data_gen", "--training_dir", str(tmp_path / "train"), "--init_model_dir",
+               "/nonexistent", "--model_type", "rdot_nll", "--output_dir", out, "--cache_dir", out, "--data_dir", data,
+               "--max_seq_length", str(a["max_seq_length"]), "--max_query_length", str(a["max_query_length"]),
+               "--per_gpu_eval_batch_size", "16", "--topk_training", str(a["topk_training"]), "--negative_sample",
+               str(a["negative_sample"]), "--end_output_num", "0", "--ann_chunk_factor", str(a["ann_chunk_factor"]),
+               "--ann_measure_topk_mrr", "--seed", str(a["seed"]), "--max_tokens", "4096"] + list(extra)
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+
+    out = str(tmp_path / "out")
+    run(out)
+    no, train_path, nd = adg.get_latest_ann_data(out)
+    assert no == 0 and adg.get_checkpoint_no(nd["checkpoint"]) == 100
+
+    # fp64 truth of the same tower
+    sd64 = {k: v.to(device="cuda", dtype=torch.float64) for k, v in sd.items()}
+
+    def enc64(name, L):
+        lens, ids = ann_ref.read_cache(os.path.join(data, name))
+        with torch.no_grad():
+            return encoder_ref.rdot_nll_ln_emb(sd64, torch.from_numpy(ids).cuda(), encoder_ref.mask_from_lengths(lens, L).cuda(),
+                                               n_layers=w["n_layers"], n_heads=16).cpu().numpy()
+
+    p64, q64 = enc64("passages", a["max_seq_length"]), enc64("train-query", a["max_query_length"])
+    model = load_model("rdot_nll", str(ckpt), max_seq_length=a["max_seq_length"], max_tokens=4096)
+    assert (model.q.hidden, model.q.n_heads) == (1024, 16)
+    eng = adg.HipEngine()
+
+    def emb(name, is_q):
+        with TokenCache(os.path.join(data, name)) as cc:
+            return eng.encode_cache(model, cc, 0, len(cc), is_q).cpu().numpy()
+
+    p_emb, train_q = emb("passages", False), emb("train-query", True)
+    emb_err = max(float(np.abs(p_emb - p64).max()), float(np.abs(train_q - q64).max()))
+    S64 = q64.astype(np.float64) @ p64.astype(np.float64).T
+    tau_G = 1.0001 * chain_score_error(torch.from_numpy(p_emb), torch.from_numpy(train_q), S64)
+    tau_R = 2e-3
+    print("large refresh job: max |delta| of the embeddings %.3e, score error %.3e" % (emb_err, tau_G))
+    assert emb_err <= 5e-5 and tau_G <= 2e-3, (emb_err, tau_G)
+    ref_lines = dict(l.split("\t", 1) for l in e["ann_training_data_0"].splitlines())
+    got_lines = dict(l.split("\t", 1) for l in open(train_path).read().splitlines())
+    assert set(ref_lines) == set(got_lines)
+    same, unexplained = 0, []
+    for q in ref_lines:
+        if ref_lines[q] == got_lines[q]:
+            same += 1
+            continue
+        pos = int(ref_lines[q].split("\t")[0])
+        ng = [int(x) for x in got_lines[q].split("\t")[1].split(",")]
+        nr = [int(x) for x in ref_lines[q].split("\t")[1].split(",")]
+        if tau_needed(S64[int(q)], ng, excluded=[pos]) > tau_G or tau_needed(S64[int(q)], nr, excluded=[pos]) > tau_R:
+            unexplained.append(int(q))
+    assert not unexplained, unexplained
+    assert same >= 0.8 * len(ref_lines), (same, len(ref_lines))
+    assert abs(nd["ndcg"] - e["ann_ndcg_0"]["ndcg"]) <= 0.02, (nd["ndcg"], e["ann_ndcg_0"]["ndcg"])
+
+    # --inference: the embedding dumps of the same job
+    inf = str(tmp_path / "inf")
+    run(inf, "--inference")
+    pe = np.load(os.path.join(inf, "passage_100__emb_p__data_obj_0.npy"))
+    assert np.array_equal(pe, p_emb)
