@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("ANCE_AMD_LIB") or os.path.join(_HERE, "libance_amd.so
 CSRC = os.path.join(_HERE, "csrc")
 
 ANCE_OK = 0
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -27,6 +27,19 @@ class AnceEncoderDesc(ctypes.Structure):
         ("max_position", ctypes.c_int32), ("pad_token_id", ctypes.c_int32), ("ln_eps", ctypes.c_float),
         ("has_head", ctypes.c_int32), ("max_seq_len", ctypes.c_int32), ("max_tokens", ctypes.c_int32),
         ("precision", ctypes.c_int32),
+    ]
+
+
+class AnceGemmDebugArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_debug_gemm_hw (field names of the encoder's GemmArgs)."""
+    _fields_ = [
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("lda", ctypes.c_int32), ("ldb", ctypes.c_int32),
+        ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("bias", ctypes.c_void_p), ("csum", ctypes.c_void_p), ("part_in", ctypes.c_void_p), ("ln_eps", ctypes.c_float),
+        ("tok_lo", ctypes.c_void_p), ("scale", ctypes.c_float), ("scale_cols", ctypes.c_int32), ("col_map", ctypes.c_void_p),
+        ("n_valid", ctypes.c_int32), ("ldc", ctypes.c_int32), ("out", ctypes.c_void_p), ("res_hi", ctypes.c_void_p),
+        ("res_lo", ctypes.c_void_p), ("res_gamma", ctypes.c_void_p), ("res_beta", ctypes.c_void_p), ("out_lo", ctypes.c_void_p),
+        ("part_out", ctypes.c_void_p), ("ldr", ctypes.c_int32), ("wscale_inv", ctypes.c_void_p), ("n_split", ctypes.c_int32),
     ]
 
 
@@ -97,6 +110,7 @@ SYMBOLS = {
     "ance_debug_gemm_split": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_debug_gemm_hw": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(AnceGemmDebugArgs), ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

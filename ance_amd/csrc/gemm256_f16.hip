@@ -554,6 +554,39 @@ extern "C" int ance_debug_gemm_split(int epi, const void *d_a_pair, const void *
     return rc ? rc : check_launch("ance_debug_gemm_split");
 }
 
+// Test hook (include/ance_amd.h): one GEMM instance the encoder dispatches (epilogues EPI_RESLN .. EPI_S_RESLN at hidden 768 or
+// 1024) with every GemmArgs field the encoder sets (encoder.hip: forward_split, forward_fp16).  Host code only: the kernels and
+// their launch are the encoder's own.
+extern "C" int ance_debug_gemm_hw(int epi, int hw, const AnceGemmDebugArgs *a, void *stream) {
+    using namespace ance;
+    const bool fold = epi == EPI_QK_F || epi == EPI_GELU_F || epi == EPI_VT_F;   // bias, csum (per feature)
+    const bool bad = !a || (hw != 768 && hw != 1024) || epi < EPI_RESLN || epi > EPI_S_RESLN || (a->n_split != 0 && a->n_split != 2) ||
+                     !a->a || !a->b || !a->bias || !a->part_in || !a->out ||
+                     ((fold || epi == EPI_S_QKV || epi == EPI_S_GELU) && !a->csum) ||
+                     (epi == EPI_QK_F && a->scale_cols % 64 != 0) ||
+                     (epi == EPI_VT_F && !a->col_map) ||
+                     (epi == EPI_RESLN && (!a->res_hi || !a->res_lo || !a->out_lo)) ||
+                     ((epi == EPI_RESLN || epi == EPI_S_RESLN) && (!a->res_gamma || !a->res_beta || !a->part_out || a->N != hw)) ||
+                     (epi == EPI_S_RESLN && !a->res_hi);
+    if (bad) {
+        set_last_error("ance_debug_gemm_hw: invalid argument");
+        return ANCE_E_INVALID;
+    }
+    GemmArgs G;
+    memset(&G, 0, sizeof(G));
+    G.A = (const _Float16 *)a->a; G.B = (const _Float16 *)a->b; G.lda = a->lda; G.ldb = a->ldb;
+    G.M = a->M; G.N = a->N; G.K = a->K;
+    G.bias = a->bias; G.csum = a->csum; G.part_in = a->part_in; G.ln_eps = a->ln_eps; G.tok_lo = (const _Float16 *)a->tok_lo;
+    G.scale = a->scale; G.scale_cols = a->scale_cols; G.col_map = a->col_map; G.n_valid = a->n_valid; G.ldc = a->ldc;
+    if (epi == EPI_S_QKV) G.out32 = (float *)a->out;
+    else G.out16 = (_Float16 *)a->out;
+    G.res_hi = (const _Float16 *)a->res_hi; G.res_lo = (const _Float16 *)a->res_lo; G.res_gamma = a->res_gamma; G.res_beta = a->res_beta;
+    G.out_lo = (_Float16 *)a->out_lo; G.part_out = a->part_out;
+    G.ldr = a->ldr; G.wscale_inv = a->wscale_inv; G.n_split = a->n_split;
+    int rc = launch_gemm_f16(epi, G, (hipStream_t)stream, hw);
+    return rc ? rc : check_launch("ance_debug_gemm_hw");
+}
+
 // Layout of the split mode's pair rows for tests and tools: column n of a W-wide row -> positions of its hi and lo halves in the
 // 2 W-half row, and the factor lo was multiplied by (1: unscaled; the round-4 A/B build reports 2048 and rows [hi (W) | lo' (W)]).
 extern "C" void ance_pair_layout(int n, int W, int *hi_col, int *lo_col, float *lo_scale) {

@@ -38,7 +38,8 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 5  /* 5: AnceEncoderDesc.precision (the arithmetic is an argument, not an environment variable), ance_encoder_range_faults,
+#define ANCE_ABI_VERSION 6  /* 6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
+                               5: AnceEncoderDesc.precision (the arithmetic is an argument, not an environment variable), ance_encoder_range_faults,
                                ance_ip_topk_scan; 4: blocked pair rows in the split mode (ance_pair_layout; ance_debug_gemm_split + d_wscale_inv);
                                3: + ance_nll_forward, ance_search_bad_image_calls, ance_debug_gemm_split; split encoder mode */
 int ance_abi_version(void);
@@ -318,6 +319,45 @@ int ance_nll_forward(const float *d_q, const float *d_a, const float *d_b, const
 int ance_debug_gemm_split(int epi, const void *d_a_pair, const void *d_b_pair, int M, int N, int K, const float *d_bias,
                           const float *d_vec1, const float *d_vec2, const float *d_part, float ln_eps, const void *d_res_pair,
                           void *d_out, float *d_part_out, const float *d_wscale_inv, void *stream);
+
+/* Test hook: ONE instance of the encoder's GEMM (epilogues 4-10 at hidden width hw = 768 or 1024) with every field the encoder
+ * sets, on caller data -- what ance_debug_gemm / ance_debug_gemm_split cannot reach: the fp16 mode's folded epilogues, the
+ * hidden-1024 instances of the split epilogues, tok_lo and n_split.  Field names are the encoder's (csrc/gemm_f16.h: GemmArgs);
+ * row strides are in elements; M, N multiples of 256, K of 64, >= 128; the token / feature arrays hold 256-row tiles.
+ *   part_in  [tokens][24]: (mean, M2) of the slices of each token's pre-LayerNorm row -- twelve 64-column slices at hw 768, eight
+ *            128-column slices (16 of the 24 floats) at hw 1024; tokens are the rows m, the columns n for epi 7
+ *   epi 4  EPI_RESLN    out / out_lo fp16 [M, ldc] = (hi, lo) of acc + bias[n] + LayerNorm(res_hi + res_lo) (res rows at stride ldc,
+ *                       statistics from part_in, res_gamma / res_beta); part_out [M][24] = output slice statistics; N = hw
+ *   epi 5  EPI_QK_F     out fp16 [M, ldc] = (r_m (acc - mu_m csum[n]) + bias[n]) * (n < scale_cols ? scale : 1); scale_cols % 64 == 0
+ *   epi 6  EPI_GELU_F   out fp16 [M, ldc] = gelu(r_m (acc - mu_m csum[n]) + bias[n])
+ *   epi 7  EPI_VT_F     out fp16 [M, ldc]: column col_map[n] = r_n (acc - mu_n csum[m]) + bias[m], tokens n < n_valid only
+ *   epi 5-7: tok_lo (nullable) = the lo halves of the token operand (A for 5 / 6, B for 7, same stride): a tile with a token
+ *            whose |mean| rstd > 2 adds acc += lo . W^T for those tokens
+ *   epi 8-10 the split epilogues of ance_debug_gemm_split (pair rows; epi 10: residual pair rows at stride ldr, N = hw) with
+ *            wscale_inv (nullable) and the partials in the hw format
+ *   n_split  0, or 2: the N-split tile order (N / 256 even)
+ * Refuses (ANCE_E_INVALID, before any launch) hw outside {768, 1024}, epi outside 4..10, a null pointer the epilogue reads and
+ * n_split outside {0, 2}. */
+typedef struct AnceGemmDebugArgs {
+    const void *a, *b;            /* fp16 [M, lda] / [N, ldb] (split: pair rows)                 */
+    int32_t lda, ldb, M, N, K;
+    const float *bias, *csum, *part_in;
+    float ln_eps;
+    const void *tok_lo;
+    float scale;
+    int32_t scale_cols;
+    const int32_t *col_map;
+    int32_t n_valid, ldc;
+    void *out;                    /* fp16 (epi 4-7, 9, 10) or fp32 (epi 8)                      */
+    const void *res_hi, *res_lo;
+    const float *res_gamma, *res_beta;
+    void *out_lo;
+    float *part_out;
+    int32_t ldr;
+    const float *wscale_inv;
+    int32_t n_split;
+} AnceGemmDebugArgs;
+int ance_debug_gemm_hw(int epi, int hw, const AnceGemmDebugArgs *args, void *stream);
 
 /* Layout of the split mode's pair rows (for tests and tools that build or read them): column n of a W-wide fp32 row has its hi
  * half at *hi_col and its lo half at *lo_col of the 2 W-half pair row, lo = fp16((v - hi) * *lo_scale).  Product library:

@@ -24,12 +24,13 @@ def test_header_and_binding_agree():
     assert sorted(_lib.SYMBOLS.keys()) == declared
 
 
-def test_library_loads_and_exports_everything():
+def test_library_loads_exports_everything_at_abi_6():
+    """ABI 6: + ance_debug_gemm_hw (include/ance_amd.h)."""
     L = _lib.lib()
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in _declared_functions():
         assert hasattr(raw, name), name
-    assert L.ance_abi_version() == _lib.ABI_VERSION == 5
+    assert L.ance_abi_version() == _lib.ABI_VERSION == 6
     assert L.ance_last_error() is not None
 
 
@@ -67,7 +68,49 @@ def test_invalid_arguments_are_rejected_before_any_launch():
     assert L.ance_ip_topk_scan_workspace_bytes(10000, 1000, 768, 200) > 0
     assert L.ance_ip_topk_scan_workspace_bytes(10000, 1000, 768, 0) == 0
     assert L.ance_encoder_range_faults(None, None, 0, None) == -1
+    _gemm_hw_refusals(L)
     assert L.ance_encoder_precision(None) == -1
+
+
+def _gemm_hw_refusals(L):
+    """ance_debug_gemm_hw: every refusal happens on the host, before a launch (the pointers below are never dereferenced)."""
+    fake = ctypes.c_void_p(0x1000)
+
+    def args(**kw):
+        a = _lib.AnceGemmDebugArgs(a=fake, b=fake, lda=1024, ldb=1024, M=256, N=1024, K=1024, bias=fake, csum=fake, part_in=fake,
+                                   ln_eps=1e-5, scale=1.0, col_map=fake, n_valid=256, ldc=1024, out=fake, res_hi=fake, res_lo=fake,
+                                   res_gamma=fake, res_beta=fake, out_lo=fake, part_out=fake, ldr=2048)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return ctypes.byref(a)
+
+    def refused(epi, hw, a):
+        rc = L.ance_debug_gemm_hw(epi, hw, a, None)
+        return rc == -1 and b"ance_debug_gemm_hw" in L.ance_last_error()
+
+    assert refused(5, 768, None)
+    for hw in (0, 512, 767, 1023, 2048):
+        assert refused(5, hw, args())
+    for epi in (-1, 0, 1, 2, 3, 11, 12):
+        assert refused(epi, 1024, args())
+    for ns in (-1, 1, 3, 4):
+        assert refused(6, 1024, args(n_split=ns))
+    for epi in range(4, 11):
+        for field in ("a", "b", "bias", "part_in", "out"):
+            assert refused(epi, 1024, args(**{field: None})), (epi, field)
+    for epi in (5, 6, 7, 8, 9):
+        assert refused(epi, 768, args(csum=None)), epi
+    assert refused(7, 1024, args(col_map=None))
+    assert refused(5, 1024, args(scale_cols=100))
+    for field in ("res_hi", "res_lo", "out_lo", "res_gamma", "res_beta", "part_out"):
+        assert refused(4, 1024, args(**{field: None})), field
+    for field in ("res_hi", "res_gamma", "res_beta", "part_out"):
+        assert refused(10, 1024, args(**{field: None})), field
+    assert refused(4, 768, args(N=1024)) and refused(10, 1024, args(N=768))  # the partials need N = hw
+    # shapes the kernel cannot tile: refused by the launcher, still before any launch
+    assert L.ance_debug_gemm_hw(5, 1024, args(M=300), None) == -1
+    assert L.ance_debug_gemm_hw(5, 1024, args(K=64), None) == -1
+    assert L.ance_debug_gemm_hw(6, 1024, args(N=768, n_split=2), None) == -1  # three N tiles: no N-split order
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

@@ -397,9 +397,9 @@ def test_split_mode_bert_and_maxp_goldens(monkeypatch, golden_dir):
 
 
 def _offset_weights(sd, offset, n_layers):
-    """A common offset of `offset` STANDARD DEVIATIONS on every pre-LayerNorm row: the embeddings (row std 0.035 at init) and
-    the dense biases of both residual branches (row std ~ 1) -- |mean| >> std, the input distribution ADVICE r3 showed the
-    single-fp16 LayerNorm fold loses 20-80 x on."""
+    """A common offset of `offset` STANDARD DEVIATIONS on every pre-LayerNorm row: the embeddings (row std 0.035 at init, at
+    either width) and the dense biases of both residual branches (row std ~ 1) -- |mean| >> std, the input distribution ADVICE r3
+    showed the single-fp16 LayerNorm fold loses 20-80 x on."""
     sd = dict(sd)
     sd["roberta.embeddings.word_embeddings.weight"] = sd["roberta.embeddings.word_embeddings.weight"] + offset * 0.035
     for i in range(n_layers):
@@ -610,14 +610,15 @@ def test_split_mode_with_weights_of_very_different_scales():
     assert np.isfinite(got).all() and e <= 4.0 * e32 + 2e-5, (e, e32)
 
 
-def _trained_like_weights(n_layers, ffn_drive=None, emb_scale=1.4):
+def _trained_like_weights(n_layers, ffn_drive=None, emb_scale=1.4, hidden=768, inter=3072, outliers=((17, 50.0), (400, -50.0))):
     """A 'trained-like' stress model (VERDICT r5 #4c): every parity fixture is random init (std 0.02, LayerNorm 1 / 0), where
     activations are O(1) and softmax is flat.  Here: embedding rows of the magnitude trained checkpoints have (0.05) with a common
-    offset; two hidden dimensions with x50 LayerNorm gains in every LayerNorm (the outlier dimensions of trained BERT / RoBERTa);
-    Q / K scaled so that the softmax saturates (one key takes almost all the mass); optionally one FFN channel driven to
-    ``ffn_drive`` in magnitude through its intermediate bias (GELU output and, through output.dense, the residual stream)."""
+    offset; hidden dimensions with x50 LayerNorm gains in every LayerNorm (the outlier dimensions of trained BERT / RoBERTa:
+    ``outliers`` = (dimension, factor) pairs); Q / K scaled so that the softmax saturates (one key takes almost all the mass);
+    optionally one FFN channel driven to ``ffn_drive`` in magnitude through its intermediate bias (GELU output and, through
+    output.dense, the residual stream).  hidden / inter: the tower's width (768 / 3072: roberta-base)."""
     from oracle import encoder_ref
-    sd = dict(encoder_ref.random_state_dict(seed=71, n_layers=n_layers, ln_jitter=0.1))
+    sd = dict(encoder_ref.random_state_dict(seed=71, n_layers=n_layers, ln_jitter=0.1, hidden=hidden, inter=inter))
     we = sd["roberta.embeddings.word_embeddings.weight"].clone() * emb_scale
     we[:, 5] += 0.04
     sd["roberta.embeddings.word_embeddings.weight"] = we
@@ -626,8 +627,8 @@ def _trained_like_weights(n_layers, ffn_drive=None, emb_scale=1.4):
         names += ["roberta.encoder.layer.%d.attention.output.LayerNorm" % i, "roberta.encoder.layer.%d.output.LayerNorm" % i]
     for n in names:
         w = sd[n + ".weight"].clone()
-        w[17] *= 50.0
-        w[400] *= -50.0
+        for dim, f in outliers:
+            w[dim] *= f
         sd[n + ".weight"] = w
     for i in range(n_layers):
         p = "roberta.encoder.layer.%d." % i
@@ -640,12 +641,15 @@ def _trained_like_weights(n_layers, ffn_drive=None, emb_scale=1.4):
     return sd
 
 
-def _oracle_pair(sd, ids, lens, L, n_layers):
+def _oracle_pair(sd, ids, lens, L, n_layers, n_heads=12):
+    """(fp64, fp32) outputs of the oracle tower on the same records"""
     from oracle import encoder_ref
     with torch.no_grad():
         sd64 = {k: v.double() for k, v in sd.items()}
-        want64 = encoder_ref.rdot_nll_ln_emb(sd64, torch.from_numpy(ids), encoder_ref.mask_from_lengths(lens, L), n_layers=n_layers).numpy()
-        want32 = encoder_ref.rdot_nll_ln_emb(sd, torch.from_numpy(ids), encoder_ref.mask_from_lengths(lens, L), n_layers=n_layers).numpy()
+        want64 = encoder_ref.rdot_nll_ln_emb(sd64, torch.from_numpy(ids), encoder_ref.mask_from_lengths(lens, L), n_layers=n_layers,
+                                             n_heads=n_heads).numpy()
+        want32 = encoder_ref.rdot_nll_ln_emb(sd, torch.from_numpy(ids), encoder_ref.mask_from_lengths(lens, L), n_layers=n_layers,
+                                             n_heads=n_heads).numpy()
     return want64, want32
 
 

@@ -106,11 +106,50 @@ def _unpair(p, n):
     return p[:, hc].double() + p[:, lc].double() / sc
 
 
-def _run_split(epi, M, N, K, seed=0, zero_a_lo=False, zero_b_lo=False, wscale=1.0):
+def part_format(hw):
+    """(slices per row, columns per slice) of the folded LayerNorm's row statistics at hidden width hw (csrc/gemm_f16.h:
+    PartFormat): twelve 64-column slices at 768, eight 128-column slices at 1024, in a slot of 24 floats per row."""
+    return (12, 64) if hw == 768 else (8, 128)
+
+
+def parts_of_rows(v, hw):
+    """Rows v [R, hw] -> their slice statistics [R, 24] fp32 in the hw format: (mean, M2) of every slice, computed in fp64; the
+    floats past the slices (hw 1024: 16 .. 23) are NaN, so a kernel that reads them cannot pass."""
+    ns, cols = part_format(hw)
+    s = v.double().reshape(v.shape[0], ns, cols)
+    m = s.mean(-1)
+    out = torch.full((v.shape[0], 24), float("nan"), dtype=torch.float32, device=v.device)
+    out[:, 0:2 * ns:2] = m.float()
+    out[:, 1:2 * ns:2] = ((s - m[..., None]) ** 2).sum(-1).float()
+    return out
+
+
+def stats_of_parts(part, hw, eps):
+    """(mean, rstd) in fp64 of the rows whose slice statistics are part [R, 24] (Chan's combination with equal counts)."""
+    ns, cols = part_format(hw)
+    m = part[:, 0:2 * ns:2].double()
+    mu = m.mean(1)
+    var = (part[:, 1:2 * ns:2].double() + cols * (m - mu[:, None]) ** 2).sum(1) / hw
+    return mu, 1.0 / torch.sqrt(var + eps)
+
+
+def _hw_args(epi, hw, ap, bp, M, N, K, bias, vec1, part, eps, out, winv, n_split=0):
+    """ance_debug_gemm_hw with the fields ance_debug_gemm_split sets for the split epilogues 8 / 9"""
+    from ance_amd import _lib
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    a = _lib.AnceGemmDebugArgs(a=P(ap), b=P(bp), lda=2 * K, ldb=2 * K, M=M, N=N, K=K, bias=P(bias), csum=P(vec1), part_in=P(part),
+                               ln_eps=eps, out=P(out), ldc=N if epi == 8 else 2 * N, wscale_inv=P(winv), n_split=n_split)
+    return _lib.lib().ance_debug_gemm_hw(epi, hw, ctypes.byref(a), _lib.current_stream_ptr())
+
+
+def _run_split(epi, M, N, K, seed=0, zero_a_lo=False, zero_b_lo=False, wscale=1.0, hw=768):
     """The split GEMM (three fp16 MFMA passes over pair operands) through its test hook with one of its three epilogues,
-    against the same expression in fp64.  Returns (got, ref, scale): scale = the magnitude rounding errors are relative to."""
+    against the same expression in fp64.  Returns (got, ref, scale): scale = the magnitude rounding errors are relative to.
+    hw: the hidden width of the slice statistics (part_format); epi 8 / 9 at 1024 go through ance_debug_gemm_hw, epi 10 through
+    ance_debug_gemm_split, whose N = 1024 selects that format."""
     from ance_amd import _lib
     L = _lib.lib()
+    ns, cols = part_format(hw)
     g = torch.Generator(device="cuda").manual_seed(seed)
     a = torch.randn((M, K), generator=g, device="cuda")
     b = torch.randn((N, K), generator=g, device="cuda") * 0.02
@@ -128,25 +167,30 @@ def _run_split(epi, M, N, K, seed=0, zero_a_lo=False, zero_b_lo=False, wscale=1.
     vec1 = torch.randn(N, generator=g, device="cuda")
     vec2 = torch.randn(N, generator=g, device="cuda")
     # slice statistics: mean m_j per 64-column slice, M2 = 64 s^2 -> row mean mu, variance s^2 + var(m_j)
-    part = torch.empty((M, 12, 2), device="cuda")
-    part[:, :, 0] = torch.randn((M, 12), generator=g, device="cuda") * 0.1
-    part[:, :, 1] = 64.0 * (0.5 + torch.rand((M, 12), generator=g, device="cuda"))
+    part = torch.full((M, 24), float("nan"), device="cuda")
+    part[:, 0:2 * ns:2] = torch.randn((M, ns), generator=g, device="cuda") * 0.1
+    part[:, 1:2 * ns:2] = cols * (0.5 + torch.rand((M, ns), generator=g, device="cuda"))
+    part = part[:, :2 * ns].reshape(M, ns, 2) if hw == 768 else part  # (hw 768: the 24 floats are all slices)
     eps = 1e-5
     res = torch.randn((M, N), generator=g, device="cuda")
     rp = _pair_rows(*_pair(res))
     out = torch.empty((M, N), dtype=torch.float32, device="cuda") if epi == 8 else torch.zeros((M, 2 * N), dtype=torch.float16, device="cuda")
-    part_out = torch.zeros((M, N // 64, 2), device="cuda")
+    part_out = torch.zeros((M, N // 64, 2), device="cuda") if hw == 768 else torch.full((M, 24), float("nan"), device="cuda")
     P = lambda t: ctypes.c_void_p(t.data_ptr())
-    rc = L.ance_debug_gemm_split(epi, P(ap), P(bp), M, N, K, P(bias), P(vec1), P(vec2), P(part), eps, P(rp), P(out), P(part_out),
-                                 P(winv), _lib.current_stream_ptr())
-    _lib.check(rc, "ance_debug_gemm_split")
+    if hw == 768 or epi == 10:
+        rc = L.ance_debug_gemm_split(epi, P(ap), P(bp), M, N, K, P(bias), P(vec1), P(vec2), P(part), eps, P(rp), P(out), P(part_out),
+                                     P(winv), _lib.current_stream_ptr())
+        _lib.check(rc, "ance_debug_gemm_split")
+    else:
+        _lib.check(_hw_args(epi, hw, ap, bp, M, N, K, bias, vec1, part, eps, out, winv), "ance_debug_gemm_hw")
+    part = part.reshape(M, 24)[:, :2 * ns].reshape(M, ns, 2)
     A = ah.double() + al.double() / lo_sc
     B = (bh.double() + bl.double() / lo_sc) / wscale
     acc = A @ B.t()
     dropped = ((al.double() / lo_sc).abs() @ (bl.double() / lo_sc / wscale).abs().t())  # the lo x lo term the kernel leaves out
     m = part[:, :, 0].double()
     mu = m.mean(1)
-    var = (part[:, :, 1].double() + 64.0 * (m - mu[:, None]) ** 2).sum(1) / 768.0
+    var = (part[:, :, 1].double() + cols * (m - mu[:, None]) ** 2).sum(1) / hw
     r = 1.0 / torch.sqrt(var + eps)
     mag = A.abs() @ B.abs().t()
     if epi in (8, 9):
@@ -162,8 +206,11 @@ def _run_split(epi, M, N, K, seed=0, zero_a_lo=False, zero_b_lo=False, wscale=1.
     ref = acc + bias.double()[None, :] + ln
     scale = mag + dropped + bias.double().abs()[None, :] + ((R.abs() + mu.abs()[:, None]) * r[:, None] * vec1.double().abs()[None, :]) + \
         vec2.double().abs()[None, :]
-    s = ref.reshape(M, N // 64, 64)
+    s = ref.reshape(M, N // cols, cols)
     want_part = torch.stack([s.mean(-1), ((s - s.mean(-1, keepdim=True)) ** 2).sum(-1)], dim=-1)
+    if hw == 1024:
+        assert bool(torch.isnan(part_out[:, 2 * ns:]).all()), "part_out written past the eight 128-column slices"
+        part_out = part_out[:, :2 * ns].reshape(M, ns, 2)
     return _unpair(out, N), ref, scale, part_out.double(), want_part
 
 
@@ -231,27 +278,32 @@ def test_mfma_keeps_f16_subnormals():
     assert torch.equal(got, want[:, None].expand(M, N).float().double()), (float(got.abs().max()), float(want.max()))
 
 
-def _split_raw(epi, M, N, K, seed, stream, monkeypatch):
+def _split_raw(epi, M, N, K, seed, stream, monkeypatch, hw=768, n_split=0):
     """One launch of the split GEMM through its test hook, with the persistent streaming kernel (the product's) or the
-    launch-per-tile kernel (ANCE_GEMM_STREAM=0); returns the raw output buffers."""
+    launch-per-tile kernel (ANCE_GEMM_STREAM=0); returns the raw output buffers.  hw 1024 (ance_debug_gemm_hw): the slice
+    statistics in that width's format, and optionally the N-split tile order."""
     from ance_amd import _lib
     monkeypatch.setenv("ANCE_GEMM_STREAM", "1" if stream else "0")
     _lib.reload_env()
     L = _lib.lib()
+    ns, cols = part_format(hw)
     g = torch.Generator(device="cuda").manual_seed(seed)
     ap = _pair_rows(*_pair(torch.randn((M, K), generator=g, device="cuda")))
     bp = _pair_rows(*_pair(torch.randn((N, K), generator=g, device="cuda") * 0.02 * 2.0 ** 17))
     winv = torch.tensor([2.0 ** -17], dtype=torch.float32, device="cuda")
     bias, vec1, vec2 = (torch.randn(N, generator=g, device="cuda") for _ in range(3))
-    part = torch.empty((M, 12, 2), device="cuda")
-    part[:, :, 0] = torch.randn((M, 12), generator=g, device="cuda") * 0.1
-    part[:, :, 1] = 64.0 * (0.5 + torch.rand((M, 12), generator=g, device="cuda"))
+    part = torch.full((M, 24), float("nan"), device="cuda")
+    part[:, 0:2 * ns:2] = torch.randn((M, ns), generator=g, device="cuda") * 0.1
+    part[:, 1:2 * ns:2] = cols * (0.5 + torch.rand((M, ns), generator=g, device="cuda"))
     rp = _pair_rows(*_pair(torch.randn((M, N), generator=g, device="cuda")))
     out = torch.zeros((M, N), dtype=torch.float32, device="cuda") if epi == 8 else torch.zeros((M, 2 * N), dtype=torch.float16, device="cuda")
     part_out = torch.zeros((M, max(N // 64, 1), 2), device="cuda")
     P = lambda t: ctypes.c_void_p(t.data_ptr())
-    rc = L.ance_debug_gemm_split(epi, P(ap), P(bp), M, N, K, P(bias), P(vec1), P(vec2), P(part), 1e-5, P(rp), P(out), P(part_out),
-                                 P(winv), _lib.current_stream_ptr())
+    if hw == 768 and n_split == 0:
+        rc = L.ance_debug_gemm_split(epi, P(ap), P(bp), M, N, K, P(bias), P(vec1), P(vec2), P(part), 1e-5, P(rp), P(out), P(part_out),
+                                     P(winv), _lib.current_stream_ptr())
+    else:
+        rc = _hw_args(epi, hw, ap, bp, M, N, K, bias, vec1, part, 1e-5, out, winv, n_split)
     _lib.check(rc, "ance_debug_gemm_split")
     torch.cuda.synchronize()
     return out, part_out
@@ -270,6 +322,56 @@ def test_streaming_split_gemm_equals_the_launch_per_tile_kernel(epi, shape, monk
     try:
         a, pa = _split_raw(epi, M, N, K, 5, True, monkeypatch)
         b, pb = _split_raw(epi, M, N, K, 5, False, monkeypatch)
+    finally:
+        monkeypatch.delenv("ANCE_GEMM_STREAM", raising=False)
+        _lib.reload_env()
+    assert bool(torch.isfinite(a.float()).all())
+    assert torch.equal(a.view(torch.int16) if a.dtype == torch.float16 else a.view(torch.int32),
+                       b.view(torch.int16) if b.dtype == torch.float16 else b.view(torch.int32)), (epi, shape)
+
+
+@pytest.mark.parametrize("epi,shape", [(8, (512, 3072, 1024)), (8, (256, 1024, 128)), (10, (512, 1024, 1024)), (10, (512, 1024, 4096))])
+@pytest.mark.parametrize("variant", ["full", "a_lo_zero", "b_lo_zero"])
+def test_split_gemm_1024_is_fp32_grade(epi, shape, variant):
+    """The hidden-1024 instances of the split GEMM (part_in as eight 128-column slices: csrc/gemm_f16.h PartFormat) at the large
+    tower's shapes -- QKV (K = 1024) and both RESLN GEMMs (K = 1024 and 4096) -- with the bound of test_split_gemm_is_fp32_grade on
+    the accumulation (epi 8), and of test_split_gemm_pair_epilogues on the pair outputs and the eight-slice part_out (epi 10)."""
+    M, N, K = shape
+    got, ref, scale, part, want_part = _run_split(epi, M, N, K, seed=17, zero_a_lo=variant == "a_lo_zero",
+                                                  zero_b_lo=variant == "b_lo_zero", wscale=2.0 ** 17, hw=1024)
+    rel = (got - ref).abs() / scale
+    bound = 5e-7 if epi == 8 else 1e-6
+    print("split epi %d %s hw 1024 %s: max rel err %.3e (bound %.0e)" % (epi, shape, variant, float(rel.max()), bound))
+    assert float(rel.max()) <= bound, (epi, variant, shape, float(rel.max()), torch.nonzero(rel > bound)[:3].tolist())
+    if part is not None:
+        dm = (part[..., 0] - want_part[..., 0]).abs()
+        dq = (part[..., 1] - want_part[..., 1]).abs() / want_part[..., 1]
+        print("split epi 10 %s hw 1024 %s part_out: max |d mean| %.3e, max rel d M2 %.3e" % (shape, variant, float(dm.max()), float(dq.max())))
+        assert float(dm.max()) <= 2e-6 and float(dq.max()) <= 2e-5, (float(dm.max()), float(dq.max()))
+
+
+@pytest.mark.parametrize("shape", [(512, 4096, 1024), (256, 256, 128)])
+def test_split_gemm_1024_gelu_pair_epilogue(shape):
+    """EPI_S_GELU at hidden 1024 (FFN1 of the large tower: N = 4096, K = 1024) on every row and column, bound of
+    test_split_gemm_pair_epilogues."""
+    M, N, K = shape
+    got, ref, scale, _, _ = _run_split(9, M, N, K, seed=19, wscale=2.0 ** 17, hw=1024)
+    rel = (got - ref).abs() / scale
+    print("split epi 9 %s hw 1024: max rel err %.3e" % (shape, float(rel.max())))
+    assert float(rel.max()) <= 1e-6, (shape, float(rel.max()), torch.nonzero(rel > 1e-6)[:5].tolist())
+
+
+@pytest.mark.parametrize("epi,shape,n_split", [(8, (2048, 3072, 1024), 0), (9, (16384, 4096, 1024), 2), (8, (16640, 3072, 1024), 0),
+                                               (9, (33024, 4096, 1024), 2), (9, (1280, 4096, 1024), 0)])
+def test_streaming_split_gemm_equals_the_launch_per_tile_kernel_at_1024(epi, shape, n_split, monkeypatch):
+    """gemm256_split_stream_kernel<.., 1024> against the launch-per-tile kernel at the large tower's QKV and FFN1 shapes (FFN1 in
+    the N-split order the encoder gives it): one tile per workgroup (96 tiles), several (1,024), ragged last rounds (780 / 2,064
+    tiles), every output bit identical."""
+    from ance_amd import _lib
+    M, N, K = shape
+    try:
+        a, _ = _split_raw(epi, M, N, K, 6, True, monkeypatch, hw=1024, n_split=n_split)
+        b, _ = _split_raw(epi, M, N, K, 6, False, monkeypatch, hw=1024, n_split=n_split)
     finally:
         monkeypatch.delenv("ANCE_GEMM_STREAM", raising=False)
         _lib.reload_env()

@@ -196,3 +196,128 @@ def test_large_refresh_job_against_the_reference_run(golden_dir, tmp_path):
     run(inf, "--inference")
     pe = np.load(os.path.join(inf, "passage_100__emb_p__data_obj_0.npy"))
     assert np.array_equal(pe, p_emb)
+
+
+# ---- the base tower's adversarial encoder tests (tests/test_gpu_encoder.py) at the large width: 3-layer towers against the fp64
+# oracle with 16 heads, the base tower's tolerances at the same depth (fp16 5e-3 and cosine 0.99999, split fp32-grade)
+
+def _oracle64(sd, ids, lens, L, n_layers):
+    from oracle import encoder_ref
+    with torch.no_grad():
+        sd64 = {k: v.double() for k, v in sd.items()}
+        return encoder_ref.rdot_nll_ln_emb(sd64, torch.from_numpy(ids), encoder_ref.mask_from_lengths(lens, L), n_layers=n_layers,
+                                           n_heads=16).float().numpy()
+
+
+def _encode_np(sd, precision, ids, lens, L=128, max_tokens=2048):
+    enc = _encoder(sd, precision, L, max_tokens)
+    return _encode(enc, ids, lens).cpu().numpy()
+
+
+LENS12 = np.array([1, 2, 31, 33, 64, 65, 96, 128, 70, 9, 100, 50], dtype=np.int32)
+
+
+@pytest.mark.parametrize("offset", [5.0, 30.0])
+def test_large_rows_with_a_large_mean_keep_the_fp16_tolerance(offset):
+    """fp16 mode on rows whose mean is 5 / 30 standard deviations away from 0 (tests/test_gpu_encoder.py: _offset_weights): at
+    hidden 1024 the folded GEMM tiles read eight 128-column slice statistics, detect the wide rows and add the K loop over their
+    lo halves."""
+    from oracle import encoder_ref, synth
+    from test_gpu_encoder import _offset_weights, _report
+    n_layers = 3
+    sd = _offset_weights(encoder_ref.random_state_dict(seed=5, n_layers=n_layers, ln_jitter=0.1, **LARGE), offset, n_layers)
+    ids = synth.make_records(np.random.default_rng(8), len(LENS12), 128, LENS12.astype(np.int64))
+    _report("large_width_mean_offset_%g" % offset, _encode_np(sd, "fp16", ids, LENS12), _oracle64(sd, ids, LENS12, 128, n_layers))
+
+
+def test_large_fp16_rows_do_not_depend_on_their_tile_mates():
+    """fp16 mode, wide-mean and ordinary tokens inside the same 256-token GEMM tiles (half of the sequences draw their tokens from
+    embeddings 8 standard deviations off zero): the masked second K loop keeps a row's bits independent of its neighbours --
+    identical under three micro-batch splits and in reverse order -- and everything stays inside the fp16 tolerance."""
+    from oracle import encoder_ref, synth
+    from test_gpu_encoder import _report
+    n_layers = 3
+    sd = dict(encoder_ref.random_state_dict(seed=21, n_layers=n_layers, ln_jitter=0.1, **LARGE))
+    we = sd["roberta.embeddings.word_embeddings.weight"].clone()
+    we[30000:] += 8 * 0.035
+    sd["roberta.embeddings.word_embeddings.weight"] = we
+    rng = np.random.default_rng(22)
+    n = 96
+    lens = rng.integers(1, 129, size=n).astype(np.int32)
+    ids = synth.make_records(rng, n, 128, lens.astype(np.int64))
+    wide_seq = (np.arange(n) % 2) == 1
+    ids[wide_seq] = np.where(ids[wide_seq] > 3, 30000 + ids[wide_seq] % 20000, ids[wide_seq])
+    ids[~wide_seq] = np.where(ids[~wide_seq] >= 30000, ids[~wide_seq] - 25000, ids[~wide_seq])
+    got = _encode_np(sd, "fp16", ids, lens, max_tokens=2048)
+    _report("large_width_mixed_wide_and_ordinary_rows", got, _oracle64(sd, ids, lens, 128, n_layers))
+    assert np.array_equal(_encode_np(sd, "fp16", ids, lens, max_tokens=512), got)
+    assert np.array_equal(_encode_np(sd, "fp16", ids, lens, max_tokens=1024), got)
+    rev = np.arange(n)[::-1].copy()
+    assert np.array_equal(_encode_np(sd, "fp16", ids[rev].copy(), lens[rev].copy(), max_tokens=768)[rev], got)
+
+
+def test_large_split_mode_with_weights_of_very_different_scales():
+    """Split mode with every weight matrix of a 3-layer large tower rescaled by factors between 2^-7 and 2^9 (and one outlier
+    element 50,000 x its matrix's typical one): within 4 x the fp32 oracle's distance from fp64, + 2e-5."""
+    from oracle import encoder_ref, synth
+    from test_gpu_encoder import _oracle_pair
+    n_layers = 3
+    sd = dict(encoder_ref.random_state_dict(seed=61, n_layers=n_layers, ln_jitter=0.1, **LARGE))
+    factors = {"attention.self.query": 6.0, "attention.self.key": 1.0 / 6.0, "attention.self.value": 37.0, "attention.output.dense": 1.0 / 40.0,
+               "intermediate.dense": 300.0, "output.dense": 1.0 / 120.0}
+    for i in range(n_layers):
+        for name, f in factors.items():
+            k = "roberta.encoder.layer.%d.%s.weight" % (i, name)
+            sd[k] = sd[k] * (f if i != 1 else 1.0 / f)
+    w = sd["roberta.encoder.layer.2.output.dense.weight"].clone()
+    w[1000, 3077] = 9.0
+    sd["roberta.encoder.layer.2.output.dense.weight"] = w
+    ids = synth.make_records(np.random.default_rng(62), len(LENS12), 128, LENS12.astype(np.int64))
+    want64, want32 = _oracle_pair(sd, ids, LENS12, 128, n_layers, n_heads=16)
+    got = _encode_np(sd, "split", ids, LENS12)
+    e32 = float(np.abs(want32.astype(np.float64) - want64).max())
+    e = float(np.abs(got.astype(np.float64) - want64).max())
+    print("large split weight scales: max |delta| vs fp64 %.3e, fp32 oracle vs fp64 %.3e" % (e, e32))
+    assert np.isfinite(got).all() and e <= 4.0 * e32 + 2e-5, (e, e32)
+
+
+@pytest.mark.parametrize("ffn_drive", [None, 300.0, 2.0e4])
+def test_large_split_mode_on_trained_like_activations(ffn_drive):
+    """tests/test_gpu_encoder.py::test_split_mode_on_trained_like_activations at hidden 1024, with a third outlier LayerNorm gain in
+    the last 128-column slice of the statistics (dimension 1000): fp32-grade -- max(2e-5, 4 x the fp32 oracle's distance from
+    fp64) -- and the range guard silent."""
+    from oracle import synth
+    from test_gpu_encoder import _oracle_pair, _trained_like_weights
+    n_layers = 3
+    sd = _trained_like_weights(n_layers, ffn_drive, hidden=1024, inter=4096, outliers=((17, 50.0), (400, -50.0), (1000, 50.0)))
+    ids = synth.make_records(np.random.default_rng(72), len(LENS12), 128, LENS12.astype(np.int64))
+    want64, want32 = _oracle_pair(sd, ids, LENS12, 128, n_layers, n_heads=16)
+    got = _encode_np(sd, "split", ids, LENS12)   # (_encode: the range guard must stay silent)
+    e32 = float(np.abs(want32.astype(np.float64) - want64).max())
+    e = float(np.abs(got.astype(np.float64) - want64).max())
+    print("large split trained-like ffn %s: max |delta| vs fp64 %.3e, fp32 oracle vs fp64 %.3e" % (ffn_drive, e, e32))
+    assert np.isfinite(got).all() and e <= max(2e-5, 4.0 * e32), (e, e32)
+
+
+@pytest.mark.parametrize("L,n,max_tokens,seed", [(128, 900, 4096, 1), (512, 60, 4096, 3), (32, 1500, 512, 4), (8, 3000, 4096, 5)])
+def test_large_random_batches_fp16_against_fp32_mode(L, n, max_tokens, seed):
+    """Random lengths 1..L across many micro-batches, with tails of more (L = 8: ~900 sequences per micro-batch) and fewer than 256
+    [CLS] rows:
+    the fp16 mode against the fp32 mode of the large tower (two independent implementations of every kernel) within 5e-3, and
+    identical one-token inputs give identical rows."""
+    from oracle import encoder_ref, synth
+    sd = encoder_ref.random_state_dict(seed=30 + seed, n_layers=3, ln_jitter=0.1, **LARGE)
+    rng = np.random.default_rng(100 + seed)
+    lens = rng.integers(1, L + 1, size=n).astype(np.int32)
+    lens[:8] = [1, 1, L, L, 2, L - 1, 33 % L + 1, 1]
+    ids = synth.make_records(rng, n, L, lens.astype(np.int64)).astype(np.int32)
+    a = _encode(_encoder(sd, "fp16", L, max_tokens), ids, lens)
+    b = _encode(_encoder(sd, "fp32", L, max_tokens), ids, lens)
+    assert torch.isfinite(a).all() and torch.isfinite(b).all()
+    d = (a - b).abs().max(dim=1).values
+    print("large fp16 vs fp32 mode L %d n %d: max |delta| %.3e" % (L, n, float(d.max())))
+    assert float(d.max()) <= 5e-3, (float(d.max()), int(d.argmax()), int(lens[int(d.argmax())]))
+    same = np.flatnonzero(lens == 1)
+    if len(same) > 1:
+        twins = [int(r) for r in same if ids[r, 0] == ids[same[0], 0]]
+        assert all(torch.equal(a[twins[0]], a[r]) for r in twins)
