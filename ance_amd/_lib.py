@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("ANCE_AMD_LIB") or os.path.join(_HERE, "libance_amd.so
 CSRC = os.path.join(_HERE, "csrc")
 
 ANCE_OK = 0
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -40,6 +40,17 @@ class AnceGemmDebugArgs(ctypes.Structure):
         ("n_valid", ctypes.c_int32), ("ldc", ctypes.c_int32), ("out", ctypes.c_void_p), ("res_hi", ctypes.c_void_p),
         ("res_lo", ctypes.c_void_p), ("res_gamma", ctypes.c_void_p), ("res_beta", ctypes.c_void_p), ("out_lo", ctypes.c_void_p),
         ("part_out", ctypes.c_void_p), ("ldr", ctypes.c_int32), ("wscale_inv", ctypes.c_void_p), ("n_split", ctypes.c_int32),
+    ]
+
+
+class AnceAttnDebugArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_debug_attention (h_desc is HOST memory)."""
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("n_heads", ctypes.c_int32), ("n_seq", ctypes.c_int32), ("max_seq_len", ctypes.c_int32),
+        ("cls_only", ctypes.c_int32), ("q_compact", ctypes.c_int32), ("h_desc", ctypes.c_void_p), ("d_desc", ctypes.c_void_p),
+        ("d_desc_bytes", ctypes.c_int64), ("qk", ctypes.c_void_p), ("ld_qk", ctypes.c_int32), ("qk_rows", ctypes.c_int32),
+        ("vt", ctypes.c_void_p), ("ld_vt", ctypes.c_int32), ("ctx", ctypes.c_void_p), ("ld_ctx", ctypes.c_int32),
+        ("ctx_rows", ctypes.c_int32),
     ]
 
 
@@ -111,6 +122,7 @@ SYMBOLS = {
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "ance_debug_gemm_hw": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(AnceGemmDebugArgs), ctypes.c_void_p]),
+    "ance_debug_attention": (ctypes.c_int, [ctypes.POINTER(AnceAttnDebugArgs), ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

@@ -38,7 +38,8 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 6  /* 6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
+#define ANCE_ABI_VERSION 7  /* 7: + ance_debug_attention (AnceAttnDebugArgs);
+                               6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
                                5: AnceEncoderDesc.precision (the arithmetic is an argument, not an environment variable), ance_encoder_range_faults,
                                ance_ip_topk_scan; 4: blocked pair rows in the split mode (ance_pair_layout; ance_debug_gemm_split + d_wscale_inv);
                                3: + ance_nll_forward, ance_search_bad_image_calls, ance_debug_gemm_split; split encoder mode */
@@ -358,6 +359,36 @@ typedef struct AnceGemmDebugArgs {
     int32_t n_split;
 } AnceGemmDebugArgs;
 int ance_debug_gemm_hw(int epi, int hw, const AnceGemmDebugArgs *args, void *stream);
+
+/* Test hook: ONE launch of one of the encoder's three attention kernels on caller data, through the encoder's own launchers
+ * (csrc/attention.hip: launch_attention, launch_attention_split; csrc/precise32.h: launch_attention32).  Head dim 64, H = 64 n_heads.
+ *   kind 0  fp16 fast mode (AttnArgs): qk fp16 [qk_rows, ld_qk] = Q (pre-scaled by log2(e) / 8) | K; vt fp16 [H, ld_vt] = V^T with
+ *           the keys of a sequence at columns vcol .. vcol + len; ctx fp16 [ctx_rows, ld_ctx].  cls_only: query 0 of every sequence
+ *           only, its output row is s; q_compact (with cls_only): that query is row s of the Q columns
+ *   kind 1  split mode: qk fp32 [qk_rows, 3 H] = Q | K | V (unscaled); ctx fp16 PAIR rows [ctx_rows, 2 H] (ance_pair_layout);
+ *           cls_only: the query of sequence s is row s of the Q columns and its output row is s (q_compact must equal cls_only)
+ *   kind 2  fp32 mode: qk fp32 [qk_rows, 3 H] = Q | K | V; ctx fp32 [ctx_rows, H]; no cls_only
+ * h_desc is HOST memory: kinds 0, 1 int32[n_seq][4] = (first token, length, first V^T column, sequence index s), kind 2 int32
+ * [n_seq + 1] = token offsets (sequence s = rows seq_off[s] .. seq_off[s + 1]).  The hook validates it, then copies it with
+ * hipMemcpyAsync on the stream into d_desc (d_desc_bytes long); h_desc must stay valid until the stream has run the copy.
+ * Refuses (ANCE_E_INVALID, before any copy or launch) a kind outside 0..2, n_heads outside {12, 16}, n_seq < 1,
+ * max_seq_len outside 1..512, a length outside 1..max_seq_len, a sequence whose token rows, Q row s (q_compact), output row or V^T
+ * columns vcol + roundup8(len) fall outside the allocation, vcol % 8 != 0, strides or pointers that break the kernels' 16-byte
+ * accesses (kinds 1, 2: the strides are fixed at 3 H and 2 H / H), a repeated or out-of-range sequence index, cls_only on
+ * kind 2, q_compact without cls_only (kind 1: q_compact != cls_only), a d_desc too small and a null pointer the kind reads. */
+typedef struct AnceAttnDebugArgs {
+    int32_t kind, n_heads, n_seq, max_seq_len, cls_only, q_compact;
+    const int32_t *h_desc;        /* HOST: int4 descriptors (kinds 0, 1) or seq_off (kind 2)      */
+    void *d_desc;
+    int64_t d_desc_bytes;
+    const void *qk;               /* fp16 (kind 0) or fp32 Q | K | V (kinds 1, 2)                 */
+    int32_t ld_qk, qk_rows;
+    const void *vt;               /* fp16 [H, ld_vt], kind 0 only                                 */
+    int32_t ld_vt;
+    void *ctx;                    /* fp16 (kind 0), fp16 pair rows (kind 1) or fp32 (kind 2)      */
+    int32_t ld_ctx, ctx_rows;
+} AnceAttnDebugArgs;
+int ance_debug_attention(const AnceAttnDebugArgs *args, void *stream);
 
 /* Layout of the split mode's pair rows (for tests and tools that build or read them): column n of a W-wide fp32 row has its hi
  * half at *hi_col and its lo half at *lo_col of the 2 W-half pair row, lo = fp16((v - hi) * *lo_scale).  Product library:
