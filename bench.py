@@ -14,17 +14,23 @@ A "step" is one pass of the hot path over one batch of synthetic input, timed pe
                is resident in HBM, sharded over the ranks (contiguous row blocks), per-shard lists
                exchanged by query owner over RCCL (all-to-all), merged, gathered on rank 0 -> queries/s
                (the refresh searches 100k-503k queries, in launch chunks of 32,768: that is the step).
-    python bench.py --full   measures ONE real refresh end to end instead (caches on disk -> files), per phase.
+    python bench.py --refresh   measures ONE real refresh end to end instead (caches on disk -> files), per phase.
 Both legs: W untimed warm-up steps, then exactly K steps between barrier + synchronize on both
 sides, MAX over ranks; `ms_per_step` is one timed step of the headline encode leg.  Rank 0 prints ONE JSON line on stdout
 (everything else the run prints goes to stderr).  --dump-outputs DIR writes what the last timed step returned (a seeded
-sample of the rows) as .npy files, so that two builds can be compared output for output.  `roofline` comes from HIP events the library
-records around every kernel launch on the launch stream during the timed steps; `cpu_baseline` is
-the oracle (a port of the reference CPU path) timed on this box's host cores on a bounded sample;
-`power` (and `search.power`) are the board's socket power and shader clock sampled from the amdgpu
+sample of the rows) as .npy files, so that two builds can be compared output for output.
+
+A plain run measures the headline alone: set-up, the warm-up and timed steps of the headline encode leg, the dumps, the line.
+It runs the search legs only for --dump-outputs, one untimed step each (a step's output does not depend on how many ran).
+--full adds everything else: the timed search legs and their exact checks, the fp16 and fp32 encoder modes, per-kernel
+`roofline` figures from a single-stream pass, `power`, the sustained MFMA rate, the other BASELINE configurations, the
+whole-refresh slice and the CPU baselines.  `roofline` comes from HIP events the library records around every kernel
+launch on the launch stream; `cpu_baseline` is the oracle (a port of the reference CPU path) timed on this box's host cores
+on a bounded sample; `power` (and `search.power`) are the board's socket power and shader clock sampled from the amdgpu
 hwmon files while the timed steps run -- reported only: both matrix-core encoder modes sit at the cap.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -64,13 +70,17 @@ def parse():
     p.add_argument("--skip-precise", action="store_true", help="skip the fp32-mode encoder sample")
     p.add_argument("--skip-encoder-like", action="store_true", help="skip the second search leg (encoder-like rows)")
     p.add_argument("--full", action="store_true",
+                   help="measure everything besides the headline: the timed search legs, the other encoder modes, rooflines, "
+                        "power, the MFMA probe, the other configurations, the refresh slice, the CPU baselines (the --skip-* "
+                        "options and those below select among them)")
+    p.add_argument("--refresh", action="store_true",
                    help="measure ONE real refresh instead of the step benchmark: write the tokenised caches of "
-                        "--n-passages passages / --full-queries train queries to --full-dir, then run "
+                        "--n-passages passages / --refresh-queries train queries to --refresh-dir, then run "
                         "ance_amd.ann_data_gen.generate_new_ann on them (stream from disk, encode, search, host stage, "
                         "files) and print the wall time per phase")
-    p.add_argument("--full-dir", type=str, default="/tmp/ance_full")
-    p.add_argument("--full-queries", type=int, default=N_TRAIN_QUERIES)
-    p.add_argument("--full-dev-queries", type=int, default=6980)
+    p.add_argument("--refresh-dir", type=str, default="/tmp/ance_refresh")
+    p.add_argument("--refresh-queries", type=int, default=N_TRAIN_QUERIES)
+    p.add_argument("--refresh-dev-queries", type=int, default=6980)
     p.add_argument("--negative-sample", type=int, default=20)
     p.add_argument("--skip-mfma-probe", action="store_true",
                    help="do not run tools/power_probe (the sustained MFMA rate of this board at its power cap, ~12 s)")
@@ -86,7 +96,7 @@ def parse():
     p.add_argument("--slice-dev-queries", type=int, default=6980)
     p.add_argument("--slice-dir", type=str, default="/tmp/ance_slice")
     p.add_argument("--encoder-precision", type=str, default=None, choices=["fp16", "split", "fp32"],
-                   help="--full only: the encoder arithmetic of the refresh (ance_amd.ann_data_gen --encoder_precision)")
+                   help="--refresh only: the encoder arithmetic of the refresh (ance_amd.ann_data_gen --encoder_precision)")
     p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                    help="write what the last timed step of each leg returned as DIR/<name>.npy (float32 / float64, a fixed seeded "
                         "sample of rows, at most 64 MB in all): the headline encode leg's embeddings, the search leg's top-k scores "
@@ -212,21 +222,22 @@ def full_refresh(a):
     import logging
     logging.basicConfig(format="%(asctime)s %(name)s %(message)s", level=logging.INFO, stream=sys.stderr)
     result = result_stream()
-    d = a.full_dir
+    d = a.refresh_dir
     mode = a.encoder_precision or precision_from_env()
-    wall, timings, prep, lines, ndcg = run_refresh(a, d, a.n_passages, a.full_queries, a.full_dev_queries, adg.Dist(), dev, rank, mode)
+    wall, timings, prep, lines, ndcg = run_refresh(a, d, a.n_passages, a.refresh_queries, a.refresh_dev_queries, adg.Dist(), dev, rank,
+                                                   mode)
     if rank == 0:
         enc_s = timings.get("encode_passages", 0.0)
         out = {"metric": "full_refresh_seconds", "value": wall, "unit": "s", "n_gpus": world, "higher_is_better": False,
                "dtype": DTYPE_OF[mode], "encoder_precision": mode, "data": "synthetic",
                "config": {"workload": "one ANN refresh: %d passages (seq_len %d, streamed from %s) + %d train queries "
                                       "(ann_chunk_factor 1) + %d dev queries, top-%d, %d negatives, roberta-base rdot_nll "
-                                      "random init" % (a.n_passages, a.seq_len, d, a.full_queries, a.full_dev_queries, a.topk,
+                                      "random init" % (a.n_passages, a.seq_len, d, a.refresh_queries, a.refresh_dev_queries, a.topk,
                                                        a.negative_sample)},
                "phases_s": {k: round(v, 3) for k, v in timings.items()},
                "prepare_s": {k: round(v, 3) for k, v in prep.items()},
                "passages_per_sec_measured": a.n_passages / enc_s if enc_s > 0 else None,
-               "train_queries_per_sec_measured": a.full_queries / timings["search_train"] if timings.get("search_train") else None,
+               "train_queries_per_sec_measured": a.refresh_queries / timings["search_train"] if timings.get("search_train") else None,
                "lines_written": lines, "dev_ndcg": ndcg}
         print(json.dumps(out), file=result, flush=True)
     if world > 1:
@@ -744,6 +755,45 @@ def measure_other_configs(torch, dev, steps, tokens_per_step, precision, max_tok
     return rows
 
 
+def search_inputs(torch, a, dev, rank, world):
+    """The search legs' inputs: this rank's contiguous block of the corpus (LayerNorm rows of N(0,1) draws, seeded per rank) and
+    the query block.  Returns (first row, rows, queries, the rows' generator, the queries' generator): encoder_like_inputs
+    draws the second leg's inputs from the same two generators."""
+    from ance_amd.cache import shard_range
+    r0, r1 = shard_range(a.n_passages, rank, world)
+    n_loc = r1 - r0
+    g = torch.Generator(device=dev).manual_seed(4321 + rank)
+    x = torch.empty((n_loc, 768), dtype=torch.float32, device=dev)
+    for b0 in range(0, n_loc, 1 << 20):
+        b1 = min(b0 + (1 << 20), n_loc)
+        z = torch.randn((b1 - b0, 768), generator=g, device=dev)
+        x[b0:b1] = torch.nn.functional.layer_norm(z, (768,))
+    gq = torch.Generator(device=dev).manual_seed(99)
+    q = torch.nn.functional.layer_norm(torch.randn((a.query_block, 768), generator=gq, device=dev), (768,))
+    return r0, x, q, g, gq
+
+
+def encoder_like_inputs(torch, x, q, g, gq):
+    """The second search leg's ENCODER-LIKE rows and queries, in place of the first leg's: one large common component + small
+    deviations per row and per query."""
+    dev = x.device
+    gc_ = torch.Generator(device=dev).manual_seed(777)
+    c = torch.randn((768,), generator=gc_, device=dev)
+    c = c / c.norm() * (768.0 ** 0.5)
+    for b0 in range(0, x.shape[0], 1 << 20):
+        b1 = min(b0 + (1 << 20), x.shape[0])
+        x[b0:b1] = c[None, :] + 0.12 * torch.randn((b1 - b0, 768), generator=g, device=dev)
+    q.copy_(c[None, :] + 0.12 * torch.randn((q.shape[0], 768), generator=gq, device=dev))
+    x.add_(0.0)  # bumps the tensor's version counter: the engine rebuilds its search image
+
+
+def dump_lists(torch, dumps, name, seed, D, I, k):
+    """--dump-outputs: a fixed seeded sample of the rows of merged top-k lists as `name`_scores / `name`_ids."""
+    sel = torch.from_numpy(dump_rows(D.shape[0], k * (4 + 8), DUMP_BUDGET[name], seed)).to(D.device)
+    dumps[name + "_scores"] = D[sel].cpu().numpy()
+    dumps[name + "_ids"] = I[sel].cpu().numpy().astype(np.float64)  # exact: ids < 2^53
+
+
 def launch_ranks(a):
     """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU, RCCL) under torch.distributed.run --
     the reference's own launch is `python -m torch.distributed.launch --nproc_per_node=N` (commands/run_ann_data_gen.sh:44-49,
@@ -774,7 +824,7 @@ def main():
         sys.exit(2)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         return launch_ranks(a)
-    if a.full:
+    if a.refresh:
         return full_refresh(a)
     result = result_stream()
     import torch
@@ -798,7 +848,6 @@ def main():
             torch.distributed.init_process_group(backend=backend)
     from ance_amd import _lib
     from ance_amd import ann_data_gen as adg
-    from ance_amd.cache import shard_range
     from ance_amd.encoder import ARCH_ROBERTA, Encoder
     dist = adg.Dist()
     eng = adg.HipEngine(dev)
@@ -818,8 +867,8 @@ def main():
     # Three arithmetic modes of the same encoder on the same block.  The HEADLINE (top-level value / ms_per_step / dtype /
     # roofline) is the library's default, the split mode: fp32-grade like the reference's own fp32 forward
     # (model/models.py:149-157 has no .half()), so it is the precision-matched number.  The fp16 fast mode and the fp32 audit
-    # mode are reported beside it (`encode_fp16_fast`, `encode_fp32`), each with its own roofline and its measured distance
-    # from the headline mode's embeddings.
+    # mode are reported beside it with --full (`encode_fp16_fast`, `encode_fp32`), each with its own roofline and its measured
+    # distance from the headline mode's embeddings.
     if not a.skip_encode:
         try:
             sd = random_init_roberta_base(torch, a.layers, seed=0)
@@ -829,14 +878,13 @@ def main():
             flops_alg = float(sum(169869312.0 * t + 36864.0 * t * t + 1179648.0 for t in lens.astype(np.float64)))
             flops_pad = a.encode_block * (169869312.0 * a.seq_len + 36864.0 * a.seq_len ** 2 + 1179648.0)
 
-            want_emb = not a.skip_precise and world == 1
+            want_emb = a.full and not a.skip_precise and world == 1
             # the rate the matrix pipe sustains on THIS board (tools/power_probe: ~12 s), single-GPU runs only, before anything is timed
-            probe_live = [sustained_mfma_rate() if (world == 1 and not a.skip_mfma_probe) else None]
+            probe_live = [sustained_mfma_rate() if (a.full and world == 1 and not a.skip_mfma_probe) else None]
 
             def measure_mode(mode, steps, kernels, peak, mfma_per_product, trace_label):
-                """K timed steps of `mode` on the product handle (two internal streams), then the same records on a single-stream
-                handle with the library's HIP events on: inside the timed region kernels of two micro-batches share the chip,
-                so a per-kernel duration is a property of the kernel only in the single-stream pass."""
+                """K timed steps of `mode` on the product handle (two internal streams); with --full also the board's power over
+                them and the mode's roofline (single_stream_roofline)."""
                 enc = Encoder(sd, ARCH_ROBERTA, "roberta.", True, max_seq_len=min(a.seq_len, 512), max_tokens=a.max_tokens,
                               device=dev, precision=mode)
                 assert enc.precision == mode
@@ -848,19 +896,39 @@ def main():
                 for _ in range(max(a.warmup, 1) if mode == HEADLINE_MODE else 1):
                     step()
                 torch.cuda.synchronize()
-                with PowerSampler(torch, dev.index or 0) as ps:
+                with (PowerSampler(torch, dev.index or 0) if a.full else contextlib.nullcontext()) as ps:
                     dt = timed_steps(step, steps, 0, dist_on, torch)
-                power = ps.report()
+                power = ps.report() if a.full else None
                 if a.dump_outputs and rank == 0 and mode == HEADLINE_MODE:  # `emb` as the last timed step left it
                     sel = torch.from_numpy(dump_rows(a.encode_block, 768 * 4, DUMP_BUDGET["encode"], 0)).to(dev)
                     dumps["encode_embeddings"] = emb[sel].cpu().numpy()
+                pps = world * a.encode_block * steps / dt
+                leg = {"value": pps, "unit": "passages/s", "ms_per_step": 1e3 * dt / steps, "steps": steps, "block": a.encode_block,
+                       "encoder_precision": mode, "dtype": DTYPE_OF[mode], "arithmetic": ARITHMETIC_OF[mode],
+                       "tokens_per_sec": pps * float(lens.mean()), "algorithmic_tflops": world * flops_alg * steps / dt / 1e12}
+                if a.full:
+                    leg["roofline"] = single_stream_roofline(mode, steps, dt, kernels, peak, mfma_per_product, trace_label)
+                    leg["power"] = power
+                e = None
+                if want_emb:  # the mode's embeddings of the block, for the distance between the modes
+                    step()
+                    torch.cuda.synchronize()
+                    e = emb.clone()
+                del enc, emb
+                torch.cuda.empty_cache()
+                return leg, e
+
+            def single_stream_roofline(mode, steps, dt, kernels, peak, mfma_per_product, trace_label):
+                """The records of the timed steps on a single-stream handle with the library's HIP events on: inside the timed
+                region kernels of two micro-batches share the chip, so a per-kernel duration is a property of the kernel only in
+                the single-stream pass."""
                 os.environ["ANCE_ENCODER_STREAMS"] = "1"
                 try:
                     enc1 = Encoder(sd, ARCH_ROBERTA, "roberta.", True, max_seq_len=min(a.seq_len, 512), max_tokens=a.max_tokens,
                                    device=dev, precision=mode)
                 finally:
                     os.environ.pop("ANCE_ENCODER_STREAMS", None)
-                emb1 = torch.empty_like(emb)
+                emb1 = torch.empty((a.encode_block, 768), dtype=torch.float32, device=dev)
                 enc1.encode_records(rec_d, h_lens=lens, out=emb1)
                 torch.cuda.synchronize()
                 n_iso = steps if mode == HEADLINE_MODE else max(1, min(steps, 3))
@@ -880,7 +948,6 @@ def main():
                 all_work = sum(prof[c]["work"] for c in gemm_cats)
                 t_ns = trace_avg_ns("%s_rocprofv3_%s_single_stream_kernel_stats.csv" % (CURRENT_ROUND, trace_label), kernels.get(dom, "?"))
                 fl = prof[dom]["work"] / max(prof[dom]["count"], 1)
-                pps = world * a.encode_block * steps / dt
                 roof = {"bound": "mfma", "kernel": "%s (%s)" % (kernels.get(dom, "?"), dom), "achieved": alg, "peak": peak,
                         "unit": "TFLOP/s", "frac": alg / peak,
                         "achieved_is": "algorithmic FLOPs (2 M N K of the launch) / average launch duration",
@@ -908,18 +975,7 @@ def main():
                         "cases": live,
                         "source": "tools/power_probe run by this bench on this box (2 s per case, before the timed legs)" if live else
                                   "profiles/r06_power_probe.txt (tools/power_probe.cpp, scripts/gpu_r6_power_probe.sh)"}
-                leg = {"value": pps, "unit": "passages/s", "ms_per_step": 1e3 * dt / steps, "steps": steps, "block": a.encode_block,
-                       "encoder_precision": mode, "dtype": DTYPE_OF[mode], "arithmetic": ARITHMETIC_OF[mode],
-                       "tokens_per_sec": pps * float(lens.mean()), "algorithmic_tflops": world * flops_alg * steps / dt / 1e12,
-                       "roofline": roof, "power": power}
-                e = None
-                if want_emb:  # the mode's embeddings of the block, for the distance between the modes
-                    step()
-                    torch.cuda.synchronize()
-                    e = emb.clone()
-                del enc, emb
-                torch.cuda.empty_cache()
-                return leg, e
+                return roof
 
             head, emb_head = measure_mode(HEADLINE_MODE, a.steps, KERNEL_OF_SPLIT, PEAK_F16_TF, 3.0, "encode_split")
             pps = head["value"]
@@ -927,8 +983,9 @@ def main():
             out["ms_per_step"] = head["ms_per_step"]
             out["dtype"] = head["dtype"]
             out["encoder_precision"] = HEADLINE_MODE
-            out["roofline"] = head["roofline"]
-            out["power"] = head["power"]  # the board while the timed steps ran (PowerSampler): both matrix-core modes sit at the cap
+            if a.full:
+                out["roofline"] = head["roofline"]
+                out["power"] = head["power"]  # the board while the timed steps ran (PowerSampler): both matrix-core modes sit at the cap
             out["encode"] = {"passages_per_sec": pps, "tokens_per_sec": head["tokens_per_sec"], "mean_len": float(lens.mean()),
                              "arithmetic": head["arithmetic"], "algorithmic_tflops": head["algorithmic_tflops"],
                              "padded_equiv_tflops": world * flops_pad * a.steps / (head["ms_per_step"] * 1e-3 * a.steps) / 1e12,
@@ -937,7 +994,7 @@ def main():
                              "full_corpus_seconds_est": N_PASSAGES / pps}
             # (single-GPU runs only: the multi-GPU runs are the driver's scaling curve of `value`, and the other two modes would
             # double their length)
-            if not a.skip_precise and world == 1:
+            if a.full and not a.skip_precise and world == 1:
                 fast, emb_fast = measure_mode("fp16", a.steps, KERNEL_OF, PEAK_F16_TF, 1.0, "encode_fp16")
                 d = (emb_fast - emb_head).abs()
                 fast["max_abs_vs_split"], fast["mean_abs_vs_split"] = float(d.max().item()), float(d.mean().item())
@@ -964,18 +1021,28 @@ def main():
             errors["encode"] = repr(e)
 
     # ------------------------------------------------------------------------------ search leg --
-    if not a.skip_search:
+    if not a.skip_search and not a.full and a.dump_outputs:
+        # a plain run times no search step: one step per leg for the arrays (a step's output does not depend on how many ran)
         try:
-            r0, r1 = shard_range(a.n_passages, rank, world)
-            n_loc = r1 - r0
-            g = torch.Generator(device=dev).manual_seed(4321 + rank)
-            x = torch.empty((n_loc, 768), dtype=torch.float32, device=dev)
-            for b0 in range(0, n_loc, 1 << 20):
-                b1 = min(b0 + (1 << 20), n_loc)
-                z = torch.randn((b1 - b0, 768), generator=g, device=dev)
-                x[b0:b1] = torch.nn.functional.layer_norm(z, (768,))
-            gq = torch.Generator(device=dev).manual_seed(99)
-            q = torch.nn.functional.layer_norm(torch.randn((a.query_block, 768), generator=gq, device=dev), (768,))
+            r0, x, q, g, gq = search_inputs(torch, a, dev, rank, world)
+            D, I = adg.sharded_search(eng, dist, x, r0, q, a.topk)
+            if rank == 0:
+                dump_lists(torch, dumps, "search", 1, D, I, a.topk)
+            if not a.skip_encoder_like:
+                del D, I
+                encoder_like_inputs(torch, x, q, g, gq)
+                D, I = adg.sharded_search(eng, dist, x, r0, q, a.topk)
+                if rank == 0:
+                    dump_lists(torch, dumps, "search_encoder_like", 2, D, I, a.topk)
+            del x, q, D, I
+        except Exception as e:
+            import traceback
+            traceback.print_exc()
+            errors["search"] = repr(e)
+    if not a.skip_search and a.full:
+        try:
+            r0, x, q, g, gq = search_inputs(torch, a, dev, rank, world)
+            n_loc = x.shape[0]
             res = {}
 
             def step_search():
@@ -983,10 +1050,7 @@ def main():
 
             def dump_search(name, seed):  # the merged lists of the last timed step (rank 0 holds them)
                 if a.dump_outputs and rank == 0:
-                    D_, I_ = res["DI"]
-                    sel = torch.from_numpy(dump_rows(D_.shape[0], a.topk * (4 + 8), DUMP_BUDGET[name], seed)).to(D_.device)
-                    dumps[name + "_scores"] = D_[sel].cpu().numpy()
-                    dumps[name + "_ids"] = I_[sel].cpu().numpy().astype(np.float64)  # exact: ids < 2^53
+                    dump_lists(torch, dumps, name, seed, *res["DI"], a.topk)
 
             for _ in range(max(a.warmup, 1)):
                 step_search()
@@ -1062,14 +1126,7 @@ def main():
             # the error slack is a larger share of the score spread, and the query-mean bias build of the kernel runs
             if not a.skip_encoder_like:
                 del res["DI"], D, I
-                gc_ = torch.Generator(device=dev).manual_seed(777)
-                c = torch.randn((768,), generator=gc_, device=dev)
-                c = c / c.norm() * (768.0 ** 0.5)
-                for b0 in range(0, n_loc, 1 << 20):
-                    b1 = min(b0 + (1 << 20), n_loc)
-                    x[b0:b1] = c[None, :] + 0.12 * torch.randn((b1 - b0, 768), generator=g, device=dev)
-                q.copy_(c[None, :] + 0.12 * torch.randn((a.query_block, 768), generator=gq, device=dev))
-                x.add_(0.0)  # bumps the tensor's version counter: the engine rebuilds its search image
+                encoder_like_inputs(torch, x, q, g, gq)
                 for _ in range(max(a.warmup, 1)):
                     step_search()
                 torch.cuda.synchronize()
@@ -1098,7 +1155,7 @@ def main():
             errors["search"] = repr(e)
 
     # ------------------------------------------------------- other BASELINE configurations --
-    if world == 1 and not a.skip_encode and not a.skip_other_configs:
+    if a.full and world == 1 and not a.skip_encode and not a.skip_other_configs:
         try:
             out["other_configs"] = measure_other_configs(torch, dev, max(1, min(a.other_config_steps, 6)), a.other_config_tokens,
                                                          HEADLINE_MODE, a.max_tokens, a.layers)
@@ -1108,7 +1165,7 @@ def main():
             errors["other_configs"] = repr(e)
 
     # --------------------------------------------------------------------- whole-refresh slice --
-    if world == 1 and not a.skip_slice and not a.skip_encode and out.get("value"):
+    if a.full and world == 1 and not a.skip_slice and not a.skip_encode and out.get("value"):
         try:
             out["full_refresh_slice"] = refresh_slice(a, dist, dev, out["value"])
         except Exception as e:
@@ -1117,7 +1174,7 @@ def main():
             errors["full_refresh_slice"] = repr(e)
 
     # ---------------------------------------------------------------------------- CPU baseline --
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             if not a.skip_encode:
                 out["cpu_baseline"] = cpu_encode_baseline(a.seq_len, a.cpu_seconds, a.layers)
@@ -1125,22 +1182,23 @@ def main():
                 out["search"]["cpu_baseline"] = cpu_search_baseline(a.n_passages, a.topk, a.cpu_seconds)
         except Exception as e:
             errors["cpu_baseline"] = repr(e)
-    try:  # measured by tests/test_gpu_retrieval.py on an MI355X (fp16-operand encoder vs the fp32 reference arithmetic)
-        src = next(n for n in ("r06_retrieval_agreement.json", "r05_retrieval_agreement.json")
-                   if os.path.exists(os.path.join(ROOT, "profiles", n)))
-        with open(os.path.join(ROOT, "profiles", src)) as f:
-            ra = json.load(f)
-        keys = ("n_passages", "n_queries", "layers", "k", "max_abs_passage", "recall_at_200", "identical_top1",
-                "first_20_negatives_overlap", "identical_first_20_negatives")
-        out["retrieval_agreement"] = {k_: ra[k_] for k_ in keys}
-        if "precise_mode" in ra:
-            out["retrieval_agreement"]["fp32_mode"] = {k_: ra["precise_mode"][k_] for k_ in keys}
-        if "split_mode" in ra:
-            out["retrieval_agreement"]["split_mode"] = {k_: ra["split_mode"][k_] for k_ in keys}
-        out["retrieval_agreement"]["measured_in_this_run"] = False
-        out["retrieval_agreement"]["source"] = "profiles/%s (tests/test_gpu_retrieval.py: the three encoder modes against the fp32 oracle)" % src
-    except Exception:
-        pass
+    if a.full:
+        try:  # measured by tests/test_gpu_retrieval.py on an MI355X (fp16-operand encoder vs the fp32 reference arithmetic)
+            src = next(n for n in ("r06_retrieval_agreement.json", "r05_retrieval_agreement.json")
+                       if os.path.exists(os.path.join(ROOT, "profiles", n)))
+            with open(os.path.join(ROOT, "profiles", src)) as f:
+                ra = json.load(f)
+            keys = ("n_passages", "n_queries", "layers", "k", "max_abs_passage", "recall_at_200", "identical_top1",
+                    "first_20_negatives_overlap", "identical_first_20_negatives")
+            out["retrieval_agreement"] = {k_: ra[k_] for k_ in keys}
+            if "precise_mode" in ra:
+                out["retrieval_agreement"]["fp32_mode"] = {k_: ra["precise_mode"][k_] for k_ in keys}
+            if "split_mode" in ra:
+                out["retrieval_agreement"]["split_mode"] = {k_: ra["split_mode"][k_] for k_ in keys}
+            out["retrieval_agreement"]["measured_in_this_run"] = False
+            out["retrieval_agreement"]["source"] = "profiles/%s (tests/test_gpu_retrieval.py: the three encoder modes against the fp32 oracle)" % src
+        except Exception:
+            pass
     if dist_on and out["rccl_ranks"] != a.gpus:
         errors["ranks"] = "process group has %d ranks, --gpus %d" % (out["rccl_ranks"], a.gpus)
     if a.dump_outputs and rank == 0:

@@ -1,11 +1,13 @@
 #!/bin/bash
-# Kernel-trace stats (no counters) of the final tree: the default bench command, and the encode leg single-stream.
+# Kernel-trace stats (no counters) of the final tree: the bench with --full, and the encode leg single-stream; logs under
+# $OUT/final.
 set -u
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out/final
+fin=${OUT:-out}/final
+mkdir -p "$fin"
 export TMPDIR=/tmp
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/final/bench -o kt -- python bench.py --no-cpu-baseline > gpurun_out/final/bench.log 2>&1; echo "rc=$?"
-tail -1 gpurun_out/final/bench.log | cut -c1-300
-ANCE_ENCODER_STREAMS=1 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/final/encode1 -o kt -- python bench.py --skip-search --no-cpu-baseline --steps 2 --warmup 1 > gpurun_out/final/encode1.log 2>&1; echo "rc=$?"
-find gpurun_out/final -name "*kernel_trace.csv" -delete
-find gpurun_out/final -name "*kernel_stats.csv" | head
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $fin/bench -o kt -- python bench.py --full --no-cpu-baseline > $fin/bench.log 2>&1; echo "rc=$?"
+tail -1 $fin/bench.log | cut -c1-300
+ANCE_ENCODER_STREAMS=1 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $fin/encode1 -o kt -- python bench.py --full --skip-search --no-cpu-baseline --steps 2 --warmup 1 > $fin/encode1.log 2>&1; echo "rc=$?"
+find $fin -name "*kernel_trace.csv" -delete
+find $fin -name "*kernel_stats.csv" | head

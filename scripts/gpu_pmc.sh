@@ -9,7 +9,7 @@ mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
 # one step, no fp32-mode sample, no second search leg, and counters only for the kernels a roofline is reported for: a pass
 # of the encode leg (~6 k dispatches) otherwise does not finish inside the 900 s limit
-S="python bench.py --skip-encode --no-cpu-baseline --skip-encoder-like --steps ${PMC_STEPS:-1} --warmup 1"
+S="python bench.py --full --skip-encode --no-cpu-baseline --skip-encoder-like --steps ${PMC_STEPS:-1} --warmup 1"
 # legs: search | encode_split (the headline arithmetic since round 5) | encode (= the fp16 fast mode) | encode_fp32 (kernel trace only)
 for what in ${PMC_LEGS:-search encode_split}; do
   cmd="$S"
@@ -37,7 +37,7 @@ done
 # kernel of the leg, a 4,096-passage block so that a counter pass (~500 dispatches) finishes, the same block timed untraced
 if [[ " ${PMC_LEGS:-search encode_split} " == *" encode_split "* ]]; then
   export ANCE_ENCODER_STREAMS=1
-  EA="python bench.py --skip-search --no-cpu-baseline --skip-precise --skip-slice --skip-other-configs --encode-block 4096 --steps 1 --warmup 1"
+  EA="python bench.py --full --skip-search --no-cpu-baseline --skip-precise --skip-slice --skip-other-configs --encode-block 4096 --steps 1 --warmup 1"
   echo "== untraced step, 4,096-passage block"
   timeout 300 $EA > gpurun_out/pmc/encode_all_plain.json 2> gpurun_out/pmc/encode_all_plain.err; echo "rc=$?"
   for c in FETCH_SIZE WRITE_SIZE; do

@@ -1,6 +1,6 @@
-"""bench.py's own data tools (CPU): the synthetic tokenised cache `bench.py --full` writes is the reference's cache format
+"""bench.py's own data tools (CPU): the synthetic tokenised cache `bench.py --refresh` writes is the reference's cache format
 (utils/util.py:257-307) as `ance_amd.cache.TokenCache` reads it, block boundaries included, and deterministic.  One GPU test
-runs the bench itself at a small size."""
+runs the bench itself at a small size, with --full and without."""
 import hashlib
 import os
 
@@ -142,7 +142,7 @@ def test_result_stream_keeps_stdout_to_the_json_line():
     assert "ANN NDCG" in r.stderr and "child" in r.stderr
 
 
-def _bench_line(root, tmp_path, steps, dump):
+def _bench_line(root, tmp_path, steps, dump, full=True):
     import json
     import subprocess
     import sys
@@ -152,7 +152,7 @@ def _bench_line(root, tmp_path, steps, dump):
            "--n-passages", "200000", "--encode-block", "2048", "--query-block", "2048", "--exact-check-queries", "8",
            "--skip-precise", "--skip-mfma-probe", "--skip-other-configs", "--no-cpu-baseline",
            "--slice-passages", "20000", "--slice-queries", "2048", "--slice-dev-queries", "256",
-           "--slice-dir", str(tmp_path / ("slice%d" % steps)), "--dump-outputs", dump]
+           "--slice-dir", str(tmp_path / ("slice%d" % steps)), "--dump-outputs", dump] + (["--full"] if full else [])
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -162,7 +162,7 @@ def _bench_line(root, tmp_path, steps, dump):
 
 @pytest.mark.gpu
 def test_bench_line_and_dumped_outputs(tmp_path):
-    """bench.py on a small corpus, twice with different --steps: stdout is exactly the JSON line (the whole-refresh slice,
+    """bench.py --full on a small corpus, twice with different --steps: stdout is exactly the JSON line (the whole-refresh slice,
     which prints the job's NDCG line, included), `steps` / `ms_per_step` describe the timed steps, and --dump-outputs writes
     the same float arrays on both runs -- the inputs are seeded, the outputs of a step do not depend on how many ran."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -185,3 +185,40 @@ def test_bench_line_and_dumped_outputs(tmp_path):
     ids = np.load(os.path.join(d1, "search_ids.npy"))
     assert ids.min() >= 0 and ids.max() < 200000 and np.array_equal(ids, np.rint(ids))
     assert (np.diff(np.load(os.path.join(d1, "search_scores.npy")), axis=1) <= 0).all()
+
+
+DUMP_NAMES = ("encode_embeddings", "search_scores", "search_ids", "search_encoder_like_scores", "search_encoder_like_ids")
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """bench.py without --full times the headline encode leg alone: the line carries the headline fields and none of what
+    --full measures, and --dump-outputs still writes every array, equal to what a --full run dumps."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dp, df = str(tmp_path / "plain"), str(tmp_path / "full")
+    o = _bench_line(root, tmp_path, 2, dp, full=False)
+    assert "errors" not in o, o.get("errors")
+    assert o["metric"] == "passages_encoded_per_sec" and o["unit"] == "passages/s" and o["higher_is_better"] is True
+    assert o["steps"] == 2 and o["warmup"] == 1 and o["encoder_precision"] == "split" and o["dtype"].startswith("f16 pair")
+    assert o["ms_per_step"] > 0 and abs(o["value"] - 2048 * 1e3 / o["ms_per_step"]) <= 1e-6 * o["value"]
+    for k in ("search", "roofline", "power", "encode_fp16_fast", "encode_fp32", "other_configs", "full_refresh_slice",
+              "cpu_baseline", "retrieval_agreement"):
+        assert k not in o, k
+    _bench_line(root, tmp_path, 1, df)
+    assert sorted(os.listdir(dp)) == sorted(n + ".npy" for n in DUMP_NAMES)
+    for n in DUMP_NAMES:
+        a, b = np.load(os.path.join(dp, n + ".npy")), np.load(os.path.join(df, n + ".npy"))
+        assert a.dtype == b.dtype and np.array_equal(a, b), n
+
+
+def test_full_is_off_by_default_and_refresh_has_its_own_flag(monkeypatch):
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and not a.refresh and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--refresh", "--refresh-queries", "10", "--refresh-dev-queries", "5"])
+    a = bench.parse()
+    assert a.refresh and not a.full and a.refresh_queries == 10 and a.refresh_dev_queries == 5
