@@ -54,6 +54,18 @@ class AnceAttnDebugArgs(ctypes.Structure):
     ]
 
 
+class AnceLambTensor(ctypes.Structure):
+    """include/ance_amd.h: one row of ance_lamb_step's host tensor table."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("numel", ctypes.c_int64), ("group", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AnceLambGroup(ctypes.Structure):
+    """include/ance_amd.h: one row of ance_lamb_step's host group table."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double)]
+
+
 # AnceEncoderDesc.precision (include/ance_amd.h: ANCE_PRECISION_*)
 PRECISION_CODES = {None: 0, "split": 1, "fp16": 2, "fp32": 3}
 PRECISION_NAMES = {1: "split", 2: "fp16", 3: "fp32"}
@@ -123,6 +135,9 @@ SYMBOLS = {
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "ance_debug_gemm_hw": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(AnceGemmDebugArgs), ctypes.c_void_p]),
     "ance_debug_attention": (ctypes.c_int, [ctypes.POINTER(AnceAttnDebugArgs), ctypes.c_void_p]),
+    "ance_lamb_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "ance_lamb_step": (ctypes.c_int, [ctypes.POINTER(AnceLambTensor), ctypes.c_int, ctypes.POINTER(AnceLambGroup), ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

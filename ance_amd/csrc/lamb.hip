@@ -1,0 +1,351 @@
+// Fused multi-tensor LAMB step (include/ance_amd.h: ance_lamb_step): the reference's utils/lamb.py Lamb.step -- a Python loop
+// of ~19 small launches and up to three host synchronisations per parameter tensor -- as three launches for every tensor of the
+// call and no host synchronisation.
+//   pass 1   (one workgroup per 16,384-element chunk)  m, v updated; u = m / (sqrt(v) + eps) [+ wd p]; the chunk's sums of p^2
+//            and u^2 (fp64) stored to its slot: reads p, g, m, v (16 B / element), writes m, v (8 B)
+//   reduce   (one wave per tensor)  the tensor's chunk sums added in chunk order (fp64) -> wn, an, tr into d_out [t][3]
+//   pass 2   (one workgroup per chunk)  u recomputed from p, m, v by the same code as pass 1; p += (-lr tr) u: reads 12 B, writes 4 B
+// 40 B of HBM traffic per element.  No atomics and a fixed summation order everywhere: the same inputs give the same bits (under
+// DDP every rank steps on the same all-reduced gradients and must stay bit-identical).  Division and sqrtf are the IEEE ones
+// (hipcc's default correctly rounded fp32 divide / sqrt), as in the reference's fp32 arithmetic.
+#include "common.h"
+
+#include <math.h>
+#include <mutex>
+#include <vector>
+
+namespace ance {
+namespace {
+
+constexpr int LAMB_CHUNK = 16384;  // elements per chunk: 16 float4 per thread and array at 256 threads
+constexpr int LAMB_THREADS = 256;
+constexpr int LAMB_UNROLL = 4;     // float4 per array in flight per thread
+
+// the tensors' pointers come from a table, so the compiler cannot see they are global: say so, for global_load / global_store
+// instead of flat accesses
+typedef __attribute__((address_space(1))) float gfloat;
+typedef __attribute__((address_space(1))) f32x4 gf32x4;
+
+struct LambDevGroup {
+    float b1, omb1, b2, omb2, eps, wd, neg_lr;
+    int32_t has_wd;
+};
+struct LambDevTensor {
+    float *p;
+    const float *g;
+    float *m, *v;
+    int64_t numel;
+    int32_t chunk0, n_chunks, group, vec;
+};
+
+__device__ __forceinline__ float lamb_u(float p, float m, float v, const LambDevGroup &G) {
+    float u = m / (sqrtf(v) + G.eps);
+    if (G.has_wd) u = __builtin_fmaf(G.wd, p, u);
+    return u;
+}
+
+// m, v update of one element; returns u
+__device__ __forceinline__ float lamb_mv(float p, float g, float &m, float &v, const LambDevGroup &G) {
+    m = __builtin_fmaf(G.omb1, g, m * G.b1);
+    v = __builtin_fmaf(G.omb2 * g, g, v * G.b2);
+    return lamb_u(p, m, v, G);
+}
+
+__device__ __forceinline__ void lamb_acc(float p, float u, double &sp, double &su) {
+    sp = __builtin_fma((double)p, (double)p, sp);
+    su = __builtin_fma((double)u, (double)u, su);
+}
+
+__global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
+                                                                  const int32_t *chunk_tensor, double2 *partial) {
+    __shared__ double red[LAMB_THREADS / 64][2];
+    const int tid = threadIdx.x;
+    const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
+    const LambDevGroup G = groups[T.group];
+    const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
+    const int len = (int)min((int64_t)LAMB_CHUNK, T.numel - base);
+    gfloat *p = (gfloat *)(T.p + base), *m = (gfloat *)(T.m + base), *v = (gfloat *)(T.v + base);
+    const gfloat *g = (const gfloat *)(T.g + base);
+    double sp = 0.0, su = 0.0;
+    int done = 0;
+    if (T.vec) {  // every pointer 16-byte aligned (chunk starts are multiples of 4 elements)
+        const int n4 = len >> 2;
+        const gf32x4 *p4 = (const gf32x4 *)p, *g4 = (const gf32x4 *)g;
+        gf32x4 *m4 = (gf32x4 *)m, *v4 = (gf32x4 *)v;
+        for (int i0 = tid; i0 < n4; i0 += LAMB_THREADS * LAMB_UNROLL) {
+            f32x4 P[LAMB_UNROLL], Gr[LAMB_UNROLL], M[LAMB_UNROLL], V[LAMB_UNROLL];
+#pragma unroll
+            for (int k = 0; k < LAMB_UNROLL; ++k) {
+                const int i = i0 + k * LAMB_THREADS;
+                if (i < n4) { P[k] = p4[i]; Gr[k] = g4[i]; M[k] = m4[i]; V[k] = v4[i]; }
+            }
+#pragma unroll
+            for (int k = 0; k < LAMB_UNROLL; ++k) {
+                const int i = i0 + k * LAMB_THREADS;
+                if (i < n4) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        float mj = M[k][j], vj = V[k][j];
+                        const float u = lamb_mv(P[k][j], Gr[k][j], mj, vj, G);
+                        M[k][j] = mj;
+                        V[k][j] = vj;
+                        lamb_acc(P[k][j], u, sp, su);
+                    }
+                    m4[i] = M[k];
+                    v4[i] = V[k];
+                }
+            }
+        }
+        done = n4 * 4;
+    }
+    for (int e = done + tid; e < len; e += LAMB_THREADS) {  // scalar tail (or the whole chunk of an unaligned tensor)
+        float mj = m[e], vj = v[e];
+        const float pj = p[e];
+        const float u = lamb_mv(pj, g[e], mj, vj, G);
+        m[e] = mj;
+        v[e] = vj;
+        lamb_acc(pj, u, sp, su);
+    }
+    // fixed-order block sum: xor-shuffle tree inside each wave, then the four waves in order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sp += __shfl_xor(sp, off);
+        su += __shfl_xor(su, off);
+    }
+    if ((tid & 63) == 0) {
+        red[tid >> 6][0] = sp;
+        red[tid >> 6][1] = su;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double a = red[0][0], b = red[0][1];
+#pragma unroll
+        for (int w = 1; w < LAMB_THREADS / 64; ++w) { a += red[w][0]; b += red[w][1]; }
+        partial[blockIdx.x] = make_double2(a, b);
+    }
+}
+
+// one wave per tensor: chunk sums in chunk order (lane-strided, then an xor-shuffle tree) -> (wn, an, tr)
+__global__ void __launch_bounds__(256) lamb_reduce_kernel(const LambDevTensor *tensors, int n_tensors, const double2 *partial,
+                                                          float *out) {
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (t >= n_tensors) return;
+    const int c0 = tensors[t].chunk0, nc = tensors[t].n_chunks;
+    double sp = 0.0, su = 0.0;
+    for (int c = l; c < nc; c += 64) {
+        const double2 s = partial[c0 + c];
+        sp += s.x;
+        su += s.y;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sp += __shfl_xor(sp, off);
+        su += __shfl_xor(su, off);
+    }
+    if (l == 0) {
+        float wn = (float)sqrt(sp);
+        wn = wn > 10.0f ? 10.0f : wn;  // clamp(0, 10) that lets a NaN through, as torch's clamp does
+        const float an = (float)sqrt(su);
+        const float tr = (wn == 0.0f || an == 0.0f) ? 1.0f : wn / an;
+        out[3 * (int64_t)t] = wn;
+        out[3 * (int64_t)t + 1] = an;
+        out[3 * (int64_t)t + 2] = tr;
+    }
+}
+
+__global__ void __launch_bounds__(LAMB_THREADS) lamb_pass2_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
+                                                                  const int32_t *chunk_tensor, const float *out, int adam) {
+    const int tid = threadIdx.x;
+    const int t = chunk_tensor[blockIdx.x];
+    const LambDevTensor T = tensors[t];
+    const LambDevGroup G = groups[T.group];
+    const float tr = adam ? 1.0f : out[3 * (int64_t)t + 2];
+    const float s = G.neg_lr * tr;  // the reference's -step_size * trust_ratio, an fp32 product
+    const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
+    const int len = (int)min((int64_t)LAMB_CHUNK, T.numel - base);
+    gfloat *p = (gfloat *)(T.p + base);
+    const gfloat *m = (const gfloat *)(T.m + base), *v = (const gfloat *)(T.v + base);
+    int done = 0;
+    if (T.vec) {
+        const int n4 = len >> 2;
+        gf32x4 *p4 = (gf32x4 *)p;
+        const gf32x4 *m4 = (const gf32x4 *)m, *v4 = (const gf32x4 *)v;
+        for (int i0 = tid; i0 < n4; i0 += LAMB_THREADS * LAMB_UNROLL) {
+            f32x4 P[LAMB_UNROLL], M[LAMB_UNROLL], V[LAMB_UNROLL];
+#pragma unroll
+            for (int k = 0; k < LAMB_UNROLL; ++k) {
+                const int i = i0 + k * LAMB_THREADS;
+                if (i < n4) { P[k] = p4[i]; M[k] = m4[i]; V[k] = v4[i]; }
+            }
+#pragma unroll
+            for (int k = 0; k < LAMB_UNROLL; ++k) {
+                const int i = i0 + k * LAMB_THREADS;
+                if (i < n4) {
+                    f32x4 r;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) r[j] = __builtin_fmaf(s, lamb_u(P[k][j], M[k][j], V[k][j], G), P[k][j]);
+                    p4[i] = r;
+                }
+            }
+        }
+        done = n4 * 4;
+    }
+    for (int e = done + tid; e < len; e += LAMB_THREADS) p[e] = __builtin_fmaf(s, lamb_u(p[e], m[e], v[e], G), p[e]);
+}
+
+size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// workspace: [groups][tensors][chunk -> tensor] (staged from the host in one copy) [fp64 (p^2, u^2) per chunk]
+size_t staged_bytes(int n_tensors, int n_groups, int64_t n_chunks) {
+    return align16(sizeof(LambDevGroup) * (size_t)n_groups) + align16(sizeof(LambDevTensor) * (size_t)n_tensors) +
+           align16(sizeof(int32_t) * (size_t)n_chunks);
+}
+size_t workspace_bytes_for(int n_tensors, int n_groups, int64_t n_chunks) {
+    return staged_bytes(n_tensors, n_groups, n_chunks) + sizeof(double2) * (size_t)n_chunks;
+}
+
+// Pinned staging buffers of the host tables.  A buffer is handed out again only once the event recorded after its last copy has
+// completed (hipEventQuery, no wait), so a pending DMA never reads a buffer that is being refilled.  When all of them are still in
+// flight the pool grows; at its cap the caller waits for the oldest copy -- a host wait on a copy enqueued LAMB_POOL steps ago.
+constexpr int LAMB_POOL = 16;
+struct Staging {
+    void *h = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+    bool recorded = false;
+    unsigned long long last_use = 0;
+};
+std::mutex g_stage_mu;
+std::vector<Staging> g_stage;
+unsigned long long g_stage_clock = 0;
+
+// under g_stage_mu; returns the index of a buffer of >= bytes whose previous copy has run, or -1 (out of memory)
+int stage_acquire(size_t bytes) {
+    for (size_t i = 0; i < g_stage.size(); ++i) {
+        Staging &s = g_stage[i];
+        if (s.bytes >= bytes && (!s.recorded || hipEventQuery(s.ev) == hipSuccess)) return (int)i;
+    }
+    size_t want = 65536;
+    while (want < bytes) want <<= 1;
+    if ((int)g_stage.size() < LAMB_POOL) {
+        Staging s;
+        if (hipHostMalloc(&s.h, want, hipHostMallocDefault) != hipSuccess) return -1;
+        if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) return -1;
+        s.bytes = want;
+        g_stage.push_back(s);
+        return (int)g_stage.size() - 1;
+    }
+    int old = 0;
+    for (int i = 1; i < (int)g_stage.size(); ++i)
+        if (g_stage[i].last_use < g_stage[old].last_use) old = i;
+    Staging &s = g_stage[old];
+    if (s.recorded && hipEventSynchronize(s.ev) != hipSuccess) return -1;
+    if (s.bytes < bytes) {  // the old buffer stays allocated: freeing pinned memory can synchronise the device
+        void *h = nullptr;
+        if (hipHostMalloc(&h, want, hipHostMallocDefault) != hipSuccess) return -1;
+        s.h = h;
+        s.bytes = want;
+    }
+    s.recorded = false;
+    return old;
+}
+
+int lamb_refuse(const char *why) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "ance_lamb_step: invalid argument (%s)", why);
+    set_last_error(buf);
+    return ANCE_E_INVALID;
+}
+
+}  // namespace
+}  // namespace ance
+
+extern "C" size_t ance_lamb_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
+    using namespace ance;
+    if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
+    const int64_t chunks = (int64_t)n_tensors + total_numel / LAMB_CHUNK;  // >= the sum of every tensor's ceil(numel / chunk)
+    if (chunks > (int64_t)INT32_MAX) return 0;
+    return workspace_bytes_for(n_tensors, n_groups, chunks);
+}
+
+extern "C" int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                              float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
+    using namespace ance;
+    if (n_tensors < 0) return lamb_refuse("n_tensors < 0");
+    if (n_tensors == 0) return ANCE_OK;
+    if (!h_tensors || !h_groups) return lamb_refuse("null table");
+    if (n_groups < 1) return lamb_refuse("n_groups < 1");
+    if (!d_out) return lamb_refuse("null d_out");
+    int64_t n_chunks = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        const AnceLambTensor &T = h_tensors[t];
+        if (T.group < 0 || T.group >= n_groups) return lamb_refuse("group index out of range");
+        if (T.numel < 0) return lamb_refuse("numel < 0");
+        if (T.numel > 0 && (!T.p || !T.g || !T.m || !T.v)) return lamb_refuse("null tensor pointer");
+        n_chunks += (T.numel + LAMB_CHUNK - 1) / LAMB_CHUNK;
+        if (n_chunks > (int64_t)INT32_MAX) return lamb_refuse("too many elements");
+    }
+    const size_t need = workspace_bytes_for(n_tensors, n_groups, n_chunks);
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return lamb_refuse("null or unaligned workspace");
+    if (workspace_bytes < need) return lamb_refuse("workspace too small");
+
+    const size_t off_t = align16(sizeof(LambDevGroup) * (size_t)n_groups);
+    const size_t off_c = off_t + align16(sizeof(LambDevTensor) * (size_t)n_tensors);
+    const size_t off_p = staged_bytes(n_tensors, n_groups, n_chunks);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)d_workspace;
+    {
+        std::lock_guard<std::mutex> lock(g_stage_mu);
+        const int si = stage_acquire(off_p);
+        if (si < 0) {
+            set_last_error("ance_lamb_step: pinned staging buffer");
+            return ANCE_E_NOMEM;
+        }
+        Staging &S = g_stage[si];
+        char *h = (char *)S.h;
+        LambDevGroup *G = (LambDevGroup *)h;
+        for (int i = 0; i < n_groups; ++i) {  // the reference's Python doubles, rounded to fp32 as torch does for a scalar
+            const AnceLambGroup &a = h_groups[i];
+            G[i].b1 = (float)a.beta1;
+            G[i].omb1 = (float)(1.0 - a.beta1);
+            G[i].b2 = (float)a.beta2;
+            G[i].omb2 = (float)(1.0 - a.beta2);
+            G[i].eps = (float)a.eps;
+            G[i].wd = (float)a.weight_decay;
+            G[i].neg_lr = (float)(-a.lr);
+            G[i].has_wd = a.weight_decay != 0.0;
+        }
+        LambDevTensor *T = (LambDevTensor *)(h + off_t);
+        int32_t *ct = (int32_t *)(h + off_c);
+        int32_t c = 0;
+        for (int t = 0; t < n_tensors; ++t) {
+            const AnceLambTensor &a = h_tensors[t];
+            T[t].p = a.p;
+            T[t].g = a.g;
+            T[t].m = a.m;
+            T[t].v = a.v;
+            T[t].numel = a.numel;
+            T[t].group = a.group;
+            T[t].chunk0 = c;
+            T[t].n_chunks = (int32_t)((a.numel + LAMB_CHUNK - 1) / LAMB_CHUNK);
+            T[t].vec = ((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) % 16 == 0;
+            for (int32_t k = 0; k < T[t].n_chunks; ++k) ct[c++] = t;
+        }
+        if (hipMemcpyAsync(ws, h, off_p, hipMemcpyHostToDevice, st) != hipSuccess) return check_launch("ance_lamb_step: tables");
+        if (hipEventRecord(S.ev, st) != hipSuccess) return check_launch("ance_lamb_step: staging event");
+        S.recorded = true;
+        S.last_use = ++g_stage_clock;
+    }
+    const LambDevGroup *dG = (const LambDevGroup *)ws;
+    const LambDevTensor *dT = (const LambDevTensor *)(ws + off_t);
+    const int32_t *dC = (const int32_t *)(ws + off_c);
+    double2 *dP = (double2 *)(ws + off_p);
+    if (n_chunks > 0)
+        hipLaunchKernelGGL(lamb_pass1_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP);
+    hipLaunchKernelGGL(lamb_reduce_kernel, dim3((unsigned)((n_tensors + 3) / 4)), dim3(256), 0, st, dT, n_tensors,
+                       (const double2 *)dP, d_out);
+    if (n_chunks > 0)
+        hipLaunchKernelGGL(lamb_pass2_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, (const float *)d_out,
+                           adam ? 1 : 0);
+    return check_launch("ance_lamb_step");
+}

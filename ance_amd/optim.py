@@ -1,0 +1,120 @@
+"""Fused LAMB for the ANCE trainers: a drop-in replacement of the reference's ``utils/lamb.py`` ``Lamb``, the optimizer
+drivers/run_ann.py:80-84 and drivers/run_warmup.py:76-78 build when ``--optimizer lamb`` is passed (both launch recipes pass it).
+
+The reference steps tensor by tensor in Python (about 19 small launches and up to three host synchronisations per tensor).
+Here one call of ``ance_lamb_step`` (csrc/lamb.hip) updates every tensor of every group in three launches, with no host
+synchronisation.  Same constructor, same errors, same state entries (``step`` an int, ``exp_avg``, ``exp_avg_sq``, and
+``weight_norm``, ``adam_norm``, ``trust_ratio`` as 0-dim device tensors), so ``log_lamb_rs``, ``optimizer.state_dict()`` /
+``torch.save`` and ``load_state_dict`` of the reference's ``optimizer.pt`` work unchanged, in both directions.
+
+No CPU fallback: every parameter, gradient and state tensor must be a contiguous fp32 tensor on one HIP device.
+"""
+import ctypes
+
+import numpy as np
+import torch
+from torch.optim import Optimizer
+
+from . import _lib
+
+# ctypes layout of AnceLambTensor (include/ance_amd.h), filled from a list of tuples in one call
+_TENSOR_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel", "<i8"), ("group", "<i4"),
+                          ("reserved", "<i4")])
+_GROUP_DTYPE = np.dtype([("lr", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("eps", "<f8"), ("weight_decay", "<f8")])
+assert _TENSOR_DTYPE.itemsize == ctypes.sizeof(_lib.AnceLambTensor)
+assert _GROUP_DTYPE.itemsize == ctypes.sizeof(_lib.AnceLambGroup)
+
+
+class Lamb(Optimizer):
+    r"""LAMB (You et al., "Large Batch Optimization for Deep Learning: Training BERT in 76 minutes"), the reference's form:
+    no bias correction, ``wn = min(|p|, 10)``, trust ratio 1 where ``wn`` or the Adam step's norm is 0, and ``adam=True``
+    for a trust ratio of 1 always (the norms and the LAMB trust ratio are still recorded).
+
+    Arguments as the reference's: params, lr (1e-3), betas ((0.9, 0.999)), eps (1e-6), weight_decay (0), adam (False).
+    """
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, adam=False):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.adam = adam
+        super(Lamb, self).__init__(params, defaults)
+        self._workspace = {}
+
+    def _checked(self, t, what, device):
+        _lib.require_cuda_tensor(t, torch.float32, what)
+        if t.device != device:
+            raise _lib.AnceLibraryError("%s is on %s, the other tensors of this step on %s (mixed devices)" % (what, t.device, device))
+        return t
+
+    def step(self, closure=None):
+        """One LAMB step of every parameter that has a gradient.  Asynchronous: enqueued on the current stream, no host wait."""
+        loss = None
+        if closure is not None:
+            loss = closure()
+
+        rows, groups, updated, device = [], [], [], None
+        for gi, group in enumerate(self.param_groups):
+            beta1, beta2 = group['betas']
+            groups.append((float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay'])))
+            for pi, p in enumerate(group['params']):
+                if p.grad is None:
+                    continue
+                grad = p.grad
+                if grad.is_sparse:
+                    raise RuntimeError('Lamb does not support sparse gradients, consider SparseAdam instad.')
+                name = "Lamb: param_groups[%d]['params'][%d]" % (gi, pi)
+                if device is None:
+                    _lib.require_cuda_tensor(p, torch.float32, name)
+                    device = p.device
+                self._checked(p, name, device)
+                self._checked(grad, name + ".grad", device)
+                if grad.shape != p.shape:
+                    raise _lib.AnceLibraryError("%s.grad has shape %s, the parameter %s" % (name, tuple(grad.shape), tuple(p.shape)))
+                state = self.state[p]
+                if len(state) == 0:
+                    state['step'] = 0
+                    state['exp_avg'] = torch.zeros_like(p.data)
+                    state['exp_avg_sq'] = torch.zeros_like(p.data)
+                m, v = state['exp_avg'], state['exp_avg_sq']
+                self._checked(m, name + " state['exp_avg']", device)
+                self._checked(v, name + " state['exp_avg_sq']", device)
+                if m.shape != p.shape or v.shape != p.shape:
+                    raise _lib.AnceLibraryError("%s: state shapes %s, %s differ from the parameter's %s"
+                                                % (name, tuple(m.shape), tuple(v.shape), tuple(p.shape)))
+                rows.append((p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi, 0))
+                updated.append(state)
+        if not rows:
+            return loss
+
+        L = _lib.lib()
+        tensors = np.array(rows, dtype=_TENSOR_DTYPE)
+        gtab = np.array(groups, dtype=_GROUP_DTYPE)
+        total = int(tensors["numel"].sum())
+        need = L.ance_lamb_workspace_bytes(len(rows), len(groups), total)
+        if need == 0:
+            raise _lib.AnceLibraryError("Lamb: %d tensors of %d elements exceed ance_lamb_step's limits" % (len(rows), total))
+        with torch.cuda.device(device):
+            ws = self._workspace.get(device)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=device)
+                self._workspace[device] = ws
+            out = torch.empty((len(rows), 3), dtype=torch.float32, device=device)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(L.ance_lamb_step(tensors.ctypes.data_as(ctypes.POINTER(_lib.AnceLambTensor)), len(rows),
+                                        gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups),
+                                        1 if self.adam else 0, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                        ws.numel(), ctypes.c_void_p(stream)), "ance_lamb_step")
+        vals = out.view(-1).unbind(0)
+        for k, state in enumerate(updated):
+            state['step'] += 1
+            state['weight_norm'] = vals[3 * k]
+            state['adam_norm'] = vals[3 * k + 1]
+            state['trust_ratio'] = vals[3 * k + 2]
+        return loss

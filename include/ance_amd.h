@@ -14,7 +14,8 @@
  *
  * Conventions: plain pointers and sizes, no exceptions, no torch types.  Every pointer named
  * d_* is DEVICE memory owned by the caller; nothing is allocated or freed behind the caller's
- * back except the small host-side handle of ance_encoder_create.  All work is enqueued on the
+ * back except the small host-side handle of ance_encoder_create and the pinned staging buffers of ance_lamb_step (kept for the
+ * process's lifetime).  All work is enqueued on the
  * caller's hipStream_t (passed as void* so this header needs no HIP include) and is asynchronous;
  * the functions never synchronise the device.  Return value: 0 on success, negative ANCE_E_* on
  * error (nothing enqueued in that case).
@@ -38,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* 7: + ance_debug_attention (AnceAttnDebugArgs);
+#define ANCE_ABI_VERSION 7  /* 7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
                                5: AnceEncoderDesc.precision (the arithmetic is an argument, not an environment variable), ance_encoder_range_faults,
                                ance_ip_topk_scan; 4: blocked pair rows in the split mode (ance_pair_layout; ance_debug_gemm_split + d_wscale_inv);
@@ -394,6 +395,40 @@ int ance_debug_attention(const AnceAttnDebugArgs *args, void *stream);
  * half at *hi_col and its lo half at *lo_col of the 2 W-half pair row, lo = fp16((v - hi) * *lo_scale).  Product library:
  * hi_col = 64 (n / 32) + n % 32, lo_col = hi_col + 32, lo_scale = 1. */
 void ance_pair_layout(int n, int W, int *hi_col, int *lo_col, float *lo_scale);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fused multi-tensor LAMB step (csrc/lamb.hip; the reference's utils/lamb.py Lamb.step, which drivers/run_ann.py and
+ * drivers/run_warmup.py train with).  Per tensor p with gradient g, state m, v and its group's lr, beta1, beta2, eps, wd:
+ *   m <- beta1 m + (1 - beta1) g ;  v <- beta2 v + (1 - beta2) g^2          (no bias correction)
+ *   u  = m / (sqrt(v) + eps) [+ wd p when wd != 0]
+ *   wn = min(|p|_2, 10) (p before the update) ;  an = |u|_2 ;  tr = 1 if wn == 0 or an == 0 else wn / an
+ *   p <- p - lr tr u    (tr = 1 in the update when adam != 0; the recorded tr is the LAMB one either way)
+ * Every tensor of the call in three launches and no host synchronisation: pass 1 updates m, v and stores per-chunk partial
+ * sums of p^2 and u^2 (fp64), a per-tensor kernel sums them in a fixed order into d_out, pass 2 recomputes u and writes p.
+ * The same inputs give the same bits (no atomics).  40 bytes of HBM traffic per element.
+ *
+ * h_tensors and h_groups are HOST tables; they are staged into d_workspace on the stream through a pinned buffer of the library
+ * (reused only once an event shows its previous copy has run), so the caller may overwrite or free them when the call returns.
+ * The workspace must not be shared by two calls that can run at the same time (streams run a call's copy and kernels in order).
+ * d_out: fp32 [n_tensors][3] = (wn, an, tr) per tensor.  Every device pointer fp32; p, m, v may not overlap one another
+ * or another tensor's.  numel == 0 is allowed (any pointers; wn = an = 0, tr = 1).  n_tensors == 0: nothing is enqueued.
+ * Refuses (ANCE_E_INVALID, before any copy or launch) a null table, n_tensors < 0, n_groups < 1, a group index out of range,
+ * numel < 0, a null p / g / m / v of a tensor with numel > 0, a null d_out and a null, unaligned (16 B) or too small workspace;
+ * ANCE_E_NOMEM when no pinned staging buffer can be allocated. */
+typedef struct AnceLambTensor {
+    float *p;                     /* parameter, updated in place                                  */
+    const float *g;               /* gradient                                                     */
+    float *m, *v;                 /* exp_avg, exp_avg_sq, updated in place                        */
+    int64_t numel;
+    int32_t group, reserved;
+} AnceLambTensor;
+typedef struct AnceLambGroup {
+    double lr, beta1, beta2, eps, weight_decay;
+} AnceLambGroup;
+/* Bytes of workspace ance_lamb_step needs for n_tensors tensors of total_numel elements in n_groups groups (0: invalid). */
+size_t ance_lamb_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel);
+int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                   float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Re-reads every ANCE_* tuning knob from the environment (they are otherwise read once per process).  For tests and
  * sweeps that change a knob between two calls; not thread-safe against concurrent searches. */
