@@ -464,10 +464,10 @@ __device__ __forceinline__ float sumsq8(const f32x4 a, const f32x4 b, float m) {
 // pair block), 4 for the fp32 rows of QKV (16 lanes write 256 contiguous bytes; with 8 columns a lane's two 16-byte stores would
 // interleave with its neighbours' -- measured +3.5 % on that GEMM).
 template <int EPI, int HW = 768>
-__device__ __forceinline__ void gemm256_epilogue_split(const GemmArgs &G, f32x16 (&acc)[2][4], float *smem_f, int m0, int n0,
+__device__ __forceinline__ void gemm256_epilogue_split(const GemmArgs &G, f32x4 (&acc)[4][8], float *smem_f, int m0, int n0,
                                                        int w, int l, float winv) {
 #pragma clang fp contract(off)
-    const int g = l >> 5, i = l & 31;
+    const int i = l & 15, c4 = 4 * (l >> 4);  // acc[x][y] (16 x 16 blocks): n = nw0 + 16 x + c4 + (0..3), m = mw0 + 16 y + i
     const int wm = w >> 2, wn = w & 3;
     const int mw0 = m0 + wm * 128, nw0 = n0 + wn * 64;
     float *slab = smem_f + w * 4096;
@@ -505,13 +505,9 @@ __device__ __forceinline__ void gemm256_epilogue_split(const GemmArgs &G, f32x16
         }
         epi_sync<true>();
 #pragma unroll
-        for (int x = 0; x < 2; ++x)
+        for (int yb = 0; yb < 2; ++yb)
 #pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const f32x16 &a = acc[x][y];
-                *reinterpret_cast<f32x4 *>(slab + i * LS + x * 32 + 8 * rq + 4 * g) =
-                    f32x4{a[4 * rq], a[4 * rq + 1], a[4 * rq + 2], a[4 * rq + 3]};
-            }
+            for (int x = 0; x < 4; ++x) *reinterpret_cast<f32x4 *>(slab + (yb * 16 + i) * LS + x * 16 + c4) = acc[x][2 * y + yb];
         epi_sync<true>();
         f32x4 vv[ITS][NV];
 #pragma unroll
@@ -582,11 +578,11 @@ constexpr int EPS_LS = 36;                       // slab row stride (floats)
 constexpr int EPS_SLAB_FLOATS = 32 * EPS_LS;     // 4,608 bytes per wave
 
 template <int EPI>
-__device__ __forceinline__ void gemm256_epilogue_split32(const GemmArgs &G, f32x16 (&acc)[2][4], float *slab, const float *stats,
+__device__ __forceinline__ void gemm256_epilogue_split32(const GemmArgs &G, f32x4 (&acc)[4][8], float *slab, const float *stats,
                                                          const float *vec, int m0, int n0, int w, int l, float winv) {
 #pragma clang fp contract(off)
     static_assert(EPI == EPI_S_QKV || EPI == EPI_S_GELU, "the RESLN GEMMs run the launch-per-tile kernel (DESIGN_REJECTED.md round 6)");
-    const int g = l >> 5, i = l & 31;
+    const int i = l & 15, c4 = 4 * (l >> 4);  // as gemm256_epilogue_split
     const int wm = w >> 2, wn = w & 3;
     const int mw0 = m0 + wm * 128, nw0 = n0 + wn * 64;
     constexpr int LS = EPS_LS;
@@ -606,10 +602,9 @@ __device__ __forceinline__ void gemm256_epilogue_split32(const GemmArgs &G, f32x
         }
         epi_sync<true>();
 #pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-            const f32x16 &a = acc[x][y];
-            *reinterpret_cast<f32x4 *>(slab + i * LS + 8 * rq + 4 * g) = f32x4{a[4 * rq], a[4 * rq + 1], a[4 * rq + 2], a[4 * rq + 3]};
-        }
+        for (int yb = 0; yb < 2; ++yb)
+#pragma unroll
+            for (int xb = 0; xb < 2; ++xb) *reinterpret_cast<f32x4 *>(slab + (yb * 16 + i) * LS + xb * 16 + c4) = acc[2 * x + xb][2 * y + yb];
         epi_sync<true>();
 #pragma unroll
         for (int it = 0; it < ITS; ++it) {

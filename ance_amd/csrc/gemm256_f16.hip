@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
 // Round 5: the pair rows are BLOCKED -- 32 columns of hi, then the same 32 columns of lo -- so the operand matrices look like
 // plain [rows, 2 K] fp16 matrices to the staging side (PipeSrcDesc, 128 contiguous bytes per row and K-tile, exactly the fp16
 // GEMM's access pattern) and a K-tile in LDS holds a 32-deep k-slice of hi AND lo of both operands: FOUR operand tiles staged
-// and read once for THREE products (Pipe256T<.., PAIR3>: 48 MFMAs per K-tile and wave instead of 32), all into one accumulator
+// and read once for THREE products (Pipe256T<.., PAIR3>: 96 v_mfma_f32_16x16x32_f16 per K-tile and wave, the work of 48 of 32x32x16), all into one accumulator
 // set.  Round 4 ran three passes over [hi | lo'] rows (six staged tiles per three products, a 2^-11 rescale between the
 // passes): per MFMA this loop issues two thirds of the LDS-DMAs, ds_reads and barriers -- the resources the K loop is bound by
 // (DESIGN.md 3.2).  One accumulator means one scale: lo is NOT multiplied by 2^11 any more; activations are O(1) (their
@@ -180,11 +180,11 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const Ge
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l = tid & 63;
-    f32x16 acc[2][4];
+    f32x4 acc[4][8];  // 16 x 16 blocks of v_mfma_f32_16x16x32_f16 (pipe256.h)
 #pragma unroll
-    for (int x = 0; x < 2; ++x)
+    for (int x = 0; x < 4; ++x)
 #pragma unroll
-        for (int y = 0; y < 4; ++y) acc[x][y] = f32x16{0};
+        for (int y = 0; y < 8; ++y) acc[x][y] = f32x4{0.f, 0.f, 0.f, 0.f};
     Pipe256T<PipeSrcDesc, true> P;
     P.init(smem, w, l);
     P.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.A + (size_t)m0 * G.lda), 0, (int)(256u * (uint32_t)G.lda * 2u), 0x00020000);
@@ -327,11 +327,11 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(c
     for (;;) {
         int mtn = 0, ntn = 0;
         const bool have_n = next_tile(&mtn, &ntn);
-        f32x16 acc[2][4];
+        f32x4 acc[4][8];
 #pragma unroll
-        for (int x = 0; x < 2; ++x)
+        for (int x = 0; x < 4; ++x)
 #pragma unroll
-            for (int y = 0; y < 4; ++y) acc[x][y] = f32x16{0};
+            for (int y = 0; y < 8; ++y) acc[x][y] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (have_n) {
             P.S.a_nxt = (uint32_t)mtn * 256u * (uint32_t)G.lda * 2u;
             P.S.b_nxt = (uint32_t)ntn * 256u * (uint32_t)G.ldb * 2u;

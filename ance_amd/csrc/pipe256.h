@@ -2,6 +2,7 @@
 // GEMM of the default arithmetic and the fp16 GEMM of the fast mode) and the search filter (ip_topk_fast.hip).
 //
 //   acc[x][y] += sum_k  B[n][k] * A[m][k]      n = wn*64 + x*32 + (C-layout row)   m = wm*128 + y*32 + lane&31
+//   (PAIR3: 16 x 16 blocks,                    n = wn*64 + x*16 + 4*(lane>>4) + r  m = wm*128 + y*16 + lane&15)
 //
 // 8 waves (2 along m x 4 along n), 128 KiB of LDS = 2 K-tile buffers x 4 half-tiles of 128 rows x 64 halves (16 KiB each):
 // A-half h holds the 64-row blocks {h, h+2} of the A tile (so a wave's fragments y = 0,1 come from A-half 0 and y = 2,3 from
@@ -13,12 +14,14 @@
 // THE SCHEDULE (two phases per K-tile, both B halves of a K-tile in registers):
 //   phase P0: read A-half0, B-half0, B-half1   MFMAs on acc[0][0..1], acc[1][0..1]   + stage A-half1 of tile t+1
 //   phase P1: read A-half1                     MFMAs on acc[1][2..3], acc[0][2..3]   + stage A0, B0, B1 of tile t+2
-// with 16 MFMAs per phase on plain fp16 operands and -- PAIR3, the split GEMM of the DEFAULT arithmetic -- 24: both operands are
-// BLOCKED pair rows (common.h: 32 columns of hi, then the same 32 columns of lo), so the 64 halves of an LDS row are
-//   [hi k 0..15 | hi k 16..31 | lo k 0..15 | lo k 16..31]          (fragment index s = 0..3)
-// i.e. a K-tile is a 32-deep k-slice of hi AND lo of both operands, and per output quadrant and k-step j the wave issues the three
-// products  hi_j x hi_j,  lo_j x hi_j,  hi_j x lo_j  (fragment pairs (j, j), (j + 2, j), (j, j + 2)) into ONE accumulator: four
-// operand tiles staged and read once for three products.  Staging, ds_reads, barriers and waits are identical in both forms.
+// with 16 v_mfma_f32_32x32x16_f16 per phase on plain fp16 operands and -- PAIR3, the split GEMM of the DEFAULT arithmetic -- 48
+// v_mfma_f32_16x16x32_f16: both operands are BLOCKED pair rows (common.h: 32 columns of hi, then the same 32 columns of lo), so the
+// 64 halves of an LDS row are  [hi k 0..31 | lo k 0..31],  a K-tile is a 32-deep k-slice of hi AND lo of both operands, and per
+// 16 x 16 output block the wave issues the three products  hi x hi,  lo x hi,  hi x lo  into ONE accumulator: four operand tiles
+// staged and read once for three products.  A 16x16x32 fragment is one ds_read_b128 per lane (row l & 15, chunk l >> 4 of the hi or
+// the lo half): the same 24 reads per K-tile and wave as the 32x32x16 form had, for 96 MFMAs of half the size.  The 16x16x32 shape
+// holds a higher clock at the board's power cap for the same work (profiles/r07_mfma_shape_probe.txt: 1.13-1.14 x the FLOP/s with
+// these fragment reads).  Staging, ds_reads, barriers and waits are identical in both forms.
 //   RAW  the wait at the end of the P1 reads of tile t-1 (vmcnt(2)) leaves only A-half1 of tile t in flight, so A0 / B0 / B1 of
 //        tile t are retired and the following barrier publishes them; the wait at the end of the P0 reads of tile t (vmcnt(6))
 //        leaves only A0 / B0 / B1 of tile t+1 in flight, so A-half1 of tile t is retired before the barrier that precedes its read.
@@ -53,7 +56,7 @@ constexpr size_t PIPE_LDS_BYTES = (size_t)2 * PIPE_BUF_HALVES * sizeof(_Float16)
 
 #define PIPE_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #ifndef PIPE_PAIR3_STAGE_GAP
-#define PIPE_PAIR3_STAGE_GAP 2  // MFMA pairs between two LDS-DMA pieces of a PAIR3 phase (1: as the plain schedule)
+#define PIPE_PAIR3_STAGE_GAP 4  // MFMA pairs (16x16x32) between two LDS-DMA pieces of a PAIR3 phase: 128 cycles of the matrix pipe
 #endif
 #define PIPE_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 // PAIR3 only: where the LDS-DMAs of a K-tile are issued.  0: all eight between the MFMAs of the two MFMA half-phases (as the plain
@@ -130,28 +133,48 @@ struct pipe_src_precomputes<S, decltype((void)S::PRECOMPUTE)> { static constexpr
 // SRC provides  template <int TYPE, int J> void issue(int t, pipe_lds_t *dst)  : the LDS-DMA (16 bytes per lane, 1 KiB per
 // wave, lane-linear at dst) of piece J of half-tile TYPE (0 A-half0, 1 A-half1, 2 B-half0, 3 B-half1) of K-tile t.
 // The B-half0 fragments of a K-tile are held in fbk, the B-half1 ones in fb: both B halves are read in P0 (schedule above).
-// PAIR3 (the split GEMM, round 5): both operands are BLOCKED pair rows (common.h), so the 64 halves of an LDS row are
-//   [hi k 0..15 | hi k 16..31 | lo k 0..15 | lo k 16..31]  (fragment index s = 0..3)
-// and a K-tile is a 32-deep k-slice of hi AND lo of both operands.  Staging, LDS reads, barriers and waits are those of the
-// plain fp16 form; only the products change: per output quadrant and k-step j the three MFMAs  hi_j x hi_j,  lo_j x hi_j,
-// hi_j x lo_j  (fragment pairs (j, j), (j + 2, j), (j, j + 2)) into the same accumulator -- 24 MFMAs per phase instead of 16,
-// i.e. per MFMA two thirds of the LDS-DMAs, ds_reads and barriers of three passes over [hi | lo'] rows (round 4).
+// PAIR3 (the split GEMM): both operands are BLOCKED pair rows (common.h), so the 64 halves of an LDS row are  [hi k 0..31 | lo k 0..31]
+// and a K-tile is a 32-deep k-slice of hi AND lo of both operands.  Staging, barriers and waits are those of the plain fp16 form;
+// the fragments and products are v_mfma_f32_16x16x32_f16's: per 16 x 16 block (acc[x][y], x = 0..3 along n, y = 0..7 along m) the
+// three MFMAs  hi x hi,  lo x hi,  hi x lo  into the same accumulator -- 48 per phase.
 // MASKED: per-lane row masks on the fragments -- a lane whose keep_a bit y (A-tile row block y = 0..3 of its wave) / keep_b bit x
 // (B-tile row block x = 0, 1) is clear feeds zeros for that row, so the pass adds nothing to it.  Used by the folded GEMMs' second
 // pass over the lo halves of the token operand, which must touch the rows with a wide mean and ONLY those (a row's bits must not
 // depend on which other rows share its tile: gemm256_f16.hip).
+template <bool PAIR3>
+struct PipeAcc { typedef f32x16 type[2][4]; };
+template <>
+struct PipeAcc<true> { typedef f32x4 type[4][8]; };
+
 template <class SRC, bool PAIR3 = false, bool MASKED = false>
 struct Pipe256T {
+    static_assert(!(PAIR3 && MASKED), "the masked pass is a plain fp16 pass");
+    // a wave's accumulators, 128 registers either way: plain fp16  acc[x][y] (f32x16) = the 32 x 32 block (n x, m y) of
+    // v_mfma_f32_32x32x16_f16;  PAIR3  acc[x][y] (f32x4) = the 16 x 16 block (n x = 0..3, m y = 0..7) of v_mfma_f32_16x16x32_f16
+    typedef typename PipeAcc<PAIR3>::type Acc;
     SRC S;
     _Float16 *smem;
     int w;
     int ra[2], rb, kx[4];  // per-lane read offsets (halves)
     unsigned keep_a = 0xFu, keep_b = 0x3u;  // MASKED only
     f16x8 fa[2][4], fb[4], fbk[4];
+    // PAIR3: [16-row block][hi | lo] -- A: the four blocks of the phase's A-half, B: the two blocks of each B half
+    f16x8 qa[4][2], qb[2][2], qbk[2][2];
 
     __device__ __forceinline__ void init(_Float16 *smem_, int w_, int l) {
         smem = smem_;
         w = w_;
+        if constexpr (PAIR3) {
+            // a 16x16x32 operand: lane l holds row l & 15 of a 16-row block, k 8 (l >> 4) .. + 7 -- chunk l >> 4 of the row's hi half
+            // (kx[0]), chunk 4 + (l >> 4) of its lo half (kx[1]).  Conflict-free: in each 16-lane group of a ds_read_b128 the lanes
+            // hit 16 different (row parity, swizzled chunk) pairs, i.e. 16 different 4-bank quads of the 64 banks.
+            const int q = l >> 4, i = l & 15;
+            kx[0] = (q ^ ((i >> 1) & 7)) * 8;  // block rows are multiples of 16: the swizzle depends on i only
+            kx[1] = kx[0] ^ 32;
+            ra[0] = ((w >> 2) * 64 + i) * 64;  // + 16 rows per A block yy
+            rb = ((w & 3) * 32 + i) * 64;      // + 16 rows per B block xx
+            return;
+        }
         const int g = l >> 5, i = l & 31, wm = w >> 2, wn = w & 3;
         const int c0 = g ^ ((i >> 1) & 7);  // row offsets below are multiples of 16: swizzle depends on i only
 #pragma unroll
@@ -175,6 +198,13 @@ struct Pipe256T {
     template <int H>
     __device__ __forceinline__ void read_a(int t) {
         const _Float16 *base = smem + (t & 1) * PIPE_BUF_HALVES + H * PIPE_HALF_HALVES;
+        if constexpr (PAIR3) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int yy = 0; yy < 4; ++yy) qa[yy][s] = *reinterpret_cast<const f16x8 *>(base + ra[0] + yy * 16 * 64 + kx[s]);
+            return;
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -187,6 +217,17 @@ struct Pipe256T {
     template <int H>
     __device__ __forceinline__ void read_b(int t) {
         const _Float16 *base = smem + (t & 1) * PIPE_BUF_HALVES + (2 + H) * PIPE_HALF_HALVES;
+        if constexpr (PAIR3) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int xx = 0; xx < 2; ++xx) {
+                    const f16x8 v = *reinterpret_cast<const f16x8 *>(base + rb + xx * 16 * 64 + kx[s]);
+                    if constexpr (H == 0) qbk[xx][s] = v;
+                    else qb[xx][s] = v;
+                }
+            return;
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             f16x8 v = *reinterpret_cast<const f16x8 *>(base + rb + kx[s]);
@@ -199,34 +240,50 @@ struct Pipe256T {
     // MFMA half-phase: 16 MFMAs on A fragments fa (A-half YH) against both B halves, with
     // N_STAGE LDS-DMA pieces (two per listed half-tile of K-tile ts) issued after every second MFMA.
     template <int YH, int ST0, int ST1, int ST2>
-    __device__ __forceinline__ void mfma16(f32x16 (&acc)[2][4], int ts) {
+    __device__ __forceinline__ void mfma16(Acc &acc, int ts) {
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         constexpr int n_stage = (ST0 >= 0) + (ST1 >= 0) + (ST2 >= 0);
         constexpr int types[3] = {ST0 >= 0 ? ST0 : 0, ST1 >= 0 ? ST1 : 0, ST2 >= 0 ? ST2 : 0};
-        // steps of two MFMAs (the two 32-row A fragments of this phase against one B fragment); PER = steps per B half
-        constexpr int PER = PAIR3 ? 6 : 4;
-        // PAIR3: (A fragment, B fragment) of step c -- hi_j x hi_j, lo_j x hi_j, hi_j x lo_j for j = 0, 1
-        constexpr int pa[6] = {0, 2, 0, 1, 3, 1}, pb[6] = {0, 0, 2, 1, 1, 3};
+        if constexpr (PAIR3) {
+            // 48 v_mfma_f32_16x16x32_f16 (the time of 24 of 32x32x16): per B half (P0 runs B-half0 first, P1 B-half1), product
+            // (hi x hi, lo x hi, hi x lo), B block xb and A block yy -- an accumulator comes back every eighth MFMA.  One LDS-DMA piece
+            // after every STAGE_GAP pairs of MFMAs: 4 pairs of 16x16x32 = 128 cycles, the spacing of 2 pairs of 32x32x16.
+            constexpr int GAP2 = 2 * PIPE_PAIR3_STAGE_GAP;
+            static_assert(GAP2 * (2 * 3 - 1) + 1 < 48, "six pieces fit the half-phase");
 #pragma unroll
-        for (int step = 0; step < 2 * PER; ++step) {
+            for (int q = 0; q < 48; ++q) {
+                const int hb = (q / 24) ^ YH, p = (q / 8) % 3, xb = (q >> 2) & 1, yy = q & 3;
+                const f16x8 &bf = hb == 0 ? qbk[xb][p == 2] : qb[xb][p == 2];
+                acc[2 * hb + xb][4 * YH + yy] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf, qa[yy][p == 1], acc[2 * hb + xb][4 * YH + yy], 0, 0, 0);
+                if (q % GAP2 == 1 && q / GAP2 < 2 * n_stage) {
+                    const int pc = q / GAP2;
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (pc == 0) stage_piece<types[0], 0, true>(ts);
+                    if (pc == 1) stage_piece<types[0], 1, true>(ts);
+                    if (pc == 2) stage_piece<types[1], 0, true>(ts);
+                    if (pc == 3) stage_piece<types[1], 1, true>(ts);
+                    if (pc == 4) stage_piece<types[2], 0, true>(ts);
+                    if (pc == 5) stage_piece<types[2], 1, true>(ts);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        } else {
+#pragma unroll
+        for (int step = 0; step < 8; ++step) {
+            // steps of two MFMAs (the two 32-row A fragments of this phase against one B fragment), four per B half.
             // P0 runs B-half0 first (it was read first); P1 runs B-half1 first (either order is fine for the result:
             // the two halves accumulate into different registers)
-            // (PAIR3 with the two B halves alternating -- an accumulator every fourth MFMA instead of every second -- measures the
-            // same: profiles/r05_ab_pair3_mfma_order.jsonl)
-            const int xx = (step / PER) ^ YH, c = step % PER;
-            const int sa = PAIR3 ? pa[c] : c, sb = PAIR3 ? pb[c] : c;
+            const int xx = (step / 4) ^ YH, c = step % 4;
 #pragma unroll
             for (int yy = 0; yy < 2; ++yy) {
-                const f16x8 &bf = xx == 0 ? fbk[sb] : fb[sb];
-                acc[xx][2 * YH + yy] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, fa[yy][sa], acc[xx][2 * YH + yy], 0, 0, 0);
+                const f16x8 &bf = xx == 0 ? fbk[c] : fb[c];
+                acc[xx][2 * YH + yy] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, fa[yy][c], acc[xx][2 * YH + yy], 0, 0, 0);
             }
-            // one LDS-DMA piece after each of the first 2 * n_stage MFMA pairs (PAIR3, STAGE_GAP = 2: after every second pair --
-            // the phase is half as long again, the pieces keep their distance in MFMA time)
-            constexpr int GAP = PAIR3 ? PIPE_PAIR3_STAGE_GAP : 1;
-            if (step % GAP == 0 && step / GAP < 2 * n_stage) {
-                const int pc = step / GAP;
+            // one LDS-DMA piece after each of the first 2 * n_stage MFMA pairs
+            if (step < 2 * n_stage) {
+                const int pc = step;
                 __builtin_amdgcn_sched_barrier(0);
                 if (pc == 0) stage_piece<types[0], 0, true>(ts);
                 if (pc == 1) stage_piece<types[0], 1, true>(ts);
@@ -236,6 +293,7 @@ struct Pipe256T {
                 if (pc == 5) stage_piece<types[2], 1, true>(ts);
                 __builtin_amdgcn_sched_barrier(0);
             }
+        }
         }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -250,7 +308,7 @@ struct Pipe256T {
     // waiting for the epilogue's stores to drain (vmcnt retires in order); from P0 of tile t+1 on the waits are the steady-state
     // ones -- A-half1 of tile t+1 is younger than those stores.
     template <int MODE, int VM0 = 6, int VM1 = 2>
-    __device__ __forceinline__ void tile2(int t, f32x16 (&acc)[2][4]) {
+    __device__ __forceinline__ void tile2(int t, Acc &acc) {
         if constexpr (pipe_src_precomputes<SRC>::value) S.prepare(t);
         if constexpr (PAIR3 && PIPE_PAIR3_EARLY > 0) {
             // in flight when a tile starts (oldest first): A1(t), A0 B0 B1 (t+1) -- what the prologue leaves, too
@@ -339,7 +397,7 @@ struct Pipe256T {
     // FIRST output tile of a persistent workgroup then starts from prologue_landed (every LDS-DMA of the prologue retired: a loose
     // wait has nothing to wait for), so that K-tile 0 is the same code for every output tile.
     template <int VM0L = 6, int VM1L = 2>
-    __device__ __forceinline__ void tiles_streaming(int NK, f32x16 (&acc)[2][4]) {
+    __device__ __forceinline__ void tiles_streaming(int NK, Acc &acc) {
         if constexpr (VM0L != 6 || VM1L != 2) {
             tile2<0, VM0L, VM1L>(0, acc);
             for (int t = 1; t < NK; ++t) tile2<0>(t, acc);
@@ -351,7 +409,7 @@ struct Pipe256T {
     // NK-1 is staged, no LDS-DMA left in flight.
     // (VM0L / VM1L as tiles_streaming; they need NK - T0 >= 3: K-tile T0 is then a steady-state tile)
     template <int VM0L = 6, int VM1L = 2>
-    __device__ __forceinline__ void tiles_final(int NK, f32x16 (&acc)[2][4], int T0 = 0) {
+    __device__ __forceinline__ void tiles_final(int NK, Acc &acc, int T0 = 0) {
         if constexpr (VM0L != 6 || VM1L != 2) {
             tile2<0, VM0L, VM1L>(T0, acc);
             for (int t = T0 + 1; t < NK - 2; ++t) tile2<0>(t, acc);
@@ -363,7 +421,7 @@ struct Pipe256T {
     }
 
     // Whole K loop of one output tile.  On return every wave has passed the same number of barriers.
-    __device__ __forceinline__ void run(int NK, f32x16 (&acc)[2][4]) {
+    __device__ __forceinline__ void run(int NK, Acc &acc) {
         prologue();
         enter();
         tiles_final(NK, acc);
