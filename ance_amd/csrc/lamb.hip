@@ -8,6 +8,13 @@
 // 40 B of HBM traffic per element.  No atomics and a fixed summation order everywhere: the same inputs give the same bits (under
 // DDP every rank steps on the same all-reduced gradients and must stay bit-identical).  Division and sqrtf are the IEEE ones
 // (hipcc's default correctly rounded fp32 divide / sqrt), as in the reference's fp32 arithmetic.
+//
+// ance_lamb_step_clipped: torch.nn.utils.clip_grad_norm_(params, max_grad_norm) (2-norm, error_if_nonfinite=False) fused in front,
+// two more launches and 4 B more per element (44 B; clip_grad_norm_ then the step moves 52 B in a dozen launches):
+//   gnorm    (one workgroup per chunk)  reads g only; the chunk's sum of g^2 (fp64) stored to its slot
+//   gtotal   (one workgroup)  the chunk sums added in chunk order (fp64), one sqrt, rounded to fp32 -> *d_grad_norm;
+//            coef = min(max_grad_norm / (total + 1e-6), 1) in fp32, NaN when the total is NaN (as torch's clamp)
+//   pass 1   as above with g * coef (an fp32 product, formed in registers) in place of g; the gradients in memory are not rescaled
 #include "common.h"
 
 #include <math.h>
@@ -56,10 +63,13 @@ __device__ __forceinline__ void lamb_acc(float p, float u, double &sp, double &s
     su = __builtin_fma((double)u, (double)u, su);
 }
 
+// CLIP: every gradient element is multiplied by *coef (ance_lamb_step_clipped) before it enters m and v
+template <bool CLIP>
 __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
-                                                                  const int32_t *chunk_tensor, double2 *partial) {
+                                                                  const int32_t *chunk_tensor, double2 *partial, const float *coef) {
     __shared__ double red[LAMB_THREADS / 64][2];
     const int tid = threadIdx.x;
+    const float cf = CLIP ? coef[0] : 1.0f;
     const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
     const LambDevGroup G = groups[T.group];
     const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
@@ -86,7 +96,7 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float mj = M[k][j], vj = V[k][j];
-                        const float u = lamb_mv(P[k][j], Gr[k][j], mj, vj, G);
+                        const float u = lamb_mv(P[k][j], CLIP ? Gr[k][j] * cf : Gr[k][j], mj, vj, G);
                         M[k][j] = mj;
                         V[k][j] = vj;
                         lamb_acc(P[k][j], u, sp, su);
@@ -101,7 +111,7 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
     for (int e = done + tid; e < len; e += LAMB_THREADS) {  // scalar tail (or the whole chunk of an unaligned tensor)
         float mj = m[e], vj = v[e];
         const float pj = p[e];
-        const float u = lamb_mv(pj, g[e], mj, vj, G);
+        const float u = lamb_mv(pj, CLIP ? g[e] * cf : g[e], mj, vj, G);
         m[e] = mj;
         v[e] = vj;
         lamb_acc(pj, u, sp, su);
@@ -122,6 +132,68 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
 #pragma unroll
         for (int w = 1; w < LAMB_THREADS / 64; ++w) { a += red[w][0]; b += red[w][1]; }
         partial[blockIdx.x] = make_double2(a, b);
+    }
+}
+
+// the chunk's sum of g^2 in fp64 (ance_lamb_step_clipped): reads g only
+__global__ void __launch_bounds__(LAMB_THREADS) lamb_gnorm_kernel(const LambDevTensor *tensors, const int32_t *chunk_tensor,
+                                                                  double *gpartial) {
+    __shared__ double red[LAMB_THREADS / 64];
+    const int tid = threadIdx.x;
+    const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
+    const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
+    const int len = (int)min((int64_t)LAMB_CHUNK, T.numel - base);
+    const gfloat *g = (const gfloat *)(T.g + base);
+    double sg = 0.0;
+    int done = 0;
+    if (T.vec) {
+        const int n4 = len >> 2;
+        const gf32x4 *g4 = (const gf32x4 *)g;
+        for (int i0 = tid; i0 < n4; i0 += LAMB_THREADS * LAMB_UNROLL) {
+            f32x4 Gr[LAMB_UNROLL];
+#pragma unroll
+            for (int k = 0; k < LAMB_UNROLL; ++k) {
+                const int i = i0 + k * LAMB_THREADS;
+                Gr[k] = i < n4 ? g4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int k = 0; k < LAMB_UNROLL; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sg = __builtin_fma((double)Gr[k][j], (double)Gr[k][j], sg);
+        }
+        done = n4 * 4;
+    }
+    for (int e = done + tid; e < len; e += LAMB_THREADS) sg = __builtin_fma((double)g[e], (double)g[e], sg);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sg += __shfl_xor(sg, off);
+    if ((tid & 63) == 0) red[tid >> 6] = sg;
+    __syncthreads();
+    if (tid == 0) {
+        double a = red[0];
+#pragma unroll
+        for (int w = 1; w < LAMB_THREADS / 64; ++w) a += red[w];
+        gpartial[blockIdx.x] = a;
+    }
+}
+
+// one workgroup: every chunk's sum in chunk order (thread-strided, then a shared-memory tree) -> the total norm and the clip factor
+__global__ void __launch_bounds__(1024) lamb_gtotal_kernel(const double *gpartial, int n_chunks, float max_norm, float *grad_norm,
+                                                           float *coef) {
+    __shared__ double s[1024];
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    for (int c = tid; c < n_chunks; c += 1024) acc += gpartial[c];
+    s[tid] = acc;
+    __syncthreads();
+    for (int off = 512; off > 0; off >>= 1) {
+        if (tid < off) s[tid] += s[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float total = (float)sqrt(s[0]);
+        const float c = max_norm / (total + 1e-6f);
+        grad_norm[0] = total;
+        coef[0] = c > 1.0f ? 1.0f : c;  // clamp(max=1) that lets a NaN through, as torch's clamp does
     }
 }
 
@@ -203,6 +275,10 @@ size_t staged_bytes(int n_tensors, int n_groups, int64_t n_chunks) {
 size_t workspace_bytes_for(int n_tensors, int n_groups, int64_t n_chunks) {
     return staged_bytes(n_tensors, n_groups, n_chunks) + sizeof(double2) * (size_t)n_chunks;
 }
+// the clipped step appends [fp64 g^2 per chunk][coef (fp32, 16 bytes)]
+size_t workspace_bytes_clipped(int n_tensors, int n_groups, int64_t n_chunks) {
+    return workspace_bytes_for(n_tensors, n_groups, n_chunks) + align16(sizeof(double) * (size_t)n_chunks) + 16;
+}
 
 // Pinned staging buffers of the host tables.  A buffer is handed out again only once the event recorded after its last copy has
 // completed (hipEventQuery, no wait), so a pending DMA never reads a buffer that is being refilled.  When all of them are still in
@@ -250,27 +326,22 @@ int stage_acquire(size_t bytes) {
     return old;
 }
 
+thread_local const char *g_lamb_fn = "ance_lamb_step";
 int lamb_refuse(const char *why) {
     char buf[160];
-    snprintf(buf, sizeof(buf), "ance_lamb_step: invalid argument (%s)", why);
+    snprintf(buf, sizeof(buf), "%s: invalid argument (%s)", g_lamb_fn, why);
     set_last_error(buf);
     return ANCE_E_INVALID;
 }
 
-}  // namespace
-}  // namespace ance
-
-extern "C" size_t ance_lamb_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
-    using namespace ance;
-    if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
-    const int64_t chunks = (int64_t)n_tensors + total_numel / LAMB_CHUNK;  // >= the sum of every tensor's ceil(numel / chunk)
-    if (chunks > (int64_t)INT32_MAX) return 0;
-    return workspace_bytes_for(n_tensors, n_groups, chunks);
+int64_t max_chunks(int n_tensors, int64_t total_numel) {  // >= the sum of every tensor's ceil(numel / chunk)
+    return (int64_t)n_tensors + total_numel / LAMB_CHUNK;
 }
 
-extern "C" int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
-                              float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
-    using namespace ance;
+
+// the body of ance_lamb_step (clip false) and ance_lamb_step_clipped (clip true: max_norm, d_grad_norm)
+int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam, float *d_out,
+                   void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm, float *d_grad_norm) {
     if (n_tensors < 0) return lamb_refuse("n_tensors < 0");
     if (n_tensors == 0) return ANCE_OK;
     if (!h_tensors || !h_groups) return lamb_refuse("null table");
@@ -285,7 +356,7 @@ extern "C" int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, co
         n_chunks += (T.numel + LAMB_CHUNK - 1) / LAMB_CHUNK;
         if (n_chunks > (int64_t)INT32_MAX) return lamb_refuse("too many elements");
     }
-    const size_t need = workspace_bytes_for(n_tensors, n_groups, n_chunks);
+    const size_t need = clip ? workspace_bytes_clipped(n_tensors, n_groups, n_chunks) : workspace_bytes_for(n_tensors, n_groups, n_chunks);
     if (!d_workspace || (uintptr_t)d_workspace % 16) return lamb_refuse("null or unaligned workspace");
     if (workspace_bytes < need) return lamb_refuse("workspace too small");
 
@@ -340,12 +411,60 @@ extern "C" int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, co
     const LambDevTensor *dT = (const LambDevTensor *)(ws + off_t);
     const int32_t *dC = (const int32_t *)(ws + off_c);
     double2 *dP = (double2 *)(ws + off_p);
-    if (n_chunks > 0)
-        hipLaunchKernelGGL(lamb_pass1_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP);
+    if (clip) {
+        double *dGP = (double *)(ws + off_p + sizeof(double2) * (size_t)n_chunks);
+        float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
+        if (n_chunks > 0) hipLaunchKernelGGL(lamb_gnorm_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP);
+        hipLaunchKernelGGL(lamb_gtotal_kernel, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks, (float)max_norm, d_grad_norm,
+                           dCoef);
+        if (n_chunks > 0)
+            hipLaunchKernelGGL(lamb_pass1_kernel<true>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP,
+                               (const float *)dCoef);
+    } else if (n_chunks > 0) {
+        hipLaunchKernelGGL(lamb_pass1_kernel<false>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP,
+                           (const float *)nullptr);
+    }
     hipLaunchKernelGGL(lamb_reduce_kernel, dim3((unsigned)((n_tensors + 3) / 4)), dim3(256), 0, st, dT, n_tensors,
                        (const double2 *)dP, d_out);
     if (n_chunks > 0)
         hipLaunchKernelGGL(lamb_pass2_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, (const float *)d_out,
                            adam ? 1 : 0);
-    return check_launch("ance_lamb_step");
+    return check_launch(g_lamb_fn);
+}
+
+}  // namespace
+}  // namespace ance
+
+extern "C" size_t ance_lamb_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
+    using namespace ance;
+    if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
+    const int64_t chunks = max_chunks(n_tensors, total_numel);
+    if (chunks > (int64_t)INT32_MAX) return 0;
+    return workspace_bytes_for(n_tensors, n_groups, chunks);
+}
+
+extern "C" int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                              float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
+    using namespace ance;
+    g_lamb_fn = "ance_lamb_step";
+    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, false, 0.0, nullptr);
+}
+
+extern "C" size_t ance_lamb_clipped_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
+    using namespace ance;
+    if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
+    const int64_t chunks = max_chunks(n_tensors, total_numel);
+    if (chunks > (int64_t)INT32_MAX) return 0;
+    return workspace_bytes_clipped(n_tensors, n_groups, chunks);
+}
+
+extern "C" int ance_lamb_step_clipped(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups,
+                                      int adam, double max_grad_norm, float *d_grad_norm, float *d_out, void *d_workspace,
+                                      size_t workspace_bytes, void *stream) {
+    using namespace ance;
+    g_lamb_fn = "ance_lamb_step_clipped";
+    if (!(max_grad_norm > 0.0) || !(max_grad_norm < (double)INFINITY)) return lamb_refuse("max_grad_norm not a positive finite number");
+    if (n_tensors > 0 && !d_grad_norm) return lamb_refuse("null d_grad_norm");
+    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, true,
+                          max_grad_norm, d_grad_norm);
 }

@@ -7,6 +7,10 @@ synchronisation.  Same constructor, same errors, same state entries (``step`` an
 ``weight_norm``, ``adam_norm``, ``trust_ratio`` as 0-dim device tensors), so ``log_lamb_rs``, ``optimizer.state_dict()`` /
 ``torch.save`` and ``load_state_dict`` of the reference's ``optimizer.pt`` work unchanged, in both directions.
 
+``max_grad_norm`` fuses the ``torch.nn.utils.clip_grad_norm_`` call every trainer of the reference makes in front of
+``optimizer.step()`` (drivers/run_ann.py:283-289, run_ann_dpr.py:235-237) into the step (``ance_lamb_step_clipped``: five launches,
+44 B per element, against 52 B and a dozen launches for the two calls).
+
 No CPU fallback: every parameter, gradient and state tensor must be a contiguous fp32 tensor on one HIP device.
 """
 import ctypes
@@ -31,9 +35,18 @@ class Lamb(Optimizer):
     for a trust ratio of 1 always (the norms and the LAMB trust ratio are still recorded).
 
     Arguments as the reference's: params, lr (1e-3), betas ((0.9, 0.999)), eps (1e-6), weight_decay (0), adam (False).
+
+    max_grad_norm (None, or a positive finite number): ``clip_grad_norm_(params, max_grad_norm)`` (2-norm,
+    ``error_if_nonfinite=False``) over every parameter of every group that has a gradient, inside the step:
+    ``coef = min(max_grad_norm / (total_norm + 1e-6), 1)`` in fp32 and every gradient element enters the moment updates as the fp32
+    product ``g * coef``.  ``last_grad_norm`` is the total norm before clipping (what ``clip_grad_norm_`` returns) as a 0-dim device
+    tensor, None before the first step.  The one visible difference from calling ``clip_grad_norm_``: ``p.grad`` is NOT rescaled in
+    memory (the trainers zero the gradients right after the step).  A non-finite total norm makes ``coef`` NaN and poisons every
+    stepped tensor, as torch's function does.  max_grad_norm is an attribute of the optimizer, not part of ``param_groups`` or
+    ``state_dict()``: the reference's ``optimizer.pt`` stays byte-compatible.
     """
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, adam=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, adam=False, max_grad_norm=None):
         if not 0.0 <= lr:
             raise ValueError("Invalid learning rate: {}".format(lr))
         if not 0.0 <= eps:
@@ -42,8 +55,17 @@ class Lamb(Optimizer):
             raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
         if not 0.0 <= betas[1] < 1.0:
             raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        if max_grad_norm is not None:
+            try:
+                ok = 0.0 < float(max_grad_norm) < float("inf")
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("Invalid max_grad_norm: {} (None or a positive finite number)".format(max_grad_norm))
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.adam = adam
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
         super(Lamb, self).__init__(params, defaults)
         self._workspace = {}
 
@@ -97,7 +119,8 @@ class Lamb(Optimizer):
         tensors = np.array(rows, dtype=_TENSOR_DTYPE)
         gtab = np.array(groups, dtype=_GROUP_DTYPE)
         total = int(tensors["numel"].sum())
-        need = L.ance_lamb_workspace_bytes(len(rows), len(groups), total)
+        clip = self.max_grad_norm is not None
+        need = (L.ance_lamb_clipped_workspace_bytes if clip else L.ance_lamb_workspace_bytes)(len(rows), len(groups), total)
         if need == 0:
             raise _lib.AnceLibraryError("Lamb: %d tensors of %d elements exceed ance_lamb_step's limits" % (len(rows), total))
         with torch.cuda.device(device):
@@ -107,10 +130,16 @@ class Lamb(Optimizer):
                 self._workspace[device] = ws
             out = torch.empty((len(rows), 3), dtype=torch.float32, device=device)
             stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(L.ance_lamb_step(tensors.ctypes.data_as(ctypes.POINTER(_lib.AnceLambTensor)), len(rows),
-                                        gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups),
-                                        1 if self.adam else 0, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                        ws.numel(), ctypes.c_void_p(stream)), "ance_lamb_step")
+            tab = (tensors.ctypes.data_as(ctypes.POINTER(_lib.AnceLambTensor)), len(rows),
+                   gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups), 1 if self.adam else 0)
+            tail = (ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream))
+            if clip:
+                norm = torch.empty((1,), dtype=torch.float32, device=device)
+                _lib.check(L.ance_lamb_step_clipped(*tab, self.max_grad_norm, ctypes.c_void_p(norm.data_ptr()), *tail),
+                           "ance_lamb_step_clipped")
+                self.last_grad_norm = norm[0]
+            else:
+                _lib.check(L.ance_lamb_step(*tab, *tail), "ance_lamb_step")
         vals = out.view(-1).unbind(0)
         for k, state in enumerate(updated):
             state['step'] += 1

@@ -39,7 +39,9 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* 7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped only ADD symbols, which
+                               callers built against the earlier 7 never look up; nothing that existed changed;
+                               7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
                                5: AnceEncoderDesc.precision (the arithmetic is an argument, not an environment variable), ance_encoder_range_faults,
                                ance_ip_topk_scan; 4: blocked pair rows in the split mode (ance_pair_layout; ance_debug_gemm_split + d_wscale_inv);
@@ -307,6 +309,35 @@ int ance_search_bad_image_calls(unsigned long long *out);
 int ance_nll_forward(const float *d_q, const float *d_a, const float *d_b, const float *d_mask_a, const float *d_mask_b, int64_t n,
                      int d, int chunks, float *d_logits, float *d_loss_rows, float *d_loss_mean, void *stream);
 
+/* Gradient of ance_nll_forward's mean loss with respect to q, a, b (csrc/nll.hip), same arguments and layouts.  With
+ * p = sigmoid(logit_b - logit_a) and s = *d_grad_output / n:  d logit_a = -p s, d logit_b = +p s;
+ *   d_gq [n, d] = d logit_a a[ca] + d logit_b b[cb];  d_ga [n * chunks, d]: row ca = d logit_a q;  d_gb: row cb = d logit_b q,
+ * ca, cb = the chunk that won the max (the lowest index among equal biased scores, the forward's comparison; the logits are
+ * recomputed, bit for bit the forward's).  Every other chunk row of d_ga, d_gb is written as zeros: no pre-zeroing.
+ * d_grad_output: DEVICE fp32 scalar (the upstream gradient of the mean loss), so the call never waits for the host.
+ * One launch; the same inputs give the same bits.  Refuses (ANCE_E_INVALID, before the launch) what ance_nll_forward refuses. */
+int ance_nll_backward(const float *d_q, const float *d_a, const float *d_b, const float *d_mask_a, const float *d_mask_b, int64_t n,
+                      int d, int chunks, const float *d_grad_output, float *d_gq, float *d_ga, float *d_gb, void *stream);
+
+/* The DPR trainer's in-batch-negatives objective (csrc/inbatch_nll.hip; drivers/run_ann_dpr.py:356-365 and its evaluate_dev):
+ *   scores = q ctx^T [nq, nc] (fp32 FMA, fixed order);  *d_loss_mean = mean_i -log_softmax(scores[i])[positive_idx[i]];
+ *   d_counts[0] = #{i : argmax_j scores[i][j] == positive_idx[i]} (the lowest j among equal scores);
+ *   d_counts[1] = #{i : positive_idx[i] outside [0, nc)}: such an index is never used as an address, the row's loss and the mean
+ *   are NaN, the row never counts as correct, and the backward makes that row's part of the gradients NaN.
+ * d_q [nq, d], d_ctx [nc, d] fp32; d_positive_idx int64 [nq] on the device; d_counts int64 [2].
+ * The scores, the rows' log-sum-exp and gS live in d_workspace (16-byte aligned, ance_inbatch_nll_workspace_bytes; 0: shape not
+ * supported); the backward reads what the forward of the SAME arguments left there and may be repeated.
+ * Backward: gS = (softmax(scores) - onehot) *d_grad_output / nq (d_grad_output a DEVICE fp32 scalar); d_gq [nq, d] = gS ctx;
+ * d_gctx [nc, d] = gS^T q.  Three launches each way, no atomics: the same inputs give the same bits.
+ * Supported: 1 <= nq <= 1024, nq <= nc <= 2048, 128 <= d <= 1024, d % 4 == 0.  Refuses (ANCE_E_INVALID, before any launch) anything
+ * else, a null pointer and a null, unaligned or too small workspace. */
+size_t ance_inbatch_nll_workspace_bytes(int64_t nq, int64_t nc, int d);
+int ance_inbatch_nll_forward(const float *d_q, const float *d_ctx, const int64_t *d_positive_idx, int64_t nq, int64_t nc, int d,
+                             float *d_loss_mean, int64_t *d_counts, void *d_workspace, size_t workspace_bytes, void *stream);
+int ance_inbatch_nll_backward(const float *d_q, const float *d_ctx, const int64_t *d_positive_idx, int64_t nq, int64_t nc, int d,
+                              const float *d_grad_output, float *d_gq, float *d_gctx, void *d_workspace, size_t workspace_bytes,
+                              void *stream);
+
 /* Test hook: the SPLIT (fp32-grade) GEMM of the encoder with one of its epilogues.  acc[m][n] = sum_k a[m][k] b[n][k] with
  * a = a_hi + a_lo (b likewise; the lo x lo products are left out); d_a_pair [M, 2K] / d_b_pair [N, 2K] fp16 PAIR ROWS -- 32-column
  * blocks [hi (32) | lo (32)], lo = fp16(v - hi) unscaled: ance_pair_layout gives the positions; (mu_m, r_m) = mean and
@@ -429,6 +460,18 @@ typedef struct AnceLambGroup {
 size_t ance_lamb_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel);
 int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
                    float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ance_lamb_step with torch.nn.utils.clip_grad_norm_(params, max_grad_norm) (norm_type 2, error_if_nonfinite=False) over every
+ * tensor of the call fused in front: total = the 2-norm of all gradients (per-chunk fp64 sums added in chunk order, one sqrt,
+ * rounded to fp32) -> *d_grad_norm (DEVICE fp32, the norm before clipping); coef = min(max_grad_norm / (total + 1e-6), 1) in fp32;
+ * every gradient element enters m and v as the fp32 product g coef (bit-neutral when coef == 1).  The gradients in memory are NOT
+ * rescaled.  A NaN total makes coef NaN and poisons every tensor of the call, as torch's function does.  Five launches, 44 bytes
+ * per element, no host synchronisation.  Workspace: ance_lamb_clipped_workspace_bytes (larger than ance_lamb_workspace_bytes).
+ * Refuses what ance_lamb_step refuses, a max_grad_norm that is not a positive finite number and a null d_grad_norm. */
+size_t ance_lamb_clipped_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel);
+int ance_lamb_step_clipped(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                           double max_grad_norm, float *d_grad_norm, float *d_out, void *d_workspace, size_t workspace_bytes,
+                           void *stream);
 
 /* Re-reads every ANCE_* tuning knob from the environment (they are otherwise read once per process).  For tests and
  * sweeps that change a knob between two calls; not thread-safe against concurrent searches. */
