@@ -20,11 +20,14 @@
 // loads software-pipelined behind the current head's compute (48 more VGPRs: 2 workgroups per CU instead of 4) --
 // 126-148 us per launch at the bench shape against 117 us for this kernel: the launch is bound by the dependent
 // MFMA -> softmax -> MFMA chain inside each wave, which only residency (waves per SIMD) hides, not by the staging latency.
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "attention.h"
+#include "precise32.h"  // launch_attention32: the fp32 mode's attention, for ance_debug_attention
 
 namespace ance {
 namespace {
@@ -567,3 +570,74 @@ int launch_attention(const AttnArgs &A, int n_seq, int max_seq_len, hipStream_t 
 }
 
 }  // namespace ance
+
+// Test hook (include/ance_amd.h): one launch of one of the encoder's attention kernels on caller data, through the encoder's own
+// launchers.  Host code only: every bound a kernel relies on is checked here, against the caller's allocations, before anything is
+// copied or launched.
+extern "C" int ance_debug_attention(const AnceAttnDebugArgs *a, void *stream) {
+    using namespace ance;
+    auto refuse = [](const char *why) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "ance_debug_attention: invalid argument (%s)", why);
+        set_last_error(buf);
+        return ANCE_E_INVALID;
+    };
+    if (!a) return refuse("null args");
+    if (a->kind < 0 || a->kind > 2) return refuse("kind");
+    if (a->n_heads != 12 && a->n_heads != 16) return refuse("n_heads");
+    if (a->n_seq < 1 || a->n_seq > (1 << 20)) return refuse("n_seq");
+    if (a->max_seq_len < 1 || a->max_seq_len > 512) return refuse("max_seq_len");
+    if (!a->h_desc || !a->d_desc || !a->qk || !a->ctx || (a->kind == 0 && !a->vt)) return refuse("null pointer");
+    const int64_t H = 64 * (int64_t)a->n_heads, n = a->n_seq;
+    const int64_t desc_bytes = a->kind == 2 ? 4 * (n + 1) : 16 * n;
+    if (a->d_desc_bytes < desc_bytes || (uintptr_t)a->d_desc % 16) return refuse("d_desc");
+    if ((uintptr_t)a->qk % 16 || (uintptr_t)a->ctx % 16 || (a->kind == 0 && (uintptr_t)a->vt % 16)) return refuse("alignment");
+    if (a->qk_rows < 1 || a->ctx_rows < 1) return refuse("rows");
+    if (a->kind == 0) {  // 16-byte rows pieces: strides in halves, multiples of 8
+        if (a->ld_qk % 8 || a->ld_qk < 2 * H || a->ld_vt % 8 || a->ld_vt < 8 || a->ld_ctx % 8 || a->ld_ctx < H) return refuse("stride");
+    } else {             // the split and fp32 kernels derive their strides from n_heads
+        if (a->ld_qk != 3 * H || a->ld_ctx != (a->kind == 1 ? 2 * H : H)) return refuse("stride");
+    }
+    if (a->kind == 2 && (a->cls_only || a->q_compact)) return refuse("cls_only on kind 2");
+    if (a->kind == 1 && a->q_compact != a->cls_only) return refuse("kind 1: q_compact != cls_only");
+    if (a->kind == 0 && a->q_compact && !a->cls_only) return refuse("q_compact without cls_only");
+    const int32_t *d = a->h_desc;
+    if (a->kind == 2) {
+        if (d[0] < 0) return refuse("tokens outside the allocation");
+        for (int64_t s = 0; s < n; ++s) {
+            const int64_t len = (int64_t)d[s + 1] - d[s];
+            if (len < 1 || len > a->max_seq_len) return refuse("length");
+        }
+        if (d[n] > a->qk_rows || d[n] > a->ctx_rows) return refuse("tokens outside the allocation");
+    } else {
+        std::vector<char> seen((size_t)n, 0);
+        const bool compact = a->cls_only && (a->q_compact || a->kind == 1);
+        for (int64_t u = 0; u < n; ++u) {
+            const int64_t tok0 = d[4 * u], len = d[4 * u + 1], vcol = d[4 * u + 2], s = d[4 * u + 3];
+            if (len < 1 || len > a->max_seq_len) return refuse("length");
+            if (s < 0 || s >= n || seen[(size_t)s]) return refuse("sequence index");
+            seen[(size_t)s] = 1;
+            if (tok0 < 0 || tok0 + len > a->qk_rows) return refuse("tokens outside the allocation");
+            if (compact && s >= a->qk_rows) return refuse("Q row s past the allocation");
+            if (a->cls_only ? s >= a->ctx_rows : tok0 + len > a->ctx_rows) return refuse("output row past the allocation");
+            if (a->kind == 0 && (vcol < 0 || vcol % 8 || vcol + ((len + 7) & ~7) > a->ld_vt)) return refuse("V^T columns");
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemcpyAsync(a->d_desc, a->h_desc, (size_t)desc_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return check_launch("ance_debug_attention: descriptors");
+    int rc;
+    if (a->kind == 0) {
+        AttnArgs A;
+        A.qk = (const _Float16 *)a->qk; A.vt = (const _Float16 *)a->vt; A.ctx = (_Float16 *)a->ctx; A.desc = (const int4 *)a->d_desc;
+        A.ld_qk = a->ld_qk; A.ld_vt = a->ld_vt; A.ld_ctx = a->ld_ctx; A.n_heads = a->n_heads;
+        A.cls_only = a->cls_only ? 1 : 0; A.q_compact = a->q_compact ? 1 : 0;
+        rc = launch_attention(A, a->n_seq, a->max_seq_len, st);
+    } else if (a->kind == 1) {
+        rc = launch_attention_split((const float *)a->qk, (_Float16 *)a->ctx, (const int4 *)a->d_desc, a->n_seq, a->n_heads,
+                                    a->max_seq_len, a->cls_only ? 1 : 0, st);
+    } else {
+        rc = launch_attention32((const float *)a->qk, (float *)a->ctx, (const int *)a->d_desc, a->n_seq, a->n_heads, st);
+    }
+    return rc ? rc : check_launch("ance_debug_attention");
+}

@@ -5,8 +5,8 @@
 //     165-199, 235-259).
 //
 // Three arithmetic modes (AnceEncoderDesc.precision), one forward each: forward_fp16, forward_split, forward_fp32.  encode_impl
-// plans the micro-batches (<= max_tokens real tokens), packs their tokens and hands each one to the forward of the handle's mode
-// on one of two lanes (activation sets) and streams.
+// plans the micro-batches (<= max_tokens real tokens; encoder_plan.h), packs their tokens and hands each one to the forward of the
+// handle's mode on one of two lanes (activation sets) and streams.  The small kernels the forwards launch: encoder_kernels.h.
 //
 // fp16 mode: fp16 MFMA operands, fp32 accumulation, fp32 LayerNorm statistics and softmax.  The residual stream of a layer is
 // never normalised by a kernel of its own ("LayerNorm without a kernel"): a LayerNorm pass would read 3 KB and write 1.5 KB per
@@ -21,7 +21,7 @@
 //     its 256 tokens, with its bias / csum / gamma / beta vectors, by LDS-DMA ahead of its main loop and combines them
 //     when its epilogue starts -- there is no LayerNorm kernel and no statistics kernel at all;
 //   * the consumers of the fp32 value (next RES epilogue, [CLS] gather, head) recompute LN(hi + lo) from the pair.
-// Per layer, x_b = the (hi, lo) pair of the previous layer's pre-LayerNorm output (or of the embeddings, embed_fold_kernel):
+// Per layer, x_b = the (hi, lo) pair of the previous layer's pre-LayerNorm output (or of the embeddings, embed_kernel):
 //   QK   = LN(x_b) Wqk^T + b          (gemm EPI_QK_F, Q pre-scaled by log2(e) / 8)   [T, 1536] f16
 //   V^T  = Wv LN(x_b)^T + b           (gemm EPI_VT_F, key-contiguous)                 [768, cols] f16
 //   ctx  = softmax(Q K^T) V           (attention.hip)                                 [T, 768] f16
@@ -42,11 +42,13 @@
 //
 // fp32 mode: fp32 operands throughout (precise32.h), the audit path.
 #include <stdlib.h>
-#include <string.h>
+#include <type_traits>
 #include <vector>
 
 #include "attention.h"
 #include "common.h"
+#include "encoder_kernels.h"
+#include "encoder_plan.h"
 #include "gemm_f16.h"
 #include "precise32.h"
 
@@ -54,589 +56,16 @@ namespace ance {
 namespace {
 
 // The hidden width H is a template parameter of every kernel and forward that depends on it: 768 (RoBERTa-base, BERT-base, SEED)
-// or 1024 (RoBERTa-large: ANCE_ARCH_ROBERTA with the head only, desc_ok).  Head dimension 64 at both.
-constexpr int HEAD_OUT = 768;   // embeddingHead output (model/models.py:145), at either width
+// or 1024 (RoBERTa-large: ANCE_ARCH_ROBERTA with the head only, desc_ok).  with_hidden calls f with the width of a descriptor as
+// a compile-time constant (constexpr int H = decltype(h)::value): the one place that picks a template instance from desc.hidden.
+template <typename F>
+auto with_hidden(int hidden, F &&f) {
+    return hidden == 1024 ? f(std::integral_constant<int, 1024>()) : f(std::integral_constant<int, 768>());
+}
+
 constexpr int S_CAP_MAX = 8192; // sequences per micro-batch
 constexpr int FETCH_CHUNK = 262144;
 constexpr int MAX_LANES = 2;     // activation sets / internal streams (3 and 4 lanes measured no gain: DESIGN.md 9)
-
-// ------------------------------------------------------------------------------------ kernels --
-
-__global__ void cvt_f32_f16_kernel(const float *src, _Float16 *dst, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dst[i] = (_Float16)src[i];
-}
-
-__device__ __forceinline__ int record_len(const int32_t *ids_or_rec, int64_t ld, const int32_t *lens, int64_t rec,
-                                          int L) {
-    int full;
-    if (lens) full = lens[rec];
-    else full = (int)__builtin_bswap32((uint32_t)ids_or_rec[rec * ld]);  // 4-byte big-endian header
-    return full < 0 ? 0 : (full > L ? L : full);
-}
-
-// lengths of records [r0, r0 + n) -> out (for the host-side planner when it has no host copy)
-__global__ void fetch_lens_kernel(const int32_t *base, int64_t ld, const int32_t *lens, int64_t r0, int n, int L,
-                                  int32_t *out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = record_len(base, ld, lens, r0 + i, L);
-}
-
-struct PlanArgs {
-    const int32_t *base;  // records (header mode: row = [len_be, ids...]) or ids
-    int64_t ld;           // row stride in int32
-    const int32_t *lens;  // nullptr in header mode
-    int hdr;              // 1: ids start at column 1
-    int64_t g0;           // first global sequence (record * n_chunks + chunk) of this micro-batch
-    int S;                // sequences in this micro-batch
-    int L, n_chunks, Lc;
-    int pad_id, arch;
-    int T, Tpad;          // real tokens / padded to 256 (host computed, same arithmetic; SEED: T is an upper bound, the device
-                          // total is seq_off[S])
-    int vt_spare;         // SEED: V^T column the pad rows below T write to (no sequence reads it)
-    int *seq_off, *seq_vtcol, *seq_len;
-    int *tok_id, *tok_pos, *tok_vtcol;
-    int4 *desc;           // attention descriptors (first token, length, V^T column, sequence), longest length bucket first
-    unsigned *faults;     // ance_encoder_range_faults; SEED: [1] counts sequences that are empty or start with the pad id
-};
-
-__device__ __forceinline__ int len_bucket(int eff) {  // ceil(eff / 32) - 1, everything above 96 tokens in bucket 3
-    const int b = (eff + 31) >> 5;
-    return b > 4 ? 3 : b - 1;
-}
-
-// SEED (ANCE_ARCH_SEED): the encoder masks every key whose id is the pad id, inside the record's length too.  Positions skip pad
-// ids already, so dropping those tokens leaves every other token's output unchanged: seq_len[s] = the number of non-pad ids in
-// [0, len), which plan_kernel / pack_kernel then treat as the sequence's length.  One wave per sequence (no MaxP: n_chunks = 1).
-// A record that is empty or starts with the pad id has no defined output in the reference (a pad row or NaN): counted in faults[1].
-__global__ void __launch_bounds__(256) seed_count_kernel(const PlanArgs P) {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (s >= P.S) return;
-    const int64_t rec = P.g0 + s;
-    const int full = record_len(P.base, P.ld, P.lens, rec, P.L);
-    const int32_t *src = P.base + rec * P.ld + P.hdr;
-    int cnt = 0;
-    for (int j0 = 0; j0 < full; j0 += 64) {
-        const int j = j0 + l;
-        cnt += __popcll(__ballot(j < full && src[j] != P.pad_id));
-    }
-    if (l == 0) {
-        P.seq_len[s] = cnt;
-        if (full == 0 || src[0] == P.pad_id) atomicAdd(P.faults + 1, 1u);
-    }
-}
-
-// effective lengths + exclusive scans (token offsets; 8-aligned V^T columns; rank inside the length bucket).  One block.
-__global__ void __launch_bounds__(1024) plan_kernel(const PlanArgs P) {
-    __shared__ int s_tot[1024], s_tot8[1024];
-    __shared__ unsigned long long s_bk[1024];  // four 16-bit bucket counts (a micro-batch has at most 8,192 sequences)
-    const int tid = threadIdx.x;
-    const int per = (P.S + 1023) / 1024;
-    const int b0 = tid * per;
-    int sum = 0, sum8 = 0;
-    unsigned long long bk = 0;
-    for (int j = 0; j < per; ++j) {
-        const int s = b0 + j;
-        if (s < P.S) {
-            int lc;
-            if (P.arch == ANCE_ARCH_SEED) {
-                lc = P.seq_len[s];  // seed_count_kernel
-            } else {
-                const int64_t gs = P.g0 + s;
-                const int64_t rec = gs / P.n_chunks;
-                const int c = (int)(gs - rec * P.n_chunks);
-                const int full = record_len(P.base, P.ld, P.lens, rec, P.L);
-                lc = full - c * P.Lc;
-                lc = lc < 0 ? 0 : (lc > P.Lc ? P.Lc : lc);
-                P.seq_len[s] = lc;
-            }
-            const int eff = lc > 0 ? lc : 1;
-            sum += eff;
-            sum8 += (eff + 7) & ~7;
-            bk += 1ull << (16 * len_bucket(eff));
-        }
-    }
-    s_tot[tid] = sum;
-    s_tot8[tid] = sum8;
-    s_bk[tid] = bk;
-    __syncthreads();
-    // Hillis-Steele inclusive scan over 1024 partials
-    for (int off = 1; off < 1024; off <<= 1) {
-        int a = 0, a8 = 0;
-        unsigned long long ab = 0;
-        if (tid >= off) {
-            a = s_tot[tid - off];
-            a8 = s_tot8[tid - off];
-            ab = s_bk[tid - off];
-        }
-        __syncthreads();
-        s_tot[tid] += a;
-        s_tot8[tid] += a8;
-        s_bk[tid] += ab;
-        __syncthreads();
-    }
-    int run = s_tot[tid] - sum, run8 = s_tot8[tid] - sum8;
-    unsigned long long rbk = s_bk[tid] - bk;  // sequences of each bucket before this thread's
-    // first descriptor of each bucket, longest sequences first, from the totals (SEED's lengths are known on the device only)
-    const unsigned long long tbk = s_bk[1023];
-    for (int j = 0; j < per; ++j) {
-        const int s = b0 + j;
-        if (s < P.S) {
-            const int lc = P.seq_len[s];
-            const int eff = lc > 0 ? lc : 1;
-            P.seq_off[s] = run;
-            P.seq_vtcol[s] = run8;
-            const int b = len_bucket(eff);
-            int bstart = 0;
-            for (int bb = 3; bb > b; --bb) bstart += (int)((tbk >> (16 * bb)) & 0xFFFF);
-            P.desc[bstart + (int)((rbk >> (16 * b)) & 0xFFFF)] = make_int4(run, eff, run8, s);
-            rbk += 1ull << (16 * b);
-            run += eff;
-            run8 += (eff + 7) & ~7;
-        }
-    }
-    if (tid == 1023) P.seq_off[P.S] = s_tot[1023];
-}
-
-// one wave per sequence: packed token ids, position ids, V^T columns
-__global__ void __launch_bounds__(256) pack_kernel(const PlanArgs P) {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (s < P.S) {
-        const int64_t gs = P.g0 + s;
-        const int64_t rec = gs / P.n_chunks;
-        const int c = (int)(gs - rec * P.n_chunks);
-        const int lc = P.seq_len[s];
-        const int t0 = P.seq_off[s], v0 = P.seq_vtcol[s];
-        if (lc == 0) {
-            // all-pad chunk == one pad token attending to itself
-            if (l == 0) {
-                P.tok_id[t0] = P.pad_id;
-                P.tok_pos[t0] = P.arch == ANCE_ARCH_BERT ? 0 : P.pad_id;
-                P.tok_vtcol[t0] = v0;
-            }
-        } else if (P.arch == ANCE_ARCH_SEED) {
-            // the non-pad ids of [0, len) back to back: rank r gets position pad + 1 + r (RoBERTa's rule on the kept tokens)
-            const int32_t *src = P.base + rec * P.ld + P.hdr;
-            const int full = record_len(P.base, P.ld, P.lens, rec, P.L);
-            int before = 0;
-            for (int j0 = 0; j0 < full; j0 += 64) {
-                const int j = j0 + l;
-                const int id = j < full ? src[j] : P.pad_id;
-                const bool keep = j < full && id != P.pad_id;
-                const u64 m = __ballot(keep);
-                const int r = before + __popcll(m & ((1ull << l) - 1ull));
-                if (keep) {
-                    P.tok_id[t0 + r] = id;
-                    P.tok_pos[t0 + r] = P.pad_id + 1 + r;
-                    P.tok_vtcol[t0 + r] = v0 + r;
-                }
-                before += __popcll(m);
-            }
-        } else {
-            const int32_t *src = P.base + rec * P.ld + P.hdr + c * P.Lc;
-            int before = 0;  // non-pad tokens seen so far (RoBERTa position ids)
-            for (int j0 = 0; j0 < lc; j0 += 64) {
-                const int j = j0 + l;
-                const bool in = j < lc;
-                const int id = in ? src[j] : P.pad_id;
-                const bool nonpad = in && id != P.pad_id;
-                const u64 m = __ballot(nonpad);
-                if (in) {
-                    int pos;
-                    if (P.arch == ANCE_ARCH_ROBERTA)
-                        pos = nonpad ? before + __popcll(m & ((2ull << l) - 1ull)) + P.pad_id : P.pad_id;
-                    else
-                        pos = j;
-                    P.tok_id[t0 + j] = id;
-                    P.tok_pos[t0 + j] = pos;
-                    P.tok_vtcol[t0 + j] = v0 + j;
-                }
-                before += __popcll(m);
-            }
-        }
-    }
-    // rows T..Tpad exist only to fill the last GEMM tile.  SEED: from the device total on; the V^T GEMM stores rows below the host's
-    // T, so those write the spare column
-    const bool seed = P.arch == ANCE_ARCH_SEED;
-    const int T = seed ? P.seq_off[P.S] : P.T;
-    const int gt = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gt < P.Tpad - T) {
-        P.tok_id[T + gt] = P.pad_id;
-        P.tok_pos[T + gt] = P.arch == ANCE_ARCH_BERT ? 0 : P.pad_id;
-        P.tok_vtcol[T + gt] = seed ? P.vt_spare : 0;
-    }
-}
-
-// Output of a tower without embeddingHead (DPR's BERT): the last layer's LayerNorm of the [CLS] row, one block per sequence.
-// pre / stats: fp32 rows and their (mean, rstd) (fp32 mode); or hi / lo / ldp: the fp16 pair of the pre-LayerNorm row with the slice
-// partials part -- pair_w = 0: two planes (fp16 mode, lo = fp16(v - hi)); pair_w = W: lo is null and hi points to pair rows of the
-// split mode (common.h: pair_hi_col / pair_lo_col)
-template <int H>
-__global__ void __launch_bounds__(256) head_kernel(const float *pre, const _Float16 *hi, const _Float16 *lo, int ldp, int pair_w,
-                                                   const float *stats, const float *part, float eps, const float *lng, const float *lnb,
-                                                   const int *seq_off, int compact, float *out, unsigned *faults) {
-    const int s = blockIdx.x, tid = threadIdx.x;
-    const size_t row = (size_t)(compact ? s : seq_off[s]);  // compact: row s already is the [CLS] row
-    float mean_h, rstd_h;  // h = LN(pre), recomputed (file header)
-    if (part) stats_from_parts<H>(part + row * PART_FLOATS, eps, &mean_h, &rstd_h);
-    else { mean_h = stats[2 * row]; rstd_h = stats[2 * row + 1]; }
-    float *dst = out + (size_t)s * HEAD_OUT;
-    auto src = [&](int j) {
-        if (!hi) return pre[row * H + j];
-        if (pair_w) return (float)hi[row * ldp + pair_hi_col(j, pair_w)] + (float)hi[row * ldp + pair_lo_col(j, pair_w)] * PAIR_LO_INV;
-        return (float)hi[row * ldp + j] + (float)lo[row * ldp + j];
-    };
-    for (int j = tid; j < H; j += 256) dst[j] = (src(j) - mean_h) * rstd_h * lng[j] + lnb[j];
-    // a NaN anywhere in the row (or an infinity: rstd 0) shows in its statistics: count the row (ance_encoder_range_faults [1])
-    if (tid == 0 && faults && (!(fabsf(mean_h) < INFINITY) || !(rstd_h > 0.f && rstd_h < INFINITY))) atomicAdd(faults + 1, 1u);
-}
-
-// slice statistics of an embedding row (PartFormat): lanes 16 j .. 16 j + 15 hold the (mean, M2) of columns 256 k + 64 j .. + 63.
-// 768: one slice per 16 lanes; 1024: two adjacent 64-column halves merged into one 128-column slice (part_merge)
-template <int H>
-__device__ __forceinline__ void store_embed_part(float *part, int t, int k, int l, float m64, float q64) {
-    if constexpr (H == 1024) {
-        const float mo = __shfl_xor(m64, 16), qo = __shfl_xor(q64, 16);
-        if ((l & 31) == 0) {
-            float m, q;
-            part_merge(m64, q64, mo, qo, &m, &q);
-            *reinterpret_cast<float2 *>(part + (size_t)t * PART_FLOATS + (2 * k + (l >> 5)) * 2) = make_float2(m, q);
-        }
-    } else if ((l & 15) == 0) {
-        float *pp = part + ((size_t)t * 12 + 4 * k + (l >> 4)) * 2;  // (12 slices x 2 = PART_FLOATS)
-        pp[0] = m64;
-        pp[1] = q64;
-    }
-}
-
-// ---- fp16 mode: folded LayerNorm (file header) ------------------------------------------------------
-__device__ __forceinline__ void split_store(const f32x4 v, _Float16 *hi, _Float16 *lo, int c4) {
-    const f16x4 h = cvt_f16x4_pinned(v);
-    const f16x4 r = f16x4{(_Float16)(v[0] - (float)h[0]), (_Float16)(v[1] - (float)h[1]), (_Float16)(v[2] - (float)h[2]),
-                          (_Float16)(v[3] - (float)h[3])};
-    reinterpret_cast<f16x4 *>(hi)[c4] = h;
-    reinterpret_cast<f16x4 *>(lo)[c4] = r;
-}
-__device__ __forceinline__ f32x4 pair_load(const _Float16 *hi, const _Float16 *lo, int c4) {
-    const f16x4 h = reinterpret_cast<const f16x4 *>(hi)[c4], r = reinterpret_cast<const f16x4 *>(lo)[c4];
-    return f32x4{(float)h[0] + (float)r[0], (float)h[1] + (float)r[1], (float)h[2] + (float)r[2], (float)h[3] + (float)r[3]};
-}
-
-// embeddings -> (hi, lo) pair of the pre-LayerNorm row + its slice statistics (the format the RES epilogue leaves: gemm_f16.h,
-// PartFormat); one wave per token, 16 lanes per 64 columns
-template <int H>
-__global__ void __launch_bounds__(256) embed_fold_kernel(const int *tok_id, const int *tok_pos, int Tpad, const float *word,
-                                                         const float *pos, const float *type0, int vocab, int max_pos,
-                                                         _Float16 *hi, _Float16 *lo, float *part) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (t >= Tpad) return;
-    int id = tok_id[t], p = tok_pos[t];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(word + (size_t)id * H);
-    const f32x4 *p4 = reinterpret_cast<const f32x4 *>(pos + (size_t)p * H);
-    const f32x4 *t4 = reinterpret_cast<const f32x4 *>(type0);
-#pragma unroll
-    for (int k = 0; k < H / 256; ++k) {
-        const int c4 = k * 64 + l;  // columns 4 c4 .. 4 c4 + 3
-        const f32x4 v = (w4[c4] + t4[c4]) + p4[c4];  // same association as the reference: (word + type) + pos
-        split_store(v, hi + (size_t)t * H, lo + (size_t)t * H, c4);
-        const float m64 = row16_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
-        const float d0 = v[0] - m64, d1 = v[1] - m64, d2 = v[2] - m64, d3 = v[3] - m64;
-        const float q64 = row16_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-        store_embed_part<H>(part, t, k, l, m64, q64);
-    }
-}
-
-// last layer, CLS-only tail: compact (hi, lo, slice partials) rows of the [CLS] tokens; rows S..S_pad zeroed
-template <int H>
-__global__ void __launch_bounds__(256) gather_cls_fold_kernel(const _Float16 *hi, const _Float16 *lo, const float *part,
-                                                              const int *seq_off, int S, int S_pad, _Float16 *chi, _Float16 *clo,
-                                                              float *cpart) {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (s >= S_pad) return;
-    f16x4 *dh = reinterpret_cast<f16x4 *>(chi + (size_t)s * H), *dl = reinterpret_cast<f16x4 *>(clo + (size_t)s * H);
-    if (s < S) {
-        const size_t row = (size_t)seq_off[s];
-        const f16x4 *sh = reinterpret_cast<const f16x4 *>(hi + row * H), *sl = reinterpret_cast<const f16x4 *>(lo + row * H);
-#pragma unroll
-        for (int k = 0; k < H / 256; ++k) {
-            dh[k * 64 + l] = sh[k * 64 + l];
-            dl[k * 64 + l] = sl[k * 64 + l];
-        }
-        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = part[row * PART_FLOATS + l];
-    } else {
-        const f16x4 z = {0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < H / 256; ++k) {
-            dh[k * 64 + l] = z;
-            dl[k * 64 + l] = z;
-        }
-        // mean 0, variance 1: a finite rstd
-        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = (l & 1) ? (float)PartFormat<H>::COLS : 0.f;
-    }
-}
-
-// weight load with the LayerNorm folded in (K = H columns): W16[n][k] = fp16(gamma[k] W[n][k]),
-// csum[n] = sum_k W16[n][k] (over the ROUNDED values), bout[n] = b[n] + sum_k beta[k] W[n][k].  One wave per row.
-template <int H>
-__global__ void __launch_bounds__(256) fold_weight_kernel(const float *W, const float *b, const float *gamma, const float *beta,
-                                                          int N, _Float16 *W16, float *csum, float *bout) {
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (n >= N) return;
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(W + (size_t)n * H);
-    float cs = 0.f, bs = 0.f;
-#pragma unroll
-    for (int k = 0; k < H / 256; ++k) {
-        const int c4 = k * 64 + l;
-        const f32x4 w = w4[c4], g = reinterpret_cast<const f32x4 *>(gamma)[c4], be = reinterpret_cast<const f32x4 *>(beta)[c4];
-        const f16x4 h = f16x4{(_Float16)(g[0] * w[0]), (_Float16)(g[1] * w[1]), (_Float16)(g[2] * w[2]), (_Float16)(g[3] * w[3])};
-        reinterpret_cast<f16x4 *>(W16 + (size_t)n * H)[c4] = h;
-        cs += ((float)h[0] + (float)h[1]) + ((float)h[2] + (float)h[3]);
-        bs += (be[0] * w[0] + be[1] * w[1]) + (be[2] * w[2] + be[3] * w[3]);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        cs += __shfl_xor(cs, off);
-        bs += __shfl_xor(bs, off);
-    }
-    if (l == 0) {
-        csum[n] = cs;
-        bout[n] = b[n] + bs;
-    }
-}
-
-// ---- split mode ---------------------------------------------------------------------------------
-// (a pair row of an H-wide stream has 2 H halves: common.h, blocked [hi (32) | lo (32)] column blocks)
-
-// embeddings -> pair rows of the pre-LayerNorm stream + the slice statistics (format of EPI_S_RESLN); one wave per token.
-// The row is stored times EMB_SCALE: the lo half of a pair is unscaled (common.h), i.e. good to 2^-25 ABSOLUTE, which is fp32-grade for
-// the O(1) post-residual streams but not for an embedding sum of magnitude 0.05 (trained BERT / RoBERTa checkpoints) that a LayerNorm
-// with rstd ~ 20 then blows up.  A LayerNorm is scale-invariant up to its epsilon: the two consumers of this stream (layer
-// 0's Q | K | V GEMM and the residual of its attention-output GEMM) run with eps EMB_SCALE^2 -- powers of two, so (v s - mean s) and
-// rstd / s are the unscaled values' bits.
-constexpr float EMB_SCALE = 16.0f;
-template <int H>
-__global__ void __launch_bounds__(256) embed_split_kernel(const int *tok_id, const int *tok_pos, int Tpad, const float *word,
-                                                          const float *pos, const float *type0, int vocab, int max_pos,
-                                                          _Float16 *xp, float *part, unsigned *faults) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (t >= Tpad) return;
-    int id = tok_id[t], p = tok_pos[t];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(word + (size_t)id * H);
-    const f32x4 *p4 = reinterpret_cast<const f32x4 *>(pos + (size_t)p * H);
-    const f32x4 *t4 = reinterpret_cast<const f32x4 *>(type0);
-    float mx = 0.f;
-#pragma unroll
-    for (int k = 0; k < H / 256; ++k) {
-        const int c4 = k * 64 + l;
-        const f32x4 v = ((w4[c4] + t4[c4]) + p4[c4]) * EMB_SCALE;  // same association as the reference: (word + type) + pos
-        range_track4(v, &mx);
-        pair_store4(v, xp + (size_t)t * 2 * H, H, c4 * 4);
-        const float m64 = row16_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
-        const float d0 = v[0] - m64, d1 = v[1] - m64, d2 = v[2] - m64, d3 = v[3] - m64;
-        const float q64 = row16_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-        store_embed_part<H>(part, t, k, l, m64, q64);
-    }
-    range_report(mx, faults);
-}
-
-// Per-matrix scale of the split GEMM's weights: s = 2^p with max |g (.) W| s in [2^13, 2^14).  Pair halves are UNSCALED differences
-// (common.h): lo = fp16(w s - hi) of an element below 2^-3 is an fp16 subnormal, good to 2^-25 absolute -- with the largest element
-// at 2^13 that is 2^-38 of it, i.e. nothing (unscaled, a 0.02 weight would keep 19 bits).  wabsmax_kernel leaves max |g (.) W| as
-// float bits (non-negative floats order as integers) with atomicMax; one slot per weight matrix, Q / K / V share one.
-__global__ void __launch_bounds__(256) wabsmax_kernel(const float *W, const float *gamma, int N, int K, unsigned *slot) {
-    const size_t total4 = (size_t)N * K / 4;
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
-        f32x4 w = reinterpret_cast<const f32x4 *>(W)[i];
-        if (gamma) w = w * reinterpret_cast<const f32x4 *>(gamma)[i % (size_t)(K / 4)];
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fmaxf(fabsf(w[2]), fabsf(w[3]))));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if ((threadIdx.x & 63) == 0 && m > 0.f && m < INFINITY) atomicMax(slot, __builtin_bit_cast(unsigned, m));
-}
-__device__ __forceinline__ float weight_pair_scale(const unsigned *slot) {
-    const float m = __builtin_bit_cast(float, *slot);
-    if (!(m > 0.f)) return 1.0f;
-    int e;
-    (void)frexpf(m, &e);  // m in [2^(e-1), 2^e)
-    int p = 14 - e;
-    p = p < -60 ? -60 : (p > 60 ? 60 : p);
-    return ldexpf(1.0f, p);
-}
-
-// weight load for the split GEMM: row n of W [N, K] -> pair row (common.h) of  s (g (.) W)  (g = the LayerNorm weight folded in, or
-// null; s = the matrix's power-of-two scale, its inverse left in *winv for the GEMM epilogue), csum[n] = sum_k (hi + lo) / s
-// (what the MFMAs actually multiply), bout[n] = b[n] + sum_k beta[k] W[n][k].  One wave per row.
-__global__ void __launch_bounds__(256) split_weight_kernel(const float *W, const float *b, const float *gamma, const float *beta,
-                                                           int N, int K, const unsigned *slot, _Float16 *Wp, float *csum, float *bout,
-                                                           float *winv) {
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (n >= N) return;
-    const float sc = weight_pair_scale(slot);
-    if (n == 0 && l == 0) *winv = 1.0f / sc;
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(W + (size_t)n * K);
-    _Float16 *row = Wp + (size_t)n * 2 * K;
-    float cs = 0.f, bs = 0.f;
-    for (int c4 = l; c4 < K / 4; c4 += 64) {
-        f32x4 w = w4[c4];
-        if (gamma) {
-            const f32x4 g = reinterpret_cast<const f32x4 *>(gamma)[c4], be = reinterpret_cast<const f32x4 *>(beta)[c4];
-            bs += (be[0] * w[0] + be[1] * w[1]) + (be[2] * w[2] + be[3] * w[3]);
-            w = w * g;
-        }
-        w = w * sc;
-        pair_store4(w, row, K, c4 * 4);
-        const f32x4 back = pair_load4(row, K, c4 * 4);
-        cs += (back[0] + back[1]) + (back[2] + back[3]);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        cs += __shfl_xor(cs, off);
-        bs += __shfl_xor(bs, off);
-    }
-    if (l == 0) {
-        if (csum) csum[n] = cs * (1.0f / sc);
-        if (bout) bout[n] = b[n] + bs;
-    }
-}
-
-// last layer, CLS-only tail in split mode: compact pair rows + slice partials of the [CLS] tokens; rows S..S_pad zeroed
-template <int H>
-__global__ void __launch_bounds__(256) gather_cls_split_kernel(const _Float16 *xp, const float *part, const int *seq_off, int S,
-                                                               int S_pad, _Float16 *cxp, float *cpart) {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (s >= S_pad) return;
-    constexpr int HP = 2 * H;
-    f16x8 *d = reinterpret_cast<f16x8 *>(cxp + (size_t)s * HP);
-    if (s < S) {
-        const size_t row = (size_t)seq_off[s];
-        const f16x8 *sp = reinterpret_cast<const f16x8 *>(xp + row * HP);
-#pragma unroll
-        for (int k = 0; k < H / 256; ++k) d[k * 64 + l] = sp[k * 64 + l];
-        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = part[row * PART_FLOATS + l];
-    } else {
-        const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < H / 256; ++k) d[k * 64 + l] = z;
-        // mean 0, variance 1: a finite rstd
-        if (l < PART_FLOATS) cpart[(size_t)s * PART_FLOATS + l] = (l & 1) ? (float)PartFormat<H>::COLS : 0.f;
-    }
-}
-
-// ---- embeddingHead as one fp32 MFMA GEMM over the [CLS] rows (model/models.py:145-152) ----------
-// z[s][n] = sum_k LN(cls_s)[k] W[n][k] + b[n]; 32 sequences x 128 features per workgroup, one 32 x 32 tile per wave
-// (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation in k order).  The 32 normalised [CLS] rows are staged
-// once in LDS (96.5 KiB at H = 768, 128.5 KiB at 1024); W rows stream from L2 as 16-byte pieces per lane.  A block per sequence
-// re-read the whole 2.36 MB W (2 GB of L2 reads per 883 rows, 166 us); this reads it 28 times.
-template <int H>
-constexpr int HEAD_LDA = H + 4;  // floats; 16 lanes x stride 4 banks: conflict-free ds_read_b128
-template <int H>
-constexpr size_t HEAD_LDS_BYTES = (size_t)32 * HEAD_LDA<H> * sizeof(float);
-static_assert(HEAD_LDS_BYTES<1024> <= 160 * 1024, "head GEMM LDS at hidden 1024");
-
-template <int H>
-__global__ void __launch_bounds__(256) head_gemm_kernel(const float *pre32, const _Float16 *hi, const _Float16 *lo, int ldp,
-                                                        int pair_w, const float *stats, const float *part, float eps, const float *lng,
-                                                        const float *lnb, const int *seq_off, int compact, int S, const float *W,
-                                                        const float *b, float *out) {
-    extern __shared__ __attribute__((aligned(16))) float cls[];
-    const int s0 = blockIdx.x * 32, n0 = blockIdx.y * 128;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 5, i = l & 31;
-    // stage LN(pre)[cls] of 32 sequences: wave w takes rows w, w + 4, ...
-    for (int r = w; r < 32; r += 4) {
-        const int s = s0 + r;
-        f32x4 *dst = reinterpret_cast<f32x4 *>(cls + r * HEAD_LDA<H>);
-        if (s < S) {
-            const size_t row = (size_t)(compact ? s : seq_off[s]);
-            float mean, rstd;
-            if (part) stats_from_parts<H>(part + row * PART_FLOATS, eps, &mean, &rstd);  // (every lane: 24 cached floats)
-            else { mean = stats[2 * row]; rstd = stats[2 * row + 1]; }
-#pragma unroll
-            for (int k = 0; k < H / 256; ++k) {
-                const int c4 = k * 64 + l;
-                const f32x4 x = !hi      ? reinterpret_cast<const f32x4 *>(pre32 + row * H)[c4]
-                                : pair_w ? pair_load4(hi + row * ldp, pair_w, c4 * 4)   // split mode: pair rows (see head_kernel)
-                                         : pair_load(hi + row * ldp, lo + row * ldp, c4);
-                dst[c4] = ln_apply4(x, mean, rstd, reinterpret_cast<const f32x4 *>(lng)[c4],
-                                    reinterpret_cast<const f32x4 *>(lnb)[c4]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < H / 256; ++k) dst[k * 64 + l] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-    __syncthreads();
-    // MFMA rows (A operand) = sequences, columns (B operand) = features n0 + 32 w + i; k-step j of a 16-byte piece uses
-    // k = 8 s' + 4 g + j on both sides
-    const float *ap = cls + i * HEAD_LDA<H> + 4 * g;
-    const float *wp = W + (size_t)(n0 + 32 * w + i) * H + 4 * g;
-    f32x16 acc = {0};
-#pragma unroll 4
-    for (int kk = 0; kk < H / 8; ++kk) {
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(ap + kk * 8);
-        const f32x4 bb = *reinterpret_cast<const f32x4 *>(wp + kk * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], bb[j], acc, 0, 0, 0);
-    }
-    // acc[r]: sequence s0 + (r & 3) + 8 (r >> 2) + 4 g, feature n0 + 32 w + i
-    const int n = n0 + 32 * w + i;
-    const float bias = b[n];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int s = s0 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (s < S) out[(size_t)s * HEAD_OUT + n] = acc[r] + bias;
-    }
-}
-
-// final LayerNorm (model/models.py:146,152 "norm") of the head output, in place; one wave per sequence
-// (a NaN anywhere upstream of a row -- or an infinity -- shows in these statistics: such rows are counted in faults[1])
-__global__ void __launch_bounds__(256) head_ln_kernel(float *out, int S, const float *gamma, const float *beta, unsigned *faults) {
-    const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int l = threadIdx.x & 63;
-    if (s >= S) return;
-    f32x4 *z4 = reinterpret_cast<f32x4 *>(out + (size_t)s * HEAD_OUT);
-    f32x4 v[3];
-    float sm = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        v[k] = z4[k * 64 + l];
-        sm += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off);
-    const float mean = sm * (1.0f / HEAD_OUT);
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float a = v[k][j] - mean;
-            q += a * a;
-        }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
-    const float rstd = rsqrtf(q * (1.0f / HEAD_OUT) + 1e-5f);
-    if (l == 0 && faults && (!(fabsf(mean) < INFINITY) || !(rstd > 0.f && rstd < INFINITY))) atomicAdd(faults + 1, 1u);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int c4 = k * 64 + l;
-        z4[c4] = ln_apply4(v[k], mean, rstd, reinterpret_cast<const f32x4 *>(gamma)[c4], reinterpret_cast<const f32x4 *>(beta)[c4]);
-    }
-}
 
 // ------------------------------------------------------------------------------- host layout --
 
@@ -714,16 +143,29 @@ struct AnceEncoder {
     unsigned *faults;  // device: [0] out-of-range stores of the split mode, [1] NaN output rows
     struct Lane {
         int *seq_off, *seq_vtcol, *seq_len, *tok_id, *tok_pos, *tok_vtcol;
-        float *preA, *preB;      // pre-LayerNorm rows: attention block output / FFN block output (or embeddings)
-        float *statsA, *statsB;  // (mean, rstd) per row of preA / preB (fp32 path: statsB of the last layer)
-        _Float16 *h16;           // (read by no mode: kept so that the workspace layout does not change)
-        _Float16 *qk16, *vt16, *ctx16, *ffn16;
-        int4 *desc;              // attention descriptors in length-bucket order
-        float *x32, *xa32, *qkv32, *ctx32, *ffn32;  // fp32 path only: hidden states, Q|K|V, attention output, FFN activation
-        float *partA, *partB;    // folded LayerNorm: slice statistics of every row of the two streams (gemm_f16.h: PartFormat)
-        // fp16 / split paths: preA / preB hold the fp16 pairs of the stream instead of fp32 rows
-        _Float16 *xa_hi() const { return reinterpret_cast<_Float16 *>(preA); }
-        _Float16 *xb_hi() const { return reinterpret_cast<_Float16 *>(preB); }
+        int4 *desc;  // attention descriptors in length-bucket order
+        // The activation buffers as each mode's forward sees them (layout_workspace: three views of the same bytes).  xa / xb: the
+        // two pre-LayerNorm streams -- attention block output / FFN block output (or embeddings) -- as Rows of the mode's form.
+        // cls(S_pad): the scratch of the CLS-only tail -- S_pad compact [CLS] rows and their partials, at the start of the FFN
+        // activation buffer (dead until FFN1 of the last layer, which runs after the scratch's last reader).
+        struct Fp16 {
+            Rows<FORM_PLANES> xa, xb;
+            _Float16 *qk, *vt, *ctx, *ffn;  // Q | K, V^T, attention output, FFN activation
+            Rows<FORM_PLANES> cls(int S_pad, int H) const {
+                _Float16 *const lo = ffn + (size_t)S_pad * H;
+                return {ffn, lo, reinterpret_cast<float *>(lo + (size_t)S_pad * H)};
+            }
+        } f16;
+        struct Split {
+            Rows<FORM_PAIR> xa, xb;
+            float *qkv;           // fp32 Q | K | V
+            _Float16 *ctx, *ffn;  // pair rows of the attention output / FFN activation
+            Rows<FORM_PAIR> cls(int S_pad, int H) const { return {ffn, reinterpret_cast<float *>(ffn + (size_t)S_pad * 2 * H)}; }
+        } sp;
+        struct Fp32 {
+            Rows<FORM_F32> xa, xb;  // (stats: xb's, of the last layer)
+            float *h, *ha, *qkv, *ctx, *ffn;  // hidden states LN(xb) / LN(xa), Q | K | V, attention output, FFN activation
+        } f32;
     } lane[MAX_LANES];
     int n_lanes;
     hipStream_t side[MAX_LANES];
@@ -813,39 +255,35 @@ void layout_workspace(const AnceEncoderDesc *d, Arena &a, AnceEncoder *e) {
     const int scap = tcap < S_CAP_MAX ? tcap : S_CAP_MAX;
     const int vcap = (int)align_up((size_t)tcap + tcap / 4 + 256, 256);
     const int mode = resolve_precision(d);
-    const int H = d->hidden;
+    const size_t H = d->hidden, I = d->intermediate;
     unsigned *faults = a.take<unsigned>(64);  // [0] out-of-range stores of the split mode, [1] NaN output rows (ance_encoder_range_faults)
     int *lens_fetch = a.take<int>(FETCH_CHUNK);
-    if (e) {
-        e->tcap = tcap; e->scap = scap; e->vcap = vcap; e->lens_fetch = lens_fetch; e->faults = faults;
-    }
+    if (e) { e->tcap = tcap; e->scap = scap; e->vcap = vcap; e->lens_fetch = lens_fetch; e->faults = faults; }
+    // an fp16 pair -- two planes or a pair row -- is as many bytes as the fp32 row: such buffers are taken as fp32 rows
+    auto halves = [](float *p) { return reinterpret_cast<_Float16 *>(p); };
     for (int ln = 0; ln < MAX_LANES; ++ln) {
         AnceEncoder::Lane L;
         L.seq_off = a.take<int>(scap + 1); L.seq_vtcol = a.take<int>(scap); L.seq_len = a.take<int>(scap);
         L.tok_id = a.take<int>(tcap); L.tok_pos = a.take<int>(tcap); L.tok_vtcol = a.take<int>(tcap);
         L.desc = a.take<int4>(scap);
-        L.preB = a.take<float>((size_t)tcap * H); L.preA = a.take<float>((size_t)tcap * H);
-        L.statsA = a.take<float>((size_t)tcap * 2); L.statsB = a.take<float>((size_t)tcap * 2);
-        L.h16 = a.take<_Float16>((size_t)tcap * H);
-        L.qk16 = a.take<_Float16>((size_t)tcap * 2 * H);
-        L.vt16 = a.take<_Float16>((size_t)H * vcap);
-        L.ctx16 = a.take<_Float16>((size_t)tcap * H);
-        L.ffn16 = a.take<_Float16>((size_t)tcap * d->intermediate);
-        L.partA = a.take<float>((size_t)tcap * PART_FLOATS);
-        L.partB = a.take<float>((size_t)tcap * PART_FLOATS);
-        L.x32 = L.xa32 = L.qkv32 = L.ctx32 = L.ffn32 = nullptr;
-        if (mode == ANCE_PRECISION_FP32) {
-            L.x32 = a.take<float>((size_t)tcap * H);
-            L.xa32 = a.take<float>((size_t)tcap * H);
-        }
-        if (mode == ANCE_PRECISION_FP32 || mode == ANCE_PRECISION_SPLIT) {
-            // split mode: qkv32 = fp32 Q | K | V; ctx32 / ffn32 hold the PAIR rows of the attention output / FFN activation
-            // (an fp16 pair row is as many bytes as the fp32 row)
-            L.qkv32 = a.take<float>((size_t)tcap * 3 * H);
-            L.ctx32 = a.take<float>((size_t)tcap * H);
-            L.ffn32 = a.take<float>((size_t)tcap * d->intermediate);
-        }
-        if (e) e->lane[ln] = L;
+        float *const preB = a.take<float>(tcap * H), *const preA = a.take<float>(tcap * H);
+        float *const statsA = a.take<float>((size_t)tcap * 2), *const statsB = a.take<float>((size_t)tcap * 2);
+        (void)a.take<_Float16>(tcap * H);  // (read by no mode: kept so that the workspace layout does not change)
+        _Float16 *const qk16 = a.take<_Float16>(tcap * 2 * H);
+        _Float16 *const vt16 = a.take<_Float16>(H * vcap);
+        _Float16 *const ctx16 = a.take<_Float16>(tcap * H);
+        _Float16 *const ffn16 = a.take<_Float16>(tcap * I);
+        float *const partA = a.take<float>((size_t)tcap * PART_FLOATS), *const partB = a.take<float>((size_t)tcap * PART_FLOATS);
+        const bool f32 = mode == ANCE_PRECISION_FP32, wide = f32 || mode == ANCE_PRECISION_SPLIT;  // (fp32 rows or pair rows)
+        float *const h32 = f32 ? a.take<float>(tcap * H) : nullptr, *const ha32 = f32 ? a.take<float>(tcap * H) : nullptr;
+        float *const qkv32 = wide ? a.take<float>(tcap * 3 * H) : nullptr, *const ctx32 = wide ? a.take<float>(tcap * H) : nullptr;
+        float *const ffn32 = wide ? a.take<float>(tcap * I) : nullptr;
+        if (!e) continue;  // (a size query)
+        // fp16 mode: the two planes of a stream share the fp32 row's bytes, hi first
+        L.f16 = {{halves(preA), halves(preA) + tcap * H, partA}, {halves(preB), halves(preB) + tcap * H, partB}, qk16, vt16, ctx16, ffn16};
+        L.sp = {{halves(preA), partA}, {halves(preB), partB}, qkv32, halves(ctx32), halves(ffn32)};
+        L.f32 = {{preA, statsA}, {preB, statsB}, h32, ha32, qkv32, ctx32, ffn32};
+        e->lane[ln] = L;
     }
 }
 
@@ -858,313 +296,295 @@ void cpy32(const void *src, float *dst, size_t n, hipStream_t st) {
     (void)hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
 }
 
-// Geometry of one micro-batch (encode_impl plans it; the forwards run it on one lane and one stream).
-struct MicroBatch {
-    int S, T;       // sequences, real tokens
-    int Tpad;       // tokens padded to the GEMM tile (256)
-    int ldvt;       // row stride of V^T (fp16 mode)
-    int maxlen;     // longest sequence
-    float *out;     // [S, HEAD_OUT] rows of the output
-};
-
-// The output of the encoder from the last layer's LayerNorm of the [CLS] rows: the embeddingHead as one MFMA GEMM + its
-// LayerNorm (has_head), or those rows as they are (DPR's BERT).  pre / stats: fp32 rows and their (mean, rstd); hi / lo / ldp /
-// pair_w / part: the fp16 pair form (head_kernel); compact: row s already is the [CLS] row of sequence s.
-template <int H>
-void encoder_output(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb, const float *pre,
-                    const _Float16 *hi, const _Float16 *lo, int ldp, int pair_w, const float *stats, const float *part, int compact) {
+// The output of the encoder from the last layer's LayerNorm of the [CLS] rows of the stream `pre`: the embeddingHead as one MFMA
+// GEMM + its LayerNorm (has_head), or those rows as they are (DPR's BERT).  compact: row s already is the [CLS] row of sequence s.
+template <int H, int FORM>
+void encoder_output(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroPlan &mb, float *out,
+                    const Rows<FORM> &pre, int compact) {
     const AnceEncoderDesc &D = e->d;
     const LayerW &WL = e->layers[D.n_layers - 1];
     ProfScope ps(PC_HEAD, st);
     if (D.has_head) {
-        hipLaunchKernelGGL(head_gemm_kernel<H>, dim3((mb.S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES<H>, st, pre, hi, lo, ldp,
-                           pair_w, stats, part, D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off, compact, mb.S, e->head_w, e->head_b, mb.out);
-        hipLaunchKernelGGL(head_ln_kernel, dim3((mb.S + 3) / 4), dim3(256), 0, st, mb.out, mb.S, e->norm_w, e->norm_b, e->faults);
+        hipLaunchKernelGGL((head_gemm_kernel<H, FORM>), dim3((mb.S + 31) / 32, HEAD_OUT / 128), dim3(256), HEAD_LDS_BYTES<H>, st, pre,
+                           D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off, compact, mb.S, e->head_w, e->head_b, out);
+        hipLaunchKernelGGL(head_ln_kernel, dim3((mb.S + 3) / 4), dim3(256), 0, st, out, mb.S, e->norm_w, e->norm_b, e->faults);
     } else {
-        hipLaunchKernelGGL(head_kernel<H>, dim3(mb.S), dim3(256), 0, st, pre, hi, lo, ldp, pair_w, stats, part, D.ln_eps, WL.ln2w, WL.ln2b,
-                           LN.seq_off, compact, mb.out, e->faults);
+        hipLaunchKernelGGL((head_kernel<H, FORM>), dim3(mb.S), dim3(256), 0, st, pre, D.ln_eps, WL.ln2w, WL.ln2b, LN.seq_off, compact,
+                           out, e->faults);
     }
 }
 
 // ---- fp32 mode (precise32.h): plain sequence of fp32 kernels, every layer on every token ----
 template <int H>
-int forward_fp32(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
+int forward_fp32(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroPlan &mb, float *out) {
     const AnceEncoderDesc &D = e->d;
+    const AnceEncoder::Lane::Fp32 &V = LN.f32;
     const int I = D.intermediate, T = mb.T, Tpad = mb.Tpad;
+    float *const no_stats = nullptr;
     {
         ProfScope pe(PC_EMBED, st);
         hipLaunchKernelGGL(embed32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
-                           e->type0, D.vocab_size, D.max_position, LN.preB);
-        hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, e->eln_w, e->eln_b, D.ln_eps,
-                           LN.x32, (float *)nullptr);
+                           e->type0, D.vocab_size, D.max_position, V.xb.x);
+        hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, V.xb.x, Tpad, e->eln_w, e->eln_b, D.ln_eps, V.h, no_stats);
     }
-    int rc = ANCE_OK;
-    for (int li = 0; li < D.n_layers && !rc; ++li) {
+    for (int li = 0; li < D.n_layers; ++li) {
         const LayerW &W = e->layers[li];
         const bool last = li == D.n_layers - 1;
-        {
-            ProfScope ps(PC_GEMM_QK, st, 2.0 * T * (3.0 * H) * H);
-            rc = launch_gemm32(P_EPI_BIAS, LN.x32, H, W.wqkv32, H, W.bqkv32, nullptr, 0, LN.qkv32, 3 * H, Tpad, 3 * H, H, st);
-        }
-        if (rc) break;
-        {
-            ProfScope ps(PC_ATTN, st);
-            rc = launch_attention32(LN.qkv32, LN.ctx32, LN.seq_off, mb.S, D.n_heads, st);
-        }
-        if (rc) break;
-        {
-            ProfScope ps(PC_GEMM_OUT, st, 2.0 * T * (double)H * H);
-            rc = launch_gemm32(P_EPI_RES, LN.ctx32, H, W.wo32, H, W.bo, LN.x32, H, LN.preA, H, Tpad, H, H, st);
-        }
-        if (rc) break;
+        if (ProfScope ps(PC_GEMM_QK, st, 2.0 * T * (3.0 * H) * H);
+            int rc = launch_gemm32(P_EPI_BIAS, V.h, H, W.wqkv32, H, W.bqkv32, nullptr, 0, V.qkv, 3 * H, Tpad, 3 * H, H, st))
+            return rc;
+        if (ProfScope ps(PC_ATTN, st); int rc = launch_attention32(V.qkv, V.ctx, LN.seq_off, mb.S, D.n_heads, st)) return rc;
+        if (ProfScope ps(PC_GEMM_OUT, st, 2.0 * T * (double)H * H);
+            int rc = launch_gemm32(P_EPI_RES, V.ctx, H, W.wo32, H, W.bo, V.h, H, V.xa.x, H, Tpad, H, H, st))
+            return rc;
         {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.preA, Tpad, W.ln1w, W.ln1b, D.ln_eps, LN.xa32,
-                               (float *)nullptr);
+            hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, V.xa.x, Tpad, W.ln1w, W.ln1b, D.ln_eps, V.ha, no_stats);
         }
-        {
-            ProfScope ps(PC_GEMM_FFN1, st, 2.0 * T * (double)I * H);
-            rc = launch_gemm32(P_EPI_GELU, LN.xa32, H, W.w132, H, W.b1, nullptr, 0, LN.ffn32, I, Tpad, I, H, st);
-        }
-        if (rc) break;
-        {
-            ProfScope ps(PC_GEMM_FFN2, st, 2.0 * T * (double)I * H);
-            rc = launch_gemm32(P_EPI_RES, LN.ffn32, I, W.w232, I, W.b2, LN.xa32, H, LN.preB, H, Tpad, H, I, st);
-        }
-        if (rc) break;
+        if (ProfScope ps(PC_GEMM_FFN1, st, 2.0 * T * (double)I * H);
+            int rc = launch_gemm32(P_EPI_GELU, V.ha, H, W.w132, H, W.b1, nullptr, 0, V.ffn, I, Tpad, I, H, st))
+            return rc;
+        if (ProfScope ps(PC_GEMM_FFN2, st, 2.0 * T * (double)I * H);
+            int rc = launch_gemm32(P_EPI_RES, V.ffn, I, W.w232, I, W.b2, V.ha, H, V.xb.x, H, Tpad, H, I, st))
+            return rc;
         {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.preB, Tpad, W.ln2w, W.ln2b, D.ln_eps, LN.x32,
-                               last ? LN.statsB : (float *)nullptr);
+            hipLaunchKernelGGL(ln32_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, V.xb.x, Tpad, W.ln2w, W.ln2b, D.ln_eps, V.h,
+                               last ? V.xb.stats : no_stats);
         }
     }
-    if (rc) return rc;
-    encoder_output<H>(e, LN, st, mb, LN.preB, nullptr, nullptr, H, 0, LN.statsB, nullptr, 0);
+    encoder_output<H>(e, LN, st, mb, out, V.xb, 0);
     return ANCE_OK;
+}
+
+// ---- GemmArgs of the folded forwards' GEMM roles (gemm_f16.h; a field that is not named stays zero) ----
+// One constructor per role, for both stream forms: planes (fp16 mode; operand rows of K halves) or pair rows (split mode; operand rows
+// of 2 K halves, the weight's scale wscale_inv and the range guard).  Which fields each epilogue reads: tests/test_gpu_gemm_fold.py,
+// ance_debug_gemm_hw.
+
+// Folded projection (EPI_QK_F / EPI_GELU_F; EPI_S_QKV / EPI_S_GELU): M rows of the pre-LayerNorm stream x as the token operand, the
+// LayerNorm finished in the epilogue from x's partials; B [N, H]: weight rows with gamma folded in, bias and csum per row of B.
+template <int H, int FORM>
+GemmArgs folded_args(const Rows<FORM> &x, int M, float eps, const _Float16 *B, int N, const float *bias, const float *csum,
+                     const float *wscale_inv = nullptr, unsigned *faults = nullptr) {
+    constexpr int ld = FORM == FORM_PAIR ? 2 * H : H;
+    GemmArgs G = {};
+    if constexpr (FORM == FORM_PAIR) G.A = x.xp;
+    else { G.A = x.hi; G.tok_lo = x.lo; }
+    G.lda = ld; G.B = B; G.ldb = ld; G.M = M; G.N = N; G.K = H;
+    G.bias = bias; G.csum = csum; G.part_in = x.part; G.ln_eps = eps; G.wscale_inv = wscale_inv; G.range_faults = faults;
+    return G;
+}
+
+// Columns [c0, c0 + n) of the Q | K projection (fp16 mode; Q = the first H columns, pre-scaled by 1/sqrt(64) and log2(e): the softmax
+// runs on exp2) or of the Q | K | V projection (split mode, fp32 out).  The CLS-only tail asks for the K (| V) columns of every token
+// and for the Q columns of the compact [CLS] rows; every element is the same arithmetic as in the one full launch.
+template <int H>
+GemmArgs qk_args(const Rows<FORM_PLANES> &x, int M, float eps, const LayerW &W, int c0, int n, _Float16 *qk) {
+    GemmArgs G = folded_args<H>(x, M, eps, W.wqk + (size_t)c0 * H, n, W.bqk + c0, W.cqk + c0);
+    G.out16 = qk + c0; G.ldc = 2 * H;
+    G.scale = 0.125f * 1.44269504088896340736f; G.scale_cols = c0 == 0 ? H : 0;
+    return G;
+}
+template <int H>
+GemmArgs qkv_args(const Rows<FORM_PAIR> &x, int M, float eps, const LayerW &W, int c0, int n, float *qkv, unsigned *faults) {
+    GemmArgs G = folded_args<H>(x, M, eps, W.wqkv_s + (size_t)c0 * 2 * H, n, W.bqkv_s + c0, W.cqkv_s + c0, W.sc_s + 4, faults);
+    G.out32 = qkv + c0; G.ldc = 3 * H;
+    return G;
+}
+
+// V^T = Wv LN(x)^T (fp16 mode, EPI_VT_F): the weight is the A operand, the Tpad token rows the B operand; token n < T goes to column
+// col_map[n] of vt (row stride ldvt)
+template <int H>
+GemmArgs vt_args(const Rows<FORM_PLANES> &x, int Tpad, int T, float eps, const LayerW &W, _Float16 *vt, int ldvt, const int *col_map) {
+    GemmArgs G = {};
+    G.A = W.wv; G.lda = H; G.B = x.hi; G.tok_lo = x.lo; G.ldb = H; G.M = H; G.N = Tpad; G.K = H;
+    G.bias = W.bv; G.csum = W.cv; G.part_in = x.part; G.ln_eps = eps;
+    G.out16 = vt; G.ldc = ldvt; G.col_map = col_map; G.n_valid = T;
+    return G;
+}
+
+// FFN1: intermediate.dense + GELU of LN(xa) (attention.output.LayerNorm folded in); n_split: gemm256_f16.hip, tile_of_block
+template <int H, int FORM>
+GemmArgs ffn1_args(const Rows<FORM> &xa, int M, float eps, const LayerW &W, int I, _Float16 *ffn, int n_split, unsigned *faults) {
+    constexpr bool P = FORM == FORM_PAIR;
+    GemmArgs G = folded_args<H>(xa, M, eps, P ? W.w1_s : W.w1, I, P ? W.b1_s : W.b1, P ? W.c1_s : W.c1, P ? W.sc_s + 6 : nullptr, faults);
+    G.out16 = ffn; G.ldc = P ? 2 * I : I; G.n_split = n_split;
+    return G;
+}
+
+// Residual + LayerNorm (EPI_RESLN / EPI_S_RESLN), the role of attention.output.dense (K = H) and of FFN2, output.dense (K = I):
+// out = A B^T + bias + LN(res), M rows; gamma / beta: the LayerNorm whose input the stream res is, finished from res's partials;
+// out: rows + partials of the new stream
+template <int H, int FORM>
+GemmArgs resln_args(const _Float16 *A, const _Float16 *B, int K, const float *bias, int M, const Rows<FORM> &res, const float *gamma,
+                    const float *beta, float eps, const Rows<FORM> &out, const float *wscale_inv, unsigned *faults) {
+    constexpr int w = FORM == FORM_PAIR ? 2 : 1;  // halves per element of a row
+    GemmArgs G = {};
+    G.A = A; G.lda = w * K; G.B = B; G.ldb = w * K; G.M = M; G.N = H; G.K = K; G.bias = bias; G.ldc = w * H;
+    G.res_gamma = gamma; G.res_beta = beta; G.part_in = res.part; G.ln_eps = eps; G.part_out = out.part;
+    G.wscale_inv = wscale_inv; G.range_faults = faults;
+    if constexpr (FORM == FORM_PAIR) { G.res_hi = res.xp; G.ldr = 2 * H; G.out16 = out.xp; }
+    else { G.res_hi = res.hi; G.res_lo = res.lo; G.out16 = out.hi; G.out_lo = out.lo; }
+    return G;
 }
 
 // ---- split (fp32-grade) mode: the fp16 mode's schedule with pair operands and the fp32 attention ----
 template <int H>
-int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
+int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroPlan &mb, float *out) {
     constexpr int HP = 2 * H;
     const AnceEncoderDesc &D = e->d;
+    const AnceEncoder::Lane::Split &V = LN.sp;
     const int I = D.intermediate, S = mb.S, T = mb.T, Tpad = mb.Tpad;
-    _Float16 *const xa = reinterpret_cast<_Float16 *>(LN.preA), *const xb = reinterpret_cast<_Float16 *>(LN.preB);
-    _Float16 *const ctxp = reinterpret_cast<_Float16 *>(LN.ctx32), *const ffnp = reinterpret_cast<_Float16 *>(LN.ffn32);
     {
         ProfScope pe(PC_EMBED, st);
-        hipLaunchKernelGGL(embed_split_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word,
-                           e->pos, e->type0, D.vocab_size, D.max_position, xb, LN.partB, e->faults);
+        hipLaunchKernelGGL((embed_kernel<H, FORM_PAIR>), dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word,
+                           e->pos, e->type0, D.vocab_size, D.max_position, V.xb, e->faults);
     }
     const bool cls_tail = e->cls_tail;
     const int S_pad = (int)align_up((size_t)S, 256);
+    const Rows<FORM_PAIR> cls = V.cls(S_pad, H);
     const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_f16.hip: tile_of_block)
-    int rc = ANCE_OK;
-    for (int li = 0; li < D.n_layers && !rc; ++li) {
+    for (int li = 0; li < D.n_layers; ++li) {
         const LayerW &W = e->layers[li];
         const bool tail = cls_tail && li == D.n_layers - 1;
         const int Mrows = tail ? S_pad : Tpad;
         const double Mwork = tail ? (double)S : (double)T;
-        // layer 0 reads the embedding stream, stored times EMB_SCALE: its LayerNorm runs with eps EMB_SCALE^2 (embed_split_kernel)
+        // layer 0 reads the embedding stream, stored times EMB_SCALE: its LayerNorm runs with eps EMB_SCALE^2 (embed_kernel)
         const float eps_b = li == 0 ? D.ln_eps * (EMB_SCALE * EMB_SCALE) : D.ln_eps;
-        GemmArgs G;
-        memset(&G, 0, sizeof(G));
-        // Q | K | V projection -> fp32 (the LayerNorm that produces this layer's input is folded in)
-        G.A = xb; G.lda = HP; G.B = W.wqkv_s; G.ldb = HP; G.M = Tpad; G.N = 3 * H; G.K = H;
-        G.bias = W.bqkv_s; G.csum = W.cqkv_s; G.part_in = LN.partB; G.ln_eps = eps_b;
-        G.out32 = LN.qkv32; G.ldc = 3 * H; G.wscale_inv = W.sc_s + 4; G.range_faults = e->faults;
+        // the LayerNorm of x_b, the previous layer's output (or the embeddings)
+        const float *const gamma_b = li == 0 ? e->eln_w : e->layers[li - 1].ln2w, *const beta_b = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
         // CLS-only tail: the last layer's attention has ONE query per sequence.  K | V of every token, but Q of the [CLS]
         // rows only: their pair rows and slice partials are compacted first (they are also the residual of the
         // attention-output GEMM below) and projected by a second, small launch into the Q columns of rows 0 .. S_pad of
-        // qkv32 -- row s = the query of sequence s (attention_split_kernel, cls_only).  A third of this GEMM's work in one
-        // layer of twelve; every element is the same arithmetic as in the full launch.
-        float *const cpt = reinterpret_cast<float *>(ffnp + (size_t)S_pad * HP);  // (the FFN buffer is dead here)
+        // qkv -- row s = the query of sequence s (attention_split_kernel, cls_only).  A third of this GEMM's work in one
+        // layer of twelve.
         if (tail) {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(gather_cls_split_kernel<H>, dim3(S_pad / 4), dim3(256), 0, st, xb, LN.partB, LN.seq_off, S, S_pad,
-                               ffnp, cpt);
+            hipLaunchKernelGGL((gather_cls_kernel<H, FORM_PAIR>), dim3(S_pad / 4), dim3(256), 0, st, V.xb, LN.seq_off, S, S_pad, cls);
         }
+        // Q | K | V projection -> fp32 (the LayerNorm that produces this layer's input is folded in)
         {
             ProfScope ps(PC_GEMM_QK, st, tail ? 2.0 * T * (2.0 * H) * H + 2.0 * S * (double)H * H : 2.0 * T * (3.0 * H) * H);
-            if (tail) {
-                G.B = W.wqkv_s + (size_t)H * HP; G.N = 2 * H; G.bias = W.bqkv_s + H; G.csum = W.cqkv_s + H;
-                G.out32 = LN.qkv32 + H;
-                rc = launch_gemm_f16(EPI_S_QKV, G, st, H);
-                G.A = ffnp; G.part_in = cpt; G.M = S_pad;
-                G.B = W.wqkv_s; G.N = H; G.bias = W.bqkv_s; G.csum = W.cqkv_s; G.out32 = LN.qkv32;
-                if (!rc) rc = launch_gemm_f16(EPI_S_QKV, G, st, H);
-            } else {
-                rc = launch_gemm_f16(EPI_S_QKV, G, st, H);
-            }
+            const int c0 = tail ? H : 0;  // (tail: K | V here, Q of the compact rows by the second launch)
+            int rc = launch_gemm_f16(EPI_S_QKV, qkv_args<H>(V.xb, Tpad, eps_b, W, c0, 3 * H - c0, V.qkv, e->faults), st, H);
+            if (tail && !rc) rc = launch_gemm_f16(EPI_S_QKV, qkv_args<H>(cls, S_pad, eps_b, W, 0, H, V.qkv, e->faults), st, H);
+            if (rc) return rc;
         }
-        if (rc) break;
         {
             ProfScope ps(PC_ATTN, st);
             if (tail && S_pad > S)  // rows S..S_pad of the compact attention output feed the GEMM tile: keep them finite
-                (void)hipMemsetAsync(ctxp + (size_t)S * HP, 0, (size_t)(S_pad - S) * HP * sizeof(_Float16), st);
+                (void)hipMemsetAsync(V.ctx + (size_t)S * HP, 0, (size_t)(S_pad - S) * HP * sizeof(_Float16), st);
             // (cls_only: one query per sequence, read from row s of the Q columns -- the tail's compact Q projection above)
-            rc = launch_attention_split(LN.qkv32, ctxp, LN.desc, S, D.n_heads, mb.maxlen, tail ? 1 : 0, st);
+            if (int rc = launch_attention_split(V.qkv, V.ctx, LN.desc, S, D.n_heads, mb.maxlen, tail ? 1 : 0, st)) return rc;
         }
-        if (rc) break;
-        // attention.output.dense + residual LayerNorm(x_b), x_b = the previous layer's output (or the embeddings)
-        memset(&G, 0, sizeof(G));
-        G.res_gamma = li == 0 ? e->eln_w : e->layers[li - 1].ln2w;
-        G.res_beta = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
-        G.res_hi = xb; G.ldr = HP; G.part_in = LN.partB; G.ln_eps = eps_b; G.range_faults = e->faults;
-        if (tail) {  // the compact pair rows + partials of the [CLS] tokens (gathered in front of the QKV GEMM)
-            G.res_hi = ffnp; G.part_in = cpt;
-        }
-        G.A = ctxp; G.lda = HP; G.B = W.wo_s; G.ldb = HP; G.M = Mrows; G.N = H; G.K = H;
-        G.bias = W.bo; G.out16 = xa; G.ldc = HP; G.part_out = LN.partA; G.wscale_inv = W.sc_s + 5;
-        {
-            ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
-            rc = launch_gemm_f16(EPI_S_RESLN, G, st, H);
-        }
-        if (rc) break;
+        // attention.output.dense + residual LayerNorm(x_b); tail: of the compact [CLS] rows
+        if (ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
+            int rc = launch_gemm_f16(EPI_S_RESLN, resln_args<H>(V.ctx, W.wo_s, H, W.bo, Mrows, tail ? cls : V.xb, gamma_b, beta_b, eps_b,
+                                                                V.xa, W.sc_s + 5, e->faults), st, H))
+            return rc;
         // intermediate.dense + exact GELU (attention.output.LayerNorm folded in)
-        memset(&G, 0, sizeof(G));
-        G.A = xa; G.lda = HP; G.B = W.w1_s; G.ldb = HP; G.M = Mrows; G.N = I; G.K = H;
-        G.bias = W.b1_s; G.csum = W.c1_s; G.part_in = LN.partA; G.ln_eps = D.ln_eps;
-        G.out16 = ffnp; G.ldc = 2 * I; G.n_split = n_split; G.wscale_inv = W.sc_s + 6;
-        G.range_faults = e->faults;
-        {
-            ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_S_GELU, G, st, H);
-        }
-        if (rc) break;
+        if (ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
+            int rc = launch_gemm_f16(EPI_S_GELU, ffn1_args<H>(V.xa, Mrows, D.ln_eps, W, I, V.ffn, n_split, e->faults), st, H))
+            return rc;
         // output.dense + residual LayerNorm(x_a)
-        memset(&G, 0, sizeof(G));
-        G.A = ffnp; G.lda = 2 * I; G.B = W.w2_s; G.ldb = 2 * I; G.M = Mrows; G.N = H; G.K = I;
-        G.bias = W.b2; G.res_gamma = W.ln1w; G.res_beta = W.ln1b; G.res_hi = xa; G.ldr = HP;
-        G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.out16 = xb; G.ldc = HP; G.part_out = LN.partB; G.wscale_inv = W.sc_s + 7;
-        G.range_faults = e->faults;
-        {
-            ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_S_RESLN, G, st, H);
-        }
+        if (ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
+            int rc = launch_gemm_f16(EPI_S_RESLN, resln_args<H>(V.ffn, W.w2_s, I, W.b2, Mrows, V.xa, W.ln1w, W.ln1b, D.ln_eps, V.xb,
+                                                                W.sc_s + 7, e->faults), st, H))
+            return rc;
     }
-    if (rc) return rc;
-    encoder_output<H>(e, LN, st, mb, nullptr, xb, nullptr, HP, H, nullptr, LN.partB, cls_tail ? 1 : 0);
+    encoder_output<H>(e, LN, st, mb, out, V.xb, cls_tail ? 1 : 0);
     return ANCE_OK;
 }
 
 // ---- fp16 mode: the folded-LayerNorm forward of the file header ----
 template <int H>
-int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroBatch &mb) {
+int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, const MicroPlan &mb, float *out) {
     const AnceEncoderDesc &D = e->d;
+    const AnceEncoder::Lane::Fp16 &V = LN.f16;
     const int I = D.intermediate, S = mb.S, T = mb.T, Tpad = mb.Tpad;
-    // the two halves of the fp16 pair of a stream share the fp32 row's 3 KB
-    _Float16 *const xa_hi = LN.xa_hi(), *const xa_lo = xa_hi + (size_t)e->tcap * H;
-    _Float16 *const xb_hi = LN.xb_hi(), *const xb_lo = xb_hi + (size_t)e->tcap * H;
     {
         ProfScope pe(PC_EMBED, st);
-        hipLaunchKernelGGL(embed_fold_kernel<H>, dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word, e->pos,
-                           e->type0, D.vocab_size, D.max_position, xb_hi, xb_lo, LN.partB);
+        hipLaunchKernelGGL((embed_kernel<H, FORM_PLANES>), dim3(Tpad / 4), dim3(256), 0, st, LN.tok_id, LN.tok_pos, Tpad, e->word,
+                           e->pos, e->type0, D.vocab_size, D.max_position, V.xb, (unsigned *)nullptr);
     }
     // Only the [CLS] row of the last layer reaches the head (model/models.py:49,152): after the
     // last layer's K / V projections everything runs on the S compact [CLS] rows.
     const bool cls_tail = e->cls_tail;
     const int S_pad = (int)align_up((size_t)S, 256);
+    const Rows<FORM_PLANES> cls = V.cls(S_pad, H);
     const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_f16.hip: tile_of_block)
     for (int li = 0; li < D.n_layers; ++li) {
         const LayerW &W = e->layers[li];
         const bool tail = cls_tail && li == D.n_layers - 1;
         const int Mrows = tail ? S_pad : Tpad;   // rows of the post-attention GEMMs
         const double Mwork = tail ? (double)S : (double)T;
-        GemmArgs G;
-        memset(&G, 0, sizeof(G));
-        // Q | K projection
-        G.A = xb_hi; G.lda = H; G.B = W.wqk; G.ldb = H; G.M = Tpad; G.N = 2 * H; G.K = H;
-        G.bias = W.bqk; G.out16 = LN.qk16; G.ldc = 2 * H; G.scale_cols = H;
-        G.scale = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) and log2(e): the softmax runs on exp2
-        G.part_in = LN.partB; G.ln_eps = D.ln_eps; G.csum = W.cqk; G.tok_lo = xb_lo;
+        // the LayerNorm that produced this layer's input x_b: the previous layer's output.LayerNorm, or the embedding LayerNorm
+        const float *const gamma_b = li == 0 ? e->eln_w : e->layers[li - 1].ln2w, *const beta_b = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
         // CLS-only tail: K of every token, Q of the compact [CLS] rows only -- row s of the Q columns is the query of sequence s
-        // (attention_kernel, q_compact); the same arithmetic per element as the full launch (split mode: above)
-        _Float16 *const chi = LN.ffn16, *const clo = chi + (size_t)S_pad * H;  // (the FFN buffer is dead here)
-        float *const cpt = reinterpret_cast<float *>(clo + (size_t)S_pad * H);
+        // (attention_kernel, q_compact; split mode: above)
         if (tail) {
             ProfScope ps(PC_LN, st);
-            hipLaunchKernelGGL(gather_cls_fold_kernel<H>, dim3(S_pad / 4), dim3(256), 0, st, xb_hi, xb_lo, LN.partB, LN.seq_off,
-                               S, S_pad, chi, clo, cpt);
+            hipLaunchKernelGGL((gather_cls_kernel<H, FORM_PLANES>), dim3(S_pad / 4), dim3(256), 0, st, V.xb, LN.seq_off, S, S_pad, cls);
         }
-        int rc;
+        // Q | K projection
         {
             ProfScope ps(PC_GEMM_QK, st, tail ? 2.0 * T * (double)H * H + 2.0 * S * (double)H * H : 2.0 * T * (2.0 * H) * H);
-            if (tail) {
-                G.B = W.wqk + (size_t)H * H; G.N = H; G.bias = W.bqk + H; G.csum = W.cqk + H; G.out16 = LN.qk16 + H; G.scale_cols = 0;
-                rc = launch_gemm_f16(EPI_QK_F, G, st, H);
-                G.A = chi; G.tok_lo = clo; G.part_in = cpt; G.M = S_pad;
-                G.B = W.wqk; G.bias = W.bqk; G.csum = W.cqk; G.out16 = LN.qk16; G.scale_cols = H;
-                if (!rc) rc = launch_gemm_f16(EPI_QK_F, G, st, H);
-            } else {
-                rc = launch_gemm_f16(EPI_QK_F, G, st, H);
-            }
+            const int c0 = tail ? H : 0;  // (tail: K here, Q of the compact rows by the second launch)
+            int rc = launch_gemm_f16(EPI_QK_F, qk_args<H>(V.xb, Tpad, D.ln_eps, W, c0, 2 * H - c0, V.qk), st, H);
+            if (tail && !rc) rc = launch_gemm_f16(EPI_QK_F, qk_args<H>(cls, S_pad, D.ln_eps, W, 0, H, V.qk), st, H);
+            if (rc) return rc;
         }
-        if (rc) return rc;
         // V^T = Wv h^T
-        memset(&G, 0, sizeof(G));
-        G.A = W.wv; G.lda = H; G.B = xb_hi; G.ldb = H; G.M = H; G.N = Tpad; G.K = H;
-        G.bias = W.bv; G.out16 = LN.vt16; G.ldc = mb.ldvt; G.col_map = LN.tok_vtcol; G.n_valid = T;
-        G.part_in = LN.partB; G.ln_eps = D.ln_eps; G.csum = W.cv; G.tok_lo = xb_lo;
-        {
-            ProfScope ps(PC_GEMM_VT, st, 2.0 * T * (double)H * H);
-            rc = launch_gemm_f16(EPI_VT_F, G, st, H);
-        }
-        if (rc) return rc;
+        if (ProfScope ps(PC_GEMM_VT, st, 2.0 * T * (double)H * H);
+            int rc = launch_gemm_f16(EPI_VT_F, vt_args<H>(V.xb, Tpad, T, D.ln_eps, W, V.vt, mb.ldvt, LN.tok_vtcol), st, H))
+            return rc;
         AttnArgs A;
-        A.qk = LN.qk16; A.vt = LN.vt16; A.ctx = LN.ctx16; A.desc = LN.desc;
+        A.qk = V.qk; A.vt = V.vt; A.ctx = V.ctx; A.desc = LN.desc;
         A.ld_qk = 2 * H; A.ld_vt = mb.ldvt; A.ld_ctx = H; A.n_heads = D.n_heads; A.cls_only = tail ? 1 : 0; A.q_compact = tail ? 1 : 0;
-        {
-            ProfScope ps(PC_ATTN, st, 0.0);
-            rc = launch_attention(A, S, mb.maxlen, st);
-        }
-        if (rc) return rc;
-        // attention.output.dense + residual.  The residual is LN(x_b) with the LayerNorm that produced this layer's input: the
-        // previous layer's output.LayerNorm, or the embedding LayerNorm.
-        memset(&G, 0, sizeof(G));
-        G.res_gamma = li == 0 ? e->eln_w : e->layers[li - 1].ln2w;
-        G.res_beta = li == 0 ? e->eln_b : e->layers[li - 1].ln2b;
-        G.res_hi = xb_hi; G.res_lo = xb_lo; G.part_in = LN.partB; G.ln_eps = D.ln_eps;
-        if (tail) {  // the compact (hi, lo, partials) rows of the [CLS] tokens (gathered in front of the Q | K GEMM)
-            G.res_hi = chi; G.res_lo = clo; G.part_in = cpt;
-        }
-        G.out16 = xa_hi; G.out_lo = xa_lo; G.part_out = LN.partA;
-        G.A = LN.ctx16; G.lda = H; G.B = W.wo; G.ldb = H; G.M = Mrows; G.N = H; G.K = H;
-        G.bias = W.bo; G.ldc = H;
-        {
-            ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
-            rc = launch_gemm_f16(EPI_RESLN, G, st, H);
-        }
-        if (rc) return rc;
+        if (ProfScope ps(PC_ATTN, st, 0.0); int rc = launch_attention(A, S, mb.maxlen, st)) return rc;
+        // attention.output.dense + residual LayerNorm(x_b); tail: of the compact [CLS] rows
+        if (ProfScope ps(PC_GEMM_OUT, st, 2.0 * Mwork * (double)H * H);
+            int rc = launch_gemm_f16(EPI_RESLN, resln_args<H>(V.ctx, W.wo, H, W.bo, Mrows, tail ? cls : V.xb, gamma_b, beta_b, D.ln_eps,
+                                                              V.xa, nullptr, nullptr), st, H))
+            return rc;
         // intermediate.dense + GELU
-        memset(&G, 0, sizeof(G));
-        G.A = xa_hi; G.lda = H; G.B = W.w1; G.ldb = H; G.M = Mrows; G.N = I; G.K = H;
-        G.bias = W.b1; G.out16 = LN.ffn16; G.ldc = I;
-        G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.csum = W.c1; G.tok_lo = xa_lo; G.n_split = n_split;
-        {
-            ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_GELU_F, G, st, H);
-        }
-        if (rc) return rc;
-        // output.dense + residual
-        memset(&G, 0, sizeof(G));
-        G.A = LN.ffn16; G.lda = I; G.B = W.w2; G.ldb = I; G.M = Mrows; G.N = H; G.K = I;
-        G.bias = W.b2; G.ldc = H;
-        G.res_gamma = W.ln1w; G.res_beta = W.ln1b; G.res_hi = xa_hi; G.res_lo = xa_lo; G.out16 = xb_hi; G.out_lo = xb_lo;
-        G.part_in = LN.partA; G.ln_eps = D.ln_eps; G.part_out = LN.partB;
-        {
-            ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
-            rc = launch_gemm_f16(EPI_RESLN, G, st, H);
-        }
-        if (rc) return rc;
+        if (ProfScope ps(PC_GEMM_FFN1, st, 2.0 * Mwork * (double)I * H);
+            int rc = launch_gemm_f16(EPI_GELU_F, ffn1_args<H>(V.xa, Mrows, D.ln_eps, W, I, V.ffn, n_split, nullptr), st, H))
+            return rc;
+        // output.dense + residual LayerNorm(x_a)
+        if (ProfScope ps(PC_GEMM_FFN2, st, 2.0 * Mwork * (double)I * H);
+            int rc = launch_gemm_f16(EPI_RESLN, resln_args<H>(V.ffn, W.w2, I, W.b2, Mrows, V.xa, W.ln1w, W.ln1b, D.ln_eps, V.xb,
+                                                              nullptr, nullptr), st, H))
+            return rc;
     }
-    encoder_output<H>(e, LN, st, mb, nullptr, xb_hi, xb_lo, H, 0, nullptr, LN.partB, cls_tail ? 1 : 0);
+    encoder_output<H>(e, LN, st, mb, out, V.xb, cls_tail ? 1 : 0);
     return ANCE_OK;
 }
 
+// The fork of encode_impl onto the side streams.  Once they have started, no path leaves encode_impl -- an error return included --
+// before join_lanes has ordered the caller's stream after every one of them.
+struct LaneFork {
+    AnceEncoder *e;
+    hipStream_t caller_st;
+    bool forked = false;
+    void fork() {  // side streams start after everything already queued by the caller
+        (void)hipEventRecord(e->ev_fork, caller_st);
+        for (int ln = 0; ln < e->n_lanes; ++ln) (void)hipStreamWaitEvent(e->side[ln], e->ev_fork, 0);
+        forked = true;
+    }
+    void join_lanes() {
+        for (int ln = 0; forked && ln < e->n_lanes; ++ln) {
+            (void)hipEventRecord(e->ev_join[ln], e->side[ln]);
+            (void)hipStreamWaitEvent(caller_st, e->ev_join[ln], 0);
+        }
+        forked = false;
+    }
+    ~LaneFork() { join_lanes(); }
+};
+
 int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *d_lens, const int32_t *h_lens, int hdr,
                 int64_t n, int L, int n_chunks, float *d_out, hipStream_t caller_st) {
-    hipStream_t st = caller_st;
     if (!e || !base || !d_out || n < 0 || L < 1 || n_chunks < 1 || L % n_chunks) {
         set_last_error("ance_encode: invalid argument");
         return ANCE_E_INVALID;
@@ -1181,7 +601,7 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
         return ANCE_E_INVALID;
     }
     int mb_index = 0;
-    bool forked = false;
+    LaneFork lanes{e, caller_st};
 
     for (int64_t r0 = 0; r0 < n; r0 += FETCH_CHUNK) {
         const int nr = (int)((n - r0) < FETCH_CHUNK ? (n - r0) : FETCH_CHUNK);
@@ -1191,10 +611,10 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
         } else {
             // no host copy of the lengths: read them back once (the only synchronising path)
             e->host_lens.resize(nr);
-            hipLaunchKernelGGL(fetch_lens_kernel, dim3((nr + 255) / 256), dim3(256), 0, st, base, ld, d_lens, r0, nr, L,
+            hipLaunchKernelGGL(fetch_lens_kernel, dim3((nr + 255) / 256), dim3(256), 0, caller_st, base, ld, d_lens, r0, nr, L,
                                e->lens_fetch);
-            if (hipMemcpyAsync(e->host_lens.data(), e->lens_fetch, (size_t)nr * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
+            if (hipMemcpyAsync(e->host_lens.data(), e->lens_fetch, (size_t)nr * 4, hipMemcpyDeviceToHost, caller_st) != hipSuccess ||
+                hipStreamSynchronize(caller_st) != hipSuccess)
                 return check_launch("ance_encode: length read-back");
             hl = e->host_lens.data();
         }
@@ -1206,11 +626,7 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
                     set_last_error("ance_encode: empty record under ANCE_ARCH_SEED (the reference defines no output for it)");
                     return ANCE_E_INVALID;
                 }
-        if (e->n_lanes > 1 && !forked) {  // side streams start after everything already queued by the caller
-            (void)hipEventRecord(e->ev_fork, caller_st);
-            for (int ln = 0; ln < e->n_lanes; ++ln) (void)hipStreamWaitEvent(e->side[ln], e->ev_fork, 0);
-            forked = true;
-        }
+        if (e->n_lanes > 1 && !lanes.forked) lanes.fork();
         // ---- greedy micro-batches over the sequences (record, chunk) of this block of records ---
         const int64_t gs_end = (int64_t)nr * n_chunks;
         int64_t gs = 0;
@@ -1218,69 +634,39 @@ int encode_impl(AnceEncoder *e, const int32_t *base, int64_t ld, const int32_t *
             const AnceEncoder::Lane &LN = e->lane[mb_index % e->n_lanes];
             hipStream_t st = e->n_lanes > 1 ? e->side[mb_index % e->n_lanes] : caller_st;
             ++mb_index;
-            // SEED: the lengths here are upper bounds of the compacted ones (they size grids, LDS and buffers only)
-            int S = 0, T = 0, V = 0, maxlen = 1;
-            int64_t g = gs;
-            while (g < gs_end && S < e->scap) {
-                const int64_t rec = g / n_chunks;
-                const int c = (int)(g - rec * n_chunks);
-                int full = hl[rec];
-                full = full < 0 ? 0 : (full > L ? L : full);
-                int lc = full - c * Lc;
-                lc = lc < 0 ? 0 : (lc > Lc ? Lc : lc);
-                const int eff = lc > 0 ? lc : 1;
-                const int v8 = (eff + 7) & ~7;
-                if (T + eff > e->tcap || V + v8 > e->vcap - 256) break;
-                T += eff; V += v8; ++S; ++g;
-                if (eff > maxlen) maxlen = eff;
-            }
-            if (S == 0) {
+            const MicroPlan mb = plan_micro_batch(hl, gs, gs_end, n_chunks, L, Lc, e->scap, e->tcap, e->vcap, seed);
+            if (mb.S == 0) {
                 set_last_error("ance_encode: max_tokens too small for one sequence");
                 return ANCE_E_INVALID;
             }
-            const int Tpad = (int)align_up((size_t)T, 256);
-            // SEED: column V (never part of a sequence) takes the V^T stores of the pad rows below T; V + 8 <= vcap - 256
-            const int ldvt = (int)align_up((size_t)V + (seed ? 8 : 0), 256);
-
             PlanArgs P;
             P.base = base; P.ld = ld; P.lens = d_lens; P.hdr = hdr;
-            P.g0 = r0 * n_chunks + gs; P.S = S; P.L = L; P.n_chunks = n_chunks; P.Lc = Lc;
-            P.pad_id = D.pad_token_id; P.arch = D.arch; P.T = T; P.Tpad = Tpad; P.vt_spare = V;
+            P.g0 = r0 * n_chunks + gs; P.S = mb.S; P.L = L; P.n_chunks = n_chunks; P.Lc = Lc;
+            P.pad_id = D.pad_token_id; P.arch = D.arch; P.T = mb.T; P.Tpad = mb.Tpad; P.vt_spare = mb.V;
             P.seq_off = LN.seq_off; P.seq_vtcol = LN.seq_vtcol; P.seq_len = LN.seq_len;
             P.tok_id = LN.tok_id; P.tok_pos = LN.tok_pos; P.tok_vtcol = LN.tok_vtcol;
             P.desc = LN.desc; P.faults = e->faults;
             {
                 ProfScope ps(PC_PLAN, st);
-                if (seed) hipLaunchKernelGGL(seed_count_kernel, dim3((S + 3) / 4), dim3(256), 0, st, P);
+                if (seed) hipLaunchKernelGGL(seed_count_kernel, dim3((mb.S + 3) / 4), dim3(256), 0, st, P);
                 hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(1024), 0, st, P);
-                const int nb_seq = (S + 3) / 4, nb_pad = ((seed ? Tpad : Tpad - T) + 255) / 256;
+                const int nb_seq = (mb.S + 3) / 4, nb_pad = ((seed ? mb.Tpad : mb.Tpad - mb.T) + 255) / 256;
                 hipLaunchKernelGGL(pack_kernel, dim3(nb_seq > nb_pad ? nb_seq : nb_pad), dim3(256), 0, st, P);
             }
-            MicroBatch mb;
-            mb.S = S; mb.T = T; mb.Tpad = Tpad; mb.ldvt = ldvt; mb.maxlen = maxlen;
-            mb.out = d_out + (size_t)(r0 * n_chunks + gs) * HEAD_OUT;
-            const bool large = D.hidden == 1024;  // desc_ok: 768 or 1024
-            const int rc = e->mode == ANCE_PRECISION_FP32    ? (large ? forward_fp32<1024>(e, LN, st, mb) : forward_fp32<768>(e, LN, st, mb))
-                           : e->mode == ANCE_PRECISION_SPLIT ? (large ? forward_split<1024>(e, LN, st, mb) : forward_split<768>(e, LN, st, mb))
-                                                             : (large ? forward_fp16<1024>(e, LN, st, mb) : forward_fp16<768>(e, LN, st, mb));
+            float *const out = d_out + (size_t)(r0 * n_chunks + gs) * HEAD_OUT;
+            const int rc = with_hidden(D.hidden, [&](auto h) {
+                constexpr int H = decltype(h)::value;
+                return e->mode == ANCE_PRECISION_FP32    ? forward_fp32<H>(e, LN, st, mb, out)
+                       : e->mode == ANCE_PRECISION_SPLIT ? forward_split<H>(e, LN, st, mb, out)
+                                                         : forward_fp16<H>(e, LN, st, mb, out);
+            });
             if (rc) return rc;
-            gs = g;
+            gs = mb.next;
         }
-        if (forked && r0 + FETCH_CHUNK < n && !h_lens) {
-            // the next block of records needs a length read-back on the caller's stream: join first
-            for (int ln = 0; ln < e->n_lanes; ++ln) {
-                (void)hipEventRecord(e->ev_join[ln], e->side[ln]);
-                (void)hipStreamWaitEvent(caller_st, e->ev_join[ln], 0);
-            }
-            forked = false;
-        }
+        // the next block of records needs a length read-back on the caller's stream: join first
+        if (r0 + FETCH_CHUNK < n && !h_lens) lanes.join_lanes();
     }
-    if (forked) {  // the caller's stream continues only after both side streams are done
-        for (int ln = 0; ln < e->n_lanes; ++ln) {
-            (void)hipEventRecord(e->ev_join[ln], e->side[ln]);
-            (void)hipStreamWaitEvent(caller_st, e->ev_join[ln], 0);
-        }
-    }
+    lanes.join_lanes();
     return check_launch("ance_encode");
 }
 
@@ -1343,10 +729,15 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
         }
     }
     const int H = desc->hidden, HP = 2 * H;
-    if ((H == 1024 ? hipFuncSetAttribute(reinterpret_cast<const void *>(head_gemm_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)HEAD_LDS_BYTES<1024>)
-                   : hipFuncSetAttribute(reinterpret_cast<const void *>(head_gemm_kernel<768>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)HEAD_LDS_BYTES<768>)) != hipSuccess) {  // per device: set for the device this handle lives on
+    // per device: set for the device this handle lives on
+    const hipError_t head_attr = with_hidden(H, [&](auto h) {
+        constexpr int HW = decltype(h)::value;
+        const void *k = e->mode == ANCE_PRECISION_FP32    ? reinterpret_cast<const void *>(head_gemm_kernel<HW, FORM_F32>)
+                        : e->mode == ANCE_PRECISION_SPLIT ? reinterpret_cast<const void *>(head_gemm_kernel<HW, FORM_PAIR>)
+                                                          : reinterpret_cast<const void *>(head_gemm_kernel<HW, FORM_PLANES>);
+        return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS_BYTES<HW>);
+    });
+    if (head_attr != hipSuccess) {
         delete e;
         return check_launch("ance_encoder_create: head attr");
     }
@@ -1380,8 +771,10 @@ extern "C" int ance_encoder_create(const AnceEncoderDesc *desc, const void *cons
         if (e->mode == ANCE_PRECISION_FP16) {
             auto foldw = [&](const void *W, const void *b, const float *g, const float *be, int N, _Float16 *W16, float *cs,
                              float *bo) {
-                hipLaunchKernelGGL(H == 1024 ? fold_weight_kernel<1024> : fold_weight_kernel<768>, dim3((N + 3) / 4), dim3(256), 0, st, (const float *)W, (const float *)b, g,
-                                   be, N, W16, cs, bo);
+                with_hidden(H, [&](auto h) {
+                    hipLaunchKernelGGL(fold_weight_kernel<decltype(h)::value>, dim3((N + 3) / 4), dim3(256), 0, st, (const float *)W,
+                                       (const float *)b, g, be, N, W16, cs, bo);
+                });
             };
             foldw(p[0], p[1], gin, bin, H, L.wqk, L.cqk, L.bqk);                                     // query
             foldw(p[2], p[3], gin, bin, H, L.wqk + (size_t)H * H, L.cqk + H, L.bqk + H);            // key
@@ -1489,75 +882,4 @@ extern "C" int ance_encode_ids(AnceEncoder *enc, const int32_t *d_ids, int64_t l
 extern "C" double ance_encoder_flops_per_sequence(int T) {
     const double t = T;
     return 169869312.0 * t + 36864.0 * t * t + 1179648.0;
-}
-
-// Test hook (include/ance_amd.h): one launch of one of the encoder's attention kernels on caller data, through the encoder's own
-// launchers.  Host code only: every bound a kernel relies on is checked here, against the caller's allocations, before anything is
-// copied or launched.
-extern "C" int ance_debug_attention(const AnceAttnDebugArgs *a, void *stream) {
-    using namespace ance;
-    auto refuse = [](const char *why) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "ance_debug_attention: invalid argument (%s)", why);
-        set_last_error(buf);
-        return ANCE_E_INVALID;
-    };
-    if (!a) return refuse("null args");
-    if (a->kind < 0 || a->kind > 2) return refuse("kind");
-    if (a->n_heads != 12 && a->n_heads != 16) return refuse("n_heads");
-    if (a->n_seq < 1 || a->n_seq > (1 << 20)) return refuse("n_seq");
-    if (a->max_seq_len < 1 || a->max_seq_len > 512) return refuse("max_seq_len");
-    if (!a->h_desc || !a->d_desc || !a->qk || !a->ctx || (a->kind == 0 && !a->vt)) return refuse("null pointer");
-    const int64_t H = 64 * (int64_t)a->n_heads, n = a->n_seq;
-    const int64_t desc_bytes = a->kind == 2 ? 4 * (n + 1) : 16 * n;
-    if (a->d_desc_bytes < desc_bytes || (uintptr_t)a->d_desc % 16) return refuse("d_desc");
-    if ((uintptr_t)a->qk % 16 || (uintptr_t)a->ctx % 16 || (a->kind == 0 && (uintptr_t)a->vt % 16)) return refuse("alignment");
-    if (a->qk_rows < 1 || a->ctx_rows < 1) return refuse("rows");
-    if (a->kind == 0) {  // 16-byte rows pieces: strides in halves, multiples of 8
-        if (a->ld_qk % 8 || a->ld_qk < 2 * H || a->ld_vt % 8 || a->ld_vt < 8 || a->ld_ctx % 8 || a->ld_ctx < H) return refuse("stride");
-    } else {             // the split and fp32 kernels derive their strides from n_heads
-        if (a->ld_qk != 3 * H || a->ld_ctx != (a->kind == 1 ? 2 * H : H)) return refuse("stride");
-    }
-    if (a->kind == 2 && (a->cls_only || a->q_compact)) return refuse("cls_only on kind 2");
-    if (a->kind == 1 && a->q_compact != a->cls_only) return refuse("kind 1: q_compact != cls_only");
-    if (a->kind == 0 && a->q_compact && !a->cls_only) return refuse("q_compact without cls_only");
-    const int32_t *d = a->h_desc;
-    if (a->kind == 2) {
-        if (d[0] < 0) return refuse("tokens outside the allocation");
-        for (int64_t s = 0; s < n; ++s) {
-            const int64_t len = (int64_t)d[s + 1] - d[s];
-            if (len < 1 || len > a->max_seq_len) return refuse("length");
-        }
-        if (d[n] > a->qk_rows || d[n] > a->ctx_rows) return refuse("tokens outside the allocation");
-    } else {
-        std::vector<char> seen((size_t)n, 0);
-        const bool compact = a->cls_only && (a->q_compact || a->kind == 1);
-        for (int64_t u = 0; u < n; ++u) {
-            const int64_t tok0 = d[4 * u], len = d[4 * u + 1], vcol = d[4 * u + 2], s = d[4 * u + 3];
-            if (len < 1 || len > a->max_seq_len) return refuse("length");
-            if (s < 0 || s >= n || seen[(size_t)s]) return refuse("sequence index");
-            seen[(size_t)s] = 1;
-            if (tok0 < 0 || tok0 + len > a->qk_rows) return refuse("tokens outside the allocation");
-            if (compact && s >= a->qk_rows) return refuse("Q row s past the allocation");
-            if (a->cls_only ? s >= a->ctx_rows : tok0 + len > a->ctx_rows) return refuse("output row past the allocation");
-            if (a->kind == 0 && (vcol < 0 || vcol % 8 || vcol + ((len + 7) & ~7) > a->ld_vt)) return refuse("V^T columns");
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemcpyAsync(a->d_desc, a->h_desc, (size_t)desc_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-        return check_launch("ance_debug_attention: descriptors");
-    int rc;
-    if (a->kind == 0) {
-        AttnArgs A;
-        A.qk = (const _Float16 *)a->qk; A.vt = (const _Float16 *)a->vt; A.ctx = (_Float16 *)a->ctx; A.desc = (const int4 *)a->d_desc;
-        A.ld_qk = a->ld_qk; A.ld_vt = a->ld_vt; A.ld_ctx = a->ld_ctx; A.n_heads = a->n_heads;
-        A.cls_only = a->cls_only ? 1 : 0; A.q_compact = a->q_compact ? 1 : 0;
-        rc = launch_attention(A, a->n_seq, a->max_seq_len, st);
-    } else if (a->kind == 1) {
-        rc = launch_attention_split((const float *)a->qk, (_Float16 *)a->ctx, (const int4 *)a->d_desc, a->n_seq, a->n_heads,
-                                    a->max_seq_len, a->cls_only ? 1 : 0, st);
-    } else {
-        rc = launch_attention32((const float *)a->qk, (float *)a->ctx, (const int *)a->d_desc, a->n_seq, a->n_heads, st);
-    }
-    return rc ? rc : check_launch("ance_debug_attention");
 }

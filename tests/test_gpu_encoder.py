@@ -576,7 +576,7 @@ def test_large_micro_batches_change_no_row():
 
 
 def test_split_mode_with_weights_of_very_different_scales():
-    """The split GEMM stores every weight matrix times its own power of two (largest element in [2^13, 2^14): csrc/encoder.hip:
+    """The split GEMM stores every weight matrix times its own power of two (largest element in [2^13, 2^14): csrc/encoder_kernels.h:
     weight_pair_scale) and undoes it in the epilogue.  Random-init weights are all ~0.02, so every other test exercises ONE
     exponent; here the matrices of a 3-layer model are rescaled by factors between 2^-7 and 2^9 (Q / K / V by different ones: they
     share a scale slot; one matrix gets a single huge outlier), and the result must stay fp32-grade: within 4 x the distance of the

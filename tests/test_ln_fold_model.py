@@ -1,4 +1,4 @@
-"""CPU model of the encoder's rounding points (csrc/encoder.hip): fp16 MFMA operands, fp32 everything else.
+"""CPU model of the encoder's rounding points (csrc/encoder.hip, csrc/encoder_kernels.h): fp16 MFMA operands, fp32 everything else.
 
 Two schemes are restated in torch and compared with the fp32 oracle on the same random-init 12-layer model:
   * "plain": the token operand of every GEMM is fp16(LayerNorm(v)), weights fp16(W), fp32 residual stream;

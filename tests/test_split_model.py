@@ -34,7 +34,7 @@ def pair(v):
 
 
 def weight_scale(w):
-    """2^p with max |w| 2^p in [2^13, 2^14) (encoder.hip: weight_pair_scale)"""
+    """2^p with max |w| 2^p in [2^13, 2^14) (encoder_kernels.h: weight_pair_scale)"""
     m = float(w.abs().max())
     return 2.0 ** (14 - math.frexp(m)[1]) if m > 0 else 1.0
 
