@@ -142,6 +142,11 @@ SYMBOLS = {
     "ance_lamb_step_clipped": (ctypes.c_int, [ctypes.POINTER(AnceLambTensor), ctypes.c_int, ctypes.POINTER(AnceLambGroup), ctypes.c_int,
                                               ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_size_t, ctypes.c_void_p]),
+    "ance_lamb_amp_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "ance_lamb_step_amp": (ctypes.c_int, [ctypes.POINTER(AnceLambTensor), ctypes.c_int, ctypes.POINTER(AnceLambGroup), ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p]),
     "ance_nll_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p]),

@@ -15,6 +15,20 @@
 //   gtotal   (one workgroup)  the chunk sums added in chunk order (fp64), one sqrt, rounded to fp32 -> *d_grad_norm;
 //            coef = min(max_grad_norm / (total + 1e-6), 1) in fp32, NaN when the total is NaN (as torch's clamp)
 //   pass 1   as above with g * coef (an fp32 product, formed in registers) in place of g; the gradients in memory are not rescaled
+//
+// ance_lamb_step_amp: either step under loss scaling (torch.amp.GradScaler's contract for optimizers that set
+// _step_supports_amp_scaling: the scale and the overflow flag arrive as device scalars and step() is called unconditionally).  No
+// launch more: three without clipping, five with it, and still no atomics, a fixed summation order and no host synchronisation.
+//   unscale  d_grad_scale given: inv = (float)(1.0 / (double)*d_grad_scale), the value GradScaler.unscale_ forms; every workgroup
+//            that reads gradients forms it from the one device scalar by the same correctly rounded fp64 divide, so it is one
+//            value.  Every gradient element enters the step as the fp32 product g * inv, formed in registers: gnorm squares and
+//            sums those products, pass 1 takes (g * inv) * coef -- two fp32 roundings in that order.  The gradients in memory are
+//            not rewritten.  A power-of-two scale is bit-neutral against the plain step on the unscaled gradients.
+//   skip     d_found_inf given and !(*d_found_inf == 0) (an overflow count or NaN): every workgroup of pass 1 and pass 2 reads the
+//            flag and returns before any store, so no bit of p, m, v changes; gnorm and gtotal still run (*d_grad_norm is
+//            written and may be inf or NaN); reduce writes the rows of d_prev_out (or (0, 0, 1)) into d_out instead of new norms
+//            and one thread adds 1 to *d_skipped with an ordinary load, add and store.
+// Without the two pointers the launches and the instantiations are those of ance_lamb_step / ance_lamb_step_clipped.
 #include "common.h"
 
 #include <math.h>
@@ -51,6 +65,21 @@ __device__ __forceinline__ float lamb_u(float p, float m, float v, const LambDev
     return u;
 }
 
+// *grad_scale -> the factor that unscales a gradient: the fp64 reciprocal rounded to fp32, as GradScaler.unscale_ (hipcc emits the
+// correctly rounded fp32 divide for it, which is the same value: a 53-bit quotient rounds to 24 bits without a double-rounding error)
+__device__ __forceinline__ float lamb_inv_scale(const float *grad_scale) { return (float)(1.0 / (double)grad_scale[0]); }
+
+// the overflow flag of ance_lamb_step_amp: anything but 0 skips, NaN included
+__device__ __forceinline__ bool lamb_skip(const float *found_inf) { return found_inf && !(found_inf[0] == 0.0f); }
+
+// the gradient element as it enters the step: unscaled, then clipped, each an fp32 product of its own
+template <bool CLIP, bool UNSCALE>
+__device__ __forceinline__ float lamb_g(float g, float inv, float cf) {
+    if (UNSCALE) g = g * inv;
+    if (CLIP) g = g * cf;
+    return g;
+}
+
 // m, v update of one element; returns u
 __device__ __forceinline__ float lamb_mv(float p, float g, float &m, float &v, const LambDevGroup &G) {
     m = __builtin_fmaf(G.omb1, g, m * G.b1);
@@ -63,13 +92,17 @@ __device__ __forceinline__ void lamb_acc(float p, float u, double &sp, double &s
     su = __builtin_fma((double)u, (double)u, su);
 }
 
-// CLIP: every gradient element is multiplied by *coef (ance_lamb_step_clipped) before it enters m and v
-template <bool CLIP>
+// CLIP: every gradient element is multiplied by *coef (ance_lamb_step_clipped) before it enters m and v; UNSCALE: by the inverse
+// of *grad_scale before that (ance_lamb_step_amp).  found_inf (nullable): a skipped step returns before any store.
+template <bool CLIP, bool UNSCALE>
 __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
-                                                                  const int32_t *chunk_tensor, double2 *partial, const float *coef) {
+                                                                  const int32_t *chunk_tensor, double2 *partial, const float *coef,
+                                                                  const float *grad_scale, const float *found_inf) {
     __shared__ double red[LAMB_THREADS / 64][2];
+    if (lamb_skip(found_inf)) return;
     const int tid = threadIdx.x;
     const float cf = CLIP ? coef[0] : 1.0f;
+    const float inv = UNSCALE ? lamb_inv_scale(grad_scale) : 1.0f;
     const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
     const LambDevGroup G = groups[T.group];
     const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
@@ -96,7 +129,7 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float mj = M[k][j], vj = V[k][j];
-                        const float u = lamb_mv(P[k][j], CLIP ? Gr[k][j] * cf : Gr[k][j], mj, vj, G);
+                        const float u = lamb_mv(P[k][j], lamb_g<CLIP, UNSCALE>(Gr[k][j], inv, cf), mj, vj, G);
                         M[k][j] = mj;
                         V[k][j] = vj;
                         lamb_acc(P[k][j], u, sp, su);
@@ -111,7 +144,7 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
     for (int e = done + tid; e < len; e += LAMB_THREADS) {  // scalar tail (or the whole chunk of an unaligned tensor)
         float mj = m[e], vj = v[e];
         const float pj = p[e];
-        const float u = lamb_mv(pj, CLIP ? g[e] * cf : g[e], mj, vj, G);
+        const float u = lamb_mv(pj, lamb_g<CLIP, UNSCALE>(g[e], inv, cf), mj, vj, G);
         m[e] = mj;
         v[e] = vj;
         lamb_acc(pj, u, sp, su);
@@ -135,11 +168,13 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
     }
 }
 
-// the chunk's sum of g^2 in fp64 (ance_lamb_step_clipped): reads g only
+// the chunk's sum of g^2 in fp64 (ance_lamb_step_clipped): reads g only.  UNSCALE: of (g * inv)^2, the fp32 product squared
+template <bool UNSCALE>
 __global__ void __launch_bounds__(LAMB_THREADS) lamb_gnorm_kernel(const LambDevTensor *tensors, const int32_t *chunk_tensor,
-                                                                  double *gpartial) {
+                                                                  double *gpartial, const float *grad_scale) {
     __shared__ double red[LAMB_THREADS / 64];
     const int tid = threadIdx.x;
+    const float inv = UNSCALE ? lamb_inv_scale(grad_scale) : 1.0f;
     const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
     const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
     const int len = (int)min((int64_t)LAMB_CHUNK, T.numel - base);
@@ -159,11 +194,17 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_gnorm_kernel(const LambDevT
 #pragma unroll
             for (int k = 0; k < LAMB_UNROLL; ++k)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) sg = __builtin_fma((double)Gr[k][j], (double)Gr[k][j], sg);
+                for (int j = 0; j < 4; ++j) {
+                    const double x = (double)lamb_g<false, UNSCALE>(Gr[k][j], inv, 1.0f);
+                    sg = __builtin_fma(x, x, sg);
+                }
         }
         done = n4 * 4;
     }
-    for (int e = done + tid; e < len; e += LAMB_THREADS) sg = __builtin_fma((double)g[e], (double)g[e], sg);
+    for (int e = done + tid; e < len; e += LAMB_THREADS) {
+        const double x = (double)lamb_g<false, UNSCALE>(g[e], inv, 1.0f);
+        sg = __builtin_fma(x, x, sg);
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sg += __shfl_xor(sg, off);
     if ((tid & 63) == 0) red[tid >> 6] = sg;
@@ -197,11 +238,24 @@ __global__ void __launch_bounds__(1024) lamb_gtotal_kernel(const double *gpartia
     }
 }
 
-// one wave per tensor: chunk sums in chunk order (lane-strided, then an xor-shuffle tree) -> (wn, an, tr)
+// one wave per tensor: chunk sums in chunk order (lane-strided, then an xor-shuffle tree) -> (wn, an, tr).  A skipped step
+// (found_inf) has no chunk sums: the tensor's row is the one of prev_out, or (0, 0, 1) without it, and one thread counts the skip.
 __global__ void __launch_bounds__(256) lamb_reduce_kernel(const LambDevTensor *tensors, int n_tensors, const double2 *partial,
-                                                          float *out) {
+                                                          float *out, const float *found_inf, const float *prev_out,
+                                                          int64_t *skipped) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
     if (t >= n_tensors) return;
+    if (lamb_skip(found_inf)) {
+        if (l == 0) {
+            const float wn = prev_out ? prev_out[3 * (int64_t)t] : 0.0f, an = prev_out ? prev_out[3 * (int64_t)t + 1] : 0.0f;
+            const float tr = prev_out ? prev_out[3 * (int64_t)t + 2] : 1.0f;
+            out[3 * (int64_t)t] = wn;
+            out[3 * (int64_t)t + 1] = an;
+            out[3 * (int64_t)t + 2] = tr;
+            if (t == 0 && skipped) skipped[0] = skipped[0] + 1;
+        }
+        return;
+    }
     const int c0 = tensors[t].chunk0, nc = tensors[t].n_chunks;
     double sp = 0.0, su = 0.0;
     for (int c = l; c < nc; c += 64) {
@@ -226,7 +280,9 @@ __global__ void __launch_bounds__(256) lamb_reduce_kernel(const LambDevTensor *t
 }
 
 __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass2_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
-                                                                  const int32_t *chunk_tensor, const float *out, int adam) {
+                                                                  const int32_t *chunk_tensor, const float *out, int adam,
+                                                                  const float *found_inf) {
+    if (lamb_skip(found_inf)) return;
     const int tid = threadIdx.x;
     const int t = chunk_tensor[blockIdx.x];
     const LambDevTensor T = tensors[t];
@@ -339,9 +395,23 @@ int64_t max_chunks(int n_tensors, int64_t total_numel) {  // >= the sum of every
 }
 
 
-// the body of ance_lamb_step (clip false) and ance_lamb_step_clipped (clip true: max_norm, d_grad_norm)
+// what ance_lamb_step_amp adds to a step: every pointer nullable, all null for the other two entry points
+struct LambAmp {
+    const float *grad_scale = nullptr, *found_inf = nullptr, *prev_out = nullptr;
+    int64_t *skipped = nullptr;
+};
+
+template <bool CLIP, bool UNSCALE>
+void launch_pass1(int64_t n_chunks, hipStream_t st, const LambDevGroup *dG, const LambDevTensor *dT, const int32_t *dC, double2 *dP,
+                  const float *dCoef, const LambAmp &amp) {
+    hipLaunchKernelGGL((lamb_pass1_kernel<CLIP, UNSCALE>), dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP, dCoef,
+                       amp.grad_scale, amp.found_inf);
+}
+
+// the body of ance_lamb_step (clip false), ance_lamb_step_clipped (clip true: max_norm, d_grad_norm) and ance_lamb_step_amp (amp)
 int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam, float *d_out,
-                   void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm, float *d_grad_norm) {
+                   void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm, float *d_grad_norm,
+                   const LambAmp &amp) {
     if (n_tensors < 0) return lamb_refuse("n_tensors < 0");
     if (n_tensors == 0) return ANCE_OK;
     if (!h_tensors || !h_groups) return lamb_refuse("null table");
@@ -411,24 +481,33 @@ int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLam
     const LambDevTensor *dT = (const LambDevTensor *)(ws + off_t);
     const int32_t *dC = (const int32_t *)(ws + off_c);
     double2 *dP = (double2 *)(ws + off_p);
+    const bool unscale = amp.grad_scale != nullptr;
     if (clip) {
         double *dGP = (double *)(ws + off_p + sizeof(double2) * (size_t)n_chunks);
         float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
-        if (n_chunks > 0) hipLaunchKernelGGL(lamb_gnorm_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP);
+        if (n_chunks > 0) {
+            if (unscale)
+                hipLaunchKernelGGL(lamb_gnorm_kernel<true>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
+                                   amp.grad_scale);
+            else
+                hipLaunchKernelGGL(lamb_gnorm_kernel<false>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
+                                   (const float *)nullptr);
+        }
         hipLaunchKernelGGL(lamb_gtotal_kernel, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks, (float)max_norm, d_grad_norm,
                            dCoef);
-        if (n_chunks > 0)
-            hipLaunchKernelGGL(lamb_pass1_kernel<true>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP,
-                               (const float *)dCoef);
+        if (n_chunks > 0) {
+            if (unscale) launch_pass1<true, true>(n_chunks, st, dG, dT, dC, dP, dCoef, amp);
+            else launch_pass1<true, false>(n_chunks, st, dG, dT, dC, dP, dCoef, amp);
+        }
     } else if (n_chunks > 0) {
-        hipLaunchKernelGGL(lamb_pass1_kernel<false>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP,
-                           (const float *)nullptr);
+        if (unscale) launch_pass1<false, true>(n_chunks, st, dG, dT, dC, dP, nullptr, amp);
+        else launch_pass1<false, false>(n_chunks, st, dG, dT, dC, dP, nullptr, amp);
     }
     hipLaunchKernelGGL(lamb_reduce_kernel, dim3((unsigned)((n_tensors + 3) / 4)), dim3(256), 0, st, dT, n_tensors,
-                       (const double2 *)dP, d_out);
+                       (const double2 *)dP, d_out, amp.found_inf, amp.prev_out, amp.skipped);
     if (n_chunks > 0)
         hipLaunchKernelGGL(lamb_pass2_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, (const float *)d_out,
-                           adam ? 1 : 0);
+                           adam ? 1 : 0, amp.found_inf);
     return check_launch(g_lamb_fn);
 }
 
@@ -447,7 +526,7 @@ extern "C" int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, co
                               float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
     using namespace ance;
     g_lamb_fn = "ance_lamb_step";
-    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, false, 0.0, nullptr);
+    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, false, 0.0, nullptr, LambAmp());
 }
 
 extern "C" size_t ance_lamb_clipped_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
@@ -466,5 +545,28 @@ extern "C" int ance_lamb_step_clipped(const AnceLambTensor *h_tensors, int n_ten
     if (!(max_grad_norm > 0.0) || !(max_grad_norm < (double)INFINITY)) return lamb_refuse("max_grad_norm not a positive finite number");
     if (n_tensors > 0 && !d_grad_norm) return lamb_refuse("null d_grad_norm");
     return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, true,
-                          max_grad_norm, d_grad_norm);
+                          max_grad_norm, d_grad_norm, LambAmp());
+}
+
+extern "C" size_t ance_lamb_amp_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
+    return ance_lamb_clipped_workspace_bytes(n_tensors, n_groups, total_numel);  // enough with and without clipping
+}
+
+extern "C" int ance_lamb_step_amp(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                                  double max_grad_norm, const float *d_grad_scale, const float *d_found_inf, const float *d_prev_out,
+                                  float *d_grad_norm, int64_t *d_skipped, float *d_out, void *d_workspace, size_t workspace_bytes,
+                                  void *stream) {
+    using namespace ance;
+    g_lamb_fn = "ance_lamb_step_amp";
+    if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
+        return lamb_refuse("max_grad_norm not 0 or a positive finite number");
+    const bool clip = max_grad_norm != 0.0;
+    if (clip && n_tensors > 0 && !d_grad_norm) return lamb_refuse("null d_grad_norm");
+    LambAmp amp;
+    amp.grad_scale = d_grad_scale;
+    amp.found_inf = d_found_inf;
+    amp.prev_out = d_prev_out;
+    amp.skipped = d_skipped;
+    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, clip, max_grad_norm,
+                          d_grad_norm, amp);
 }

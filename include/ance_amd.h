@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -472,6 +472,34 @@ size_t ance_lamb_clipped_workspace_bytes(int n_tensors, int n_groups, int64_t to
 int ance_lamb_step_clipped(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
                            double max_grad_norm, float *d_grad_norm, float *d_out, void *d_workspace, size_t workspace_bytes,
                            void *stream);
+
+/* Either step under loss scaling -- torch.amp.GradScaler's contract for an optimizer that sets _step_supports_amp_scaling: the
+ * scale and the overflow flag are DEVICE fp32 scalars and the step is called unconditionally.  max_grad_norm == 0: ance_lamb_step,
+ * else ance_lamb_step_clipped, with:
+ *   unscale  d_grad_scale != NULL: inv = (float)(1.0 / (double)*d_grad_scale), formed on the device (the value
+ *            GradScaler.unscale_ forms).  Every gradient element enters the step as the single fp32 product g inv, formed in
+ *            registers: with clipping the 2-norm is taken over those products (squared and summed in fp64 in chunk order),
+ *            coef is formed as in ance_lamb_step_clipped, and the element enters m, v as (g inv) coef -- two fp32 roundings in that
+ *            order.  The gradients in memory are never rewritten.  A scale of 0 or a non-finite scale cannot be checked on the
+ *            host and POISONS the step (inv is inf, 0 or NaN); a power-of-two scale is bit-neutral.
+ *   skip     d_found_inf != NULL and !(*d_found_inf == 0) (NaN skips too): no bit of any p, m, v changes -- the workgroups of
+ *            both passes read the flag and return before any store.  *d_grad_norm is still written when clipping and may be inf
+ *            or NaN.  Row t of d_out is row t of d_prev_out when that is given (fp32 [n_tensors][3], e.g. the previous step's
+ *            d_out; it may be d_out itself), else (0, 0, 1).  *d_skipped (DEVICE int64, nullable) is incremented by one.
+ * Launches: three without clipping, five with it -- none more than the step it extends -- no atomics, a fixed summation order,
+ * no host synchronisation.  With d_grad_scale == NULL and d_found_inf == NULL the result has the bits of ance_lamb_step /
+ * ance_lamb_step_clipped.  Workspace: ance_lamb_amp_workspace_bytes (>= ance_lamb_clipped_workspace_bytes; 0 where that is 0).
+ * Refuses (ANCE_E_INVALID, before any copy or launch) everything ance_lamb_step refuses, a negative, NaN or infinite
+ * max_grad_norm, and clipping with a null d_grad_norm.  n_tensors == 0: nothing is enqueued (and nothing counted). */
+size_t ance_lamb_amp_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel);
+int ance_lamb_step_amp(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                       double max_grad_norm,            /* 0: no clipping; else positive finite */
+                       const float *d_grad_scale,       /* nullable: no unscale */
+                       const float *d_found_inf,        /* nullable: never skip */
+                       const float *d_prev_out,         /* nullable, [n_tensors][3] */
+                       float *d_grad_norm,              /* required iff max_grad_norm != 0 */
+                       int64_t *d_skipped,              /* nullable */
+                       float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Re-reads every ANCE_* tuning knob from the environment (they are otherwise read once per process).  For tests and
  * sweeps that change a knob between two calls; not thread-safe against concurrent searches. */

@@ -6,6 +6,14 @@ variants alternated --rounds times (each round times every variant once, --steps
     (b) unfused   torch.nn.utils.clip_grad_norm_(params, 1.0); Lamb.step()  -> 52 B per element and a dozen launches more
     (c) plain     Lamb.step() alone                                        -> 40 B per element (profiles/r07_lamb_step.json's leg)
     (d) the 44 B per element HBM floor at the copy rate scripts/bench_lamb.py uses
+    under loss scaling (RoBERTa-base shapes; torch.amp.GradScaler at 2^16, Lamb(max_grad_norm=1.0)):
+    (e) amp_fused    scaler.step(opt); scaler.update()  -> ance_lamb_step_amp unscales in registers and skips on the device
+    (f) amp_unfused  what a Lamb without _step_supports_amp_scaling does: scaler.unscale_(opt), the clipped step behind the
+                     scaler's found_inf .item(), update()
+    Both keep the scaler's own finite-check pass over the gradients, so by bytes (e) is no lighter than (f) minus the 8 B per
+    element of unscale_'s rewrite; what (e) removes is the host wait and launches.  Launch counts: a separate
+    `rocprofv3 --kernel-trace --stats` run of `--trace amp:amp_fused` / `--trace amp:amp_unfused` (--trace-calls steps and nothing
+    else; the parameters' upload adds a fixed number of kernels, which the difference of two call counts removes).
  2. objective forward + backward at the trainers' sizes against the reference's torch expression on the same tensors: triplets
     n = 8, 32, 128 (FirstP; MaxP 4 chunks), in-batch 128 x 256 and 1024 x 2048.  Launch-bound: the figure of merit is the launch
     count (from a separate `rocprofv3 --kernel-trace --stats` run of `--trace CASE:VARIANT`, which makes --trace-calls calls and
@@ -98,6 +106,55 @@ def bench_optimizer(kind, rounds, steps, warmup):
     return res
 
 
+def amp_legs(kind="base"):
+    """{amp_fused, amp_unfused}: one GradScaler step each on a parameter set of its own (gradients stay in memory: unscale_ shrinks
+    them call after call towards zero, which changes no traffic), and the number of elements with a gradient."""
+    import torch
+    import lamb_util as U
+    from ance_amd.optim import Lamb
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(2)
+
+    class UnfusedLamb(Lamb):  # the optimizer as it was before it spoke the scaler's contract: GradScaler takes its unfused branch
+        _step_supports_amp_scaling = False
+
+    legs, n = {}, 0
+    for name, cls in (("amp_fused", Lamb), ("amp_unfused", UnfusedLamb)):
+        groups, n = [], 0
+        for gname, plist in U.roberta_param_groups(kind):
+            ps = []
+            for pname, t, has_grad in plist:
+                p = torch.nn.Parameter(t.to(dev))
+                if has_grad:
+                    p.grad = torch.randn(t.shape, device=dev, generator=gen) * 1e-3
+                    n += p.numel()
+                ps.append(p)
+            groups.append(dict(params=ps))
+        opt = cls(groups, lr=1e-4, eps=1e-6, max_grad_norm=1.0)
+        scaler = torch.amp.GradScaler("cuda", init_scale=2.0 ** 16, growth_interval=1 << 30)
+        scaler.scale(torch.zeros((), device=dev))
+
+        def fused(opt=opt, scaler=scaler):
+            scaler.step(opt)
+            scaler.update()
+
+        def unfused(opt=opt, scaler=scaler):
+            scaler.unscale_(opt)
+            scaler.step(opt)
+            scaler.update()
+
+        legs[name] = fused if cls is Lamb else unfused
+    return legs, n
+
+
+def bench_amp(rounds, steps, warmup):
+    legs, n = amp_legs("base")
+    res = dict(n_elements_with_grad=n, scale=65536.0, max_grad_norm=1.0, legs=alternate(legs, rounds, steps, warmup))
+    res["amp_unfused_minus_amp_fused_ms"] = round(res["legs"]["amp_unfused"]["median_ms"] - res["legs"]["amp_fused"]["median_ms"], 4)
+    res["largest_spread_of_the_alternations_ms"] = max(leg["spread_ms"] for leg in res["legs"].values())
+    return res
+
+
 def objective_cases():
     import torch
     import torch.nn.functional as F
@@ -167,7 +224,7 @@ def trace_calls(spec, calls):
     the launches per call are the trace's kernel count divided by `calls`."""
     import torch
     case, variant = spec.split(":")
-    fn = objective_cases()[case][0 if variant == "ance_amd" else 1]
+    fn = amp_legs()[0][variant] if case == "amp" else objective_cases()[case][0 if variant == "ance_amd" else 1]
     torch.cuda.synchronize()
     print("TRACE_BEGIN %s calls=%d" % (spec, calls), flush=True)
     for _ in range(calls):
@@ -182,7 +239,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="alternations of the variants (at least three)")
     ap.add_argument("--sizes", default="base,large")
     ap.add_argument("--skip-objectives", action="store_true")
-    ap.add_argument("--trace", default=None, help="CASE:VARIANT (VARIANT ance_amd or torch_expression): only call it, for a kernel trace")
+    ap.add_argument("--trace", default=None, help="CASE:VARIANT (VARIANT ance_amd or torch_expression; amp:amp_fused or amp:amp_unfused): "
+                    "only call it, for a kernel trace")
+    ap.add_argument("--skip-amp", action="store_true")
+    ap.add_argument("--amp-launches", default=None, help="FUSED,UNFUSED: traced kernel launches per GradScaler step, recorded in the output")
     ap.add_argument("--trace-calls", type=int, default=10)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_step_tail.json"))
     a = ap.parse_args()
@@ -192,12 +252,19 @@ def main():
         trace_calls(a.trace, a.trace_calls)
         return
     assert a.rounds >= 3
-    out = dict(what="the tail of a trainer's step: clip + LAMB, and the objectives' forward + backward",
+    out = dict(what="the tail of a trainer's step: clip + LAMB (also under a GradScaler), and the objectives' forward + backward",
                device=torch.cuda.get_device_name(0), torch=torch.__version__, steps=a.steps, warmup=a.warmup, rounds=a.rounds,
                hbm_floor_basis="6.3 TB/s achievable copy rate", optimizer={})
     for kind in [k for k in a.sizes.split(",") if k]:
         out["optimizer"][kind] = bench_optimizer(kind, a.rounds, a.steps, a.warmup)
         print(kind, json.dumps(out["optimizer"][kind]), flush=True)
+        torch.cuda.empty_cache()
+    if not a.skip_amp:
+        out["amp"] = bench_amp(a.rounds, a.steps, a.warmup)
+        if a.amp_launches:
+            fused, unfused = (float(x) for x in a.amp_launches.split(","))
+            out["amp"]["traced_launches_per_step"] = dict(amp_fused=fused, amp_unfused=unfused)
+        print("amp", json.dumps(out["amp"]), flush=True)
         torch.cuda.empty_cache()
     if not a.skip_objectives:
         out["objectives"] = bench_objectives(a.rounds, a.steps, a.warmup)
