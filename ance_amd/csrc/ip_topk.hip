@@ -359,14 +359,7 @@ int exact_scan_fallback(const float *d_x, int64_t n, const float *d_q, int64_t n
 using namespace ance;
 
 namespace ance {
-size_t ip_index_bytes(int64_t n, int d);
-int ip_index_build(const float *d_x, int64_t n, int d, void *d_index, size_t index_bytes, hipStream_t st);
-size_t ip_topk_fast_workspace_bytes(int64_t n, int64_t nq, int d, int k, bool with_index);
-int ip_topk_fast(const float *d_x, int64_t n, int64_t row_base, const void *d_index, const float *d_q, int64_t nq, int d, int k,
-                 float *d_out_d, int64_t *d_out_i, void *d_workspace, size_t workspace_bytes, hipStream_t st);
-void set_fast_stamps(unsigned long long *d_stamps);
-void reload_fast_knobs();
-void reload_gemm_knobs();
+void reload_gemm_knobs();  // gemm256_f16.hip
 }
 
 extern "C" void ance_debug_search_stamps(void *d_stamps) { ance::set_fast_stamps(reinterpret_cast<unsigned long long *>(d_stamps)); }

@@ -1,9 +1,23 @@
-// Device code shared by the exact-scan (ip_topk.hip) and the split-precision (ip_topk_fast.hip)
-// searches: wave-level exact k-th selection over packed keys, LDS bitonic sort, list finalisation.
+// Device code shared by the exact-scan (ip_topk.hip) and the two-precision (ip_topk_fast.hip) searches: wave
+// reductions, wave-level exact k-th selection over packed keys, LDS bitonic sort, list finalisation -- and the host
+// entry points each of the two files offers the other.
 #pragma once
 #include "common.h"
 
 namespace ance {
+
+// Butterfly reductions over the 64 lanes of a wave: every lane ends with the result.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off));
+    return v;
+}
 
 // k-th largest selection + compaction of one query's candidate list, by one wave.
 // keys are distinct (distinct rows), 0 is the empty sentinel.
@@ -65,7 +79,7 @@ __device__ __forceinline__ void bitonic_sort_desc(u64 *s, int P2) {
     }
 }
 
-// ---- duplicate classes of a search image (ip_topk_fast.hip) ----------------------------------------------
+// ---- duplicate classes of a search image (search_image.h) ------------------------------------------------
 constexpr int DEDUP_MAXC = 4;       // classes of bit-identical rows collapsed per shard
 constexpr int DEDUP_MEMCAP = 1024;  // member ids kept per class (the smallest ones: no list needs more than k)
 struct DedupHeader {                // first 256 bytes of a search image
@@ -167,7 +181,6 @@ __global__ void __launch_bounds__(256) topk_finalize_kernel(const u64 *keys, con
             out_i[o] = row_base + (int64_t)key_row(v);
         }
     }
-    (void)P2;
 }
 
 // top-k keys of nq lists of m keys each (unsorted in, sorted out): the per-query exact-scan lists of the fast path
@@ -180,7 +193,6 @@ static __global__ void __launch_bounds__(256) topk_reduce_keys_kernel(const u64 
     bitonic_sort_desc(s, P2);
     for (int i = threadIdx.x; i < k; i += blockDim.x) out[(size_t)blockIdx.x * k + i] = i < P2 ? s[i] : 0ull;
 }
-
 
 inline int next_pow2(int v) {
     int p = 1;
@@ -199,5 +211,15 @@ int launch_reduce_keys(const u64 *keys, int nq_max, int m, int k, u64 *out, cons
 size_t exact_scan_fallback_bytes(int64_t n, int64_t nq, int k);
 int exact_scan_fallback(const float *d_x, int64_t n, const float *d_q, int64_t nq, int64_t nq_plan, int d, int k, void *d_ws,
                         const int *only_if, const int *nq_dev, const u64 **part_out, int *m_out, hipStream_t st);
+
+// ---- the two-precision search (ip_topk_fast.hip), as ip_topk.hip dispatches to it ------------------------
+size_t ip_index_bytes(int64_t n, int d);
+int ip_index_build(const float *d_x, int64_t n, int d, void *d_index, size_t index_bytes, hipStream_t st);
+size_t ip_topk_fast_workspace_bytes(int64_t n, int64_t nq, int d, int k, bool with_index);
+// d_index: a search image built by ip_index_build for exactly (d_x, n, d), or NULL (then it is built inside the workspace)
+int ip_topk_fast(const float *d_x, int64_t n, int64_t row_base, const void *d_index, const float *d_q, int64_t nq, int d, int k,
+                 float *d_out_d, int64_t *d_out_i, void *d_workspace, size_t workspace_bytes, hipStream_t st);
+void set_fast_stamps(unsigned long long *d_stamps);
+void reload_fast_knobs();
 
 }  // namespace ance

@@ -5,7 +5,7 @@ Call sites it replaces: drivers/run_ann_data_gen.py:269-276,303 and
 drivers/run_ann_data_gen_dpr.py:238-252.  The corpus lives in HBM as fp32 [n, d].  ``add`` is lazy;
 the first search builds the shard's search image once (``ance_ip_index_build``: fp16 rows, duplicate
 classes) and every later search reuses it, like faiss reuses what ``add`` built.  Search itself is
-``ance_ip_topk_indexed``: the two-precision kernel of csrc/ip_topk_fast.hip (fp16 MFMA filter, exact
+``ance_ip_topk_indexed``: the two-precision search of csrc/ip_topk_fast.hip and csrc/search_*.h (fp16 MFMA filter, exact
 fp32 re-scoring) where the shape allows it -- d % 128 == 0, d <= 2048, k <= ``FAST_MAX_K``, n >= 4096 --
 and the fp32-MFMA scan of csrc/ip_topk.hip otherwise (k up to ``MAX_K``); both return the same bits.
 Results follow the canonical order (score desc, row id asc), ``I = -1`` / ``D = -FLT_MAX`` when

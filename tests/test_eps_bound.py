@@ -1,4 +1,4 @@
-"""The error slack of the two-precision search (ance_amd/csrc/ip_topk_fast.hip) restated and attacked on the CPU.
+"""The error slack of the two-precision search (ance_amd/csrc/search_query.h) restated and attacked on the CPU.
 
 The fast search filters the corpus with  s~ = b + fp16(dq) . fp16(x')  (fp32 accumulation starting from b), where
 x' = fl32(x - mu) is the row centred on the shard mean, dq = fl32(q - mq) the query centred on the mean query of the call
@@ -15,7 +15,7 @@ import re
 import numpy as np
 import pytest
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ance_amd", "csrc", "ip_topk_fast.hip")
+SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ance_amd", "csrc", "search_query.h")
 
 
 def slack(d):

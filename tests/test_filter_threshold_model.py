@@ -1,4 +1,4 @@
-"""CPU model of the threshold rules of the two-precision search (csrc/ip_topk_fast.hip): the filter keeps a row when its
+"""CPU model of the threshold rules of the two-precision search (csrc/search_filter.h, csrc/search_rescore.h): the filter keeps a row when its
 approximate score is >= t~ - 2 eps, where t~ is the k-th best approximate score over ANY subset of the rows seen so far
 (own list, another split's list, the union of two lists in rescore_kernel).  With |s~ - s| <= eps for every row, no row
 of the exact top-k may ever be dropped, whatever the order of the rows, the prune points and the subsets are.  The model

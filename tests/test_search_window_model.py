@@ -1,4 +1,4 @@
-"""CPU model of the corpus-tile sequence of ip_topk_fast_kernel (csrc/ip_topk_fast.hip): every workgroup
+"""CPU model of the corpus-tile sequence of ip_topk_fast_kernel (csrc/search_filter.h): every workgroup
 (query tile, split) walks the windows in order and inside a window the Ws tiles of its split.  The model
 restates the kernel's index arithmetic line by line and checks what the kernel relies on: the splits of one
 query tile cover every corpus tile exactly once, a workgroup arrives at every window boundary that is not
