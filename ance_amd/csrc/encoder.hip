@@ -404,7 +404,7 @@ GemmArgs vt_args(const Rows<FORM_PLANES> &x, int Tpad, int T, float eps, const L
     return G;
 }
 
-// FFN1: intermediate.dense + GELU of LN(xa) (attention.output.LayerNorm folded in); n_split: gemm256_f16.hip, tile_of_block
+// FFN1: intermediate.dense + GELU of LN(xa) (attention.output.LayerNorm folded in); n_split: gemm256_tile.h, tile_of_block
 template <int H, int FORM>
 GemmArgs ffn1_args(const Rows<FORM> &xa, int M, float eps, const LayerW &W, int I, _Float16 *ffn, int n_split, unsigned *faults) {
     constexpr bool P = FORM == FORM_PAIR;
@@ -444,7 +444,7 @@ int forward_split(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, c
     const bool cls_tail = e->cls_tail;
     const int S_pad = (int)align_up((size_t)S, 256);
     const Rows<FORM_PAIR> cls = V.cls(S_pad, H);
-    const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_f16.hip: tile_of_block)
+    const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_tile.h: tile_of_block)
     for (int li = 0; li < D.n_layers; ++li) {
         const LayerW &W = e->layers[li];
         const bool tail = cls_tail && li == D.n_layers - 1;
@@ -513,7 +513,7 @@ int forward_fp16(AnceEncoder *e, const AnceEncoder::Lane &LN, hipStream_t st, co
     const bool cls_tail = e->cls_tail;
     const int S_pad = (int)align_up((size_t)S, 256);
     const Rows<FORM_PLANES> cls = V.cls(S_pad, H);
-    const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_f16.hip: tile_of_block)
+    const int n_split = (I / 256) % 2 == 0 ? 2 : 0;  // FFN1: N-split tile order (gemm256_tile.h: tile_of_block)
     for (int li = 0; li < D.n_layers; ++li) {
         const LayerW &W = e->layers[li];
         const bool tail = cls_tail && li == D.n_layers - 1;

@@ -7,6 +7,8 @@
 //   EPI_RES32  out32 = acc + bias[n] + res32[m][n]                        attention.output.dense / output.dense
 //   (ance_debug_gemm reaches the main loop through these three; the encoder runs the folded-LayerNorm forms EPI_*_F /
 //   EPI_RESLN of gemm_f16.h and the split GEMM below)
+// This file: the three kernels, their table and their launch.  gemm256_tile.h: tile order, LDS maps, parameter block.  pipe256.h:
+// the main loop.  gemm256_epilogue.h / gemm256_epilogue_split.h: the epilogues.  gemm256_hooks.hip: the C-ABI test hooks.
 //
 // Why this tile: a 128 x 128 tile has 64 FLOP per staged byte, i.e. 39 TB/s of L2 traffic at the
 // 2.5 PFLOP/s MFMA rate -- more than the 34.5 TB/s the eight L2s deliver -- so it is L2-bound by
@@ -26,18 +28,13 @@
 #include "common.h"
 #include "gemm_f16.h"
 #include "gemm256_epilogue.h"
+#include "gemm256_epilogue_split.h"
+#include "gemm256_tile.h"
 #include "pipe256.h"
 #include <stdlib.h>
-#include <string.h>
 
 namespace ance {
 namespace {
-
-constexpr int TM = 256, TN = 256, TK = 64;      // TK halves = 128 B per LDS row
-constexpr int OPER_HALVES = 256 * TK;           // one operand tile (32 KiB)
-constexpr int STAGE_HALVES = 2 * OPER_HALVES;   // A-rows tile + B-rows tile (64 KiB)
-constexpr int G256_THREADS = 512;
-constexpr size_t G256_LDS_BYTES = (size_t)2 * STAGE_HALVES * sizeof(_Float16);  // 128 KiB
 
 // fp16 GEMM: operands through buffer descriptors (PipeSrcDesc), epilogue passes ordered inside the wave instead of by workgroup
 // barriers.
@@ -49,33 +46,6 @@ __device__ unsigned long long *g_gemm_stamps = nullptr;
 #else
 #define GSTAMP(slot) do { } while (0)
 #endif
-
-// XCD-aware tile order (speed only).  Blocks b, b + 8, ... share an XCD (and its 4 MiB L2).  The dimension with more tiles
-// is dealt round-robin to the XCDs, the other one is swept fastest, so the panel of the outer dimension stays in that XCD's L2
-// while the inner panels stream through it.  N-SPLIT (round 4): when the inner dimension's operand does not fit the L2 -- FFN1:
-// 12 weight tiles x 384 KiB = 4.5 MiB, re-fetched for every token panel: 994 MB of L2 fills + writes per launch against
-// 510 MB algorithmic (profiles/pmc_traffic.json, r03) -- the XCDs pair up: XCD x sweeps only the N-tiles of half x & 1 (2.25 MiB,
-// resident) for the token panels = x >> 1 (mod 4).  A token panel is then fetched by two XCDs instead of one, the weights
-// by every XCD once.
-__device__ __forceinline__ bool tile_of_block(const GemmArgs &G, int b, int *mt_, int *nt_) {
-    const int NT = G.N / TN, MT = G.M / TM;
-    const int xcd = b & 7, jx = b >> 3;
-    int mt, nt;
-    if (G.n_split == 2) {
-        const int nh = NT >> 1;
-        mt = (jx / nh) * 4 + (xcd >> 1);
-        nt = (xcd & 1) * nh + jx % nh;
-    } else if (MT >= NT) {
-        mt = (jx / NT) * 8 + xcd;
-        nt = jx % NT;
-    } else {
-        nt = (jx / MT) * 8 + xcd;
-        mt = jx % MT;
-    }
-    *mt_ = mt;
-    *nt_ = nt;
-    return mt < MT && nt < NT;
-}
 
 // HW: the hidden width of the slice partials the folded epilogues read and write (gemm_f16.h: PartFormat)
 template <int EPI, int HW = 768>
@@ -95,17 +65,10 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
         for (int y = 0; y < 4; ++y) acc[x][y] = f32x16{0};
     Pipe256T<PipeSrcDesc> P;
     P.init(smem, w, l);
-    // descriptors of this tile's 256 rows of each operand (bases are wave-uniform: kernel arguments and blockIdx)
-    P.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.A + (size_t)m0 * G.lda), 0, (int)(256u * (uint32_t)G.lda * 2u), 0x00020000);
-    P.S.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.B + (size_t)n0 * G.ldb), 0, (int)(256u * (uint32_t)G.ldb * 2u), 0x00020000);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r = pipe_stage_row(w, l, j), ch = pipe_stage_chunk(r, l);
-            P.S.voff[h][j] = (uint32_t)(pipe_a_tile_row(h, r) * G.lda + ch) * 2u;
-            P.S.voff[2 + h][j] = (uint32_t)(pipe_b_tile_row(h, r) * G.ldb + ch) * 2u;
-        }
+    // descriptors of this tile's 256 rows of each operand (bases are wave-uniform: kernel arguments and blockIdx), staging offsets
+    P.S.ra = pipe_rows_rsrc(G.A, m0, G.lda);
+    P.S.rb = pipe_rows_rsrc(G.B, n0, G.ldb);
+    pipe_fill_voff(P.S.voff, w, l, G.lda, G.ldb);
     constexpr bool EPB = EPI >= EPI_RESLN;  // folded-LayerNorm epilogues: parameter block by LDS-DMA, ahead of the pipeline's own
 #ifdef ANCE_MEASURE
     unsigned long long *stamps_ = (EPI == EPI_RESLN && G.stamp) ? g_gemm_stamps : nullptr;
@@ -131,10 +94,10 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
             const int i = l & 31;
             auto tok_wide = [&](int t) { return __builtin_fabsf(st[2 * t]) * st[2 * t + 1] > FOLD_WIDE_MEAN; };
             if constexpr (EPI == EPI_VT_F) {  // tokens are the B-operand rows n = wn * 64 + x * 32 + i
-                P2.S.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.tok_lo + (size_t)n0 * G.ldb), 0, (int)(256u * (uint32_t)G.ldb * 2u), 0x00020000);
+                P2.S.rb = pipe_rows_rsrc(G.tok_lo, n0, G.ldb);
                 P2.keep_b = (tok_wide((w & 3) * 64 + i) ? 1u : 0u) | (tok_wide((w & 3) * 64 + 32 + i) ? 2u : 0u);
             } else {                          // tokens are the A-operand rows m = wm * 128 + y * 32 + i
-                P2.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.tok_lo + (size_t)m0 * G.lda), 0, (int)(256u * (uint32_t)G.lda * 2u), 0x00020000);
+                P2.S.ra = pipe_rows_rsrc(G.tok_lo, m0, G.lda);
                 unsigned k = 0;
 #pragma unroll
                 for (int y = 0; y < 4; ++y) k |= tok_wide((w >> 2) * 128 + y * 32 + i) ? (1u << y) : 0u;
@@ -149,10 +112,10 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_f16_desc_kernel(const
     }
     GSTAMP(2);
 #ifdef ANCE_MEASURE
-    gemm256_epilogue<EPI, true, HW>(G, acc, smem_f, m0, n0, w, l, stamps_ ? stamps_ + (size_t)blockIdx.x * 8 + 4 : nullptr);
+    gemm256_epilogue<EPI, HW>(G, acc, smem_f, m0, n0, w, l, stamps_ ? stamps_ + (size_t)blockIdx.x * 8 + 4 : nullptr);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
-    gemm256_epilogue<EPI, true, HW>(G, acc, smem_f, m0, n0, w, l);
+    gemm256_epilogue<EPI, HW>(G, acc, smem_f, m0, n0, w, l);
 #endif
     GSTAMP(3);
 }
@@ -187,16 +150,9 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const Ge
         for (int y = 0; y < 8; ++y) acc[x][y] = f32x4{0.f, 0.f, 0.f, 0.f};
     Pipe256T<PipeSrcDesc, true> P;
     P.init(smem, w, l);
-    P.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.A + (size_t)m0 * G.lda), 0, (int)(256u * (uint32_t)G.lda * 2u), 0x00020000);
-    P.S.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.B + (size_t)n0 * G.ldb), 0, (int)(256u * (uint32_t)G.ldb * 2u), 0x00020000);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r = pipe_stage_row(w, l, j), ch = pipe_stage_chunk(r, l);
-            P.S.voff[h][j] = (uint32_t)(pipe_a_tile_row(h, r) * G.lda + ch) * 2u;
-            P.S.voff[2 + h][j] = (uint32_t)(pipe_b_tile_row(h, r) * G.ldb + ch) * 2u;
-        }
+    P.S.ra = pipe_rows_rsrc(G.A, m0, G.lda);
+    P.S.rb = pipe_rows_rsrc(G.B, n0, G.ldb);
+    pipe_fill_voff(P.S.voff, w, l, G.lda, G.ldb);
     const float winv = G.wscale_inv ? *G.wscale_inv : 1.0f;  // wave-uniform: a scalar load, long back when the epilogue starts
 #ifdef ANCE_MEASURE
     unsigned long long *stamps_ = G.stamp ? g_gemm_stamps : nullptr;  // [block][8]: start, main loop done, statistics, end
@@ -220,77 +176,20 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_kernel(const Ge
 // the next tile's first operand bytes in flight and the next K loop starts where a steady-state K-tile starts: no pipeline fill
 // (3 us of a 58-62 us tile at K = 768), no workgroup launch between two tiles, no launch ramp; the epilogue's stores drain under
 // the next tile's first MFMA phase.  What that costs is LDS: the stage buffers are busy during the epilogue, so the epilogue lives
-// in a quarter of the slab space (gemm256_epilogue_split32: 32 x 32 passes) --
-//   [0, 128 KiB)          stage buffers; the A-half1 slot of buffer 1 is free between two tiles (K-tile 1's A-half1 is staged by
-//                         P0 of K-tile 0): slabs of waves 0-2
-//   STATS 2 KiB, VEC 3 KiB   (mean, rstd) of the tile's 256 tokens; bias | csum or gamma | beta of its 256 features
-//   R 27 KiB              during the K loop the slice partials of the tile's tokens (24 KiB at either hidden width: PART_FLOATS
-//                         floats per token; LDS-DMA issued after the previous
-//                         epilogue, retired by the pipeline's counted waits); during the epilogue the slabs of waves 3-7
-// = 160 KiB exactly.  Tile order: workgroup b is on XCD b & 7 (round-robin dispatch) and takes the virtual blocks
+// in a quarter of the slab space (gemm256_epilogue_split32: 32 x 32 passes; LDS map, EPS_*: gemm256_tile.h), 160 KiB in all.
+// Tile order: workgroup b is on XCD b & 7 (round-robin dispatch) and takes the virtual blocks
 // ((i * slots + (b >> 3)) << 3) | xcd, i = 0, 1, ... of tile_of_block's order -- at any time the 32 CUs of an XCD work on the 32
 // consecutive blocks the launch-per-tile kernel would have had in flight there, so the L2 behaviour (and the N-split order of FFN1)
 // carries over.  Results are bit-identical to the kernel above (same K order, same epilogue arithmetic, same reduction trees).
-constexpr int EPS_STATS = 32768;                 // floats: above the 128 KiB of stage buffers
-constexpr int EPS_VEC = EPS_STATS + 512;
-constexpr int EPS_R = EPS_VEC + 768;             // 27,648 bytes: slice partials (24 KiB) | slabs of waves 3-7 (5 x 4,608 B)
-constexpr size_t GS_LDS_BYTES = (size_t)(EPS_R + 256 * 24 + 768) * sizeof(float);  // 163,840
-static_assert(GS_LDS_BYTES == 160 * 1024, "the streaming kernel uses the whole LDS of a CU");
-static_assert(256 * PART_FLOATS == 256 * 24 && 2 * PartFormat<768>::N <= PART_FLOATS && 2 * PartFormat<1024>::N <= PART_FLOATS,
-              "the slice partials of 256 tokens fill R at hidden 768 and fit it at hidden 1024");
-static_assert(5 * EPS_SLAB_FLOATS <= 256 * 24 + 768 && 3 * EPS_SLAB_FLOATS * 4 <= 16384, "slab layout");
-#ifndef ANCE_STREAM_LOOSE_FIRST
-#define ANCE_STREAM_LOOSE_FIRST 1  // 1: K-tile 0 of a prefetched tile does not wait for the previous epilogue's stores (pipe256.h: tile2); 0: steady-state waits
-#endif
-// vector-memory operations EVERY wave issues between the hand-over's last LDS-DMA and K-tile 0 of the next output tile: the
-// epilogue's stores (gemm256_epilogue_split32: 8 passes x 4 16-byte stores of fp32 rows for QKV, 8 x 2 x (hi + lo) for the pair rows of
-// GELU: 32 either way) and the three LDS-DMAs of the slice partials (eps_issue; the vector DMAs are issued by two waves only and do not
-// count)
-constexpr int EPS_FOREIGN_OPS = 32 + 3;
-
-template <int EPI_>
-__device__ __forceinline__ void eps_issue(const GemmArgs &G, float *smem_f, int m0, int n0, int w, int l) {
-    typedef __attribute__((address_space(3))) void lds_t;
-    typedef const __attribute__((address_space(1))) void glb_t;
-    const float *psrc = G.part_in + (size_t)m0 * PART_FLOATS;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int piece = w + 8 * j;  // 24 pieces of 1 KiB
-        __builtin_amdgcn_global_load_lds((glb_t *)(psrc + piece * 256 + l * 4), (lds_t *)(smem_f + EPS_R + piece * 256), 16, 0, 0);
-    }
-    if (w == 0) __builtin_amdgcn_global_load_lds((glb_t *)(G.bias + n0 + l * 4), (lds_t *)(smem_f + EPS_VEC), 16, 0, 0);
-    if (w == 1) __builtin_amdgcn_global_load_lds((glb_t *)(G.csum + n0 + l * 4), (lds_t *)(smem_f + EPS_VEC + 256), 16, 0, 0);
-}
-
-// the kernel's GemmArgs re-read from the kernarg segment (first argument) behind an opaque pointer: see the call site
-__device__ __forceinline__ GemmArgs kernarg_reload(const GemmArgs &G) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) GemmArgs *kernarg_ptr_t;
-    kernarg_ptr_t gp = (kernarg_ptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(gp));
-    (void)G;
-    return *gp;
-#else
-    return G;
-#endif
-}
-
-// workgroup barrier that does NOT drain the vector-memory counter (the next tile's LDS-DMAs and this tile's stores stay in flight)
-__device__ __forceinline__ void eps_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 template <int EPI, int HW = 768>
-__global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(const GemmArgs G, const int n_blocks) {
+__global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(const GemmArgs G) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     _Float16 *smem = reinterpret_cast<_Float16 *>(smem_f);
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l = tid & 63;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
+    const int n_blocks = gemm256_virtual_blocks(G);
     int round = 0;
     // next valid tile of this workgroup's sequence (virtual blocks past the matrix -- the padding of tile_of_block's order -- are skipped)
     auto next_tile = [&](int *mt, int *nt) -> bool {
@@ -305,23 +204,15 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(c
     if (!next_tile(&mt, &nt)) return;
     Pipe256T<PipeSrcStream, true> P;
     P.init(smem, w, l);
-    P.S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.A), 0, (int)((uint32_t)G.M * (uint32_t)G.lda * 2u), 0x00020000);
-    P.S.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(G.B), 0, (int)((uint32_t)G.N * (uint32_t)G.ldb * 2u), 0x00020000);
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r = pipe_stage_row(w, l, j), ch = pipe_stage_chunk(r, l);
-            P.S.voff[h][j] = (uint32_t)(pipe_a_tile_row(h, r) * G.lda + ch) * 2u;
-            P.S.voff[2 + h][j] = (uint32_t)(pipe_b_tile_row(h, r) * G.ldb + ch) * 2u;
-        }
+    P.S.ra = pipe_rows_rsrc(G.A, 0, G.lda, (uint32_t)G.M);  // the whole matrices: tiles are SGPR offsets (PipeSrcStream)
+    P.S.rb = pipe_rows_rsrc(G.B, 0, G.ldb, (uint32_t)G.N);
+    pipe_fill_voff(P.S.voff, w, l, G.lda, G.ldb);
     const int NK = G.K / 32;  // K-tile = 64 halves of a blocked pair row = 32 k of hi and lo
     P.S.NK = NK;
     P.S.a_cur = P.S.a_nxt = (uint32_t)mt * 256u * (uint32_t)G.lda * 2u;
     P.S.b_cur = P.S.b_nxt = (uint32_t)nt * 256u * (uint32_t)G.ldb * 2u;
     const float winv = G.wscale_inv ? *G.wscale_inv : 1.0f;
-    // (slab of a wave: waves 0-2 in the A-half1 slot of stage buffer 1, waves 3-7 in R)
-    eps_issue<EPI>(G, smem_f, mt * TM, nt * TN, w, l);
+    pb_issue<EPI>(G, smem_f + EPS_R, smem_f + EPS_VEC, mt * TM, nt * TN, w, l);
     if constexpr (ANCE_STREAM_LOOSE_FIRST) P.prologue_landed(); else P.prologue();
     P.enter();
     for (;;) {
@@ -352,22 +243,16 @@ __global__ void __launch_bounds__(G256_THREADS, 2) gemm256_split_stream_kernel(c
         const GemmArgs Ge = kernarg_reload(G);
         // (mean, rstd) of the tile's tokens from their slice partials (in R since before this K loop), published by one barrier;
         // after it R belongs to the slabs
-        if (tf < 256) {
-            float mean, rstd;
-            stats_from_parts<HW>(smem_f + EPS_R + tf * PART_FLOATS, Ge.ln_eps, &mean, &rstd);
-            smem_f[EPS_STATS + 2 * tf] = mean;
-            smem_f[EPS_STATS + 2 * tf + 1] = rstd;
-        }
+        if (tf < 256) (void)pb_token_stats<HW>(smem_f + EPS_R, smem_f + EPS_STATS, tf, Ge.ln_eps);
         eps_barrier();
-        float *slab = w < 3 ? smem_f + (PIPE_BUF_HALVES + PIPE_HALF_HALVES) / 2 + w * EPS_SLAB_FLOATS : smem_f + EPS_R + (w - 3) * EPS_SLAB_FLOATS;
-        gemm256_epilogue_split32<EPI>(Ge, acc, slab, smem_f + EPS_STATS, smem_f + EPS_VEC, mt * TM, nt * TN, w, lf, winv);
+        gemm256_epilogue_split32<EPI>(Ge, acc, eps_slab(smem_f, w), smem_f + EPS_STATS, smem_f + EPS_VEC, mt * TM, nt * TN, w, lf, winv);
         if (!have_n) break;
         eps_barrier();  // every wave is done with STATS, VEC and its slab: R and the A-half1 slot may be refilled
         mt = mtn;
         nt = ntn;
         P.S.a_cur = P.S.a_nxt;
         P.S.b_cur = P.S.b_nxt;
-        eps_issue<EPI>(Ge, smem_f, mt * TM, nt * TN, w, lf);
+        pb_issue<EPI>(Ge, smem_f + EPS_R, smem_f + EPS_VEC, mt * TM, nt * TN, w, lf);
         P.enter();
     }
 }
@@ -401,9 +286,18 @@ int device_cu_count() {
     return cus[dev];
 }
 
-// the kernels of one hidden width (gemm_f16.h: PartFormat); the plain epilogues (ance_debug_gemm) read no partials: 768 only
+// the kernels of one hidden width (gemm_f16.h: PartFormat); the plain epilogues (ance_debug_gemm) read no partials: 768 only.
+// stream: the persistent streaming form (EPI_S_QKV and EPI_S_GELU have one)
+typedef void (*gemm_kernel_t)(const GemmArgs);
 template <int HW>
-void (*gemm_kernel_of(int epi))(const GemmArgs) {
+gemm_kernel_t gemm_kernel_of(int epi, bool stream) {
+    if (stream) {
+        switch (epi) {
+            case EPI_S_QKV: return gemm256_split_stream_kernel<EPI_S_QKV, HW>;
+            case EPI_S_GELU: return gemm256_split_stream_kernel<EPI_S_GELU, HW>;
+            default: return nullptr;
+        }
+    }
     switch (epi) {
         case EPI_QK: return HW == 768 ? gemm256_f16_desc_kernel<EPI_QK> : nullptr;
         case EPI_GELU: return HW == 768 ? gemm256_f16_desc_kernel<EPI_GELU> : nullptr;
@@ -419,53 +313,44 @@ void (*gemm_kernel_of(int epi))(const GemmArgs) {
     }
 }
 
+// the dynamic-LDS limit of a kernel instance, set once per instance AND per device (common.h: attr_needed / attr_mark)
+bool dynamic_lds_ready(gemm_kernel_t k, unsigned long long *done, size_t bytes) {
+    if (!attr_needed(done)) return true;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+    attr_mark(done);
+    return true;
+}
+
 int launch256(int epi, const GemmArgs &G, hipStream_t st, int hw) {
-    const int MT = G.M / TM, NT = G.N / TN;
-    if (G.n_split != 0 && (G.n_split != 2 || (NT & 1) || epi < EPI_RESLN)) {
+    if (G.n_split != 0 && (G.n_split != 2 || ((G.N / TN) & 1) || epi < EPI_RESLN)) {
         set_last_error("gemm256: n_split needs an even number of N tiles and a descriptor-form kernel");
         return ANCE_E_INVALID;
     }
-    const unsigned blocks = G.n_split == 2 ? (unsigned)((MT + 3) / 4 * 4) * (unsigned)NT
-                            : MT >= NT     ? (unsigned)((MT + 7) / 8 * 8) * (unsigned)NT
-                                           : (unsigned)((NT + 7) / 8 * 8) * (unsigned)MT;
+    const unsigned blocks = (unsigned)gemm256_virtual_blocks(G);
     const int wi = hw == 1024 ? 1 : 0;  // instance set
-    void (*k)(const GemmArgs) = nullptr;
-    if (epi >= 0 && epi < EPI_COUNT && (hw == 768 || hw == 1024)) k = wi ? gemm_kernel_of<1024>(epi) : gemm_kernel_of<768>(epi);
+    const bool known = epi >= 0 && epi < EPI_COUNT && (hw == 768 || hw == 1024);
+    bool stream = (epi == EPI_S_QKV || epi == EPI_S_GELU) && gemm_stream_mode() == 1 && G.K >= 96 &&
+                  (uint64_t)G.M * (uint64_t)G.lda * 2u < (1ull << 31) && (uint64_t)G.N * (uint64_t)G.ldb * 2u < (1ull << 31);
+#ifdef ANCE_MEASURE
+    const bool stamped = epi == g_gemm_stamps_epi && g_gemm_stamps_host;
+    stream = stream && !stamped;
+#endif
+    const gemm_kernel_t k = !known ? nullptr : wi ? gemm_kernel_of<1024>(epi, stream) : gemm_kernel_of<768>(epi, stream);
     if (!k) {
         set_last_error("gemm256: bad epilogue or hidden width");
         return ANCE_E_INVALID;
     }
-    // the dynamic-LDS attribute is per template instance AND per device
-    static unsigned long long attr_done[2][EPI_COUNT] = {{0}};
-    if (attr_needed(&attr_done[wi][epi])) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(G256_LDS_BYTES + (size_t)EPB_FLOATS * sizeof(float))) != hipSuccess)
-            return check_launch("gemm256 attr");
-        attr_mark(&attr_done[wi][epi]);
-    }
-    if ((epi == EPI_S_QKV || epi == EPI_S_GELU) && gemm_stream_mode() == 1 && G.K >= 96 && (uint64_t)G.M * (uint64_t)G.lda * 2u < (1ull << 31) &&
-        (uint64_t)G.N * (uint64_t)G.ldb * 2u < (1ull << 31)
-#ifdef ANCE_MEASURE
-        && !(epi == g_gemm_stamps_epi && g_gemm_stamps_host)
-#endif
-    ) {
-        void (*ks)(const GemmArgs, int) =
-            wi ? (epi == EPI_S_QKV ? gemm256_split_stream_kernel<EPI_S_QKV, 1024> : gemm256_split_stream_kernel<EPI_S_GELU, 1024>)
-               : (epi == EPI_S_QKV ? gemm256_split_stream_kernel<EPI_S_QKV> : gemm256_split_stream_kernel<EPI_S_GELU>);
-        static unsigned long long sattr_done[2][2] = {{0, 0}, {0, 0}};
-        if (attr_needed(&sattr_done[wi][epi - EPI_S_QKV])) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS_LDS_BYTES) != hipSuccess)
-                return check_launch("gemm256 stream attr");
-            attr_mark(&sattr_done[wi][epi - EPI_S_QKV]);
-        }
+    const size_t lds = stream ? GS_LDS_BYTES : epi >= EPI_RESLN ? G256_EPB_LDS_BYTES : G256_LDS_BYTES;
+    static unsigned long long attr_done[2][2][EPI_COUNT] = {{{0}}};  // [stream][instance set][epilogue]
+    // (the launch-per-tile instances always ask for the parameter block's room, the plain epilogues launch without it)
+    if (!dynamic_lds_ready(k, &attr_done[stream][wi][epi], stream ? GS_LDS_BYTES : G256_EPB_LDS_BYTES)) return check_launch("gemm256 attr");
+    if (stream) {
         const unsigned cus = (unsigned)device_cu_count() & ~7u;  // one workgroup per CU (160 KiB of LDS each), a multiple of the 8 XCDs
-        const unsigned grid = blocks < cus ? blocks : cus;
-        hipLaunchKernelGGL(ks, dim3(grid), dim3(G256_THREADS), GS_LDS_BYTES, st, G, (int)blocks);
+        hipLaunchKernelGGL(k, dim3(blocks < cus ? blocks : cus), dim3(G256_THREADS), lds, st, G);
         return ANCE_OK;
     }
-    const size_t lds = epi >= EPI_RESLN ? G256_LDS_BYTES + (size_t)EPB_FLOATS * sizeof(float) : G256_LDS_BYTES;
 #ifdef ANCE_MEASURE
-    if (epi == g_gemm_stamps_epi && g_gemm_stamps_host) {
+    if (stamped) {
         GemmArgs G2 = G;
         G2.stamp = 1;
         hipLaunchKernelGGL(k, dim3(blocks), dim3(G256_THREADS), lds, st, G2);
@@ -505,92 +390,3 @@ extern "C" void ance_debug_gemm_stamps(void *d_stamps) {
 // (EPI_S_QKV 8, EPI_S_GELU 9, EPI_S_RESLN 10) fill slots 0..3: start, main loop done, statistics ready, stores drained
 extern "C" void ance_debug_gemm_stamps_epi(int epi) { ance::g_gemm_stamps_epi = epi; }
 #endif
-
-// Test hook (include/ance_amd.h): the fp16 GEMM kernel on caller-provided data.  ablate is kept for the ABI and must be 0.
-extern "C" int ance_debug_gemm(int ablate, int epi, const void *d_a_f16, const void *d_b_f16, int M, int N, int K,
-                               const float *d_bias, void *d_out, const float *d_res32, void *stream) {
-    using namespace ance;
-    if (ablate != 0 || !d_a_f16 || !d_b_f16 || !d_bias || !d_out || epi < 0 || epi > 2 || (epi == EPI_RES32 && !d_res32)) {
-        set_last_error("ance_debug_gemm: invalid argument");
-        return ANCE_E_INVALID;
-    }
-    GemmArgs G;
-    memset(&G, 0, sizeof(G));
-    G.A = (const _Float16 *)d_a_f16; G.lda = K; G.B = (const _Float16 *)d_b_f16; G.ldb = K;
-    G.M = M; G.N = N; G.K = K; G.bias = d_bias; G.ldc = N; G.scale = 1.0f; G.scale_cols = 0;
-    if (epi == EPI_RES32) { G.out32 = (float *)d_out; G.res32 = d_res32; }
-    else G.out16 = (_Float16 *)d_out;
-    ProfScope ps(PC_GEMM_FFN1, (hipStream_t)stream, 2.0 * M * (double)N * K);
-    int rc = launch_gemm_f16(epi, G, (hipStream_t)stream);
-    return rc ? rc : check_launch("ance_debug_gemm");
-}
-
-// Test hook (include/ance_amd.h): the SPLIT GEMM with each of its three epilogues on caller-provided pair operands (blocked pair
-// rows: ance_pair_layout); d_wscale_inv: optional device scalar the accumulators are multiplied by (the inverse of the power of
-// two the B operand was stored with).
-extern "C" int ance_debug_gemm_split(int epi, const void *d_a_pair, const void *d_b_pair, int M, int N, int K, const float *d_bias,
-                                     const float *d_vec1, const float *d_vec2, const float *d_part, float ln_eps,
-                                     const void *d_res_pair, void *d_out, float *d_part_out, const float *d_wscale_inv, void *stream) {
-    using namespace ance;
-    if (!d_a_pair || !d_b_pair || !d_bias || !d_vec1 || !d_part || !d_out || epi < EPI_S_QKV || epi > EPI_S_RESLN ||
-        (epi == EPI_S_RESLN && (!d_vec2 || !d_res_pair || !d_part_out || (N != 768 && N != 1024))) || K % 64 != 0) {
-        set_last_error("ance_debug_gemm_split: invalid argument");
-        return ANCE_E_INVALID;
-    }
-    GemmArgs G;
-    memset(&G, 0, sizeof(G));
-    G.A = (const _Float16 *)d_a_pair; G.lda = 2 * K; G.B = (const _Float16 *)d_b_pair; G.ldb = 2 * K;
-    G.M = M; G.N = N; G.K = K; G.bias = d_bias; G.part_in = d_part; G.ln_eps = ln_eps; G.wscale_inv = d_wscale_inv;
-    if (epi == EPI_S_QKV) {
-        G.csum = d_vec1; G.out32 = (float *)d_out; G.ldc = N;
-    } else if (epi == EPI_S_GELU) {
-        G.csum = d_vec1; G.out16 = (_Float16 *)d_out; G.ldc = 2 * N;
-    } else {
-        G.res_gamma = d_vec1; G.res_beta = d_vec2; G.res_hi = (const _Float16 *)d_res_pair; G.ldr = 2 * N;
-        G.out16 = (_Float16 *)d_out; G.ldc = 2 * N; G.part_out = d_part_out;
-    }
-    // EPI_S_RESLN at N = 1024: the partials (in and out) are the hidden-1024 format (gemm_f16.h: PartFormat)
-    int rc = launch_gemm_f16(epi, G, (hipStream_t)stream, epi == EPI_S_RESLN && N == 1024 ? 1024 : 768);
-    return rc ? rc : check_launch("ance_debug_gemm_split");
-}
-
-// Test hook (include/ance_amd.h): one GEMM instance the encoder dispatches (epilogues EPI_RESLN .. EPI_S_RESLN at hidden 768 or
-// 1024) with every GemmArgs field the encoder sets (encoder.hip: forward_split, forward_fp16).  Host code only: the kernels and
-// their launch are the encoder's own.
-extern "C" int ance_debug_gemm_hw(int epi, int hw, const AnceGemmDebugArgs *a, void *stream) {
-    using namespace ance;
-    const bool fold = epi == EPI_QK_F || epi == EPI_GELU_F || epi == EPI_VT_F;   // bias, csum (per feature)
-    const bool bad = !a || (hw != 768 && hw != 1024) || epi < EPI_RESLN || epi > EPI_S_RESLN || (a->n_split != 0 && a->n_split != 2) ||
-                     !a->a || !a->b || !a->bias || !a->part_in || !a->out ||
-                     ((fold || epi == EPI_S_QKV || epi == EPI_S_GELU) && !a->csum) ||
-                     (epi == EPI_QK_F && a->scale_cols % 64 != 0) ||
-                     (epi == EPI_VT_F && !a->col_map) ||
-                     (epi == EPI_RESLN && (!a->res_hi || !a->res_lo || !a->out_lo)) ||
-                     ((epi == EPI_RESLN || epi == EPI_S_RESLN) && (!a->res_gamma || !a->res_beta || !a->part_out || a->N != hw)) ||
-                     (epi == EPI_S_RESLN && !a->res_hi);
-    if (bad) {
-        set_last_error("ance_debug_gemm_hw: invalid argument");
-        return ANCE_E_INVALID;
-    }
-    GemmArgs G;
-    memset(&G, 0, sizeof(G));
-    G.A = (const _Float16 *)a->a; G.B = (const _Float16 *)a->b; G.lda = a->lda; G.ldb = a->ldb;
-    G.M = a->M; G.N = a->N; G.K = a->K;
-    G.bias = a->bias; G.csum = a->csum; G.part_in = a->part_in; G.ln_eps = a->ln_eps; G.tok_lo = (const _Float16 *)a->tok_lo;
-    G.scale = a->scale; G.scale_cols = a->scale_cols; G.col_map = a->col_map; G.n_valid = a->n_valid; G.ldc = a->ldc;
-    if (epi == EPI_S_QKV) G.out32 = (float *)a->out;
-    else G.out16 = (_Float16 *)a->out;
-    G.res_hi = (const _Float16 *)a->res_hi; G.res_lo = (const _Float16 *)a->res_lo; G.res_gamma = a->res_gamma; G.res_beta = a->res_beta;
-    G.out_lo = (_Float16 *)a->out_lo; G.part_out = a->part_out;
-    G.ldr = a->ldr; G.wscale_inv = a->wscale_inv; G.n_split = a->n_split;
-    int rc = launch_gemm_f16(epi, G, (hipStream_t)stream, hw);
-    return rc ? rc : check_launch("ance_debug_gemm_hw");
-}
-
-// Layout of the split mode's pair rows for tests and tools: column n of a W-wide row -> positions of its hi and lo halves in the
-// 2 W-half row, and the factor lo was multiplied by (1: unscaled; the round-4 A/B build reports 2048 and rows [hi (W) | lo' (W)]).
-extern "C" void ance_pair_layout(int n, int W, int *hi_col, int *lo_col, float *lo_scale) {
-    if (hi_col) *hi_col = ance::pair_hi_col(n, W);
-    if (lo_col) *lo_col = ance::pair_lo_col(n, W);
-    if (lo_scale) *lo_scale = ance::PAIR_LO_SCALE;
-}

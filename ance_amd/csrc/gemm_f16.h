@@ -9,10 +9,10 @@ namespace ance {
 // per-token (mu, r) and the per-feature c = csum.  EPI_RESLN: EPI_RES32 with the residual stream kept as an fp16 (hi, lo)
 // pair and the per-row statistics of its OUTPUT left as partial (mean, M2) of every 64-column slice (part_out).
 // The statistics a tile needs come from part_in: the slice partials of its 256 token rows are copied into LDS by LDS-DMA
-// before the main loop (with the tile's bias / csum / gamma / beta vectors) and combined there when the epilogue starts --
-// no LayerNorm kernel, no statistics kernel, no parameter load left on the epilogue's critical path.
+// before the main loop (with the tile's bias / csum / gamma / beta vectors: gemm256_tile.h) and combined there when the epilogue
+// starts -- no LayerNorm kernel, no statistics kernel, no parameter load left on the epilogue's critical path.
 // EPI_S_*: the SPLIT (fp32-grade) GEMM of gemm256_f16.hip -- operands are fp16 (hi, lo) pair rows, three MFMAs per k-step from four
-// staged operand tiles (pipe256.h: PAIR3); epilogues in gemm256_epilogue.h.
+// staged operand tiles (pipe256.h: PAIR3); epilogues in gemm256_epilogue_split.h.
 // EPI_QK / GELU / RES32: the plain epilogues, reached through ance_debug_gemm.  EPI_VT has no launch of its own: it names the
 // epilogue form EPI_VT_F runs.
 enum { EPI_QK = 0, EPI_GELU = 1, EPI_RES32 = 2, EPI_VT = 3, EPI_RESLN = 4, EPI_QK_F = 5, EPI_GELU_F = 6, EPI_VT_F = 7,
@@ -53,7 +53,7 @@ struct GemmArgs {
     int ldr;
     const float *wscale_inv;
     unsigned *range_faults;  // split epilogues: sticky counter of threads that stored a value outside the fp16 range (common.h: range_report), or null
-    int n_split;         // 2: N-split tile order (gemm256_f16.hip: tile_of_block; desc / split kernels only, N / 256 even); else 0
+    int n_split;         // 2: N-split tile order (gemm256_tile.h: tile_of_block; desc / split kernels only, N / 256 even); else 0
 #ifdef ANCE_MEASURE
     int stamp;           // measurement library: this launch leaves per-workgroup stamps (ance_debug_gemm_stamps)
 #endif
@@ -74,6 +74,18 @@ __device__ __forceinline__ float row16_sum(float x) {
     x += __builtin_amdgcn_update_dpp(0.f, x, 0x124, 0xF, 0xF, true);  // row_ror:4
     x += __builtin_amdgcn_update_dpp(0.f, x, 0x128, 0xF, 0xF, true);  // row_ror:8
     return x;
+}
+// the same for eight independent rows at once, INTERLEAVED: all eight take step 1, then all eight take step 2, ... (a DPP add
+// right behind the add that feeds it needs wait states; one row at a time the chain is serial)
+__device__ __forceinline__ void row16_sum8(float (&x)[8]) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) x[it] += __builtin_amdgcn_update_dpp(0.f, x[it], 0xB1, 0xF, 0xF, true);
+#pragma unroll
+    for (int it = 0; it < 8; ++it) x[it] += __builtin_amdgcn_update_dpp(0.f, x[it], 0x4E, 0xF, 0xF, true);
+#pragma unroll
+    for (int it = 0; it < 8; ++it) x[it] += __builtin_amdgcn_update_dpp(0.f, x[it], 0x124, 0xF, 0xF, true);
+#pragma unroll
+    for (int it = 0; it < 8; ++it) x[it] += __builtin_amdgcn_update_dpp(0.f, x[it], 0x128, 0xF, 0xF, true);
 }
 
 // Row statistics of the folded LayerNorm: every stream row carries PART_FLOATS floats of partial (mean, M2) pairs.  Hidden 768:
@@ -113,13 +125,6 @@ __device__ __forceinline__ void stats_from_parts(const float *pp, float eps, flo
     *mean = m;
     *rstd = rsqrtf(q * (1.0f / (float)HW) + eps);
 }
-
-// epilogue parameter block in LDS, above the 128 KiB of stage buffers (floats)
-constexpr int EPB_OFF = 32768;           // = 128 KiB
-constexpr int EPB_PART = 0;              // [256 tokens][24]: slice partials (24 KiB)
-constexpr int EPB_STATS = 256 * 24;      // [256][2]: (mean, rstd), filled when the epilogue starts
-constexpr int EPB_VEC = EPB_STATS + 512; // three vectors of 256 floats: bias, csum | gamma, beta
-constexpr int EPB_FLOATS = EPB_VEC + 768;
 
 // 256 x 256 x 64 tile kernel of gemm256_f16.hip (M, N multiples of 256, K of 64).
 // hw: the hidden width whose slice partials part_in / part_out hold (PartFormat): 768 or 1024.

@@ -40,7 +40,7 @@
 // 1.48-1.50 M; the wm stagger itself is worth 1.36 vs 1.78 M.
 // Needs NK >= 2 K-tiles.  The last two tiles are peeled (nothing left to stage, smaller counts).
 // tests/test_pipe_schedule_model.py replays these tables (prologue, steady state, peeled tiles, streaming hand-over, both wave
-// groups, every form -- the retired four-phase one included) on a slot timeline and asserts the RAW / WAR conditions for every
+// groups, every form -- the retired four-phase and early-staging ones included) on a slot timeline and asserts the RAW / WAR conditions for every
 // K-tile count.
 #pragma once
 #include "common.h"
@@ -58,17 +58,6 @@ constexpr size_t PIPE_LDS_BYTES = (size_t)2 * PIPE_BUF_HALVES * sizeof(_Float16)
 #ifndef PIPE_PAIR3_STAGE_GAP
 #define PIPE_PAIR3_STAGE_GAP 4  // MFMA pairs (16x16x32) between two LDS-DMA pieces of a PAIR3 phase: 128 cycles of the matrix pipe
 #endif
-#define PIPE_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-// PAIR3 only: where the LDS-DMAs of a K-tile are issued.  0: all eight between the MFMAs of the two MFMA half-phases (as the plain
-// coarse schedule).  1: A-half1 of tile t+1 and A-half0 of tile t+2 (two pieces each) in the READ half-phases of P0 / P1 -- after the
-// phase's ds_reads, before its barrier, i.e. by the wave of the SIMD that is NOT in its MFMA half-phase, whose 24 MFMAs take 768
-// cycles while a read half-phase needs ~250 -- and only B-half0 / B-half1 of tile t+2 between the MFMAs of P1.  2: all eight in the
-// read half-phases.  The early forms wait for their own ds_reads BEFORE the barrier (s_waitcnt lgkmcnt(0)), so that a read has
-// completed in its read half-phase: the WAR distance of an early restage is then one full slot for both wave groups
-// (tests/test_pipe_schedule_model.py replays all three forms).
-#ifndef PIPE_PAIR3_EARLY
-#define PIPE_PAIR3_EARLY 0
-#endif
 
 // Row of the 256-row operand tile held at row r of half-tile h.
 __device__ __forceinline__ int pipe_a_tile_row(int h, int r) { return (((r >> 6) * 2 + h) << 6) + (r & 63); }
@@ -80,6 +69,23 @@ __device__ __forceinline__ int pipe_b_tile_row(int h, int r) { return (((r >> 5)
 // source address because the LDS image of an LDS-DMA is lane-linear).
 __device__ __forceinline__ int pipe_stage_row(int w, int l, int j) { return (w + 8 * j) * 8 + (l >> 3); }
 __device__ __forceinline__ int pipe_stage_chunk(int row, int l) { return ((l & 7) ^ ((row >> 1) & 7)) * 8; }
+
+// Operand set-up every kernel on this loop shares.  pipe_rows_rsrc: the descriptor of `rows` rows (256: one operand tile) of a
+// row-major fp16 matrix with row stride ld, from row `first` on (wave-uniform arguments).  pipe_fill_voff: the per-lane byte
+// offsets [A0 A1 B0 B1][piece] inside a 256-row tile with row strides lda / ldb.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t pipe_rows_rsrc(const _Float16 *base, size_t first, int ld, uint32_t rows = 256u) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(base + first * ld), 0, (int)(rows * (uint32_t)ld * 2u), 0x00020000);
+}
+__device__ __forceinline__ void pipe_fill_voff(uint32_t (&voff)[4][2], int w, int l, int lda, int ldb) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int r = pipe_stage_row(w, l, j), ch = pipe_stage_chunk(r, l);
+            voff[h][j] = (uint32_t)(pipe_a_tile_row(h, r) * lda + ch) * 2u;
+            voff[2 + h][j] = (uint32_t)(pipe_b_tile_row(h, r) * ldb + ch) * 2u;
+        }
+}
 
 // Source policy of a plain GEMM through buffer descriptors: one descriptor per operand matrix (wave-uniform SGPRs), one
 // 32-bit per-lane byte offset per staged piece that never changes, the K offset in an SGPR -- no 64-bit address
@@ -195,6 +201,19 @@ struct Pipe256T {
         stage_piece<TYPE, 0>(t);
         stage_piece<TYPE, 1>(t);
     }
+    // LDS-DMA piece pc (0..5) of an MFMA half-phase, fenced off from the MFMAs around it: the two pieces of half-tile T0, then of
+    // T1, then of T2 (K-tile ts, offsets precomputed where the source policy does that)
+    template <int T0, int T1, int T2>
+    __device__ __forceinline__ void stage_ladder(int pc, int ts) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (pc == 0) stage_piece<T0, 0, true>(ts);
+        if (pc == 1) stage_piece<T0, 1, true>(ts);
+        if (pc == 2) stage_piece<T1, 0, true>(ts);
+        if (pc == 3) stage_piece<T1, 1, true>(ts);
+        if (pc == 4) stage_piece<T2, 0, true>(ts);
+        if (pc == 5) stage_piece<T2, 1, true>(ts);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     template <int H>
     __device__ __forceinline__ void read_a(int t) {
         const _Float16 *base = smem + (t & 1) * PIPE_BUF_HALVES + H * PIPE_HALF_HALVES;
@@ -257,17 +276,7 @@ struct Pipe256T {
                 const int hb = (q / 24) ^ YH, p = (q / 8) % 3, xb = (q >> 2) & 1, yy = q & 3;
                 const f16x8 &bf = hb == 0 ? qbk[xb][p == 2] : qb[xb][p == 2];
                 acc[2 * hb + xb][4 * YH + yy] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf, qa[yy][p == 1], acc[2 * hb + xb][4 * YH + yy], 0, 0, 0);
-                if (q % GAP2 == 1 && q / GAP2 < 2 * n_stage) {
-                    const int pc = q / GAP2;
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (pc == 0) stage_piece<types[0], 0, true>(ts);
-                    if (pc == 1) stage_piece<types[0], 1, true>(ts);
-                    if (pc == 2) stage_piece<types[1], 0, true>(ts);
-                    if (pc == 3) stage_piece<types[1], 1, true>(ts);
-                    if (pc == 4) stage_piece<types[2], 0, true>(ts);
-                    if (pc == 5) stage_piece<types[2], 1, true>(ts);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                if (q % GAP2 == 1 && q / GAP2 < 2 * n_stage) stage_ladder<types[0], types[1], types[2]>(q / GAP2, ts);
             }
         } else {
 #pragma unroll
@@ -282,17 +291,7 @@ struct Pipe256T {
                 acc[xx][2 * YH + yy] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf, fa[yy][c], acc[xx][2 * YH + yy], 0, 0, 0);
             }
             // one LDS-DMA piece after each of the first 2 * n_stage MFMA pairs
-            if (step < 2 * n_stage) {
-                const int pc = step;
-                __builtin_amdgcn_sched_barrier(0);
-                if (pc == 0) stage_piece<types[0], 0, true>(ts);
-                if (pc == 1) stage_piece<types[0], 1, true>(ts);
-                if (pc == 2) stage_piece<types[1], 0, true>(ts);
-                if (pc == 3) stage_piece<types[1], 1, true>(ts);
-                if (pc == 4) stage_piece<types[2], 0, true>(ts);
-                if (pc == 5) stage_piece<types[2], 1, true>(ts);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            if (step < 2 * n_stage) stage_ladder<types[0], types[1], types[2]>(step, ts);
         }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -310,41 +309,6 @@ struct Pipe256T {
     template <int MODE, int VM0 = 6, int VM1 = 2>
     __device__ __forceinline__ void tile2(int t, Acc &acc) {
         if constexpr (pipe_src_precomputes<SRC>::value) S.prepare(t);
-        if constexpr (PAIR3 && PIPE_PAIR3_EARLY > 0) {
-            // in flight when a tile starts (oldest first): A1(t), A0 B0 B1 (t+1) -- what the prologue leaves, too
-            // P0
-            read_a<0>(t);
-            read_b<0>(t);
-            read_b<1>(t);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (MODE <= 1) {
-                stage<1>(t + 1);
-                PIPE_WAIT_VM(8);  // retires A1(t); leaves A0 B0 B1 A1 of tile t+1
-            } else {
-                PIPE_WAIT_VM(0);
-            }
-            PIPE_WAIT_LGKM0();
-            mfma16<0, -1, -1, -1>(acc, t + 1);
-            // P1
-            read_a<1>(t);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (MODE == 0) {
-                stage<0>(t + 2);
-                if constexpr (PIPE_PAIR3_EARLY == 2) {
-                    stage<2>(t + 2);
-                    stage<3>(t + 2);
-                    PIPE_WAIT_VM(8);  // retires A0 B0 B1 of tile t+1; leaves A1(t+1) and A0 B0 B1 of tile t+2
-                } else {
-                    PIPE_WAIT_VM(4);  // retires A0 B0 B1 of tile t+1; leaves A1(t+1), A0(t+2)
-                }
-            } else if constexpr (MODE == 1) {
-                PIPE_WAIT_VM(2);      // retires A0 B0 B1 of tile t+1; leaves A1(t+1)
-            }
-            PIPE_WAIT_LGKM0();
-            if constexpr (MODE == 0 && PIPE_PAIR3_EARLY == 1) mfma16<1, 2, 3, -1>(acc, t + 2);
-            else mfma16<1, -1, -1, -1>(acc, t + 2);
-            return;
-        }
         // P0
         read_a<0>(t);
         read_b<0>(t);

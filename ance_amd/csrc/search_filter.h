@@ -84,9 +84,7 @@ struct FastSrc {
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const _Float16 *base, uint32_t first_row, uint32_t n_rows, int d) {
-    const uint32_t rows = first_row < n_rows ? min(n_rows - first_row, 256u) : 0u;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(base + (size_t)first_row * d), 0, (int)(rows * (uint32_t)d * 2u),
-                                             0x00020000);
+    return pipe_rows_rsrc(base, first_row, d, first_row < n_rows ? min(n_rows - first_row, 256u) : 0u);
 }
 
 // v_max3_f32 without the canonicalisation (v_max_f32 x, x) hipcc puts in front of every fmaxf operand it cannot prove quiet.
@@ -197,6 +195,7 @@ __global__ void __launch_bounds__(F_THREADS, 2) ip_topk_fast_kernel(const FastPa
         FastSrc &S = pipe.S;
         S.NK = d / FK;
         S.rq = tile_rsrc(P.q2, q0, P.nq, d);
+        // (pipe_fill_voff would do; written out because this kernel's instruction stream comes out different with it: profiles/README.md, r10)
         const int ch = pipe_stage_chunk(pipe_stage_row(w, l, 0), l);  // rows of piece 1 are 64 further: same swizzle
 #pragma unroll
         for (int h = 0; h < 2; ++h)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Round 5: where the LDS-DMAs of the split GEMM's K-tile are issued (PIPE_PAIR3_EARLY = 0 / 1 / 2): correctness of the two early
 # forms (direct GEMM tests on every element, encoder goldens), then the same-box A/B.
+# The two early forms have left pipe256.h (DESIGN_REJECTED.md, round 5): the libraries this script runs build only at commit 3c6f5f5 or before.
 set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/ab

@@ -1,4 +1,4 @@
-"""The split (fp32-grade) mode's GELU (csrc/gemm256_epilogue.h: gelu_exact) restated in fp32 emulation: the erf form of the
+"""The split (fp32-grade) mode's GELU (csrc/gemm256_gelu.h: gelu_exact) restated in fp32 emulation: the erf form of the
 reference (transformers "gelu", model/models.py via RobertaModel) computed as  x (x >= 0 ? 1 - e : e),  e = 2^q(z),
 z = min(|x| / sqrt 2, 6.6),  q = a degree-9 fit of log2(erfc(z) / 2)  -- 9 fma and one hardware exp2 instead of ocml's two-branch
 erff.  The claim pinned here: it is at least as close to the exact GELU as the reference's OWN fp32 arithmetic (torch's fp32
@@ -31,7 +31,7 @@ def gelu_poly32(x):
 
 
 def test_header_carries_these_coefficients():
-    src = open(os.path.join(ROOT, "ance_amd", "csrc", "gemm256_epilogue.h")).read()
+    src = open(os.path.join(ROOT, "ance_amd", "csrc", "gemm256_gelu.h")).read()
     body = re.search(r"GELU_Q\[10\] = \{([^}]*)\}", src).group(1)
     got = [float(t.strip().rstrip("f")) for t in body.replace("\n", " ").split(",")]
     assert got == Q

@@ -297,7 +297,7 @@ def test_resln_epilogue_against_fp64(hw, k_of):
 @pytest.mark.parametrize("hw", [768, 1024])
 @pytest.mark.parametrize("epi,stream", [(6, "1"), (9, "1"), (9, "0")])   # (ANCE_GEMM_STREAM selects among the split kernels only)
 def test_n_split_tile_order_changes_no_bit(hw, epi, stream, monkeypatch):
-    """FFN1 runs with n_split = 2 (the N-split tile order of gemm256_f16.hip: tile_of_block) in both fp16 (EPI_GELU_F) and split
+    """FFN1 runs with n_split = 2 (the N-split tile order of gemm256_tile.h: tile_of_block) in both fp16 (EPI_GELU_F) and split
     (EPI_S_GELU: the streaming kernel and the launch-per-tile kernel) modes: the same output bits as the plain order, on a token
     count that is not a multiple of four tiles (the padded grid of the N-split order)."""
     from ance_amd import _lib

@@ -32,7 +32,7 @@ def stats_from_slices(v, eps):
     return m, torch.rsqrt(q / H + eps)
 
 
-WIDE_MEAN = 2.0  # csrc/gemm256_epilogue.h: FOLD_WIDE_MEAN
+WIDE_MEAN = 2.0  # csrc/gemm256_tile.h: FOLD_WIDE_MEAN
 GUARD = True     # the second K loop over the lo halves for tiles with a wide-mean token (round 4)
 
 

@@ -45,7 +45,8 @@ def coarse(mode, t):
 
 
 def coarse_pair3_early(form):
-    """pipe256.h ``tile2<MODE>`` with PIPE_PAIR3_EARLY = form (1 or 2): phases carry a fourth entry, the half-tiles staged in the
+    """The RETIRED early-staging forms of pipe256.h ``tile2<MODE>`` (PIPE_PAIR3_EARLY = form, 1 or 2; measured and rejected in round 5,
+    DESIGN_REJECTED.md names the last commit with the code): phases carry a fourth entry, the half-tiles staged in the
     READ half-phase (after the reads, before the wait), and these forms wait for their own ds_reads before the barrier."""
     def phases(mode, t):
         p0 = ([(A0, t), (B0, t), (B1, t)], 8 if mode <= 1 else 0, [], [(A1, t + 1)] if mode <= 1 else [])
@@ -156,7 +157,8 @@ def test_coarse_schedule(nk):
 @pytest.mark.parametrize("nk", range(2, 14))
 @pytest.mark.parametrize("form", [1, 2])
 def test_coarse_pair3_early_schedules(nk, form):
-    """The split GEMM's forms with LDS-DMAs issued in the read half-phases (PIPE_PAIR3_EARLY)."""
+    """The split GEMM's forms with LDS-DMAs issued in the read half-phases (PIPE_PAIR3_EARLY): retired from pipe256.h, kept here as
+    the retired four-phase form is."""
     replay(nk, coarse_pair3_early(form), coarse_prologue(), reads_complete_before_barrier=True)
     with pytest.raises(AssertionError):  # without the lgkmcnt(0) before the barrier the early restage races the other group's reads
         replay(max(nk, 4), coarse_pair3_early(form), coarse_prologue(), reads_complete_before_barrier=False)
@@ -276,7 +278,7 @@ def replay_persistent(nk, n_out, f_actual, f_claimed, extra_ops_group1=1):
 @pytest.mark.parametrize("n_out", [1, 2, 3])
 @pytest.mark.parametrize("f", [0, 35])
 def test_persistent_gemm_hand_over(nk, n_out, f):
-    """f = the foreign operations of gemm256_f16.hip: EPS_FOREIGN_OPS (32 stores + 3 LDS-DMAs for QKV and GELU alike); 0 = the
+    """f = the foreign operations of gemm256_tile.h: EPS_FOREIGN_OPS (32 stores + 3 LDS-DMAs for QKV and GELU alike); 0 = the
     steady-state waits on K-tile 0 (ANCE_STREAM_LOOSE_FIRST=0: correct whatever the epilogue issues)."""
     replay_persistent(nk, n_out, f_actual=f, f_claimed=f)
     replay_persistent(nk, n_out, f_actual=f + 20, f_claimed=f)   # an epilogue that issues MORE than claimed only waits longer
