@@ -60,6 +60,12 @@ class AnceLambTensor(ctypes.Structure):
                 ("numel", ctypes.c_int64), ("group", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class AnceAdamwTensor(ctypes.Structure):
+    """include/ance_amd.h: one row of ance_adamw_step's host tensor table."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("step", ctypes.c_void_p), ("numel", ctypes.c_int64), ("group", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class AnceLambGroup(ctypes.Structure):
     """include/ance_amd.h: one row of ance_lamb_step's host group table."""
     _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
@@ -147,6 +153,10 @@ SYMBOLS = {
                                           ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                           ctypes.c_void_p]),
+    "ance_adamw_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "ance_adamw_step": (ctypes.c_int, [ctypes.POINTER(AnceAdamwTensor), ctypes.c_int, ctypes.POINTER(AnceLambGroup), ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "ance_nll_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p]),

@@ -29,23 +29,17 @@
 //            written and may be inf or NaN); reduce writes the rows of d_prev_out (or (0, 0, 1)) into d_out instead of new norms
 //            and one thread adds 1 to *d_skipped with an ordinary load, add and store.
 // Without the two pointers the launches and the instantiations are those of ance_lamb_step / ance_lamb_step_clipped.
-#include "common.h"
-
-#include <math.h>
-#include <mutex>
-#include <vector>
+#include "multi_tensor.h"
 
 namespace ance {
 namespace {
 
-constexpr int LAMB_CHUNK = 16384;  // elements per chunk: 16 float4 per thread and array at 256 threads
-constexpr int LAMB_THREADS = 256;
-constexpr int LAMB_UNROLL = 4;     // float4 per array in flight per thread
-
-// the tensors' pointers come from a table, so the compiler cannot see they are global: say so, for global_load / global_store
-// instead of flat accesses
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) f32x4 gf32x4;
+// the chunking, the gradient element under loss scaling and clipping, the gradient-norm pass and the staging pool: multi_tensor.h
+using mt::align16;
+using mt::gf32x4;
+using mt::gfloat;
+using mt::max_chunks;
+constexpr int LAMB_CHUNK = mt::CHUNK, LAMB_THREADS = mt::THREADS, LAMB_UNROLL = mt::UNROLL;
 
 struct LambDevGroup {
     float b1, omb1, b2, omb2, eps, wd, neg_lr;
@@ -63,21 +57,6 @@ __device__ __forceinline__ float lamb_u(float p, float m, float v, const LambDev
     float u = m / (sqrtf(v) + G.eps);
     if (G.has_wd) u = __builtin_fmaf(G.wd, p, u);
     return u;
-}
-
-// *grad_scale -> the factor that unscales a gradient: the fp64 reciprocal rounded to fp32, as GradScaler.unscale_ (hipcc emits the
-// correctly rounded fp32 divide for it, which is the same value: a 53-bit quotient rounds to 24 bits without a double-rounding error)
-__device__ __forceinline__ float lamb_inv_scale(const float *grad_scale) { return (float)(1.0 / (double)grad_scale[0]); }
-
-// the overflow flag of ance_lamb_step_amp: anything but 0 skips, NaN included
-__device__ __forceinline__ bool lamb_skip(const float *found_inf) { return found_inf && !(found_inf[0] == 0.0f); }
-
-// the gradient element as it enters the step: unscaled, then clipped, each an fp32 product of its own
-template <bool CLIP, bool UNSCALE>
-__device__ __forceinline__ float lamb_g(float g, float inv, float cf) {
-    if (UNSCALE) g = g * inv;
-    if (CLIP) g = g * cf;
-    return g;
 }
 
 // m, v update of one element; returns u
@@ -99,10 +78,10 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
                                                                   const int32_t *chunk_tensor, double2 *partial, const float *coef,
                                                                   const float *grad_scale, const float *found_inf) {
     __shared__ double red[LAMB_THREADS / 64][2];
-    if (lamb_skip(found_inf)) return;
+    if (mt::skip(found_inf)) return;
     const int tid = threadIdx.x;
     const float cf = CLIP ? coef[0] : 1.0f;
-    const float inv = UNSCALE ? lamb_inv_scale(grad_scale) : 1.0f;
+    const float inv = UNSCALE ? mt::inv_scale(grad_scale) : 1.0f;
     const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
     const LambDevGroup G = groups[T.group];
     const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
@@ -129,7 +108,7 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float mj = M[k][j], vj = V[k][j];
-                        const float u = lamb_mv(P[k][j], lamb_g<CLIP, UNSCALE>(Gr[k][j], inv, cf), mj, vj, G);
+                        const float u = lamb_mv(P[k][j], mt::grad<CLIP, UNSCALE>(Gr[k][j], inv, cf), mj, vj, G);
                         M[k][j] = mj;
                         V[k][j] = vj;
                         lamb_acc(P[k][j], u, sp, su);
@@ -144,7 +123,7 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
     for (int e = done + tid; e < len; e += LAMB_THREADS) {  // scalar tail (or the whole chunk of an unaligned tensor)
         float mj = m[e], vj = v[e];
         const float pj = p[e];
-        const float u = lamb_mv(pj, lamb_g<CLIP, UNSCALE>(g[e], inv, cf), mj, vj, G);
+        const float u = lamb_mv(pj, mt::grad<CLIP, UNSCALE>(g[e], inv, cf), mj, vj, G);
         m[e] = mj;
         v[e] = vj;
         lamb_acc(pj, u, sp, su);
@@ -168,74 +147,11 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevG
     }
 }
 
-// the chunk's sum of g^2 in fp64 (ance_lamb_step_clipped): reads g only.  UNSCALE: of (g * inv)^2, the fp32 product squared
-template <bool UNSCALE>
-__global__ void __launch_bounds__(LAMB_THREADS) lamb_gnorm_kernel(const LambDevTensor *tensors, const int32_t *chunk_tensor,
-                                                                  double *gpartial, const float *grad_scale) {
-    __shared__ double red[LAMB_THREADS / 64];
-    const int tid = threadIdx.x;
-    const float inv = UNSCALE ? lamb_inv_scale(grad_scale) : 1.0f;
-    const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
-    const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
-    const int len = (int)min((int64_t)LAMB_CHUNK, T.numel - base);
-    const gfloat *g = (const gfloat *)(T.g + base);
-    double sg = 0.0;
-    int done = 0;
-    if (T.vec) {
-        const int n4 = len >> 2;
-        const gf32x4 *g4 = (const gf32x4 *)g;
-        for (int i0 = tid; i0 < n4; i0 += LAMB_THREADS * LAMB_UNROLL) {
-            f32x4 Gr[LAMB_UNROLL];
-#pragma unroll
-            for (int k = 0; k < LAMB_UNROLL; ++k) {
-                const int i = i0 + k * LAMB_THREADS;
-                Gr[k] = i < n4 ? g4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int k = 0; k < LAMB_UNROLL; ++k)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double x = (double)lamb_g<false, UNSCALE>(Gr[k][j], inv, 1.0f);
-                    sg = __builtin_fma(x, x, sg);
-                }
-        }
-        done = n4 * 4;
-    }
-    for (int e = done + tid; e < len; e += LAMB_THREADS) {
-        const double x = (double)lamb_g<false, UNSCALE>(g[e], inv, 1.0f);
-        sg = __builtin_fma(x, x, sg);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sg += __shfl_xor(sg, off);
-    if ((tid & 63) == 0) red[tid >> 6] = sg;
-    __syncthreads();
-    if (tid == 0) {
-        double a = red[0];
-#pragma unroll
-        for (int w = 1; w < LAMB_THREADS / 64; ++w) a += red[w];
-        gpartial[blockIdx.x] = a;
-    }
-}
-
 // one workgroup: every chunk's sum in chunk order (thread-strided, then a shared-memory tree) -> the total norm and the clip factor
 __global__ void __launch_bounds__(1024) lamb_gtotal_kernel(const double *gpartial, int n_chunks, float max_norm, float *grad_norm,
                                                            float *coef) {
     __shared__ double s[1024];
-    const int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int c = tid; c < n_chunks; c += 1024) acc += gpartial[c];
-    s[tid] = acc;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if (tid < off) s[tid] += s[tid + off];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float total = (float)sqrt(s[0]);
-        const float c = max_norm / (total + 1e-6f);
-        grad_norm[0] = total;
-        coef[0] = c > 1.0f ? 1.0f : c;  // clamp(max=1) that lets a NaN through, as torch's clamp does
-    }
+    mt::grad_total(gpartial, n_chunks, max_norm, grad_norm, coef, s);
 }
 
 // one wave per tensor: chunk sums in chunk order (lane-strided, then an xor-shuffle tree) -> (wn, an, tr).  A skipped step
@@ -245,7 +161,7 @@ __global__ void __launch_bounds__(256) lamb_reduce_kernel(const LambDevTensor *t
                                                           int64_t *skipped) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
     if (t >= n_tensors) return;
-    if (lamb_skip(found_inf)) {
+    if (mt::skip(found_inf)) {
         if (l == 0) {
             const float wn = prev_out ? prev_out[3 * (int64_t)t] : 0.0f, an = prev_out ? prev_out[3 * (int64_t)t + 1] : 0.0f;
             const float tr = prev_out ? prev_out[3 * (int64_t)t + 2] : 1.0f;
@@ -282,7 +198,7 @@ __global__ void __launch_bounds__(256) lamb_reduce_kernel(const LambDevTensor *t
 __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass2_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
                                                                   const int32_t *chunk_tensor, const float *out, int adam,
                                                                   const float *found_inf) {
-    if (lamb_skip(found_inf)) return;
+    if (mt::skip(found_inf)) return;
     const int tid = threadIdx.x;
     const int t = chunk_tensor[blockIdx.x];
     const LambDevTensor T = tensors[t];
@@ -321,8 +237,6 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass2_kernel(const LambDevG
     for (int e = done + tid; e < len; e += LAMB_THREADS) p[e] = __builtin_fmaf(s, lamb_u(p[e], m[e], v[e], G), p[e]);
 }
 
-size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // workspace: [groups][tensors][chunk -> tensor] (staged from the host in one copy) [fp64 (p^2, u^2) per chunk]
 size_t staged_bytes(int n_tensors, int n_groups, int64_t n_chunks) {
     return align16(sizeof(LambDevGroup) * (size_t)n_groups) + align16(sizeof(LambDevTensor) * (size_t)n_tensors) +
@@ -336,52 +250,6 @@ size_t workspace_bytes_clipped(int n_tensors, int n_groups, int64_t n_chunks) {
     return workspace_bytes_for(n_tensors, n_groups, n_chunks) + align16(sizeof(double) * (size_t)n_chunks) + 16;
 }
 
-// Pinned staging buffers of the host tables.  A buffer is handed out again only once the event recorded after its last copy has
-// completed (hipEventQuery, no wait), so a pending DMA never reads a buffer that is being refilled.  When all of them are still in
-// flight the pool grows; at its cap the caller waits for the oldest copy -- a host wait on a copy enqueued LAMB_POOL steps ago.
-constexpr int LAMB_POOL = 16;
-struct Staging {
-    void *h = nullptr;
-    size_t bytes = 0;
-    hipEvent_t ev = nullptr;
-    bool recorded = false;
-    unsigned long long last_use = 0;
-};
-std::mutex g_stage_mu;
-std::vector<Staging> g_stage;
-unsigned long long g_stage_clock = 0;
-
-// under g_stage_mu; returns the index of a buffer of >= bytes whose previous copy has run, or -1 (out of memory)
-int stage_acquire(size_t bytes) {
-    for (size_t i = 0; i < g_stage.size(); ++i) {
-        Staging &s = g_stage[i];
-        if (s.bytes >= bytes && (!s.recorded || hipEventQuery(s.ev) == hipSuccess)) return (int)i;
-    }
-    size_t want = 65536;
-    while (want < bytes) want <<= 1;
-    if ((int)g_stage.size() < LAMB_POOL) {
-        Staging s;
-        if (hipHostMalloc(&s.h, want, hipHostMallocDefault) != hipSuccess) return -1;
-        if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) return -1;
-        s.bytes = want;
-        g_stage.push_back(s);
-        return (int)g_stage.size() - 1;
-    }
-    int old = 0;
-    for (int i = 1; i < (int)g_stage.size(); ++i)
-        if (g_stage[i].last_use < g_stage[old].last_use) old = i;
-    Staging &s = g_stage[old];
-    if (s.recorded && hipEventSynchronize(s.ev) != hipSuccess) return -1;
-    if (s.bytes < bytes) {  // the old buffer stays allocated: freeing pinned memory can synchronise the device
-        void *h = nullptr;
-        if (hipHostMalloc(&h, want, hipHostMallocDefault) != hipSuccess) return -1;
-        s.h = h;
-        s.bytes = want;
-    }
-    s.recorded = false;
-    return old;
-}
-
 thread_local const char *g_lamb_fn = "ance_lamb_step";
 int lamb_refuse(const char *why) {
     char buf[160];
@@ -389,11 +257,6 @@ int lamb_refuse(const char *why) {
     set_last_error(buf);
     return ANCE_E_INVALID;
 }
-
-int64_t max_chunks(int n_tensors, int64_t total_numel) {  // >= the sum of every tensor's ceil(numel / chunk)
-    return (int64_t)n_tensors + total_numel / LAMB_CHUNK;
-}
-
 
 // what ance_lamb_step_amp adds to a step: every pointer nullable, all null for the other two entry points
 struct LambAmp {
@@ -436,13 +299,13 @@ int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLam
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)d_workspace;
     {
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        const int si = stage_acquire(off_p);
+        std::lock_guard<std::mutex> lock(mt::g_stage_mu);
+        const int si = mt::stage_acquire(off_p);
         if (si < 0) {
             set_last_error("ance_lamb_step: pinned staging buffer");
             return ANCE_E_NOMEM;
         }
-        Staging &S = g_stage[si];
+        mt::Staging &S = mt::g_stage[si];
         char *h = (char *)S.h;
         LambDevGroup *G = (LambDevGroup *)h;
         for (int i = 0; i < n_groups; ++i) {  // the reference's Python doubles, rounded to fp32 as torch does for a scalar
@@ -472,10 +335,8 @@ int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLam
             T[t].vec = ((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) % 16 == 0;
             for (int32_t k = 0; k < T[t].n_chunks; ++k) ct[c++] = t;
         }
-        if (hipMemcpyAsync(ws, h, off_p, hipMemcpyHostToDevice, st) != hipSuccess) return check_launch("ance_lamb_step: tables");
-        if (hipEventRecord(S.ev, st) != hipSuccess) return check_launch("ance_lamb_step: staging event");
-        S.recorded = true;
-        S.last_use = ++g_stage_clock;
+        const int sent = mt::stage_send(S, ws, off_p, st);
+        if (sent) return check_launch(sent == 1 ? "ance_lamb_step: tables" : "ance_lamb_step: staging event");
     }
     const LambDevGroup *dG = (const LambDevGroup *)ws;
     const LambDevTensor *dT = (const LambDevTensor *)(ws + off_t);
@@ -487,10 +348,10 @@ int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLam
         float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
         if (n_chunks > 0) {
             if (unscale)
-                hipLaunchKernelGGL(lamb_gnorm_kernel<true>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
+                hipLaunchKernelGGL((mt::gnorm_kernel<LambDevTensor, true>), dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
                                    amp.grad_scale);
             else
-                hipLaunchKernelGGL(lamb_gnorm_kernel<false>, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
+                hipLaunchKernelGGL((mt::gnorm_kernel<LambDevTensor, false>), dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
                                    (const float *)nullptr);
         }
         hipLaunchKernelGGL(lamb_gtotal_kernel, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks, (float)max_norm, d_grad_norm,

@@ -1,4 +1,6 @@
-"""Fused LAMB for the ANCE trainers: a drop-in replacement of the reference's ``utils/lamb.py`` ``Lamb``, the optimizer
+"""Fused optimizers for the ANCE trainers.  ``Lamb`` first; ``AdamW`` (transformers 2.3.0's, the DPR trainer's default) below it.
+
+Fused LAMB: a drop-in replacement of the reference's ``utils/lamb.py`` ``Lamb``, the optimizer
 drivers/run_ann.py:80-84 and drivers/run_warmup.py:76-78 build when ``--optimizer lamb`` is passed (both launch recipes pass it).
 
 The reference steps tensor by tensor in Python (about 19 small launches and up to three host synchronisations per tensor).
@@ -32,6 +34,22 @@ _TENSOR_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8")
 _GROUP_DTYPE = np.dtype([("lr", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("eps", "<f8"), ("weight_decay", "<f8")])
 assert _TENSOR_DTYPE.itemsize == ctypes.sizeof(_lib.AnceLambTensor)
 assert _GROUP_DTYPE.itemsize == ctypes.sizeof(_lib.AnceLambGroup)
+# AnceAdamwTensor
+_ADAMW_TENSOR_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("step", "<u8"), ("numel", "<i8"),
+                                ("group", "<i4"), ("reserved", "<i4")])
+assert _ADAMW_TENSOR_DTYPE.itemsize == ctypes.sizeof(_lib.AnceAdamwTensor)
+
+
+def _valid_max_grad_norm(max_grad_norm):
+    if max_grad_norm is None:
+        return None
+    try:
+        ok = 0.0 < float(max_grad_norm) < float("inf")
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("Invalid max_grad_norm: {} (None or a positive finite number)".format(max_grad_norm))
+    return float(max_grad_norm)
 
 
 class Lamb(Optimizer):
@@ -74,21 +92,17 @@ class Lamb(Optimizer):
             raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
         if not 0.0 <= betas[1] < 1.0:
             raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
-        if max_grad_norm is not None:
-            try:
-                ok = 0.0 < float(max_grad_norm) < float("inf")
-            except (TypeError, ValueError):
-                ok = False
-            if not ok:
-                raise ValueError("Invalid max_grad_norm: {} (None or a positive finite number)".format(max_grad_norm))
+        max_grad_norm = _valid_max_grad_norm(max_grad_norm)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.adam = adam
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
         self.last_grad_norm = None
         self.skipped_steps = None
         super(Lamb, self).__init__(params, defaults)
         self._workspace = {}
         self._prev_out = None  # (out of the last step, the ids of the parameters its rows belong to)
+
+    _name = "Lamb"  # in front of every AnceLibraryError
 
     def _amp_scalar(self, name, device):
         """optimizer.grad_scale / optimizer.found_inf as GradScaler attaches them: None, or a one-element fp32 tensor on the step's
@@ -96,7 +110,7 @@ class Lamb(Optimizer):
         t = getattr(self, name, None)
         if t is None:
             return None
-        what = "Lamb: optimizer.%s" % name
+        what = "%s: optimizer.%s" % (self._name, name)
         _lib.require_cuda_tensor(t, torch.float32, what)
         if t.numel() != 1:
             raise _lib.AnceLibraryError("%s must have one element, got shape %s" % (what, tuple(t.shape)))
@@ -200,4 +214,166 @@ class Lamb(Optimizer):
             state['weight_norm'] = vals[3 * k]
             state['adam_norm'] = vals[3 * k + 1]
             state['trust_ratio'] = vals[3 * k + 2]
+        return loss
+
+
+class AdamW(Optimizer):
+    r"""AdamW as transformers 2.3.0 has it (optimization.py, ``AdamW``) -- the optimizer drivers/run_ann_dpr.py:501-504 makes the DPR
+    trainer's default through utils/dpr_utils.py:80-92, and run_ann.py:85-89 / run_warmup.py:79-81 build for ``--optimizer adamW``.
+    transformers 5 no longer has the class, and ``torch.optim.AdamW`` is another arithmetic: it decays before the update and puts
+    ``eps`` inside the bias correction.  Here, per tensor::
+
+        m <- beta1 m + (1 - beta1) g ;  v <- beta2 v + (1 - beta2) g g ;  t = step + 1
+        ss = lr sqrt(1 - beta2^t) / (1 - beta1^t)          (lr when correct_bias is False)
+        p <- p - ss m / (sqrt(v) + eps) ;  then p <- p - lr weight_decay p on the UPDATED p when weight_decay > 0
+
+    One call of ``ance_adamw_step`` (csrc/adamw.hip) steps every tensor of every group: two launches (28 B per element), three with
+    ``max_grad_norm`` (32 B), no host synchronisation.
+
+    Arguments as 2.3.0's: params, lr (1e-3), betas ((0.9, 0.999)), eps (1e-6), weight_decay (0.0), correct_bias (True), and
+    ``max_grad_norm`` as ``Lamb``'s: ``clip_grad_norm_`` fused in front (``last_grad_norm``; ``p.grad`` is not rescaled in memory).
+    ``correct_bias`` is a group default as in 2.3.0, but one step has one value: groups that disagree are refused.
+
+    ``state['step']`` is a 0-dim fp32 DEVICE tensor (what torch's fused Adam keeps; exact up to 2^24 steps), advanced by the kernel:
+    the count enters the bias correction, so a step skipped for overflow must not advance it, and only the device knows.  A
+    parameter without a gradient is skipped and gets no state, so under ``find_unused_parameters=True`` tensors carry different
+    counts and each uses its own bias correction.  A parameter of no elements keeps ``step`` 0.
+
+    Loss scaling exactly as ``Lamb``'s (``_step_supports_amp_scaling``; ``grad_scale`` / ``found_inf`` attached by
+    ``torch.amp.GradScaler.step``): unscale in registers, the clipping norm over the unscaled gradients, and with a ``found_inf``
+    that is not 0 (NaN included) no bit of any parameter, moment or ``step`` changes and ``skipped_steps`` grows by one.
+
+    Resume: ``state_dict()`` returns ``step`` as a Python int (one device read per save, off the step path), the layout 2.3.0 writes
+    and reads; ``load_state_dict`` takes that layout (int steps, CPU tensors) as well as tensors and moves ``step`` to the device as
+    fp32.  ``max_grad_norm`` is an attribute, not part of ``param_groups`` or ``state_dict()``.
+
+    No CPU fallback: every parameter, gradient and state tensor must be a contiguous fp32 tensor on one HIP device.
+    """
+    _step_supports_amp_scaling = True
+    _name = "AdamW"
+    _amp_scalar = Lamb._amp_scalar
+    _checked = Lamb._checked
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, max_grad_norm=None):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        self.max_grad_norm = _valid_max_grad_norm(max_grad_norm)
+        self.last_grad_norm = None
+        self.skipped_steps = None
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
+        super(AdamW, self).__init__(params, defaults)
+        self._workspace = {}
+
+    def state_dict(self):
+        """The reference's layout: ``step`` a Python int.  One device read for all of them."""
+        sd = super(AdamW, self).state_dict()
+        keys = [k for k, s in sd["state"].items() if isinstance(s.get("step"), torch.Tensor)]
+        if keys:
+            steps = torch.stack([sd["state"][k]["step"].detach().reshape(()).float() for k in keys]).cpu().tolist()
+            sd["state"] = dict(sd["state"])
+            for k, n in zip(keys, steps):
+                sd["state"][k] = dict(sd["state"][k], step=int(n))   # a copy: the live state keeps its device tensor
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Accepts ``step`` as an int (the reference's and this class's files) or a tensor; it lives on the parameter's device."""
+        super(AdamW, self).load_state_dict(state_dict)
+        for group in self.param_groups:
+            for p in group['params']:
+                st = self.state.get(p)
+                if st and 'step' in st:
+                    n = st['step']
+                    n = float(n.item()) if isinstance(n, torch.Tensor) else float(n)
+                    st['step'] = torch.full((), n, dtype=torch.float32, device=p.device)
+
+    def step(self, closure=None):
+        """One AdamW step of every parameter that has a gradient.  Asynchronous: enqueued on the current stream, no host wait --
+        also under a GradScaler: a skipped step is skipped on the device, its step counts included."""
+        loss = None
+        if closure is not None:
+            loss = closure()
+
+        todo, groups, device, correct_bias = [], [], None, None
+        for gi, group in enumerate(self.param_groups):
+            beta1, beta2 = group['betas']
+            groups.append((float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay'])))
+            for pi, p in enumerate(group['params']):
+                if p.grad is None:
+                    continue
+                grad = p.grad
+                if grad.is_sparse:
+                    raise RuntimeError('Adam does not support sparse gradients, please consider SparseAdam instead')
+                name = "AdamW: param_groups[%d]['params'][%d]" % (gi, pi)
+                if device is None:
+                    _lib.require_cuda_tensor(p, torch.float32, name)
+                    device = p.device
+                self._checked(p, name, device)
+                self._checked(grad, name + ".grad", device)
+                if grad.shape != p.shape:
+                    raise _lib.AnceLibraryError("%s.grad has shape %s, the parameter %s" % (name, tuple(grad.shape), tuple(p.shape)))
+                if correct_bias is None:
+                    correct_bias = bool(group['correct_bias'])
+                elif correct_bias != bool(group['correct_bias']):
+                    raise _lib.AnceLibraryError("AdamW: param_groups[%d]['correct_bias'] differs from an earlier group's: one step "
+                                                "has one value" % gi)
+                state = self.state.get(p)   # .get: a refused call must not leave an entry behind
+                if state:
+                    m, v, n = state['exp_avg'], state['exp_avg_sq'], state['step']
+                    self._checked(m, name + " state['exp_avg']", device)
+                    self._checked(v, name + " state['exp_avg_sq']", device)
+                    self._checked(n, name + " state['step']", device)
+                    if m.shape != p.shape or v.shape != p.shape:
+                        raise _lib.AnceLibraryError("%s: state shapes %s, %s differ from the parameter's %s"
+                                                    % (name, tuple(m.shape), tuple(v.shape), tuple(p.shape)))
+                    if n.numel() != 1:
+                        raise _lib.AnceLibraryError("%s: state['step'] must have one element, got shape %s" % (name, tuple(n.shape)))
+                todo.append((p, grad, gi))
+        if not todo:
+            return loss
+        grad_scale, found_inf = self._amp_scalar("grad_scale", device), self._amp_scalar("found_inf", device)
+        rows = []   # everything is checked: only now is state created
+        for p, grad, gi in todo:
+            state = self.state[p]
+            if len(state) == 0:
+                state['step'] = torch.zeros((), dtype=torch.float32, device=device)
+                state['exp_avg'] = torch.zeros_like(p.data)
+                state['exp_avg_sq'] = torch.zeros_like(p.data)
+            rows.append((p.data_ptr(), grad.data_ptr(), state['exp_avg'].data_ptr(), state['exp_avg_sq'].data_ptr(),
+                         state['step'].data_ptr(), p.numel(), gi, 0))
+        amp = grad_scale is not None or found_inf is not None
+
+        L = _lib.lib()
+        tensors = np.array(rows, dtype=_ADAMW_TENSOR_DTYPE)
+        gtab = np.array(groups, dtype=_GROUP_DTYPE)
+        total = int(tensors["numel"].sum())
+        clip = self.max_grad_norm is not None
+        need = L.ance_adamw_workspace_bytes(len(rows), len(groups), total, 1 if clip else 0)
+        if need == 0:
+            raise _lib.AnceLibraryError("AdamW: %d tensors of %d elements exceed ance_adamw_step's limits" % (len(rows), total))
+        with torch.cuda.device(device):
+            ws = self._workspace.get(device)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=device)
+                self._workspace[device] = ws
+            if amp and (self.skipped_steps is None or self.skipped_steps.device != device):
+                self.skipped_steps = torch.zeros((), dtype=torch.int64, device=device)
+            norm = torch.empty((1,), dtype=torch.float32, device=device) if clip else None
+
+            def ptr(t):
+                return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+            _lib.check(L.ance_adamw_step(tensors.ctypes.data_as(ctypes.POINTER(_lib.AnceAdamwTensor)), len(rows),
+                                         gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups), 1 if correct_bias else 0,
+                                         self.max_grad_norm if clip else 0.0, ptr(grad_scale), ptr(found_inf), ptr(norm),
+                                         ptr(self.skipped_steps if amp else None), ctypes.c_void_p(ws.data_ptr()),
+                                         ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                       "ance_adamw_step")
+            if clip:
+                self.last_grad_norm = norm[0]
         return loss

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -500,6 +500,52 @@ int ance_lamb_step_amp(const AnceLambTensor *h_tensors, int n_tensors, const Anc
                        float *d_grad_norm,              /* required iff max_grad_norm != 0 */
                        int64_t *d_skipped,              /* nullable */
                        float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fused multi-tensor AdamW step (csrc/adamw.hip; transformers 2.3.0 optimization.py AdamW.step, which drivers/run_ann_dpr.py
+ * trains with by default and run_ann.py / run_warmup.py with --optimizer adamW).  Per tensor p with gradient g, state m, v, a
+ * DEVICE step counter and its group's lr, beta1, beta2, eps, wd:
+ *   g' = g [inv, then coef: below]
+ *   m <- beta1 m + (1 - beta1) g' ;  v <- beta2 v + (1 - beta2) g' g'
+ *   t  = *step + 1
+ *   ss = float32(lr sqrt(1 - beta2^t) / (1 - beta1^t))   in fp64 on the device; float32(lr) when correct_bias == 0
+ *   p <- p - ss (m / (sqrt(v) + eps))
+ *   p <- p + float32(-lr wd) p   when wd > 0: on the UPDATED p -- the decay comes after the update (torch.optim.AdamW decays
+ *                                before it, and puts eps inside the bias correction: it is another arithmetic)
+ *   *step <- t
+ * beta1, beta2, 1 - beta1, 1 - beta2 and eps enter the moment updates rounded to fp32 as torch rounds a scalar; ss and the decay
+ * factor are formed from the doubles.  *step is an fp32 scalar per tensor (exact up to 2^24 steps): tensors of one call may
+ * carry different counts and each uses its own bias correction.
+ *   clip     max_grad_norm != 0: the 2-norm of all gradients -> *d_grad_norm and coef = min(max_grad_norm / (total + 1e-6), 1)
+ *            exactly as ance_lamb_step_clipped forms them; g' = g coef.
+ *   unscale  d_grad_scale != NULL: inv = (float)(1.0 / (double)*d_grad_scale) formed on the device; g' = (g inv) coef, two fp32
+ *            roundings in that order; the norm is taken over the products g inv.  The gradients in memory are never rewritten.
+ *   skip     d_found_inf != NULL and !(*d_found_inf == 0) (NaN skips too): no bit of any p, m, v or *step changes -- every
+ *            workgroup returns before any store -- and *d_skipped (DEVICE int64, nullable) grows by one.  *d_grad_norm is still
+ *            written when clipping.  The next step therefore uses the bias correction of the steps that were applied.
+ * Launches: two without clipping (a per-tensor kernel that forms t, ss and the decay factor and advances *step; one elementwise
+ * pass, 28 bytes per element), three with it (the gradient-norm pass in front, 32 bytes per element; its total shares the
+ * per-tensor launch).  No atomics, a fixed summation order, no host synchronisation: the same inputs give the same bits.
+ * Tables, staging and workspace rules as ance_lamb_step; the groups are AnceLambGroup rows.  numel == 0 is allowed (any pointers:
+ * that tensor's step is neither read nor written).  n_tensors == 0: nothing is enqueued.  Refuses (ANCE_E_INVALID, before any copy
+ * or launch) everything ance_lamb_step_amp refuses (it has no d_out) and a null step of a tensor with numel > 0. */
+typedef struct AnceAdamwTensor {
+    float *p;                     /* parameter, updated in place                                  */
+    const float *g;               /* gradient                                                     */
+    float *m, *v;                 /* exp_avg, exp_avg_sq, updated in place                        */
+    float *step;                  /* DEVICE fp32 scalar: applied steps, advanced in place         */
+    int64_t numel;
+    int32_t group, reserved;
+} AnceAdamwTensor;
+/* Bytes of workspace ance_adamw_step needs (0: invalid); larger with clip != 0. */
+size_t ance_adamw_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel, int clip);
+int ance_adamw_step(const AnceAdamwTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int correct_bias,
+                    double max_grad_norm,            /* 0: no clipping; else positive finite */
+                    const float *d_grad_scale,       /* nullable: no unscale */
+                    const float *d_found_inf,        /* nullable: never skip */
+                    float *d_grad_norm,              /* required iff max_grad_norm != 0 */
+                    int64_t *d_skipped,              /* nullable */
+                    void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Re-reads every ANCE_* tuning knob from the environment (they are otherwise read once per process).  For tests and
  * sweeps that change a knob between two calls; not thread-safe against concurrent searches. */
