@@ -234,6 +234,38 @@ def det_state_dict(kind="roberta", n_layers=12, hidden=768, inter=3072, vocab=50
     return sd
 
 
+def trained_like_state_dict(n_layers, ffn_drive=None, emb_scale=1.4, hidden=768, inter=3072, outliers=((17, 50.0), (400, -50.0)),
+                            seed=71, kind="roberta", prefixes=("roberta.",), ln_jitter=0.1, **kw):
+    """A 'trained-like' stress model on ``det_state_dict`` weights (reproducible: ``state_dict_sha256`` of the result is what a
+    golden manifest records).  Random init has O(1) activations and a flat softmax; here, per tower in ``prefixes``: word-embedding
+    rows scaled by ``emb_scale`` with a common offset of 0.04 on column 5; ``outliers`` = (dimension, factor) pairs applied to the
+    weight of every LayerNorm of the tower (the outlier dimensions of trained BERT / RoBERTa; the head's ``norm`` is left alone);
+    Q and K weights x 6, so that the softmax saturates; optionally one FFN channel driven to ``ffn_drive`` through
+    ``layer.1.intermediate.dense.bias[123]``.  ``kw`` goes to ``det_state_dict`` (vocab, max_pos, head)."""
+    sd = det_state_dict(kind=kind, n_layers=n_layers, hidden=hidden, inter=inter, seed=seed, prefixes=prefixes, ln_jitter=ln_jitter, **kw)
+    for prefix in prefixes:
+        we = sd[prefix + "embeddings.word_embeddings.weight"] * emb_scale
+        we[:, 5] += 0.04
+        sd[prefix + "embeddings.word_embeddings.weight"] = we
+        names = [prefix + "embeddings.LayerNorm"]
+        for i in range(n_layers):
+            names += ["%sencoder.layer.%d.attention.output.LayerNorm" % (prefix, i), "%sencoder.layer.%d.output.LayerNorm" % (prefix, i)]
+        for n in names:
+            w = sd[n + ".weight"].clone()
+            for dim, f in outliers:
+                w[dim] *= f
+            sd[n + ".weight"] = w
+        for i in range(n_layers):
+            p = "%sencoder.layer.%d." % (prefix, i)
+            sd[p + "attention.self.query.weight"] = sd[p + "attention.self.query.weight"] * 6.0
+            sd[p + "attention.self.key.weight"] = sd[p + "attention.self.key.weight"] * 6.0
+        if ffn_drive is not None:
+            b = sd[prefix + "encoder.layer.1.intermediate.dense.bias"].clone()
+            b[123] = ffn_drive
+            sd[prefix + "encoder.layer.1.intermediate.dense.bias"] = b
+    return sd
+
+
 def state_dict_sha256(sd):
     """Content hash of a weight dict (names + raw float32 bytes): what the golden manifests record."""
     import hashlib
