@@ -72,6 +72,18 @@ class AnceLambGroup(ctypes.Structure):
                 ("weight_decay", ctypes.c_double)]
 
 
+class AnceGatherSegment(ctypes.Structure):
+    """include/ance_amd.h: one segment (tower) of ance_gather_batch."""
+    _fields_ = [("d_records", ctypes.c_void_p), ("n_records", ctypes.c_int64), ("d_index", ctypes.c_void_p),
+                ("n_index", ctypes.c_int64), ("d_ids", ctypes.c_void_p), ("d_mask", ctypes.c_void_p), ("d_types", ctypes.c_void_p),
+                ("L", ctypes.c_int32), ("mask_rule", ctypes.c_int32), ("type_rule", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# ance_gather_batch codes (include/ance_amd.h: ANCE_GATHER_*)
+GATHER_MASK_LENGTH, GATHER_MASK_NONZERO = 0, 1
+GATHER_TYPES_ZERO, GATHER_TYPES_LENGTH = 0, 1
+GATHER_REFERENCE, GATHER_WIDE = 0, 1
+
 # AnceEncoderDesc.precision (include/ance_amd.h: ANCE_PRECISION_*)
 PRECISION_CODES = {None: 0, "split": 1, "fp16": 2, "fp32": 3}
 PRECISION_NAMES = {1: "split", 2: "fp16", 3: "fp32"}
@@ -167,6 +179,8 @@ SYMBOLS = {
     "ance_inbatch_nll_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_size_t, ctypes.c_void_p]),
+    "ance_gather_batch": (ctypes.c_int, [ctypes.POINTER(AnceGatherSegment), ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                         ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -546,6 +546,38 @@ int ance_adamw_step(const AnceAdamwTensor *h_tensors, int n_tensors, const AnceL
                     float *d_grad_norm,              /* required iff max_grad_norm != 0 */
                     int64_t *d_skipped,              /* nullable */
                     void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training batches gathered on the device (csrc/batch_gather.hip): what the reference's loaders build per item in Python
+ * (data/msmarco_data.py:275-362, data/DPR_data.py:276-344), collate, copy and cast (drivers/run_ann.py:237-254).  A segment is one
+ * tower's share of a batch: item first + b of its index names the record whose tokens become row b of its outputs.
+ *   d_records  the token cache file's bytes on the device: n_records rows of 4 + 4 L bytes (big-endian passage_len, L little-endian
+ *              int32), 4-byte aligned
+ *   d_index    int64 [n_index]: one record index per item of the plan.  The host validates it when the plan is made; the kernel
+ *              clamps every value into [0, n_records), so no value makes it read outside the records
+ *   mask_rule  ANCE_GATHER_MASK_LENGTH: 1 x min(passage_len, L) then 0 (MS MARCO); ANCE_GATHER_MASK_NONZERO: ids != 0 (DPR)
+ *   type_rule  ANCE_GATHER_TYPES_ZERO (MS MARCO query, both DPR towers); ANCE_GATHER_TYPES_LENGTH: 1 x min(passage_len, L) then 0
+ *   outputs    [B, L] each, every byte written (pad region included).  width ANCE_GATHER_REFERENCE: int32 ids, 1-byte bool mask;
+ *              ANCE_GATHER_WIDE: int64 ids and mask (what the trainers' .long() makes).  d_types (nullable): uint8 in both.
+ * ONE launch for all segments; no host/device copy, no allocation, no synchronisation.  Refuses (ANCE_E_INVALID, before any launch):
+ * a null table or a null pointer other than d_types; n_segs outside 1..3; L < 1; n_records < 1; B < 1; first < 0; first + B past
+ * n_index; an unknown mask, type or width code; d_records or an output not 4-byte aligned (int64 outputs and d_index: 8-byte). */
+#define ANCE_GATHER_MASK_LENGTH 0
+#define ANCE_GATHER_MASK_NONZERO 1
+#define ANCE_GATHER_TYPES_ZERO 0
+#define ANCE_GATHER_TYPES_LENGTH 1
+#define ANCE_GATHER_REFERENCE 0
+#define ANCE_GATHER_WIDE 1
+typedef struct AnceGatherSegment {
+    const void *d_records;
+    int64_t n_records;
+    const int64_t *d_index;
+    int64_t n_index;
+    void *d_ids, *d_mask;
+    void *d_types;                /* nullable: no token types written */
+    int32_t L, mask_rule, type_rule, reserved;
+} AnceGatherSegment;
+int ance_gather_batch(const AnceGatherSegment *h_segs, int n_segs, int64_t first, int64_t B, int width, void *stream);
 
 /* Re-reads every ANCE_* tuning knob from the environment (they are otherwise read once per process).  For tests and
  * sweeps that change a knob between two calls; not thread-safe against concurrent searches. */
