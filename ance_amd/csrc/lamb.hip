@@ -11,7 +11,7 @@
 //
 // ance_lamb_step_clipped: torch.nn.utils.clip_grad_norm_(params, max_grad_norm) (2-norm, error_if_nonfinite=False) fused in front,
 // two more launches and 4 B more per element (44 B; clip_grad_norm_ then the step moves 52 B in a dozen launches):
-//   gnorm    (one workgroup per chunk)  reads g only; the chunk's sum of g^2 (fp64) stored to its slot
+//   gnorm    (one workgroup per chunk; multi_tensor.hip)  reads g only; the chunk's sum of g^2 (fp64) stored to its slot
 //   gtotal   (one workgroup)  the chunk sums added in chunk order (fp64), one sqrt, rounded to fp32 -> *d_grad_norm;
 //            coef = min(max_grad_norm / (total + 1e-6), 1) in fp32, NaN when the total is NaN (as torch's clamp)
 //   pass 1   as above with g * coef (an fp32 product, formed in registers) in place of g; the gradients in memory are not rescaled
@@ -29,28 +29,22 @@
 //            written and may be inf or NaN); reduce writes the rows of d_prev_out (or (0, 0, 1)) into d_out instead of new norms
 //            and one thread adds 1 to *d_skipped with an ordinary load, add and store.
 // Without the two pointers the launches and the instantiations are those of ance_lamb_step / ance_lamb_step_clipped.
+//
+// Here: LAMB's arithmetic, pass 1, reduce, gtotal and pass 2, its group rows and its entry points.  The walk of a workgroup over its
+// chunk, the block sum and the device tensor row are multi_tensor.h's; the checks and the fill of the tables, the staging pool and
+// gnorm are multi_tensor.hip's, shared with adamw.hip.
 #include "multi_tensor.h"
 
 namespace ance {
 namespace {
 
-// the chunking, the gradient element under loss scaling and clipping, the gradient-norm pass and the staging pool: multi_tensor.h
 using mt::align16;
-using mt::gf32x4;
-using mt::gfloat;
-using mt::max_chunks;
-constexpr int LAMB_CHUNK = mt::CHUNK, LAMB_THREADS = mt::THREADS, LAMB_UNROLL = mt::UNROLL;
+using mt::DevTensor;
+constexpr int LAMB_THREADS = mt::THREADS;
 
 struct LambDevGroup {
     float b1, omb1, b2, omb2, eps, wd, neg_lr;
     int32_t has_wd;
-};
-struct LambDevTensor {
-    float *p;
-    const float *g;
-    float *m, *v;
-    int64_t numel;
-    int32_t chunk0, n_chunks, group, vec;
 };
 
 __device__ __forceinline__ float lamb_u(float p, float m, float v, const LambDevGroup &G) {
@@ -66,85 +60,26 @@ __device__ __forceinline__ float lamb_mv(float p, float g, float &m, float &v, c
     return lamb_u(p, m, v, G);
 }
 
-__device__ __forceinline__ void lamb_acc(float p, float u, double &sp, double &su) {
-    sp = __builtin_fma((double)p, (double)p, sp);
-    su = __builtin_fma((double)u, (double)u, su);
-}
-
 // CLIP: every gradient element is multiplied by *coef (ance_lamb_step_clipped) before it enters m and v; UNSCALE: by the inverse
 // of *grad_scale before that (ance_lamb_step_amp).  found_inf (nullable): a skipped step returns before any store.
 template <bool CLIP, bool UNSCALE>
-__global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
+__global__ void __launch_bounds__(LAMB_THREADS) lamb_pass1_kernel(const LambDevGroup *groups, const DevTensor *tensors,
                                                                   const int32_t *chunk_tensor, double2 *partial, const float *coef,
                                                                   const float *grad_scale, const float *found_inf) {
-    __shared__ double red[LAMB_THREADS / 64][2];
     if (mt::skip(found_inf)) return;
-    const int tid = threadIdx.x;
     const float cf = CLIP ? coef[0] : 1.0f;
     const float inv = UNSCALE ? mt::inv_scale(grad_scale) : 1.0f;
-    const LambDevTensor T = tensors[chunk_tensor[blockIdx.x]];
+    const DevTensor T = tensors[chunk_tensor[blockIdx.x]];
     const LambDevGroup G = groups[T.group];
-    const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
-    const int len = (int)min((int64_t)LAMB_CHUNK, T.numel - base);
-    gfloat *p = (gfloat *)(T.p + base), *m = (gfloat *)(T.m + base), *v = (gfloat *)(T.v + base);
-    const gfloat *g = (const gfloat *)(T.g + base);
-    double sp = 0.0, su = 0.0;
-    int done = 0;
-    if (T.vec) {  // every pointer 16-byte aligned (chunk starts are multiples of 4 elements)
-        const int n4 = len >> 2;
-        const gf32x4 *p4 = (const gf32x4 *)p, *g4 = (const gf32x4 *)g;
-        gf32x4 *m4 = (gf32x4 *)m, *v4 = (gf32x4 *)v;
-        for (int i0 = tid; i0 < n4; i0 += LAMB_THREADS * LAMB_UNROLL) {
-            f32x4 P[LAMB_UNROLL], Gr[LAMB_UNROLL], M[LAMB_UNROLL], V[LAMB_UNROLL];
-#pragma unroll
-            for (int k = 0; k < LAMB_UNROLL; ++k) {
-                const int i = i0 + k * LAMB_THREADS;
-                if (i < n4) { P[k] = p4[i]; Gr[k] = g4[i]; M[k] = m4[i]; V[k] = v4[i]; }
-            }
-#pragma unroll
-            for (int k = 0; k < LAMB_UNROLL; ++k) {
-                const int i = i0 + k * LAMB_THREADS;
-                if (i < n4) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float mj = M[k][j], vj = V[k][j];
-                        const float u = lamb_mv(P[k][j], mt::grad<CLIP, UNSCALE>(Gr[k][j], inv, cf), mj, vj, G);
-                        M[k][j] = mj;
-                        V[k][j] = vj;
-                        lamb_acc(P[k][j], u, sp, su);
-                    }
-                    m4[i] = M[k];
-                    v4[i] = V[k];
-                }
-            }
-        }
-        done = n4 * 4;
-    }
-    for (int e = done + tid; e < len; e += LAMB_THREADS) {  // scalar tail (or the whole chunk of an unaligned tensor)
-        float mj = m[e], vj = v[e];
-        const float pj = p[e];
-        const float u = lamb_mv(pj, mt::grad<CLIP, UNSCALE>(g[e], inv, cf), mj, vj, G);
-        m[e] = mj;
-        v[e] = vj;
-        lamb_acc(pj, u, sp, su);
-    }
-    // fixed-order block sum: xor-shuffle tree inside each wave, then the four waves in order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sp += __shfl_xor(sp, off);
-        su += __shfl_xor(su, off);
-    }
-    if ((tid & 63) == 0) {
-        red[tid >> 6][0] = sp;
-        red[tid >> 6][1] = su;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double a = red[0][0], b = red[0][1];
-#pragma unroll
-        for (int w = 1; w < LAMB_THREADS / 64; ++w) { a += red[w][0]; b += red[w][1]; }
-        partial[blockIdx.x] = make_double2(a, b);
-    }
+    float *a[4];
+    const int len = mt::chunk_of(T, a);
+    double s[2] = {0.0, 0.0};  // of p^2, of u^2
+    mt::stream_chunk<0b1111, 0b1100>(a, len, T.vec, [&](float(&x)[4]) {
+        const float u = lamb_mv(x[0], mt::grad<CLIP, UNSCALE>(x[1], inv, cf), x[2], x[3], G);
+        s[0] = __builtin_fma((double)x[0], (double)x[0], s[0]);
+        s[1] = __builtin_fma((double)u, (double)u, s[1]);
+    });
+    if (mt::block_sum(s)) partial[blockIdx.x] = make_double2(s[0], s[1]);
 }
 
 // one workgroup: every chunk's sum in chunk order (thread-strided, then a shared-memory tree) -> the total norm and the clip factor
@@ -156,7 +91,7 @@ __global__ void __launch_bounds__(1024) lamb_gtotal_kernel(const double *gpartia
 
 // one wave per tensor: chunk sums in chunk order (lane-strided, then an xor-shuffle tree) -> (wn, an, tr).  A skipped step
 // (found_inf) has no chunk sums: the tensor's row is the one of prev_out, or (0, 0, 1) without it, and one thread counts the skip.
-__global__ void __launch_bounds__(256) lamb_reduce_kernel(const LambDevTensor *tensors, int n_tensors, const double2 *partial,
+__global__ void __launch_bounds__(256) lamb_reduce_kernel(const DevTensor *tensors, int n_tensors, const double2 *partial,
                                                           float *out, const float *found_inf, const float *prev_out,
                                                           int64_t *skipped) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
@@ -195,67 +130,39 @@ __global__ void __launch_bounds__(256) lamb_reduce_kernel(const LambDevTensor *t
     }
 }
 
-__global__ void __launch_bounds__(LAMB_THREADS) lamb_pass2_kernel(const LambDevGroup *groups, const LambDevTensor *tensors,
+__global__ void __launch_bounds__(LAMB_THREADS) lamb_pass2_kernel(const LambDevGroup *groups, const DevTensor *tensors,
                                                                   const int32_t *chunk_tensor, const float *out, int adam,
                                                                   const float *found_inf) {
     if (mt::skip(found_inf)) return;
-    const int tid = threadIdx.x;
     const int t = chunk_tensor[blockIdx.x];
-    const LambDevTensor T = tensors[t];
+    const DevTensor T = tensors[t];
     const LambDevGroup G = groups[T.group];
     const float tr = adam ? 1.0f : out[3 * (int64_t)t + 2];
     const float s = G.neg_lr * tr;  // the reference's -step_size * trust_ratio, an fp32 product
-    const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * LAMB_CHUNK;
-    const int len = (int)min((int64_t)LAMB_CHUNK, T.numel - base);
-    gfloat *p = (gfloat *)(T.p + base);
-    const gfloat *m = (const gfloat *)(T.m + base), *v = (const gfloat *)(T.v + base);
-    int done = 0;
-    if (T.vec) {
-        const int n4 = len >> 2;
-        gf32x4 *p4 = (gf32x4 *)p;
-        const gf32x4 *m4 = (const gf32x4 *)m, *v4 = (const gf32x4 *)v;
-        for (int i0 = tid; i0 < n4; i0 += LAMB_THREADS * LAMB_UNROLL) {
-            f32x4 P[LAMB_UNROLL], M[LAMB_UNROLL], V[LAMB_UNROLL];
-#pragma unroll
-            for (int k = 0; k < LAMB_UNROLL; ++k) {
-                const int i = i0 + k * LAMB_THREADS;
-                if (i < n4) { P[k] = p4[i]; M[k] = m4[i]; V[k] = v4[i]; }
-            }
-#pragma unroll
-            for (int k = 0; k < LAMB_UNROLL; ++k) {
-                const int i = i0 + k * LAMB_THREADS;
-                if (i < n4) {
-                    f32x4 r;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) r[j] = __builtin_fmaf(s, lamb_u(P[k][j], M[k][j], V[k][j], G), P[k][j]);
-                    p4[i] = r;
-                }
-            }
-        }
-        done = n4 * 4;
-    }
-    for (int e = done + tid; e < len; e += LAMB_THREADS) p[e] = __builtin_fmaf(s, lamb_u(p[e], m[e], v[e], G), p[e]);
+    float *a[4];
+    const int len = mt::chunk_of(T, a);
+    mt::stream_chunk<0b1101, 0b0001>(a, len, T.vec, [&](float(&x)[4]) { x[0] = __builtin_fmaf(s, lamb_u(x[0], x[2], x[3], G), x[0]); });
 }
 
-// workspace: [groups][tensors][chunk -> tensor] (staged from the host in one copy) [fp64 (p^2, u^2) per chunk]
-size_t staged_bytes(int n_tensors, int n_groups, int64_t n_chunks) {
-    return align16(sizeof(LambDevGroup) * (size_t)n_groups) + align16(sizeof(LambDevTensor) * (size_t)n_tensors) +
-           align16(sizeof(int32_t) * (size_t)n_chunks);
-}
+// workspace: [groups][tensors][chunk -> tensor] (staged from the host in one copy: multi_tensor.h) [fp64 (p^2, u^2) per chunk]
 size_t workspace_bytes_for(int n_tensors, int n_groups, int64_t n_chunks) {
-    return staged_bytes(n_tensors, n_groups, n_chunks) + sizeof(double2) * (size_t)n_chunks;
+    return mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks).end + sizeof(double2) * (size_t)n_chunks;
 }
 // the clipped step appends [fp64 g^2 per chunk][coef (fp32, 16 bytes)]
 size_t workspace_bytes_clipped(int n_tensors, int n_groups, int64_t n_chunks) {
     return workspace_bytes_for(n_tensors, n_groups, n_chunks) + align16(sizeof(double) * (size_t)n_chunks) + 16;
 }
 
-thread_local const char *g_lamb_fn = "ance_lamb_step";
-int lamb_refuse(const char *why) {
-    char buf[160];
-    snprintf(buf, sizeof(buf), "%s: invalid argument (%s)", g_lamb_fn, why);
-    set_last_error(buf);
-    return ANCE_E_INVALID;
+void lamb_group_row(void *row, const AnceLambGroup &a) {  // the reference's Python doubles, rounded to fp32 as torch does for a scalar
+    LambDevGroup &G = *(LambDevGroup *)row;
+    G.b1 = (float)a.beta1;
+    G.omb1 = (float)(1.0 - a.beta1);
+    G.b2 = (float)a.beta2;
+    G.omb2 = (float)(1.0 - a.beta2);
+    G.eps = (float)a.eps;
+    G.wd = (float)a.weight_decay;
+    G.neg_lr = (float)(-a.lr);
+    G.has_wd = a.weight_decay != 0.0;
 }
 
 // what ance_lamb_step_amp adds to a step: every pointer nullable, all null for the other two entry points
@@ -265,95 +172,42 @@ struct LambAmp {
 };
 
 template <bool CLIP, bool UNSCALE>
-void launch_pass1(int64_t n_chunks, hipStream_t st, const LambDevGroup *dG, const LambDevTensor *dT, const int32_t *dC, double2 *dP,
+void launch_pass1(int64_t n_chunks, hipStream_t st, const LambDevGroup *dG, const DevTensor *dT, const int32_t *dC, double2 *dP,
                   const float *dCoef, const LambAmp &amp) {
     hipLaunchKernelGGL((lamb_pass1_kernel<CLIP, UNSCALE>), dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, dP, dCoef,
                        amp.grad_scale, amp.found_inf);
 }
 
-// the body of ance_lamb_step (clip false), ance_lamb_step_clipped (clip true: max_norm, d_grad_norm) and ance_lamb_step_amp (amp)
-int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam, float *d_out,
-                   void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm, float *d_grad_norm,
-                   const LambAmp &amp) {
-    if (n_tensors < 0) return lamb_refuse("n_tensors < 0");
+// the body of ance_lamb_step (clip false), ance_lamb_step_clipped (clip true: max_norm, d_grad_norm) and ance_lamb_step_amp (amp);
+// fn: the entry point's name, for the error text
+int lamb_step_impl(const char *fn, const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                   float *d_out, void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm,
+                   float *d_grad_norm, const LambAmp &amp) {
+    if (n_tensors < 0) return mt::refuse(fn, "n_tensors < 0");
     if (n_tensors == 0) return ANCE_OK;
-    if (!h_tensors || !h_groups) return lamb_refuse("null table");
-    if (n_groups < 1) return lamb_refuse("n_groups < 1");
-    if (!d_out) return lamb_refuse("null d_out");
+    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
+    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
+    if (!d_out) return mt::refuse(fn, "null d_out");
     int64_t n_chunks = 0;
-    for (int t = 0; t < n_tensors; ++t) {
-        const AnceLambTensor &T = h_tensors[t];
-        if (T.group < 0 || T.group >= n_groups) return lamb_refuse("group index out of range");
-        if (T.numel < 0) return lamb_refuse("numel < 0");
-        if (T.numel > 0 && (!T.p || !T.g || !T.m || !T.v)) return lamb_refuse("null tensor pointer");
-        n_chunks += (T.numel + LAMB_CHUNK - 1) / LAMB_CHUNK;
-        if (n_chunks > (int64_t)INT32_MAX) return lamb_refuse("too many elements");
-    }
+    if (const int e = mt::count_chunks(fn, h_tensors, n_tensors, n_groups, &n_chunks)) return e;
     const size_t need = clip ? workspace_bytes_clipped(n_tensors, n_groups, n_chunks) : workspace_bytes_for(n_tensors, n_groups, n_chunks);
-    if (!d_workspace || (uintptr_t)d_workspace % 16) return lamb_refuse("null or unaligned workspace");
-    if (workspace_bytes < need) return lamb_refuse("workspace too small");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < need) return mt::refuse(fn, "workspace too small");
 
-    const size_t off_t = align16(sizeof(LambDevGroup) * (size_t)n_groups);
-    const size_t off_c = off_t + align16(sizeof(LambDevTensor) * (size_t)n_tensors);
-    const size_t off_p = staged_bytes(n_tensors, n_groups, n_chunks);
+    const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)d_workspace;
-    {
-        std::lock_guard<std::mutex> lock(mt::g_stage_mu);
-        const int si = mt::stage_acquire(off_p);
-        if (si < 0) {
-            set_last_error("ance_lamb_step: pinned staging buffer");
-            return ANCE_E_NOMEM;
-        }
-        mt::Staging &S = mt::g_stage[si];
-        char *h = (char *)S.h;
-        LambDevGroup *G = (LambDevGroup *)h;
-        for (int i = 0; i < n_groups; ++i) {  // the reference's Python doubles, rounded to fp32 as torch does for a scalar
-            const AnceLambGroup &a = h_groups[i];
-            G[i].b1 = (float)a.beta1;
-            G[i].omb1 = (float)(1.0 - a.beta1);
-            G[i].b2 = (float)a.beta2;
-            G[i].omb2 = (float)(1.0 - a.beta2);
-            G[i].eps = (float)a.eps;
-            G[i].wd = (float)a.weight_decay;
-            G[i].neg_lr = (float)(-a.lr);
-            G[i].has_wd = a.weight_decay != 0.0;
-        }
-        LambDevTensor *T = (LambDevTensor *)(h + off_t);
-        int32_t *ct = (int32_t *)(h + off_c);
-        int32_t c = 0;
-        for (int t = 0; t < n_tensors; ++t) {
-            const AnceLambTensor &a = h_tensors[t];
-            T[t].p = a.p;
-            T[t].g = a.g;
-            T[t].m = a.m;
-            T[t].v = a.v;
-            T[t].numel = a.numel;
-            T[t].group = a.group;
-            T[t].chunk0 = c;
-            T[t].n_chunks = (int32_t)((a.numel + LAMB_CHUNK - 1) / LAMB_CHUNK);
-            T[t].vec = ((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) % 16 == 0;
-            for (int32_t k = 0; k < T[t].n_chunks; ++k) ct[c++] = t;
-        }
-        const int sent = mt::stage_send(S, ws, off_p, st);
-        if (sent) return check_launch(sent == 1 ? "ance_lamb_step: tables" : "ance_lamb_step: staging event");
-    }
+    if (const int e = mt::stage_tables(fn, h_tensors, n_tensors, h_groups, n_groups, sizeof(LambDevGroup), lamb_group_row, L, ws, st))
+        return e;
     const LambDevGroup *dG = (const LambDevGroup *)ws;
-    const LambDevTensor *dT = (const LambDevTensor *)(ws + off_t);
-    const int32_t *dC = (const int32_t *)(ws + off_c);
-    double2 *dP = (double2 *)(ws + off_p);
+    const DevTensor *dT = (const DevTensor *)(ws + L.tensors);
+    const int32_t *dC = (const int32_t *)(ws + L.chunk_tensor);
+    double2 *dP = (double2 *)(ws + L.end);
     const bool unscale = amp.grad_scale != nullptr;
     if (clip) {
-        double *dGP = (double *)(ws + off_p + sizeof(double2) * (size_t)n_chunks);
+        double *dGP = (double *)(ws + L.end + sizeof(double2) * (size_t)n_chunks);
         float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
-        if (n_chunks > 0) {
-            if (unscale)
-                hipLaunchKernelGGL((mt::gnorm_kernel<LambDevTensor, true>), dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
-                                   amp.grad_scale);
-            else
-                hipLaunchKernelGGL((mt::gnorm_kernel<LambDevTensor, false>), dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dT, dC, dGP,
-                                   (const float *)nullptr);
-        }
+        mt::launch_gnorm(n_chunks, st, dT, dC, dGP, amp.grad_scale);
         hipLaunchKernelGGL(lamb_gtotal_kernel, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks, (float)max_norm, d_grad_norm,
                            dCoef);
         if (n_chunks > 0) {
@@ -369,7 +223,7 @@ int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLam
     if (n_chunks > 0)
         hipLaunchKernelGGL(lamb_pass2_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, (const float *)d_out,
                            adam ? 1 : 0, amp.found_inf);
-    return check_launch(g_lamb_fn);
+    return check_launch(fn);
 }
 
 }  // namespace
@@ -378,7 +232,7 @@ int lamb_step_impl(const AnceLambTensor *h_tensors, int n_tensors, const AnceLam
 extern "C" size_t ance_lamb_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
     using namespace ance;
     if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
-    const int64_t chunks = max_chunks(n_tensors, total_numel);
+    const int64_t chunks = mt::max_chunks(n_tensors, total_numel);
     if (chunks > (int64_t)INT32_MAX) return 0;
     return workspace_bytes_for(n_tensors, n_groups, chunks);
 }
@@ -386,14 +240,13 @@ extern "C" size_t ance_lamb_workspace_bytes(int n_tensors, int n_groups, int64_t
 extern "C" int ance_lamb_step(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
                               float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
     using namespace ance;
-    g_lamb_fn = "ance_lamb_step";
-    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, false, 0.0, nullptr, LambAmp());
+    return lamb_step_impl("ance_lamb_step", h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, false, 0.0, nullptr, LambAmp());
 }
 
 extern "C" size_t ance_lamb_clipped_workspace_bytes(int n_tensors, int n_groups, int64_t total_numel) {
     using namespace ance;
     if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
-    const int64_t chunks = max_chunks(n_tensors, total_numel);
+    const int64_t chunks = mt::max_chunks(n_tensors, total_numel);
     if (chunks > (int64_t)INT32_MAX) return 0;
     return workspace_bytes_clipped(n_tensors, n_groups, chunks);
 }
@@ -402,10 +255,10 @@ extern "C" int ance_lamb_step_clipped(const AnceLambTensor *h_tensors, int n_ten
                                       int adam, double max_grad_norm, float *d_grad_norm, float *d_out, void *d_workspace,
                                       size_t workspace_bytes, void *stream) {
     using namespace ance;
-    g_lamb_fn = "ance_lamb_step_clipped";
-    if (!(max_grad_norm > 0.0) || !(max_grad_norm < (double)INFINITY)) return lamb_refuse("max_grad_norm not a positive finite number");
-    if (n_tensors > 0 && !d_grad_norm) return lamb_refuse("null d_grad_norm");
-    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, true,
+    const char *fn = "ance_lamb_step_clipped";
+    if (!(max_grad_norm > 0.0) || !(max_grad_norm < (double)INFINITY)) return mt::refuse(fn, "max_grad_norm not a positive finite number");
+    if (n_tensors > 0 && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
+    return lamb_step_impl(fn, h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, true,
                           max_grad_norm, d_grad_norm, LambAmp());
 }
 
@@ -418,16 +271,16 @@ extern "C" int ance_lamb_step_amp(const AnceLambTensor *h_tensors, int n_tensors
                                   float *d_grad_norm, int64_t *d_skipped, float *d_out, void *d_workspace, size_t workspace_bytes,
                                   void *stream) {
     using namespace ance;
-    g_lamb_fn = "ance_lamb_step_amp";
+    const char *fn = "ance_lamb_step_amp";
     if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
-        return lamb_refuse("max_grad_norm not 0 or a positive finite number");
+        return mt::refuse(fn, "max_grad_norm not 0 or a positive finite number");
     const bool clip = max_grad_norm != 0.0;
-    if (clip && n_tensors > 0 && !d_grad_norm) return lamb_refuse("null d_grad_norm");
+    if (clip && n_tensors > 0 && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
     LambAmp amp;
     amp.grad_scale = d_grad_scale;
     amp.found_inf = d_found_inf;
     amp.prev_out = d_prev_out;
     amp.skipped = d_skipped;
-    return lamb_step_impl(h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, clip, max_grad_norm,
-                          d_grad_norm, amp);
+    return lamb_step_impl(fn, h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, clip,
+                          max_grad_norm, d_grad_norm, amp);
 }

@@ -1,12 +1,12 @@
-// What the fused multi-tensor optimizer steps share (lamb.hip, adamw.hip): the chunking of every tensor of a call into
-// 16,384-element pieces that one workgroup each streams with float4 accesses, the gradient element as it enters a step under loss
-// scaling and clipping, the gradient-norm pass and its fixed-order total, and the pinned staging pool of the host tables.
+// What the fused multi-tensor optimizer steps share (lamb.hip, adamw.hip).  Device side, here: the chunking of every tensor of a
+// call into 16,384-element pieces, the walk of one workgroup over one chunk with float4 accesses (stream_chunk), the fixed-order
+// block sum, the gradient element as it enters a step under loss scaling and clipping, and the total of the gradient-norm pass.
+// Host side, declared here and defined in multi_tensor.hip: the checks and the fill of the host tables, their pinned staging pool,
+// and the gradient-norm pass itself.
 #pragma once
 #include "common.h"
 
 #include <math.h>
-#include <mutex>
-#include <vector>
 
 namespace ance {
 namespace mt {
@@ -35,55 +35,102 @@ __device__ __forceinline__ float grad(float g, float inv, float cf) {
     return g;
 }
 
-// the chunk's sum of g^2 in fp64: reads g only.  UNSCALE: of (g * inv)^2, the fp32 product squared.  Tensor: a device table row
-// with g, numel and chunk0 (each step has its own, so the instantiations of two source files never share a name)
-template <class Tensor, bool UNSCALE>
-__global__ void __launch_bounds__(THREADS) gnorm_kernel(const Tensor *tensors, const int32_t *chunk_tensor, double *gpartial,
-                                                        const float *grad_scale) {
-    __shared__ double red[THREADS / 64];
-    const int tid = threadIdx.x;
-    const float inv = UNSCALE ? inv_scale(grad_scale) : 1.0f;
-    const Tensor T = tensors[chunk_tensor[blockIdx.x]];
+// one row of a step's device table: a tensor of the call and its chunks [chunk0, chunk0 + n_chunks) of the launch grid
+struct DevTensor {
+    float *p;
+    const float *g;
+    float *m, *v;
+    float *step;  // AdamW's device step count; null for LAMB
+    int64_t numel;
+    int32_t chunk0, n_chunks, group, vec;  // vec: p, g, m and v are all 16-byte aligned
+};
+
+// workgroup blockIdx.x's chunk of T: its start in (p, g, m, v) -> a; returns its length
+__device__ __forceinline__ int chunk_of(const DevTensor &T, float *(&a)[4]) {
     const int64_t base = (int64_t)(blockIdx.x - T.chunk0) * CHUNK;
-    const int len = (int)min((int64_t)CHUNK, T.numel - base);
-    const gfloat *g = (const gfloat *)(T.g + base);
-    double sg = 0.0;
+    a[0] = T.p + base;
+    a[1] = const_cast<float *>(T.g) + base;
+    a[2] = T.m + base;
+    a[3] = T.v + base;
+    return (int)min((int64_t)CHUNK, T.numel - base);
+}
+
+// One workgroup of THREADS streams one chunk of N arrays: f(x) sees one element of every array, x[n] that of a[n]; the arrays of
+// LOAD (bit n: a[n]) are read before it and those of STORE written after it.  vec: float4 accesses, UNROLL per array in flight
+// (chunk starts are multiples of 4 elements, so an aligned tensor's chunks are aligned), and a scalar tail; else the whole chunk
+// goes through the scalar loop.
+template <unsigned LOAD, unsigned STORE, int N, class F>
+__device__ __forceinline__ void stream_chunk(float *const (&a)[N], int len, int vec, F f) {
+    const int tid = threadIdx.x;
     int done = 0;
-    if (T.vec) {
+    if (vec) {
         const int n4 = len >> 2;
-        const gf32x4 *g4 = (const gf32x4 *)g;
         for (int i0 = tid; i0 < n4; i0 += THREADS * UNROLL) {
-            f32x4 Gr[UNROLL];
+            f32x4 X[UNROLL][N];
 #pragma unroll
             for (int k = 0; k < UNROLL; ++k) {
                 const int i = i0 + k * THREADS;
-                Gr[k] = i < n4 ? g4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+                if (i < n4) {
+#pragma unroll
+                    for (int n = 0; n < N; ++n)
+                        if (LOAD >> n & 1) X[k][n] = ((const gf32x4 *)a[n])[i];
+                }
             }
 #pragma unroll
-            for (int k = 0; k < UNROLL; ++k)
+            for (int k = 0; k < UNROLL; ++k) {
+                const int i = i0 + k * THREADS;
+                if (i < n4) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double x = (double)grad<false, UNSCALE>(Gr[k][j], inv, 1.0f);
-                    sg = __builtin_fma(x, x, sg);
+                    for (int j = 0; j < 4; ++j) {
+                        float x[N];
+#pragma unroll
+                        for (int n = 0; n < N; ++n) x[n] = (LOAD >> n & 1) ? X[k][n][j] : 0.0f;
+                        f(x);
+#pragma unroll
+                        for (int n = 0; n < N; ++n)
+                            if (STORE >> n & 1) X[k][n][j] = x[n];
+                    }
+#pragma unroll
+                    for (int n = 0; n < N; ++n)
+                        if (STORE >> n & 1) ((gf32x4 *)a[n])[i] = X[k][n];
                 }
+            }
         }
         done = n4 * 4;
     }
     for (int e = done + tid; e < len; e += THREADS) {
-        const double x = (double)grad<false, UNSCALE>(g[e], inv, 1.0f);
-        sg = __builtin_fma(x, x, sg);
-    }
-    // fixed-order block sum: xor-shuffle tree inside each wave, then the four waves in order
+        float x[N];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sg += __shfl_xor(sg, off);
-    if ((tid & 63) == 0) red[tid >> 6] = sg;
+        for (int n = 0; n < N; ++n) x[n] = (LOAD >> n & 1) ? ((const gfloat *)a[n])[e] : 0.0f;
+        f(x);
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+            if (STORE >> n & 1) ((gfloat *)a[n])[e] = x[n];
+    }
+}
+
+// fixed-order sum of K doubles per thread over a workgroup of THREADS: an xor-shuffle tree inside each wave, then the waves in
+// order.  True for thread 0, whose s holds the sums.
+template <int K>
+__device__ __forceinline__ bool block_sum(double (&s)[K]) {
+    __shared__ double red[THREADS / 64][K];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < K; ++k) s[k] += __shfl_xor(s[k], off);
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[tid >> 6][k] = s[k];
     __syncthreads();
-    if (tid == 0) {
-        double a = red[0];
+    if (tid != 0) return false;
 #pragma unroll
-        for (int w = 1; w < THREADS / 64; ++w) a += red[w];
-        gpartial[blockIdx.x] = a;
+    for (int k = 0; k < K; ++k) {
+        s[k] = red[0][k];
+#pragma unroll
+        for (int w = 1; w < THREADS / 64; ++w) s[k] += red[w][k];
     }
+    return true;
 }
 
 // every thread of ONE workgroup of 1024: every chunk's sum in chunk order (thread-strided, then a shared-memory tree) -> the total
@@ -108,71 +155,45 @@ __device__ __forceinline__ void grad_total(const double *gpartial, int n_chunks,
     }
 }
 
+// ---- host side (multi_tensor.hip) ----
 inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 inline int64_t max_chunks(int n_tensors, int64_t total_numel) {  // >= the sum of every tensor's ceil(numel / chunk)
     return (int64_t)n_tensors + total_numel / CHUNK;
 }
 
-// Pinned staging buffers of the host tables, one pool for every step of the library.  A buffer is handed out again only once the
-// event recorded after its last copy has completed (hipEventQuery, no wait), so a pending DMA never reads a buffer that is being
-// refilled.  When all of them are still in flight the pool grows; at its cap the caller waits for the oldest copy -- a host wait on
-// a copy enqueued POOL steps ago.
-constexpr int POOL = 16;
-struct Staging {
-    void *h = nullptr;
-    size_t bytes = 0;
-    hipEvent_t ev = nullptr;
-    bool recorded = false;
-    unsigned long long last_use = 0;
+// "<fn>: invalid argument (<why>)" -> the last error; returns ANCE_E_INVALID
+int refuse(const char *fn, const char *why);
+
+// every row of a host table checked (Host: AnceLambTensor or AnceAdamwTensor) and the chunks of the call counted -> *n_chunks;
+// ANCE_OK or a refusal in fn's name
+template <class Host>
+int count_chunks(const char *fn, const Host *h_tensors, int n_tensors, int n_groups, int64_t *n_chunks);
+
+// what a step stages from the host in one copy, at the start of its workspace: [group rows][DevTensor rows][chunk -> tensor];
+// byte offsets, end: where the step's own arrays begin
+struct Staged {
+    size_t tensors, chunk_tensor, end;
 };
-// one definition for every source file of the library (C++17 inline variables), hidden: the library exports its C ABI only
-#define ANCE_MT_SHARED inline __attribute__((visibility("hidden")))
-ANCE_MT_SHARED std::mutex g_stage_mu;
-ANCE_MT_SHARED std::vector<Staging> g_stage;
-ANCE_MT_SHARED unsigned long long g_stage_clock = 0;
-#undef ANCE_MT_SHARED
-
-// under g_stage_mu; returns the index of a buffer of >= bytes whose previous copy has run, or -1 (out of memory)
-inline int stage_acquire(size_t bytes) {
-    for (size_t i = 0; i < g_stage.size(); ++i) {
-        Staging &s = g_stage[i];
-        if (s.bytes >= bytes && (!s.recorded || hipEventQuery(s.ev) == hipSuccess)) return (int)i;
-    }
-    size_t want = 65536;
-    while (want < bytes) want <<= 1;
-    if ((int)g_stage.size() < POOL) {
-        Staging s;
-        if (hipHostMalloc(&s.h, want, hipHostMallocDefault) != hipSuccess) return -1;
-        if (hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) return -1;
-        s.bytes = want;
-        g_stage.push_back(s);
-        return (int)g_stage.size() - 1;
-    }
-    int old = 0;
-    for (int i = 1; i < (int)g_stage.size(); ++i)
-        if (g_stage[i].last_use < g_stage[old].last_use) old = i;
-    Staging &s = g_stage[old];
-    if (s.recorded && hipEventSynchronize(s.ev) != hipSuccess) return -1;
-    if (s.bytes < bytes) {  // the old buffer stays allocated: freeing pinned memory can synchronise the device
-        void *h = nullptr;
-        if (hipHostMalloc(&h, want, hipHostMallocDefault) != hipSuccess) return -1;
-        s.h = h;
-        s.bytes = want;
-    }
-    s.recorded = false;
-    return old;
+inline Staged staged(size_t group_row_bytes, int n_tensors, int n_groups, int64_t n_chunks) {
+    Staged L;
+    L.tensors = align16(group_row_bytes * (size_t)n_groups);
+    L.chunk_tensor = L.tensors + align16(sizeof(DevTensor) * (size_t)n_tensors);
+    L.end = L.chunk_tensor + align16(sizeof(int32_t) * (size_t)n_chunks);
+    return L;
 }
 
-// under g_stage_mu: the first `bytes` of buffer S to the device on st, and the event that frees the buffer for its next use.
-// Returns 0, 1 (the copy failed) or 2 (the event)
-inline int stage_send(Staging &S, void *d_dst, size_t bytes, hipStream_t st) {
-    if (hipMemcpyAsync(d_dst, S.h, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
-    if (hipEventRecord(S.ev, st) != hipSuccess) return 2;
-    S.recorded = true;
-    S.last_use = ++g_stage_clock;
-    return 0;
-}
+// the three tables filled in a pinned staging buffer -- group row i by group_row(row, h_groups[i]) -- and sent to d_workspace on
+// st.  ANCE_OK or an error in fn's name
+template <class Host>
+int stage_tables(const char *fn, const Host *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups,
+                 size_t group_row_bytes, void (*group_row)(void *row, const AnceLambGroup &a), const Staged &L, void *d_workspace,
+                 hipStream_t st);
+
+// gnorm: one workgroup per chunk reads g only; the chunk's sum of g^2 in fp64 -> gpartial[chunk].  grad_scale (nullable): of
+// (g * inv)^2, the fp32 product squared
+void launch_gnorm(int64_t n_chunks, hipStream_t st, const DevTensor *tensors, const int32_t *chunk_tensor, double *gpartial,
+                  const float *grad_scale);
 
 }  // namespace mt
 }  // namespace ance

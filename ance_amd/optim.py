@@ -52,7 +52,134 @@ def _valid_max_grad_norm(max_grad_norm):
     return float(max_grad_norm)
 
 
-class Lamb(Optimizer):
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+class _Call(object):
+    """What ``_FusedOptimizer.step`` hands to a subclass's ``_launch``: the library, the two host tables as the leading arguments
+    of every step entry point (``tab``), the workspace and the stream, the scaler's tensors and what is stepped
+    (``todo``: [(parameter, gradient, group index, state)]; ``group0``: the group of the first of them)."""
+    __slots__ = ("L", "tab", "n", "device", "ws", "stream", "clip", "amp", "grad_scale", "found_inf", "todo", "group0")
+
+
+class _FusedOptimizer(Optimizer):
+    """What ``Lamb`` and ``AdamW`` share: the walk over ``param_groups`` with its checks, the host tables, the workspace cache, the
+    scaler's contract.  A subclass names its table row (``_TENSOR_DTYPE``, ``_TENSOR_CTYPE``, ``_rows``), its state (``_init_state``,
+    ``_check_state``), its workspace size and its library call (``_launch``)."""
+    _step_supports_amp_scaling = True  # torch.amp.GradScaler.step: attach grad_scale / found_inf and call step() unconditionally
+    _STATE_TENSORS = (('exp_avg', " state['exp_avg']"), ('exp_avg_sq', " state['exp_avg_sq']"))   # checked in this order
+
+    def _amp_scalar(self, name, device):
+        """optimizer.grad_scale / optimizer.found_inf as GradScaler attaches them: None, or a one-element fp32 tensor on the step's
+        device."""
+        t = getattr(self, name, None)
+        if t is None:
+            return None
+        what = "%s: optimizer.%s" % (self._name, name)
+        _lib.require_cuda_tensor(t, torch.float32, what)
+        if t.numel() != 1:
+            raise _lib.AnceLibraryError("%s must have one element, got shape %s" % (what, tuple(t.shape)))
+        if t.device != device:
+            raise _lib.AnceLibraryError("%s is on %s, the parameters of this step on %s (mixed devices)" % (what, t.device, device))
+        return t
+
+    def _checked(self, t, what, device):
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == device:
+            return t   # the common case in one test: several tensors per parameter pass here at every step
+        _lib.require_cuda_tensor(t, torch.float32, what)
+        if t.device != device:
+            raise _lib.AnceLibraryError("%s is on %s, the other tensors of this step on %s (mixed devices)" % (what, t.device, device))
+        return t
+
+    def _check_group(self, gi, group, first_group):
+        """A subclass's check of a group that has a parameter to step; first_group: the first such group."""
+
+    def _check_state(self, state, name, p, device):
+        for key, suffix in self._STATE_TENSORS:
+            self._checked(state[key], name + suffix, device)
+        m, v = state['exp_avg'], state['exp_avg_sq']
+        if m.shape != p.shape or v.shape != p.shape:
+            raise _lib.AnceLibraryError("%s: state shapes %s, %s differ from the parameter's %s"
+                                        % (name, tuple(m.shape), tuple(v.shape), tuple(p.shape)))
+
+    def _walk(self):
+        """([(parameter, gradient, group index, its state or None)] of the parameters that have a gradient, the group table, their
+        device).  Checks everything and changes nothing: a refused step leaves no entry in ``self.state`` behind."""
+        todo, groups, device, first_group = [], [], None, None
+        checked, check_state, state_of = self._checked, self._check_state, self.state.get   # .get: no entry is created
+        for gi, group in enumerate(self.param_groups):
+            beta1, beta2 = group['betas']
+            groups.append((float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay'])))
+            group_checked = False
+            for pi, p in enumerate(group['params']):
+                if p.grad is None:
+                    continue
+                grad = p.grad
+                if grad.is_sparse:
+                    raise RuntimeError(self._SPARSE)
+                name = "%s: param_groups[%d]['params'][%d]" % (self._name, gi, pi)
+                if device is None:
+                    _lib.require_cuda_tensor(p, torch.float32, name)
+                    device, first_group = p.device, group
+                checked(p, name, device)
+                checked(grad, name + ".grad", device)
+                if grad.shape != p.shape:
+                    raise _lib.AnceLibraryError("%s.grad has shape %s, the parameter %s" % (name, tuple(grad.shape), tuple(p.shape)))
+                if not group_checked:
+                    self._check_group(gi, group, first_group)
+                    group_checked = True
+                state = state_of(p)
+                if state:
+                    check_state(state, name, p, device)
+                todo.append((p, grad, gi, state))
+        return todo, groups, device
+
+    def step(self, closure=None):
+        """One step of every parameter that has a gradient.  Asynchronous: enqueued on the current stream, no host wait -- also
+        under a GradScaler (``grad_scale`` / ``found_inf``, see the class): a skipped step is skipped on the device."""
+        loss = None
+        if closure is not None:
+            loss = closure()
+
+        todo, groups, device = self._walk()
+        if not todo:
+            return loss
+        c = _Call()
+        c.group0 = self.param_groups[todo[0][2]]
+        c.grad_scale, c.found_inf = self._amp_scalar("grad_scale", device), self._amp_scalar("found_inf", device)
+        c.amp = c.grad_scale is not None or c.found_inf is not None
+        for k, (p, grad, gi, state) in enumerate(todo):   # everything is checked: only now is state created
+            if not state:
+                state = self.state[p]
+                self._init_state(state, p)
+                todo[k] = (p, grad, gi, state)
+        c.todo = todo
+        rows = self._rows(todo)
+
+        c.L = _lib.lib()
+        tensors = np.array(rows, dtype=self._TENSOR_DTYPE)
+        gtab = np.array(groups, dtype=_GROUP_DTYPE)
+        total = int(tensors["numel"].sum())
+        c.n, c.device, c.clip = len(rows), device, self.max_grad_norm is not None
+        need = self._workspace_bytes(c, len(groups), total)
+        if need == 0:
+            raise _lib.AnceLibraryError("%s: %d tensors of %d elements exceed %s's limits" % (self._name, c.n, total, self._ENTRY))
+        with torch.cuda.device(device):
+            c.ws = self._workspace.get(device)
+            if c.ws is None or c.ws.numel() < need:
+                c.ws = torch.empty(need, dtype=torch.uint8, device=device)
+                self._workspace[device] = c.ws
+            if c.amp and (self.skipped_steps is None or self.skipped_steps.device != device):
+                self.skipped_steps = torch.zeros((), dtype=torch.int64, device=device)
+            c.stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            c.tab = (tensors.ctypes.data_as(ctypes.POINTER(self._TENSOR_CTYPE)), c.n,
+                     gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups))
+            self._launch(c)
+        return loss
+
+
+class Lamb(_FusedOptimizer):
     r"""LAMB (You et al., "Large Batch Optimization for Deep Learning: Training BERT in 76 minutes"), the reference's form:
     no bias correction, ``wn = min(|p|, 10)``, trust ratio 1 where ``wn`` or the Adam step's norm is 0, and ``adam=True``
     for a trust ratio of 1 always (the norms and the LAMB trust ratio are still recorded).
@@ -81,7 +208,10 @@ class Lamb(Optimizer):
     ones included (no arithmetic reads it: the reference's LAMB has no bias correction).  A scale of 0 or a non-finite scale
     poisons the step.
     """
-    _step_supports_amp_scaling = True  # torch.amp.GradScaler.step: attach grad_scale / found_inf and call step() unconditionally
+    _name = "Lamb"  # in front of every AnceLibraryError
+    _ENTRY = "ance_lamb_step"
+    _SPARSE = 'Lamb does not support sparse gradients, consider SparseAdam instad.'
+    _TENSOR_DTYPE, _TENSOR_CTYPE = _TENSOR_DTYPE, _lib.AnceLambTensor
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, adam=False, max_grad_norm=None):
         if not 0.0 <= lr:
@@ -102,122 +232,47 @@ class Lamb(Optimizer):
         self._workspace = {}
         self._prev_out = None  # (out of the last step, the ids of the parameters its rows belong to)
 
-    _name = "Lamb"  # in front of every AnceLibraryError
+    def _init_state(self, state, p):
+        state['step'] = 0
+        state['exp_avg'] = torch.zeros_like(p.data)
+        state['exp_avg_sq'] = torch.zeros_like(p.data)
 
-    def _amp_scalar(self, name, device):
-        """optimizer.grad_scale / optimizer.found_inf as GradScaler attaches them: None, or a one-element fp32 tensor on the step's
-        device."""
-        t = getattr(self, name, None)
-        if t is None:
-            return None
-        what = "%s: optimizer.%s" % (self._name, name)
-        _lib.require_cuda_tensor(t, torch.float32, what)
-        if t.numel() != 1:
-            raise _lib.AnceLibraryError("%s must have one element, got shape %s" % (what, tuple(t.shape)))
-        if t.device != device:
-            raise _lib.AnceLibraryError("%s is on %s, the parameters of this step on %s (mixed devices)" % (what, t.device, device))
-        return t
+    def _rows(self, todo):
+        return [(p.data_ptr(), grad.data_ptr(), state['exp_avg'].data_ptr(), state['exp_avg_sq'].data_ptr(), p.numel(), gi, 0)
+                for p, grad, gi, state in todo]
 
-    def _checked(self, t, what, device):
-        _lib.require_cuda_tensor(t, torch.float32, what)
-        if t.device != device:
-            raise _lib.AnceLibraryError("%s is on %s, the other tensors of this step on %s (mixed devices)" % (what, t.device, device))
-        return t
+    def _workspace_bytes(self, c, n_groups, total):
+        L = c.L
+        size_fn = L.ance_lamb_amp_workspace_bytes if c.amp else L.ance_lamb_clipped_workspace_bytes if c.clip else L.ance_lamb_workspace_bytes
+        return size_fn(c.n, n_groups, total)
 
-    def step(self, closure=None):
-        """One LAMB step of every parameter that has a gradient.  Asynchronous: enqueued on the current stream, no host wait --
-        also under a GradScaler (``grad_scale`` / ``found_inf``, see the class): a skipped step is skipped on the device."""
-        loss = None
-        if closure is not None:
-            loss = closure()
-
-        rows, groups, updated, stepped, device = [], [], [], [], None
-        for gi, group in enumerate(self.param_groups):
-            beta1, beta2 = group['betas']
-            groups.append((float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay'])))
-            for pi, p in enumerate(group['params']):
-                if p.grad is None:
-                    continue
-                grad = p.grad
-                if grad.is_sparse:
-                    raise RuntimeError('Lamb does not support sparse gradients, consider SparseAdam instad.')
-                name = "Lamb: param_groups[%d]['params'][%d]" % (gi, pi)
-                if device is None:
-                    _lib.require_cuda_tensor(p, torch.float32, name)
-                    device = p.device
-                self._checked(p, name, device)
-                self._checked(grad, name + ".grad", device)
-                if grad.shape != p.shape:
-                    raise _lib.AnceLibraryError("%s.grad has shape %s, the parameter %s" % (name, tuple(grad.shape), tuple(p.shape)))
-                state = self.state[p]
-                if len(state) == 0:
-                    state['step'] = 0
-                    state['exp_avg'] = torch.zeros_like(p.data)
-                    state['exp_avg_sq'] = torch.zeros_like(p.data)
-                m, v = state['exp_avg'], state['exp_avg_sq']
-                self._checked(m, name + " state['exp_avg']", device)
-                self._checked(v, name + " state['exp_avg_sq']", device)
-                if m.shape != p.shape or v.shape != p.shape:
-                    raise _lib.AnceLibraryError("%s: state shapes %s, %s differ from the parameter's %s"
-                                                % (name, tuple(m.shape), tuple(v.shape), tuple(p.shape)))
-                rows.append((p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi, 0))
-                updated.append(state)
-                stepped.append(id(p))
-        if not rows:
-            return loss
-        grad_scale, found_inf = self._amp_scalar("grad_scale", device), self._amp_scalar("found_inf", device)
-        amp = grad_scale is not None or found_inf is not None
-
-        L = _lib.lib()
-        tensors = np.array(rows, dtype=_TENSOR_DTYPE)
-        gtab = np.array(groups, dtype=_GROUP_DTYPE)
-        total = int(tensors["numel"].sum())
-        clip = self.max_grad_norm is not None
-        size_fn = L.ance_lamb_amp_workspace_bytes if amp else L.ance_lamb_clipped_workspace_bytes if clip else L.ance_lamb_workspace_bytes
-        need = size_fn(len(rows), len(groups), total)
-        if need == 0:
-            raise _lib.AnceLibraryError("Lamb: %d tensors of %d elements exceed ance_lamb_step's limits" % (len(rows), total))
-        with torch.cuda.device(device):
-            ws = self._workspace.get(device)
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=device)
-                self._workspace[device] = ws
-            out = torch.empty((len(rows), 3), dtype=torch.float32, device=device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            tab = (tensors.ctypes.data_as(ctypes.POINTER(_lib.AnceLambTensor)), len(rows),
-                   gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups), 1 if self.adam else 0)
-            tail = (ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream))
-            if amp:
-                if self.skipped_steps is None or self.skipped_steps.device != device:
-                    self.skipped_steps = torch.zeros((), dtype=torch.int64, device=device)
-                prev = self._prev_out[0] if self._prev_out is not None and self._prev_out[1] == stepped else None
-                norm = torch.empty((1,), dtype=torch.float32, device=device) if clip else None
-
-                def ptr(t):
-                    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-                _lib.check(L.ance_lamb_step_amp(*tab, self.max_grad_norm if clip else 0.0, ptr(grad_scale), ptr(found_inf), ptr(prev),
-                                                ptr(norm), ptr(self.skipped_steps), *tail), "ance_lamb_step_amp")
-                if clip:
-                    self.last_grad_norm = norm[0]
-            elif clip:
-                norm = torch.empty((1,), dtype=torch.float32, device=device)
-                _lib.check(L.ance_lamb_step_clipped(*tab, self.max_grad_norm, ctypes.c_void_p(norm.data_ptr()), *tail),
-                           "ance_lamb_step_clipped")
-                self.last_grad_norm = norm[0]
-            else:
-                _lib.check(L.ance_lamb_step(*tab, *tail), "ance_lamb_step")
+    def _launch(self, c):
+        L, device, clip = c.L, c.device, c.clip
+        stepped = [id(t[0]) for t in c.todo]
+        out = torch.empty((c.n, 3), dtype=torch.float32, device=device)
+        tab = c.tab + (1 if self.adam else 0,)
+        tail = (ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), c.stream)
+        norm = torch.empty((1,), dtype=torch.float32, device=device) if clip else None
+        if c.amp:
+            prev = self._prev_out[0] if self._prev_out is not None and self._prev_out[1] == stepped else None
+            _lib.check(L.ance_lamb_step_amp(*tab, self.max_grad_norm if clip else 0.0, _ptr(c.grad_scale), _ptr(c.found_inf), _ptr(prev),
+                                            _ptr(norm), _ptr(self.skipped_steps), *tail), "ance_lamb_step_amp")
+        elif clip:
+            _lib.check(L.ance_lamb_step_clipped(*tab, self.max_grad_norm, _ptr(norm), *tail), "ance_lamb_step_clipped")
+        else:
+            _lib.check(L.ance_lamb_step(*tab, *tail), "ance_lamb_step")
+        if clip:
+            self.last_grad_norm = norm[0]
         self._prev_out = (out, stepped)
         vals = out.view(-1).unbind(0)
-        for k, state in enumerate(updated):
+        for k, (_, _, _, state) in enumerate(c.todo):
             state['step'] += 1
             state['weight_norm'] = vals[3 * k]
             state['adam_norm'] = vals[3 * k + 1]
             state['trust_ratio'] = vals[3 * k + 2]
-        return loss
 
 
-class AdamW(Optimizer):
+class AdamW(_FusedOptimizer):
     r"""AdamW as transformers 2.3.0 has it (optimization.py, ``AdamW``) -- the optimizer drivers/run_ann_dpr.py:501-504 makes the DPR
     trainer's default through utils/dpr_utils.py:80-92, and run_ann.py:85-89 / run_warmup.py:79-81 build for ``--optimizer adamW``.
     transformers 5 no longer has the class, and ``torch.optim.AdamW`` is another arithmetic: it decays before the update and puts
@@ -249,10 +304,11 @@ class AdamW(Optimizer):
 
     No CPU fallback: every parameter, gradient and state tensor must be a contiguous fp32 tensor on one HIP device.
     """
-    _step_supports_amp_scaling = True
     _name = "AdamW"
-    _amp_scalar = Lamb._amp_scalar
-    _checked = Lamb._checked
+    _ENTRY = "ance_adamw_step"
+    _SPARSE = 'Adam does not support sparse gradients, please consider SparseAdam instead'
+    _TENSOR_DTYPE, _TENSOR_CTYPE = _ADAMW_TENSOR_DTYPE, _lib.AnceAdamwTensor
+    _STATE_TENSORS = _FusedOptimizer._STATE_TENSORS + (('step', " state['step']"),)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, max_grad_norm=None):
         if lr < 0.0:
@@ -292,88 +348,34 @@ class AdamW(Optimizer):
                     n = float(n.item()) if isinstance(n, torch.Tensor) else float(n)
                     st['step'] = torch.full((), n, dtype=torch.float32, device=p.device)
 
-    def step(self, closure=None):
-        """One AdamW step of every parameter that has a gradient.  Asynchronous: enqueued on the current stream, no host wait --
-        also under a GradScaler: a skipped step is skipped on the device, its step counts included."""
-        loss = None
-        if closure is not None:
-            loss = closure()
+    def _check_group(self, gi, group, first_group):
+        if bool(group['correct_bias']) != bool(first_group['correct_bias']):
+            raise _lib.AnceLibraryError("AdamW: param_groups[%d]['correct_bias'] differs from an earlier group's: one step "
+                                        "has one value" % gi)
 
-        todo, groups, device, correct_bias = [], [], None, None
-        for gi, group in enumerate(self.param_groups):
-            beta1, beta2 = group['betas']
-            groups.append((float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay'])))
-            for pi, p in enumerate(group['params']):
-                if p.grad is None:
-                    continue
-                grad = p.grad
-                if grad.is_sparse:
-                    raise RuntimeError('Adam does not support sparse gradients, please consider SparseAdam instead')
-                name = "AdamW: param_groups[%d]['params'][%d]" % (gi, pi)
-                if device is None:
-                    _lib.require_cuda_tensor(p, torch.float32, name)
-                    device = p.device
-                self._checked(p, name, device)
-                self._checked(grad, name + ".grad", device)
-                if grad.shape != p.shape:
-                    raise _lib.AnceLibraryError("%s.grad has shape %s, the parameter %s" % (name, tuple(grad.shape), tuple(p.shape)))
-                if correct_bias is None:
-                    correct_bias = bool(group['correct_bias'])
-                elif correct_bias != bool(group['correct_bias']):
-                    raise _lib.AnceLibraryError("AdamW: param_groups[%d]['correct_bias'] differs from an earlier group's: one step "
-                                                "has one value" % gi)
-                state = self.state.get(p)   # .get: a refused call must not leave an entry behind
-                if state:
-                    m, v, n = state['exp_avg'], state['exp_avg_sq'], state['step']
-                    self._checked(m, name + " state['exp_avg']", device)
-                    self._checked(v, name + " state['exp_avg_sq']", device)
-                    self._checked(n, name + " state['step']", device)
-                    if m.shape != p.shape or v.shape != p.shape:
-                        raise _lib.AnceLibraryError("%s: state shapes %s, %s differ from the parameter's %s"
-                                                    % (name, tuple(m.shape), tuple(v.shape), tuple(p.shape)))
-                    if n.numel() != 1:
-                        raise _lib.AnceLibraryError("%s: state['step'] must have one element, got shape %s" % (name, tuple(n.shape)))
-                todo.append((p, grad, gi))
-        if not todo:
-            return loss
-        grad_scale, found_inf = self._amp_scalar("grad_scale", device), self._amp_scalar("found_inf", device)
-        rows = []   # everything is checked: only now is state created
-        for p, grad, gi in todo:
-            state = self.state[p]
-            if len(state) == 0:
-                state['step'] = torch.zeros((), dtype=torch.float32, device=device)
-                state['exp_avg'] = torch.zeros_like(p.data)
-                state['exp_avg_sq'] = torch.zeros_like(p.data)
-            rows.append((p.data_ptr(), grad.data_ptr(), state['exp_avg'].data_ptr(), state['exp_avg_sq'].data_ptr(),
-                         state['step'].data_ptr(), p.numel(), gi, 0))
-        amp = grad_scale is not None or found_inf is not None
+    def _check_state(self, state, name, p, device):
+        _FusedOptimizer._check_state(self, state, name, p, device)
+        n = state['step']
+        if n.numel() != 1:
+            raise _lib.AnceLibraryError("%s: state['step'] must have one element, got shape %s" % (name, tuple(n.shape)))
 
-        L = _lib.lib()
-        tensors = np.array(rows, dtype=_ADAMW_TENSOR_DTYPE)
-        gtab = np.array(groups, dtype=_GROUP_DTYPE)
-        total = int(tensors["numel"].sum())
-        clip = self.max_grad_norm is not None
-        need = L.ance_adamw_workspace_bytes(len(rows), len(groups), total, 1 if clip else 0)
-        if need == 0:
-            raise _lib.AnceLibraryError("AdamW: %d tensors of %d elements exceed ance_adamw_step's limits" % (len(rows), total))
-        with torch.cuda.device(device):
-            ws = self._workspace.get(device)
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=device)
-                self._workspace[device] = ws
-            if amp and (self.skipped_steps is None or self.skipped_steps.device != device):
-                self.skipped_steps = torch.zeros((), dtype=torch.int64, device=device)
-            norm = torch.empty((1,), dtype=torch.float32, device=device) if clip else None
+    def _init_state(self, state, p):
+        state['step'] = torch.zeros((), dtype=torch.float32, device=p.device)
+        state['exp_avg'] = torch.zeros_like(p.data)
+        state['exp_avg_sq'] = torch.zeros_like(p.data)
 
-            def ptr(t):
-                return None if t is None else ctypes.c_void_p(t.data_ptr())
+    def _rows(self, todo):
+        return [(p.data_ptr(), grad.data_ptr(), state['exp_avg'].data_ptr(), state['exp_avg_sq'].data_ptr(), state['step'].data_ptr(),
+                 p.numel(), gi, 0) for p, grad, gi, state in todo]
 
-            _lib.check(L.ance_adamw_step(tensors.ctypes.data_as(ctypes.POINTER(_lib.AnceAdamwTensor)), len(rows),
-                                         gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups), 1 if correct_bias else 0,
-                                         self.max_grad_norm if clip else 0.0, ptr(grad_scale), ptr(found_inf), ptr(norm),
-                                         ptr(self.skipped_steps if amp else None), ctypes.c_void_p(ws.data_ptr()),
-                                         ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
-                       "ance_adamw_step")
-            if clip:
-                self.last_grad_norm = norm[0]
-        return loss
+    def _workspace_bytes(self, c, n_groups, total):
+        return c.L.ance_adamw_workspace_bytes(c.n, n_groups, total, 1 if c.clip else 0)
+
+    def _launch(self, c):
+        """A skipped step is skipped on the device, its step counts included."""
+        norm = torch.empty((1,), dtype=torch.float32, device=c.device) if c.clip else None
+        _lib.check(c.L.ance_adamw_step(*c.tab, 1 if c.group0['correct_bias'] else 0, self.max_grad_norm if c.clip else 0.0, _ptr(c.grad_scale),
+                                       _ptr(c.found_inf), _ptr(norm), _ptr(self.skipped_steps if c.amp else None),
+                                       ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), c.stream), "ance_adamw_step")
+        if c.clip:
+            self.last_grad_norm = norm[0]
