@@ -16,7 +16,9 @@
 //   fp16 subnormal inputs, 2^-25 per element:  <= 2^-25 sqrt(d) (|dq| + |x'|)
 //   the chain itself, C vs q . x:              <= d 2^-24 |q| |x|       (the un-centred norms)
 // |s~ - (C - q . mu)| <= eps = 1.25 * [ (2^-10 + 1.1 d 2^-24) |dq| X' + 2.1 d 2^-24 |mq| X' + 2^-23 |q| X' + 2^-24 sqrt(d) (|dq| + X') + d 2^-24 |q| X ]
-// with X' = max |x'|, X = max |x| (tests/test_eps_bound.py attacks it on the CPU).  The query mean is only used when it
+// with X' = max |x'|, X = max |x| (tests/test_eps_bound.py attacks it on the CPU).  tests/test_gpu_search_adversarial.py runs
+// the device code on corpora whose true neighbours the filter under-estimates by 30-35 % of 2 eps: a slack about three
+// times too small at any site that applies it loses rows there.  The query mean is only used when it
 // is a sizeable part of the queries (|mq| > 0.05 X); otherwise mq = 0, dq = q, b = 0 and the bias pass is skipped.
 #pragma once
 #include "search_image.h"
