@@ -79,6 +79,23 @@ class AnceGatherSegment(ctypes.Structure):
                 ("L", ctypes.c_int32), ("mask_rule", ctypes.c_int32), ("type_rule", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class AnceAttnTrainArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_attention_forward / ance_attention_backward."""
+    _fields_ = [("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("ctx", ctypes.c_void_p),
+                ("ld_q", ctypes.c_int32), ("ld_k", ctypes.c_int32), ("ld_v", ctypes.c_int32), ("ld_ctx", ctypes.c_int32),
+                ("d_seq_first", ctypes.c_void_p), ("d_seq_len", ctypes.c_void_p), ("n_seq", ctypes.c_int32),
+                ("max_seq_len", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_heads", ctypes.c_int32),
+                ("seq_rows", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("dropout_p", ctypes.c_float), ("training", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("d_workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class AnceAttnGradArgs(ctypes.Structure):
+    """include/ance_amd.h: the gradient side of ance_attention_backward."""
+    _fields_ = [("dctx", ctypes.c_void_p), ("dq", ctypes.c_void_p), ("dk", ctypes.c_void_p), ("dv", ctypes.c_void_p),
+                ("ld_dctx", ctypes.c_int32), ("ld_dq", ctypes.c_int32), ("ld_dk", ctypes.c_int32), ("ld_dv", ctypes.c_int32)]
+
+
 # ance_gather_batch codes (include/ance_amd.h: ANCE_GATHER_*)
 GATHER_MASK_LENGTH, GATHER_MASK_NONZERO = 0, 1
 GATHER_TYPES_ZERO, GATHER_TYPES_LENGTH = 0, 1
@@ -181,6 +198,9 @@ SYMBOLS = {
                                                  ctypes.c_size_t, ctypes.c_void_p]),
     "ance_gather_batch": (ctypes.c_int, [ctypes.POINTER(AnceGatherSegment), ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                          ctypes.c_void_p]),
+    "ance_attention_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_attention_forward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.c_void_p]),
+    "ance_attention_backward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.POINTER(AnceAttnGradArgs), ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

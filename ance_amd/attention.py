@@ -1,0 +1,208 @@
+"""The trainers' self-attention core, differentiable (csrc/attention_train.hip behind ance_attention_forward / _backward).
+
+What transformers' eager ``BertSelfAttention.forward`` computes between its three Linear outputs and ``context_layer``, for
+right-padded sequences and heads of width 64: scores * 0.125, softmax over the valid keys in fp32, dropout on the probabilities,
+probabilities times values.  Nothing of size L^2 is stored: the forward keeps one log-sum-exp per (head, row), the backward
+recomputes the probabilities and regenerates the dropout mask.  Pad query rows of the result and of the three gradients are zeros;
+a sequence of length 0 is skipped.
+
+    ctx = attention_padded(q, k, v, lens_from_mask(attention_mask), n_heads, dropout_p, self.training)     # [B, L, H] each
+    ctx = attention_packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, self.training)               # [T, H] each
+
+Dropout: Philox4x32-10 under (seed, offset), stated in include/ance_amd.h.  ``seed`` is ``manual_seed(n)``'s (default:
+``torch.initial_seed()``, read on the host when first needed); ``offset`` is a per-device call counter that every dropout forward
+advances by one.  The backward gets the forward's pair through the autograd context.  Both are HOST values baked into the launch:
+a captured graph replays the pair it was captured with -- the same mask at every replay.  The masks are not torch's.
+"""
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+
+try:  # torch >= 2.4
+    from torch.amp import custom_bwd as _amp_bwd, custom_fwd as _amp_fwd
+    _custom_fwd = _amp_fwd(device_type="cuda", cast_inputs=torch.float32)
+    _custom_bwd = _amp_bwd(device_type="cuda")
+except ImportError:  # pragma: no cover
+    from torch.cuda.amp import custom_bwd as _custom_bwd, custom_fwd as _amp_fwd
+    _custom_fwd = _amp_fwd(cast_inputs=torch.float32)
+
+__all__ = ["attention_padded", "attention_packed", "lens_from_mask", "manual_seed", "dropout_state"]
+
+
+class _DropoutState:
+    """The seed and the per-device call counters of the dropout stream (host values)."""
+
+    def __init__(self):
+        self.seed = None
+        self.offsets = {}
+
+    def manual_seed(self, n):
+        self.seed = int(n) & 0xFFFFFFFFFFFFFFFF
+        self.offsets = {}
+
+    def next_pair(self, device):
+        if self.seed is None:
+            self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        dev = device.index if device.index is not None else torch.cuda.current_device()
+        off = self.offsets.get(dev, 0)
+        self.offsets[dev] = off + 1
+        return self.seed, off
+
+
+dropout_state = _DropoutState()
+
+
+def manual_seed(n):
+    """Seeds the dropout stream and resets every device's call counter: the same calls after it give the same bits."""
+    dropout_state.manual_seed(n)
+
+
+def lens_from_mask(attention_mask):
+    """[B] int32 lengths of a [B, L] attention mask, computed on the device with no synchronisation.  The mask must be a right-padded
+    prefix (ones, then zeros), as every loader of the reference produces; a mask with holes is outside the contract -- it is read as
+    the prefix with the same number of ones."""
+    if attention_mask.dim() != 2:
+        raise _lib.AnceLibraryError("attention_mask must be [B, L]")
+    return (attention_mask != 0).sum(dim=1, dtype=torch.int32)
+
+
+def _rows(t):
+    """A [.., H] fp32 CUDA tensor as a row matrix: (tensor to keep alive, row stride).  A view whose rows are evenly spaced passes as
+    it is; anything else is copied."""
+    if t.dim() == 3:
+        if t.stride(2) != 1 or t.stride(0) != t.size(1) * t.stride(1) or t.stride(1) % 4 or t.stride(1) < t.size(2) or t.data_ptr() % 16:
+            t = t.contiguous()
+        return t, t.stride(1)
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.size(1) or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t, t.stride(0)
+
+
+def _check_inputs(q, k, v, n_heads, dropout_p, dims):
+    for t, what in ((q, "q"), (k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor" % what)
+        if t.dtype != torch.float32 and not (torch.is_autocast_enabled() and t.is_floating_point()):  # autocast: cast below
+            raise _lib.AnceLibraryError("%s must have dtype torch.float32, got %s" % (what, t.dtype))
+        if t.dim() != dims or t.shape != q.shape or t.device != q.device:
+            raise _lib.AnceLibraryError("q, k, v must be %d-dimensional, of one shape, on one device" % dims)
+    if n_heads not in (12, 16):
+        raise _lib.AnceLibraryError("n_heads must be 12 or 16, got %r" % (n_heads,))
+    if q.shape[-1] != 64 * n_heads:
+        raise _lib.AnceLibraryError("the last dimension must be 64 * n_heads = %d, got %d" % (64 * n_heads, q.shape[-1]))
+    if not 0.0 <= float(dropout_p) < 1.0:
+        raise _lib.AnceLibraryError("dropout_p must be in [0, 1), got %r" % (dropout_p,))
+    if q.numel() == 0:
+        raise _lib.AnceLibraryError("empty input")
+
+
+def _int32(t, what, n, device):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device or t.dim() != 1 or t.numel() != n \
+            or t.dtype not in (torch.int32, torch.int64):
+        raise _lib.AnceLibraryError("%s must be a device integer tensor [%d] on %s" % (what, n, device))
+    return t.to(torch.int32).contiguous()
+
+
+def _grads_like(q, k, v, zero):
+    """Gradients in the inputs' own strides (zeroed for the packed form; in the padded form the kernels write every row).  Views of
+    one fused buffer ([.., 3H] rows) get views of one fused gradient."""
+    ts = (q, k, v)
+    make = torch.zeros if zero else torch.empty
+    if all(t.is_contiguous() for t in ts):
+        return tuple(make(t.shape, dtype=t.dtype, device=t.device) for t in ts)
+    H, ld = q.shape[-1], q.stride(-2)
+    same = all(t.stride() == q.stride() and t.untyped_storage().data_ptr() == q.untyped_storage().data_ptr() for t in ts)
+    offs = [t.storage_offset() for t in ts]
+    if same and ld >= 3 * H and max(offs) - min(offs) + H <= ld and offs[0] // ld == offs[1] // ld == offs[2] // ld:
+        base = min(offs)
+        fused = torch.zeros(q.shape[:-1] + (ld,), dtype=q.dtype, device=q.device) if zero or ld > 3 * H else \
+            torch.empty(q.shape[:-1] + (ld,), dtype=q.dtype, device=q.device)
+        return tuple(fused[..., o - base:o - base + H] for o in offs)
+    out = tuple(torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device) for t in ts)
+    return tuple(t.zero_() for t in out) if zero else out
+
+
+class _Attention(torch.autograd.Function):
+    """q, k, v: [B, L, H] or [T, H]; first, lens: int32 [n_seq] on the device."""
+
+    @staticmethod
+    @_custom_fwd
+    def forward(ctx, q, k, v, first, lens, max_seq_len, n_heads, dropout_p, training):
+        L = _lib.lib()
+        (q, ld_q), (k, ld_k), (v, ld_v) = _rows(q), _rows(k), _rows(v)
+        n_rows = q.numel() // q.shape[-1]
+        # padded form: the kernels write the pad rows' zeros themselves; packed form: rows that no sequence covers stay zero
+        seq_rows = max_seq_len if q.dim() == 3 else 0
+        out = (torch.empty if seq_rows else torch.zeros)(q.shape, dtype=torch.float32, device=q.device)
+        ws_bytes = L.ance_attention_workspace_bytes(n_rows, n_heads)
+        if ws_bytes == 0:
+            raise _lib.AnceLibraryError("attention: unsupported shape (rows %d, heads %d)" % (n_rows, n_heads))
+        ws = torch.zeros(ws_bytes // 4, dtype=torch.float32, device=q.device)
+        drop = bool(training) and dropout_p > 0.0
+        seed, offset = dropout_state.next_pair(q.device) if drop else (0, 0)
+        args = _lib.AnceAttnTrainArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
+                                      ld_ctx=out.shape[-1], d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(),
+                                      n_seq=first.numel(), max_seq_len=max_seq_len, n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows,
+                                      dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed, offset=offset,
+                                      d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+        with torch.cuda.device(q.device):
+            _lib.check(L.ance_attention_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_attention_forward")
+        ctx.save_for_backward(q, k, v, out, first, lens, ws)
+        ctx.args = args
+        lse = ws[:n_heads * n_rows].view(n_heads, n_rows)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dctx, _dlse):
+        L = _lib.lib()
+        q, k, v, out, first, lens, ws = ctx.saved_tensors
+        a = ctx.args
+        dctx, ld_d = _rows(dctx.to(torch.float32))
+        dq, dk, dv = _grads_like(q, k, v, zero=a.seq_rows == 0)
+        g = _lib.AnceAttnGradArgs(dctx=dctx.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
+                                  ld_dq=dq.stride(-2), ld_dk=dk.stride(-2), ld_dv=dv.stride(-2))
+        with torch.cuda.device(q.device):
+            _lib.check(L.ance_attention_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_attention_backward")
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def _padded(q, k, v, lens, n_heads, dropout_p, training):
+    _check_inputs(q, k, v, n_heads, dropout_p, 3)
+    B, Lq = q.shape[0], q.shape[1]
+    if not 1 <= Lq <= 512:
+        raise _lib.AnceLibraryError("sequence length must be in 1 .. 512, got %d" % Lq)
+    lens = _int32(lens, "lens", B, q.device)
+    first = torch.arange(0, B * Lq, Lq, dtype=torch.int32, device=q.device)
+    return _Attention.apply(q, k, v, first, lens, Lq, n_heads, float(dropout_p), bool(training))
+
+
+def _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training):
+    _check_inputs(q, k, v, n_heads, dropout_p, 2)
+    if not 1 <= int(max_seq_len) <= 512:
+        raise _lib.AnceLibraryError("max_seq_len must be in 1 .. 512, got %r" % (max_seq_len,))
+    if not isinstance(seq_off, torch.Tensor) or seq_off.dim() != 1 or seq_off.numel() < 2:
+        raise _lib.AnceLibraryError("seq_off must be a device integer tensor [n_seq + 1]")
+    off = _int32(seq_off, "seq_off", seq_off.numel(), q.device)
+    first, lens = off[:-1].contiguous(), (off[1:] - off[:-1]).contiguous()
+    return _Attention.apply(q, k, v, first, lens, int(max_seq_len), n_heads, float(dropout_p), bool(training))
+
+
+# _padded / _packed return (ctx, lse): lse is the saved fp32 log-sum-exp [n_heads, rows] (zeros at pad rows), non-differentiable.  It
+# is not part of the interface; the tests read it.
+def attention_padded(q, k, v, lens, n_heads, dropout_p=0.0, training=True):
+    """ctx [B, L, H] of right-padded sequences: q, k, v [B, L, H] fp32 (views with a contiguous last dimension pass as they are, so
+    three Linear outputs and the three thirds of a fused [B, L, 3H] both work), lens [B] device integers (lens_from_mask).  Rows
+    >= lens[b] of ctx and of the gradients are zeros; L <= 512."""
+    return _padded(q, k, v, lens, n_heads, dropout_p, training)[0]
+
+
+def attention_packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p=0.0, training=True):
+    """ctx [T, H] of packed sequences: sequence s is rows seq_off[s] .. seq_off[s + 1] - 1 (seq_off: device integers [n_seq + 1]),
+    each at most max_seq_len <= 512 rows (a longer one is cut there)."""
+    return _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training)[0]

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_* only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -337,6 +337,59 @@ int ance_inbatch_nll_forward(const float *d_q, const float *d_ctx, const int64_t
 int ance_inbatch_nll_backward(const float *d_q, const float *d_ctx, const int64_t *d_positive_idx, int64_t nq, int64_t nc, int d,
                               const float *d_grad_output, float *d_gq, float *d_gctx, void *d_workspace, size_t workspace_bytes,
                               void *stream);
+
+/* The trainers' self-attention core with its gradient (csrc/attention_train.hip): what transformers' eager BertSelfAttention.forward
+ * computes between its three Linear outputs and context_layer, for right-padded sequences and heads of width 64.  Per sequence s
+ * (len_s valid rows) and head h:
+ *   S = Q_h K_h^T * 0.125 over keys j < len_s;  P = softmax_j(S) in fp32 with a full-precision exp;
+ *   P' = keep o P / (1 - p) when training != 0 and dropout_p > 0, else P;  ctx_h = P' V_h
+ *   backward, given dctx:  dV = P'^T dctx;  dP = keep o (dctx V^T) / (1 - p);  dS = P o (dP - rowsum(dP o P));
+ *   dQ = 0.125 dS K;  dK = 0.125 dS^T Q.
+ * Pad keys (j >= len_s) are skipped: in fp32 that is the reference's additive -10000 mask, whose terms underflow to exactly 0 in the
+ * exp.  Pad query rows are not computed, and whatever dctx holds there is ignored.  seq_rows > 0 (the padded form): sequence s owns
+ * rows d_seq_first[s] .. + seq_rows - 1 (clamped to n_rows), and the rows behind its length are WRITTEN AS ZEROS in ctx, dq, dk and
+ * dv by the call -- no pre-zeroing; seq_rows = 0 (the packed form): nothing outside the valid rows is written.  A sequence of
+ * length <= 0 is skipped (in the padded form all its rows are zeroed; the reference's all-pad chunk attends uniformly instead; its
+ * embedding never reaches the loss: INTEGRATION.md 3i).
+ * Layout: q, k, v, ctx (and dctx, dq, dk, dv) are fp32 row matrices of at least n_rows rows, each with its own 16-byte aligned base
+ * and its own row stride in elements (a multiple of 4, at least 64 n_heads); head h is columns 64 h .. 64 h + 63.  So three separate
+ * [B, L, H] tensors, views of a fused [B, L, 3H] and the packed [T, 3H] form all pass as they are.  Sequence s is rows
+ * d_seq_first[s] .. d_seq_first[s] + d_seq_len[s] - 1 (two DEVICE int32 arrays of n_seq entries).  The grid is sized from n_seq and
+ * max_seq_len; the kernels clamp a length to max_seq_len and to n_rows - first and skip a first row outside [0, n_rows): no row
+ * >= n_rows is touched whatever the descriptors say, nothing is read back, nothing synchronises -- both calls can be captured.
+ * Dropout: Philox4x32-10 with key (seed lo32, seed hi32) and counter (i * 128 + (j >> 2), s * n_heads + h, offset lo32, offset
+ * hi32) for query i and key j inside sequence s; output word j & 3 decides key j: keep iff word >= floor(dropout_p * 2^32); kept
+ * values are scaled by 1.0f / (1.0f - dropout_p).  The backward regenerates the mask from the same (seed, offset).
+ * d_workspace (16-byte aligned, ance_attention_workspace_bytes) is the saved state, linear in the rows: the forward leaves the
+ * log-sum-exp there as fp32 [n_heads][n_rows] (entry h * n_rows + row; only valid rows are written), the backward reads it, recomputes P
+ * from q, k and it, and adds its own [n_heads][n_rows] of dctx . ctx behind it.  Nothing of size L^2 is ever stored.  The backward
+ * takes the SAME AnceAttnTrainArgs as the forward, with ctx as the forward left it.  One launch forward, three backward, no
+ * atomics, one owning workgroup per output tile: the same inputs give the same bits.
+ * Supported: n_heads 12 or 16, 1 <= max_seq_len <= 512, 1 <= n_seq <= 65535, n_rows >= 1.  Refuses (ANCE_E_INVALID, before any
+ * launch) anything else, a null pointer, an unaligned base, a stride that is not a multiple of 4 or below 64 n_heads, seq_rows
+ * outside 0 .. max_seq_len, dropout_p outside [0, 1), and a null, unaligned or too small workspace. */
+typedef struct AnceAttnTrainArgs {
+    const float *q, *k, *v;
+    float *ctx;
+    int32_t ld_q, ld_k, ld_v, ld_ctx;
+    const int32_t *d_seq_first, *d_seq_len;
+    int32_t n_seq, max_seq_len, n_rows, n_heads;
+    int32_t seq_rows; /* 0: packed form; 1 .. max_seq_len: rows per sequence of the padded form, pad rows zeroed */
+    int32_t reserved; /* 0 */
+    float dropout_p;
+    int32_t training;
+    uint64_t seed, offset;
+    void *d_workspace;
+    size_t workspace_bytes;
+} AnceAttnTrainArgs;
+typedef struct AnceAttnGradArgs {
+    const float *dctx;
+    float *dq, *dk, *dv;
+    int32_t ld_dctx, ld_dq, ld_dk, ld_dv;
+} AnceAttnGradArgs;
+size_t ance_attention_workspace_bytes(int64_t n_rows, int n_heads); /* 0: n_heads not 12 or 16, or n_rows outside 1 .. 2^31 - 1 */
+int ance_attention_forward(const AnceAttnTrainArgs *args, void *stream);
+int ance_attention_backward(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, void *stream);
 
 /* Test hook: the SPLIT (fp32-grade) GEMM of the encoder with one of its epilogues.  acc[m][n] = sum_k a[m][k] b[n][k] with
  * a = a_hi + a_lo (b likewise; the lo x lo products are left out); d_a_pair [M, 2K] / d_b_pair [N, 2K] fp16 PAIR ROWS -- 32-column
