@@ -96,6 +96,39 @@ class AnceAttnGradArgs(ctypes.Structure):
                 ("ld_dctx", ctypes.c_int32), ("ld_dq", ctypes.c_int32), ("ld_dk", ctypes.c_int32), ("ld_dv", ctypes.c_int32)]
 
 
+class AnceLayerTailArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_layer_tail_forward / ance_layer_tail_backward."""
+    _fields_ = [("x", ctypes.c_void_p), ("res", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
+                ("beta", ctypes.c_void_p), ("y", ctypes.c_void_p), ("ld_x", ctypes.c_int32), ("ld_res", ctypes.c_int32),
+                ("ld_y", ctypes.c_int32), ("H", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("eps", ctypes.c_float),
+                ("dropout_p", ctypes.c_float), ("training", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("d_workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class AnceLayerTailGradArgs(ctypes.Structure):
+    """include/ance_amd.h: the gradient side of ance_layer_tail_backward (every output nullable)."""
+    _fields_ = [("dy", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dres", ctypes.c_void_p), ("dgamma", ctypes.c_void_p),
+                ("dbeta", ctypes.c_void_p), ("dbias", ctypes.c_void_p), ("ld_dy", ctypes.c_int32), ("ld_dx", ctypes.c_int32),
+                ("ld_dres", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AnceBiasGeluArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_bias_gelu_forward / ance_bias_gelu_backward."""
+    _fields_ = [("x", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p), ("ld_x", ctypes.c_int32),
+                ("ld_y", ctypes.c_int32), ("N", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("d_workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_size_t)]
+
+
+class AnceBiasGeluGradArgs(ctypes.Structure):
+    """include/ance_amd.h: the gradient side of ance_bias_gelu_backward."""
+    _fields_ = [("dy", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dbias", ctypes.c_void_p), ("ld_dy", ctypes.c_int32),
+                ("ld_dx", ctypes.c_int32)]
+
+
+# rows per workgroup of the layer-tail and bias-GELU kernels (include/ance_amd.h: ANCE_LAYER_TAIL_ROWS_PER_WORKGROUP; the library
+# states the same number through ance_layer_tail_rows_per_workgroup)
+LAYER_TAIL_ROWS_PER_WORKGROUP = 16
+
 # ance_gather_batch codes (include/ance_amd.h: ANCE_GATHER_*)
 GATHER_MASK_LENGTH, GATHER_MASK_NONZERO = 0, 1
 GATHER_TYPES_ZERO, GATHER_TYPES_LENGTH = 0, 1
@@ -201,6 +234,13 @@ SYMBOLS = {
     "ance_attention_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "ance_attention_forward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.c_void_p]),
     "ance_attention_backward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.POINTER(AnceAttnGradArgs), ctypes.c_void_p]),
+    "ance_layer_tail_rows_per_workgroup": (ctypes.c_int, []),
+    "ance_layer_tail_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_bias_gelu_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_layer_tail_forward": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.c_void_p]),
+    "ance_layer_tail_backward": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.POINTER(AnceLayerTailGradArgs), ctypes.c_void_p]),
+    "ance_bias_gelu_forward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGeluArgs), ctypes.c_void_p]),
+    "ance_bias_gelu_backward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGeluArgs), ctypes.POINTER(AnceBiasGeluGradArgs), ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

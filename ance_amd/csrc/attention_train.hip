@@ -30,6 +30,7 @@
 // lane (one Philox call per four elements); dkv holds one key of sixteen queries, and the four lanes of a quad (four consecutive
 // keys) share each query's call: one call per four elements there too, the words exchanged by DPP quad broadcasts.
 #include "common.h"
+#include "philox.h"
 
 namespace ance {
 namespace {
@@ -46,21 +47,6 @@ struct AttnParams {
     uint32_t seed_lo, seed_hi, off_lo, off_hi, keep_thr;
     float keep_scale;
 };
-
-__device__ __forceinline__ void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;  // one 32 x 32 -> 64 multiply each
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
 
 // word c of the four words that lane E of this lane's quad holds (DPP quad broadcast, then a select on the lane's own c)
 template <int E>

@@ -1,0 +1,244 @@
+"""The row-wise seams of a BertLayer, differentiable (csrc/layer_tail.hip behind ance_layer_tail_* / ance_bias_gelu_*), and a
+drop-in BertLayer built from them and the attention core.
+
+    y = dropout_add_layer_norm(dense_out, dense.bias, input_tensor, LayerNorm.weight, LayerNorm.bias, eps, p, self.training)
+    y = bias_gelu(dense_out, dense.bias)
+
+``dropout_add_layer_norm`` is what transformers' eager ``BertSelfOutput.forward`` / ``BertOutput.forward`` compute after the dense
+matmul -- ``LayerNorm(dropout(x + bias) + input_tensor)`` -- in one launch; it keeps two floats per row (mean, 1 / sqrt(var + eps))
+and no mask: the backward recomputes the normalised row from its inputs and regenerates the mask.  ``bias_gelu`` is
+``BertIntermediate.forward`` after its matmul, the erf form; it keeps nothing but its input.  The parameter gradients (weight, beta,
+bias) are column sums without atomics: the same inputs give the same bits.
+
+Dropout draws its (seed, offset) from ``ance_amd.attention.dropout_state`` -- the one stream that ``attention.manual_seed`` seeds and
+that every dropout forward, the attention's included, advances by one, so no two calls share a pair.  A call with ``training`` false
+or ``dropout_p == 0`` draws nothing.  Both are HOST values baked into the launch: a captured graph replays the pair it was captured
+with -- the same mask at every replay.  The masks are not torch's.
+"""
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .attention import _custom_bwd, _custom_fwd, _rows, attention_padded, dropout_state
+
+__all__ = ["dropout_add_layer_norm", "bias_gelu", "BertLayer"]
+
+TAIL_WIDTHS, GELU_WIDTHS = (768, 1024), (3072, 4096)
+
+
+def _check_rows(t, what, widths):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor" % what)
+    if t.dtype != torch.float32 and not (torch.is_autocast_enabled() and t.is_floating_point()):  # autocast: cast below
+        raise _lib.AnceLibraryError("%s must have dtype torch.float32, got %s" % (what, t.dtype))
+    if t.dim() < 2 or t.shape[-1] not in widths:
+        raise _lib.AnceLibraryError("%s must be [.., W] with W in %r, got %r" % (what, widths, tuple(t.shape)))
+    if t.numel() == 0:
+        raise _lib.AnceLibraryError("empty input")
+
+
+def _check_vector(t, what, width, like, optional=False):
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != like.device or t.dim() != 1 or t.numel() != width:
+        raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor [%d] on %s" % (what, width, like.device))
+    if t.dtype != torch.float32 and not (torch.is_autocast_enabled() and t.is_floating_point()):
+        raise _lib.AnceLibraryError("%s must have dtype torch.float32, got %s" % (what, t.dtype))
+
+
+def _matrix(t):
+    """[.., W] as (tensor to keep alive, row stride): 2- and 3-dimensional views with evenly spaced rows pass as they are."""
+    if t.dim() > 3:
+        t = t.reshape(-1, t.shape[-1])
+    return _rows(t)
+
+
+def _vector(t):
+    """A [W] parameter as the kernels read it: contiguous and 16-byte aligned (a slice of a flat parameter buffer is copied)."""
+    if t is None:
+        return None
+    t = t.detach()
+    return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _stats_floats(n_rows):
+    """include/ance_amd.h: the saved state of the layer tail, mean [n_rows] and rstd [n_rows], each rounded up to 256 bytes."""
+    return 2 * ((4 * n_rows + 255) // 256 * 256) // 4
+
+
+class _DropoutAddLayerNorm(torch.autograd.Function):
+    @staticmethod
+    @_custom_fwd
+    def forward(ctx, x, bias, residual, weight, beta, eps, dropout_p, training):
+        L = _lib.lib()
+        shape, H = x.shape, x.shape[-1]
+        (x, ld_x), (residual, ld_r) = _matrix(x), _matrix(residual)
+        bias, weight, beta = _vector(bias), _vector(weight), _vector(beta)
+        n_rows = x.numel() // H
+        if L.ance_layer_tail_workspace_bytes(n_rows, H) == 0:
+            raise _lib.AnceLibraryError("dropout_add_layer_norm: unsupported shape (rows %d, width %d)" % (n_rows, H))
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=x.device)
+        drop = bool(training) and dropout_p > 0.0
+        seed, offset = dropout_state.next_pair(x.device) if drop else (0, 0)
+        args = _lib.AnceLayerTailArgs(x=x.data_ptr(), res=residual.data_ptr(), bias=_ptr(bias), gamma=weight.data_ptr(),
+                                      beta=beta.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_res=ld_r, ld_y=H, H=H, n_rows=n_rows,
+                                      eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed, offset=offset,
+                                      d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_layer_tail_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_layer_tail_forward")
+        ctx.save_for_backward(x, residual, bias, weight, stats)
+        ctx.args = args
+        ctx.shape = shape
+        return y
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dy):
+        L = _lib.lib()
+        x, residual, bias, weight, stats = ctx.saved_tensors
+        a = _lib.AnceLayerTailArgs.from_buffer_copy(ctx.args)  # y and beta are not touched by the backward
+        H, n_rows = a.H, a.n_rows
+        dy, ld_dy = _matrix(dy.to(torch.float32))
+        want_x, want_bias, want_res, want_w, want_b = ctx.needs_input_grad[:5]
+
+        def out(want, shape):
+            return torch.empty(shape, dtype=torch.float32, device=x.device) if want else None
+
+        dx, dres = out(want_x, ctx.shape), out(want_res, ctx.shape)
+        dbias, dgamma, dbeta = out(want_bias and bias is not None, (H,)), out(want_w, (H,)), out(want_b, (H,))
+        # the saved state is the statistics alone; the backward's partial rows live only as long as this call
+        ws_bytes = L.ance_layer_tail_workspace_bytes(n_rows, H)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+        ws[:stats.numel()].copy_(stats)
+        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        g = _lib.AnceLayerTailGradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dres=_ptr(dres), dgamma=_ptr(dgamma), dbeta=_ptr(dbeta),
+                                       dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=H, ld_dres=H)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_layer_tail_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_layer_tail_backward")
+        return dx, dbias, dres, dgamma, dbeta, None, None, None
+
+
+class _BiasGelu(torch.autograd.Function):
+    @staticmethod
+    @_custom_fwd
+    def forward(ctx, x, bias):
+        L = _lib.lib()
+        shape, N = x.shape, x.shape[-1]
+        x, ld_x = _matrix(x)
+        bias = _vector(bias)
+        n_rows = x.numel() // N
+        if L.ance_bias_gelu_workspace_bytes(n_rows, N) == 0:
+            raise _lib.AnceLibraryError("bias_gelu: unsupported shape (rows %d, width %d)" % (n_rows, N))
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        args = _lib.AnceBiasGeluArgs(x=x.data_ptr(), bias=bias.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_y=N, N=N, n_rows=n_rows,
+                                     d_workspace=None, workspace_bytes=0)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_bias_gelu_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_bias_gelu_forward")
+        ctx.save_for_backward(x, bias)
+        ctx.args = args
+        ctx.shape = shape
+        return y
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dy):
+        L = _lib.lib()
+        x, bias = ctx.saved_tensors
+        a = _lib.AnceBiasGeluArgs.from_buffer_copy(ctx.args)
+        dy, ld_dy = _matrix(dy.to(torch.float32))
+        want_x, want_bias = ctx.needs_input_grad[:2]
+        dx = torch.empty(ctx.shape, dtype=torch.float32, device=x.device) if want_x else None
+        dbias = torch.empty(a.N, dtype=torch.float32, device=x.device) if want_bias else None
+        ws_bytes = L.ance_bias_gelu_workspace_bytes(a.n_rows, a.N)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        g = _lib.AnceBiasGeluGradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=a.N)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_bias_gelu_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_bias_gelu_backward")
+        return dx, dbias
+
+
+def dropout_add_layer_norm(x, bias, residual, weight, beta, eps, dropout_p=0.0, training=True):
+    """LayerNorm(dropout(x + bias) + residual) * weight + beta over the last dimension: x, residual [.., H] fp32 with H 768 or 1024
+    (views with evenly spaced rows pass as they are, anything else is copied), bias [H] or None, weight, beta [H].  Returns y shaped
+    like x; gradients for x, bias, residual, weight and beta."""
+    _check_rows(x, "x", TAIL_WIDTHS)
+    _check_rows(residual, "residual", TAIL_WIDTHS)
+    if residual.shape != x.shape or residual.device != x.device:
+        raise _lib.AnceLibraryError("x and residual must be of one shape, on one device")
+    H = x.shape[-1]
+    _check_vector(bias, "bias", H, x, optional=True)
+    _check_vector(weight, "weight", H, x)
+    _check_vector(beta, "beta", H, x)
+    if not 0.0 <= float(dropout_p) < 1.0:
+        raise _lib.AnceLibraryError("dropout_p must be in [0, 1), got %r" % (dropout_p,))
+    if not float(eps) > 0.0:
+        raise _lib.AnceLibraryError("eps must be positive, got %r" % (eps,))
+    return _DropoutAddLayerNorm.apply(x, bias, residual, weight, beta, float(eps), float(dropout_p), bool(training))
+
+
+def bias_gelu(x, bias):
+    """gelu(x + bias), the erf form, over [.., N] fp32 with N 3072 or 4096; gradients for x and bias."""
+    _check_rows(x, "x", GELU_WIDTHS)
+    _check_vector(bias, "bias", x.shape[-1], x)
+    return _BiasGelu.apply(x, bias)
+
+
+class _Namespace(torch.nn.Module):
+    """A module that only holds submodules: the names of transformers' BertLayer, so that its state dict loads as it is."""
+
+
+class BertLayer(torch.nn.Module):
+    """transformers' BertLayer (2.3.0 modeling_bert.py; RoBERTa's towers run the same class) for right-padded batches, with the same
+    submodule and parameter names: attention.self.query / key / value, attention.output.dense / LayerNorm, intermediate.dense,
+    output.dense / LayerNorm.  ``forward(hidden_states [B, L, H] fp32, lens [B])`` runs six F.linear calls (the three dense ones
+    without their bias, which goes into the fused call behind them), attention_padded, two dropout_add_layer_norm and one bias_gelu.
+    Pad rows are computed like any other in the three row-wise seams, as the reference does; the attention core writes zeros there
+    (INTEGRATION.md 3i), so a pad row of the output is the LayerNorm tail of zeros, not the reference's value, and never reaches a
+    loss."""
+
+    def __init__(self, hidden_size, num_attention_heads, intermediate_size, layer_norm_eps=1e-12, hidden_dropout_prob=0.1,
+                 attention_probs_dropout_prob=0.1):
+        super().__init__()
+        if hidden_size not in TAIL_WIDTHS or hidden_size != 64 * num_attention_heads or intermediate_size not in GELU_WIDTHS:
+            raise _lib.AnceLibraryError("BertLayer: hidden_size must be 768 (12 heads) or 1024 (16 heads), intermediate_size 3072 or "
+                                        "4096; got %r, %r heads, %r" % (hidden_size, num_attention_heads, intermediate_size))
+        nn = torch.nn
+        self.num_attention_heads, self.layer_norm_eps = num_attention_heads, float(layer_norm_eps)
+        self.hidden_dropout_prob, self.attention_probs_dropout_prob = float(hidden_dropout_prob), float(attention_probs_dropout_prob)
+        self.attention = _Namespace()
+        self.attention.self = _Namespace()
+        for name in ("query", "key", "value"):
+            setattr(self.attention.self, name, nn.Linear(hidden_size, hidden_size))
+        self.attention.output = _Namespace()
+        self.attention.output.dense = nn.Linear(hidden_size, hidden_size)
+        self.attention.output.LayerNorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
+        self.intermediate = _Namespace()
+        self.intermediate.dense = nn.Linear(hidden_size, intermediate_size)
+        self.output = _Namespace()
+        self.output.dense = nn.Linear(intermediate_size, hidden_size)
+        self.output.LayerNorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
+
+    def forward(self, hidden_states, lens):
+        F = torch.nn.functional
+        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
+        q = F.linear(hidden_states, att.self.query.weight, att.self.query.bias)
+        k = F.linear(hidden_states, att.self.key.weight, att.self.key.bias)
+        v = F.linear(hidden_states, att.self.value.weight, att.self.value.bias)
+        ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training)
+        ln = att.output.LayerNorm
+        h = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, hidden_states, ln.weight, ln.bias,
+                                   eps, p, self.training)
+        t = bias_gelu(F.linear(h, self.intermediate.dense.weight), self.intermediate.dense.bias)
+        ln = self.output.LayerNorm
+        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
+                                      self.training)

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_* only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_* only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -390,6 +390,86 @@ typedef struct AnceAttnGradArgs {
 size_t ance_attention_workspace_bytes(int64_t n_rows, int n_heads); /* 0: n_heads not 12 or 16, or n_rows outside 1 .. 2^31 - 1 */
 int ance_attention_forward(const AnceAttnTrainArgs *args, void *stream);
 int ance_attention_backward(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, void *stream);
+
+/* The row-wise seams of a BertLayer with their gradients (csrc/layer_tail.hip), fp32 throughout: what transformers' eager
+ * BertSelfOutput.forward / BertOutput.forward compute after their dense matmul (the layer tail), and BertIntermediate.forward after
+ * its own (bias + GELU).
+ * Layer tail, per row r of n_rows, H = 768 or 1024:
+ *   u = x[r] + bias (bias NULL: zeros);  d = keep o u * (1.0f / (1.0f - dropout_p)) when training != 0 and dropout_p > 0, else u;
+ *   z = d + res[r];  mean = sum z / H;  var = sum (z - mean)^2 / H (two passes over the row in registers, biased);
+ *   rstd = 1.0f / sqrtf(var + eps);  xhat = (z - mean) rstd;  y[r] = xhat o gamma + beta
+ *   backward, given dy:  g = dy o gamma;  dz = rstd (g - mean_H(g) - xhat mean_H(g o xhat));  dres = dz;
+ *   dx = keep o dz / (1 - dropout_p);  dgamma = sum_r dy o xhat;  dbeta = sum_r dy;  dbias = sum_r dx.
+ *   xhat is recomputed from x, bias, res, the regenerated mask and the saved (mean, rstd) -- never from y: gamma may hold zeros.
+ * Bias + GELU, per row, N = 3072 or 4096:
+ *   u = x[r] + bias;  y[r] = 0.5 u (1 + erff(u / sqrt 2));  dx = dy (0.5 (1 + erff(u / sqrt 2)) + u expf(-u^2 / 2) / sqrt(2 pi));
+ *   dbias = sum_r dx.  u is recomputed from x; nothing else is saved.
+ * Layout: x, res, y (and dy, dx, dres) are fp32 row matrices of n_rows rows, each with its own 16-byte aligned base and its own row
+ * stride in elements (a multiple of 4, at least the width); bias, gamma, beta and the three column sums are 16-byte aligned vectors
+ * of the width.  No element outside the n_rows x width window of an output is written.  No output may overlap an input or another
+ * output.  1 <= n_rows <= 2^31 - 1; the grid is sized from n_rows, nothing is read back, nothing synchronises: every call can be
+ * captured.
+ * Dropout: Philox4x32-10 with key (seed lo32, seed hi32) and counter (row lo32, col >> 2, offset lo32, offset hi32); output word
+ * col & 3 decides column col (one call per four columns): keep iff word >= floor(dropout_p * 2^32); kept values are scaled by
+ * 1.0f / (1.0f - dropout_p).  The backward regenerates the mask from the same (seed, offset).
+ * Column sums: a workgroup owns ANCE_LAYER_TAIL_ROWS_PER_WORKGROUP consecutive rows (ance_layer_tail_rows_per_workgroup returns
+ * the same number), sums their terms per column in a fixed order and writes ONE partial row; a second launch sums the
+ * n_part = ceil(n_rows / ANCE_LAYER_TAIL_ROWS_PER_WORKGROUP) partial rows per column as a fixed binary tree.  No atomics: the same
+ * inputs give the same bits.
+ * d_workspace (16-byte aligned):
+ *   layer tail  ance_layer_tail_workspace_bytes(n_rows, H) = S + n_part * 3 * H * 4, S = 2 * roundup(4 * n_rows, 256): mean [n_rows]
+ *               at byte 0 and rstd [n_rows] at byte S / 2, fp32, written by the forward and read by the backward -- the only saved
+ *               state; behind them the backward's partial rows [n_part][3][H] (dgamma, dbeta, dbias).  The forward touches and
+ *               requires only the first S bytes; the backward requires all of it and takes the SAME AnceLayerTailArgs (of which
+ *               it reads neither y nor beta: they are not checked there).
+ *   bias + GELU ance_bias_gelu_workspace_bytes(n_rows, N) = n_part * N * 4: the backward's partial rows [n_part][N].  The forward
+ *               neither reads nor checks d_workspace; the backward neither reads nor checks y.
+ * One launch forward, two backward.  dx, dres, dgamma, dbeta, dbias may each be NULL when not wanted (the bias + GELU's dx and
+ * dbias likewise); with bias NULL no dbias is produced.
+ * Refuses (ANCE_E_INVALID, before any launch) a width outside {768, 1024} / {3072, 4096}, n_rows < 1, a null pointer other than
+ * those named above, an unaligned base, a stride that is not a multiple of 4 or below the width, dropout_p outside [0, 1),
+ * eps <= 0, and a null, unaligned or too small workspace.  The workspace queries return 0 for what is not supported. */
+#define ANCE_LAYER_TAIL_ROWS_PER_WORKGROUP 16
+typedef struct AnceLayerTailArgs {
+    const float *x, *res;
+    const float *bias;            /* [H] or NULL                                                  */
+    const float *gamma, *beta;    /* [H]                                                          */
+    float *y;
+    int32_t ld_x, ld_res, ld_y;
+    int32_t H, n_rows;
+    float eps;
+    float dropout_p;
+    int32_t training;
+    uint64_t seed, offset;
+    void *d_workspace;
+    size_t workspace_bytes;
+} AnceLayerTailArgs;
+typedef struct AnceLayerTailGradArgs {
+    const float *dy;
+    float *dx, *dres;             /* [n_rows, ld], each nullable                                  */
+    float *dgamma, *dbeta, *dbias; /* [H], each nullable                                          */
+    int32_t ld_dy, ld_dx, ld_dres;
+    int32_t reserved;             /* 0 */
+} AnceLayerTailGradArgs;
+typedef struct AnceBiasGeluArgs {
+    const float *x, *bias;
+    float *y;
+    int32_t ld_x, ld_y, N, n_rows;
+    void *d_workspace;
+    size_t workspace_bytes;
+} AnceBiasGeluArgs;
+typedef struct AnceBiasGeluGradArgs {
+    const float *dy;
+    float *dx, *dbias;            /* each nullable                                                */
+    int32_t ld_dy, ld_dx;
+} AnceBiasGeluGradArgs;
+int ance_layer_tail_rows_per_workgroup(void);
+size_t ance_layer_tail_workspace_bytes(int64_t n_rows, int H);
+size_t ance_bias_gelu_workspace_bytes(int64_t n_rows, int N);
+int ance_layer_tail_forward(const AnceLayerTailArgs *args, void *stream);
+int ance_layer_tail_backward(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads, void *stream);
+int ance_bias_gelu_forward(const AnceBiasGeluArgs *args, void *stream);
+int ance_bias_gelu_backward(const AnceBiasGeluArgs *args, const AnceBiasGeluGradArgs *grads, void *stream);
 
 /* Test hook: the SPLIT (fp32-grade) GEMM of the encoder with one of its epilogues.  acc[m][n] = sum_k a[m][k] b[n][k] with
  * a = a_hi + a_lo (b likewise; the lo x lo products are left out); d_a_pair [M, 2K] / d_b_pair [N, 2K] fp16 PAIR ROWS -- 32-column
