@@ -96,6 +96,26 @@ class AnceAttnGradArgs(ctypes.Structure):
                 ("ld_dctx", ctypes.c_int32), ("ld_dq", ctypes.c_int32), ("ld_dk", ctypes.c_int32), ("ld_dv", ctypes.c_int32)]
 
 
+ANCE_DTYPE_F16, ANCE_DTYPE_BF16 = 1, 2
+
+
+class AnceAttn16Args(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_attention16_forward / ance_attention16_backward (16-bit rows, a dtype)."""
+    _fields_ = [("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("ctx", ctypes.c_void_p),
+                ("ld_q", ctypes.c_int32), ("ld_k", ctypes.c_int32), ("ld_v", ctypes.c_int32), ("ld_ctx", ctypes.c_int32),
+                ("d_seq_first", ctypes.c_void_p), ("d_seq_len", ctypes.c_void_p), ("n_seq", ctypes.c_int32),
+                ("max_seq_len", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_heads", ctypes.c_int32),
+                ("seq_rows", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("dropout_p", ctypes.c_float), ("training", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("d_workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class AnceAttn16GradArgs(ctypes.Structure):
+    """include/ance_amd.h: the gradient side of ance_attention16_backward."""
+    _fields_ = [("dctx", ctypes.c_void_p), ("dq", ctypes.c_void_p), ("dk", ctypes.c_void_p), ("dv", ctypes.c_void_p),
+                ("ld_dctx", ctypes.c_int32), ("ld_dq", ctypes.c_int32), ("ld_dk", ctypes.c_int32), ("ld_dv", ctypes.c_int32)]
+
+
 class AnceLayerTailArgs(ctypes.Structure):
     """include/ance_amd.h: the arguments of ance_layer_tail_forward / ance_layer_tail_backward."""
     _fields_ = [("x", ctypes.c_void_p), ("res", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
@@ -234,6 +254,9 @@ SYMBOLS = {
     "ance_attention_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "ance_attention_forward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.c_void_p]),
     "ance_attention_backward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.POINTER(AnceAttnGradArgs), ctypes.c_void_p]),
+    "ance_attention16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_attention16_forward": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.c_void_p]),
+    "ance_attention16_backward": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.POINTER(AnceAttn16GradArgs), ctypes.c_void_p]),
     "ance_layer_tail_rows_per_workgroup": (ctypes.c_int, []),
     "ance_layer_tail_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "ance_bias_gelu_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),

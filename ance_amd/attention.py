@@ -24,10 +24,12 @@ from . import _lib
 try:  # torch >= 2.4
     from torch.amp import custom_bwd as _amp_bwd, custom_fwd as _amp_fwd
     _custom_fwd = _amp_fwd(device_type="cuda", cast_inputs=torch.float32)
+    _custom_fwd_as_is = _amp_fwd(device_type="cuda")   # precision="half": the inputs go in as they are
     _custom_bwd = _amp_bwd(device_type="cuda")
 except ImportError:  # pragma: no cover
     from torch.cuda.amp import custom_bwd as _custom_bwd, custom_fwd as _amp_fwd
     _custom_fwd = _amp_fwd(cast_inputs=torch.float32)
+    _custom_fwd_as_is = _amp_fwd
 
 __all__ = ["attention_padded", "attention_packed", "lens_from_mask", "manual_seed", "dropout_state"]
 
@@ -81,11 +83,35 @@ def _rows(t):
     return t, t.stride(0)
 
 
-def _check_inputs(q, k, v, n_heads, dropout_p, dims):
+def _rows16(t):
+    """_rows for a 16-bit tensor: the kernels read 16-byte pieces, so a row stride must be a multiple of 8 elements."""
+    if t.dim() == 3:
+        if t.stride(2) != 1 or t.stride(0) != t.size(1) * t.stride(1) or t.stride(1) % 8 or t.stride(1) < t.size(2) or t.data_ptr() % 16:
+            t = t.contiguous()
+        return t, t.stride(1)
+    if t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.size(1) or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t, t.stride(0)
+
+
+HALF_DTYPES = {torch.float16: _lib.ANCE_DTYPE_F16, torch.bfloat16: _lib.ANCE_DTYPE_BF16}
+
+
+def _check_precision(precision):
+    if precision not in ("fp32", "half"):
+        raise _lib.AnceLibraryError("precision must be \"fp32\" or \"half\", got %r" % (precision,))
+    return precision == "half"
+
+
+def _check_inputs(q, k, v, n_heads, dropout_p, dims, half=False):
     for t, what in ((q, "q"), (k, "k"), (v, "v")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor" % what)
-        if t.dtype != torch.float32 and not (torch.is_autocast_enabled() and t.is_floating_point()):  # autocast: cast below
+        if half:  # precision="half": fp16 or bf16 as they are; fp32 only under autocast, which casts it (_half_inputs)
+            if t.dtype not in HALF_DTYPES and not (torch.is_autocast_enabled() and t.dtype == torch.float32):
+                raise _lib.AnceLibraryError("%s must have dtype torch.float16 or bfloat16 with precision=\"half\", got %s"
+                                            % (what, t.dtype))
+        elif t.dtype != torch.float32 and not (torch.is_autocast_enabled() and t.is_floating_point()):  # autocast: cast below
             raise _lib.AnceLibraryError("%s must have dtype torch.float32, got %s" % (what, t.dtype))
         if t.dim() != dims or t.shape != q.shape or t.device != q.device:
             raise _lib.AnceLibraryError("q, k, v must be %d-dimensional, of one shape, on one device" % dims)
@@ -172,37 +198,106 @@ class _Attention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None, None
 
 
-def _padded(q, k, v, lens, n_heads, dropout_p, training):
-    _check_inputs(q, k, v, n_heads, dropout_p, 3)
+class _AttentionHalf(torch.autograd.Function):
+    """_Attention with fp16 / bf16 rows (csrc/attention_train_half.hip): nothing is cast, ctx and the gradients have the inputs' dtype,
+    the log-sum-exp stays fp32."""
+
+    @staticmethod
+    @_custom_fwd_as_is
+    def forward(ctx, q, k, v, first, lens, max_seq_len, n_heads, dropout_p, training):
+        L = _lib.lib()
+        (q, ld_q), (k, ld_k), (v, ld_v) = _rows16(q), _rows16(k), _rows16(v)
+        n_rows = q.numel() // q.shape[-1]
+        seq_rows = max_seq_len if q.dim() == 3 else 0
+        out = (torch.empty if seq_rows else torch.zeros)(q.shape, dtype=q.dtype, device=q.device)
+        ws_bytes = L.ance_attention16_workspace_bytes(n_rows, n_heads)
+        if ws_bytes == 0:
+            raise _lib.AnceLibraryError("attention: unsupported shape (rows %d, heads %d)" % (n_rows, n_heads))
+        ws = torch.zeros(ws_bytes // 4, dtype=torch.float32, device=q.device)
+        drop = bool(training) and dropout_p > 0.0
+        seed, offset = dropout_state.next_pair(q.device) if drop else (0, 0)
+        args = _lib.AnceAttn16Args(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
+                                   ld_ctx=out.shape[-1], d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(),
+                                   n_seq=first.numel(), max_seq_len=max_seq_len, n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows,
+                                   dtype=HALF_DTYPES[q.dtype], dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed,
+                                   offset=offset, d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+        with torch.cuda.device(q.device):
+            _lib.check(L.ance_attention16_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_attention16_forward")
+        ctx.save_for_backward(q, k, v, out, first, lens, ws)
+        ctx.args = args
+        lse = ws[:n_heads * n_rows].view(n_heads, n_rows)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dctx, _dlse):
+        L = _lib.lib()
+        q, k, v, out, first, lens, ws = ctx.saved_tensors
+        a = ctx.args
+        dctx, ld_d = _rows16(dctx.to(q.dtype))
+        dq, dk, dv = _grads_like(q, k, v, zero=a.seq_rows == 0)
+        g = _lib.AnceAttn16GradArgs(dctx=dctx.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
+                                    ld_dq=dq.stride(-2), ld_dk=dk.stride(-2), ld_dv=dv.stride(-2))
+        with torch.cuda.device(q.device):
+            _lib.check(L.ance_attention16_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()),
+                       "ance_attention16_backward")
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def _half_inputs(q, k, v):
+    """precision="half": under autocast fp32 inputs are cast to the autocast dtype (a differentiable cast, as autocast's own); then
+    all three must be of one 16-bit dtype."""
+    if torch.is_autocast_enabled():
+        to = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+        q, k, v = (t.to(to) if t.dtype == torch.float32 else t for t in (q, k, v))
+    if q.dtype not in HALF_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _lib.AnceLibraryError("q, k, v must all be torch.float16 or all bfloat16 with precision=\"half\", got %s, %s, %s"
+                                    % (q.dtype, k.dtype, v.dtype))
+    return q, k, v
+
+
+def _padded(q, k, v, lens, n_heads, dropout_p, training, precision="fp32"):
+    half = _check_precision(precision)
+    _check_inputs(q, k, v, n_heads, dropout_p, 3, half)
     B, Lq = q.shape[0], q.shape[1]
     if not 1 <= Lq <= 512:
         raise _lib.AnceLibraryError("sequence length must be in 1 .. 512, got %d" % Lq)
     lens = _int32(lens, "lens", B, q.device)
     first = torch.arange(0, B * Lq, Lq, dtype=torch.int32, device=q.device)
+    if half:
+        return _AttentionHalf.apply(*_half_inputs(q, k, v), first, lens, Lq, n_heads, float(dropout_p), bool(training))
     return _Attention.apply(q, k, v, first, lens, Lq, n_heads, float(dropout_p), bool(training))
 
 
-def _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training):
-    _check_inputs(q, k, v, n_heads, dropout_p, 2)
+def _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training, precision="fp32"):
+    half = _check_precision(precision)
+    _check_inputs(q, k, v, n_heads, dropout_p, 2, half)
     if not 1 <= int(max_seq_len) <= 512:
         raise _lib.AnceLibraryError("max_seq_len must be in 1 .. 512, got %r" % (max_seq_len,))
     if not isinstance(seq_off, torch.Tensor) or seq_off.dim() != 1 or seq_off.numel() < 2:
         raise _lib.AnceLibraryError("seq_off must be a device integer tensor [n_seq + 1]")
     off = _int32(seq_off, "seq_off", seq_off.numel(), q.device)
     first, lens = off[:-1].contiguous(), (off[1:] - off[:-1]).contiguous()
+    if half:
+        return _AttentionHalf.apply(*_half_inputs(q, k, v), first, lens, int(max_seq_len), n_heads, float(dropout_p), bool(training))
     return _Attention.apply(q, k, v, first, lens, int(max_seq_len), n_heads, float(dropout_p), bool(training))
 
 
 # _padded / _packed return (ctx, lse): lse is the saved fp32 log-sum-exp [n_heads, rows] (zeros at pad rows), non-differentiable.  It
 # is not part of the interface; the tests read it.
-def attention_padded(q, k, v, lens, n_heads, dropout_p=0.0, training=True):
+def attention_padded(q, k, v, lens, n_heads, dropout_p=0.0, training=True, precision="fp32"):
     """ctx [B, L, H] of right-padded sequences: q, k, v [B, L, H] fp32 (views with a contiguous last dimension pass as they are, so
     three Linear outputs and the three thirds of a fused [B, L, 3H] both work), lens [B] device integers (lens_from_mask).  Rows
-    >= lens[b] of ctx and of the gradients are zeros; L <= 512."""
-    return _padded(q, k, v, lens, n_heads, dropout_p, training)[0]
+    >= lens[b] of ctx and of the gradients are zeros; L <= 512.
+    precision="half": q, k, v all fp16 or all bf16 (under autocast fp32 ones are cast to the autocast dtype; outside it they are
+    refused); the products run on the 16-bit matrix cores with fp32 softmax and accumulation, and ctx and the gradients have the
+    inputs' dtype.  The default casts to fp32 under autocast and refuses 16-bit inputs outside it."""
+    return _padded(q, k, v, lens, n_heads, dropout_p, training, precision)[0]
 
 
-def attention_packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p=0.0, training=True):
+def attention_packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p=0.0, training=True, precision="fp32"):
     """ctx [T, H] of packed sequences: sequence s is rows seq_off[s] .. seq_off[s + 1] - 1 (seq_off: device integers [n_seq + 1]),
-    each at most max_seq_len <= 512 rows (a longer one is cut there)."""
-    return _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training)[0]
+    each at most max_seq_len <= 512 rows (a longer one is cut there).  precision: as attention_padded."""
+    return _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training, precision)[0]

@@ -202,13 +202,19 @@ class BertLayer(torch.nn.Module):
     submodule and parameter names: attention.self.query / key / value, attention.output.dense / LayerNorm, intermediate.dense,
     output.dense / LayerNorm.  ``forward(hidden_states [B, L, H] fp32, lens [B])`` runs six F.linear calls (the three dense ones
     without their bias, which goes into the fused call behind them), attention_padded, two dropout_add_layer_norm and one bias_gelu.
+    ``attention_precision="half"`` is for ``torch.autocast``: the fp16 / bf16 Linear outputs enter the attention core as they are and
+    ctx goes into attention.output.dense without a cast (attention_padded, precision="half"); with fp32 hidden states outside autocast
+    it raises.  The three row-wise seams stay fp32 either way.
     Pad rows are computed like any other in the three row-wise seams, as the reference does; the attention core writes zeros there
     (INTEGRATION.md 3i), so a pad row of the output is the LayerNorm tail of zeros, not the reference's value, and never reaches a
     loss."""
 
     def __init__(self, hidden_size, num_attention_heads, intermediate_size, layer_norm_eps=1e-12, hidden_dropout_prob=0.1,
-                 attention_probs_dropout_prob=0.1):
+                 attention_probs_dropout_prob=0.1, attention_precision="fp32"):
         super().__init__()
+        if attention_precision not in ("fp32", "half"):
+            raise _lib.AnceLibraryError("BertLayer: attention_precision must be \"fp32\" or \"half\", got %r" % (attention_precision,))
+        self.attention_precision = attention_precision
         if hidden_size not in TAIL_WIDTHS or hidden_size != 64 * num_attention_heads or intermediate_size not in GELU_WIDTHS:
             raise _lib.AnceLibraryError("BertLayer: hidden_size must be 768 (12 heads) or 1024 (16 heads), intermediate_size 3072 or "
                                         "4096; got %r, %r heads, %r" % (hidden_size, num_attention_heads, intermediate_size))
@@ -234,7 +240,8 @@ class BertLayer(torch.nn.Module):
         q = F.linear(hidden_states, att.self.query.weight, att.self.query.bias)
         k = F.linear(hidden_states, att.self.key.weight, att.self.key.bias)
         v = F.linear(hidden_states, att.self.value.weight, att.self.value.bias)
-        ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training)
+        ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
+                               precision=self.attention_precision)
         ln = att.output.LayerNorm
         h = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, hidden_states, ln.weight, ln.bias,
                                    eps, p, self.training)

@@ -391,6 +391,49 @@ size_t ance_attention_workspace_bytes(int64_t n_rows, int n_heads); /* 0: n_head
 int ance_attention_forward(const AnceAttnTrainArgs *args, void *stream);
 int ance_attention_backward(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, void *stream);
 
+/* The same core with 16-bit I/O (csrc/attention_train_half.hip): the recipe's --fp16, i.e. torch.autocast plus a GradScaler.  q, k,
+ * v, ctx (and dctx, dq, dk, dv) are fp16 (dtype ANCE_DTYPE_F16) or bf16 (ANCE_DTYPE_BF16) row matrices, all of the one type; strides
+ * are in elements, multiples of 8, at least 64 n_heads; bases 16-byte aligned.  Everything else -- the two forms, the pad-row zeros,
+ * the device lengths and their clamps, the dropout stream (the same (seed, offset, s, h, i, j) keeps the same element as in the fp32
+ * core), the workspace (fp32 log-sum-exp [n_heads][n_rows], then [n_heads][n_rows] of dctx . ctx; ance_attention16_workspace_bytes
+ * equals the fp32 query), no atomics, one owner per output tile, capturable -- is as stated above.  The arithmetic, T = the I/O type,
+ * "rounded" = to nearest even with overflow to +-inf (never a truncating or saturating conversion: under a GradScaler an overflowing
+ * dS must reach found_inf as a non-finite gradient):
+ *   S = Q K^T with T operands, fp32 accumulation (v_mfma_f32_32x32x16_f16 / _bf16); the 0.125 scale, max, exp and sum are fp32;
+ *   the exp is the hardware exp2 of (x * log2 e), one expression for the forward and the backward;
+ *   forward: online softmax over ascending 32-key blocks; P' (the unnormalised exp after keep) is rounded to T before P' V; ctx
+ *   accumulates in fp32 over all key blocks and is rounded once at the store, after the fp32 factor (1.0f / (1.0f - p)) / sum;
+ *   backward: P = exp(S * 0.125f - lse) recomputed from the same score expression; D = dctx . ctx in fp32 from the stored ctx;
+ *   dP = dctx V^T accumulates in fp32; dS = P o (dP - D) in fp32, rounded to T for dQ = 0.125 dS K and dK = 0.125 dS^T Q;
+ *   P' = keep o P * (1.0f / (1.0f - p)) rounded to T for dV; dq, dk, dv accumulate in fp32 registers in a fixed block order and are
+ *   rounded once at the store (dq, dk after the fp32 factor 0.125f).
+ * One launch forward, three backward.  Refuses what the fp32 calls refuse, a dtype that is neither, and a stride that is not a
+ * multiple of 8. */
+#define ANCE_DTYPE_F16 1
+#define ANCE_DTYPE_BF16 2
+typedef struct AnceAttn16Args {
+    const void *q, *k, *v;
+    void *ctx;
+    int32_t ld_q, ld_k, ld_v, ld_ctx;
+    const int32_t *d_seq_first, *d_seq_len;
+    int32_t n_seq, max_seq_len, n_rows, n_heads;
+    int32_t seq_rows; /* 0: packed form; 1 .. max_seq_len: rows per sequence of the padded form, pad rows zeroed */
+    int32_t dtype;    /* ANCE_DTYPE_F16 or ANCE_DTYPE_BF16 */
+    float dropout_p;
+    int32_t training;
+    uint64_t seed, offset;
+    void *d_workspace;
+    size_t workspace_bytes;
+} AnceAttn16Args;
+typedef struct AnceAttn16GradArgs {
+    const void *dctx;
+    void *dq, *dk, *dv;
+    int32_t ld_dctx, ld_dq, ld_dk, ld_dv;
+} AnceAttn16GradArgs;
+size_t ance_attention16_workspace_bytes(int64_t n_rows, int n_heads); /* 0: n_heads not 12 or 16, or n_rows outside 1 .. 2^31 - 1 */
+int ance_attention16_forward(const AnceAttn16Args *args, void *stream);
+int ance_attention16_backward(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, void *stream);
+
 /* The row-wise seams of a BertLayer with their gradients (csrc/layer_tail.hip), fp32 throughout: what transformers' eager
  * BertSelfOutput.forward / BertOutput.forward compute after their dense matmul (the layer tail), and BertIntermediate.forward after
  * its own (bias + GELU).
