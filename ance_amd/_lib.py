@@ -145,6 +145,30 @@ class AnceBiasGeluGradArgs(ctypes.Structure):
                 ("ld_dx", ctypes.c_int32)]
 
 
+class AnceEmbedArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_embed_forward / ance_embed_backward."""
+    _fields_ = [("ids", ctypes.c_void_p), ("type_ids", ctypes.c_void_p), ("word", ctypes.c_void_p), ("pos", ctypes.c_void_p),
+                ("type", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("positions", ctypes.c_void_p), ("n_seq", ctypes.c_int32), ("L", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("vocab", ctypes.c_int32), ("max_pos", ctypes.c_int32), ("n_types", ctypes.c_int32),
+                ("position_mode", ctypes.c_int32), ("padding_idx", ctypes.c_int32), ("eps", ctypes.c_float),
+                ("dropout_p", ctypes.c_float), ("training", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("d_workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_size_t)]
+
+
+class AnceEmbedGradArgs(ctypes.Structure):
+    """include/ance_amd.h: the gradient side of ance_embed_backward (every output nullable; the tables zero-filled by the caller)."""
+    _fields_ = [("dy", ctypes.c_void_p), ("dword", ctypes.c_void_p), ("dpos", ctypes.c_void_p), ("dtype", ctypes.c_void_p),
+                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p), ("word_keys", ctypes.c_void_p), ("word_perm", ctypes.c_void_p),
+                ("pos_keys", ctypes.c_void_p), ("pos_perm", ctypes.c_void_p), ("type_keys", ctypes.c_void_p),
+                ("type_perm", ctypes.c_void_p)]
+
+
+# include/ance_amd.h: ANCE_EMBED_SEGMENT_CHUNK (the library states the same number through ance_embed_segment_chunk), ANCE_EMBED_POSITION_*
+EMBED_SEGMENT_CHUNK = 64
+EMBED_POSITION_MODES = {"absolute": 0, "roberta": 1}
+
 # rows per workgroup of the layer-tail and bias-GELU kernels (include/ance_amd.h: ANCE_LAYER_TAIL_ROWS_PER_WORKGROUP; the library
 # states the same number through ance_layer_tail_rows_per_workgroup)
 LAYER_TAIL_ROWS_PER_WORKGROUP = 16
@@ -264,6 +288,10 @@ SYMBOLS = {
     "ance_layer_tail_backward": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.POINTER(AnceLayerTailGradArgs), ctypes.c_void_p]),
     "ance_bias_gelu_forward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGeluArgs), ctypes.c_void_p]),
     "ance_bias_gelu_backward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGeluArgs), ctypes.POINTER(AnceBiasGeluGradArgs), ctypes.c_void_p]),
+    "ance_embed_segment_chunk": (ctypes.c_int, []),
+    "ance_embed_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_embed_forward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p]),
+    "ance_embed_backward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

@@ -1,0 +1,204 @@
+"""The input end of a trainable tower, differentiable (csrc/embed_train.hip behind ance_embed_*).
+
+    y = bert_embeddings(input_ids, word, position, token_type, LayerNorm.weight, LayerNorm.bias, eps, token_type_ids,
+                        position_mode, padding_idx, dropout_p, self.training)
+
+is what transformers' eager ``BertEmbeddings.forward`` (``position_mode="absolute"``) and ``RobertaEmbeddings.forward``
+(``"roberta"``: positions counted from the non-pad ids, pads anywhere in the row) compute --
+``dropout(LayerNorm((word[ids] + token_type[types]) + position[p]))`` -- in one launch.  It keeps two floats per token (mean,
+1 / sqrt(var + eps)) and, in roberta mode, the int32 positions; no mask and no [T, H] activation.  The backward recomputes the sum
+from the tables, regenerates the mask and returns DENSE gradients for the three tables and the LayerNorm: a table gradient is a
+segmented sum over the rows in the order of a stable device sort of the ids (``torch.sort(stable=True)``: the only torch kernels on
+the path), without atomics -- the same inputs give the same bits (include/ance_amd.h states the order).  The row ``padding_idx`` of
+the word table and, in roberta mode, of the position table gets a zero gradient, as ``nn.Embedding(padding_idx=...)`` gives it.
+
+Ids outside a table are CLAMPED into it by the kernels (forward bits and gradient row of the nearest valid id); nothing is raised,
+because finding out would mean a synchronisation.  Dropout draws from ``ance_amd.attention.dropout_state`` as every other dropout
+of this package does; a call with ``training`` false or ``dropout_p == 0`` draws nothing.
+"""
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .attention import _custom_bwd, _custom_fwd, dropout_state
+from .layers import TAIL_WIDTHS, _check_vector, _ptr, _stats_floats, _vector
+
+__all__ = ["bert_embeddings", "BertEmbeddings"]
+
+MAX_SEQ_LEN = 512
+
+
+def _table(t):
+    """A [n, H] table as the kernels read it: contiguous and 16-byte aligned."""
+    t = t.detach()
+    return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _ids32(t):
+    return t.to(torch.int32).contiguous()
+
+
+def _sorted(keys):
+    """The grouping of include/ance_amd.h: (the keys in stable ascending order, the permutation), on the device."""
+    return torch.sort(keys.view(-1), stable=True)
+
+
+class _BertEmbeddings(torch.autograd.Function):
+    @staticmethod
+    @_custom_fwd
+    def forward(ctx, word, position, token_type, weight, beta, input_ids, token_type_ids, eps, mode, padding_idx, dropout_p, training):
+        L = _lib.lib()
+        word, position, token_type = _table(word), _table(position), _table(token_type)
+        weight, beta = _vector(weight), _vector(beta)
+        n_seq, seq_len = input_ids.shape
+        H, n_rows, dev = word.shape[1], n_seq * seq_len, word.device
+        if L.ance_embed_workspace_bytes(n_rows, H) == 0:
+            raise _lib.AnceLibraryError("bert_embeddings: unsupported shape (rows %d, width %d)" % (n_rows, H))
+        ids = _ids32(input_ids)
+        types = _ids32(token_type_ids) if token_type_ids is not None else None
+        y = torch.empty((n_seq, seq_len, H), dtype=torch.float32, device=dev)
+        stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=dev)
+        positions = torch.empty(n_rows, dtype=torch.int32, device=dev) if mode == 1 else None
+        drop = bool(training) and dropout_p > 0.0
+        seed, offset = dropout_state.next_pair(dev) if drop else (0, 0)
+        args = _lib.AnceEmbedArgs(ids=ids.data_ptr(), type_ids=_ptr(types), word=word.data_ptr(), pos=position.data_ptr(),
+                                  type=token_type.data_ptr(), gamma=weight.data_ptr(), beta=beta.data_ptr(), y=y.data_ptr(),
+                                  positions=_ptr(positions), n_seq=n_seq, L=seq_len, H=H, vocab=word.shape[0],
+                                  max_pos=position.shape[0], n_types=token_type.shape[0], position_mode=mode, padding_idx=padding_idx,
+                                  eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed, offset=offset,
+                                  d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
+        with torch.cuda.device(dev):
+            _lib.check(L.ance_embed_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_embed_forward")
+        ctx.save_for_backward(word, position, token_type, weight, ids, types, positions, stats)
+        ctx.args = args
+        return y
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dy):
+        L = _lib.lib()
+        word, position, token_type, weight, ids, types, positions, stats = ctx.saved_tensors
+        a = _lib.AnceEmbedArgs.from_buffer_copy(ctx.args)  # y and beta are not touched by the backward
+        H, n_rows, dev = a.H, a.n_seq * a.L, word.device
+        dy = dy.to(torch.float32).contiguous()
+        if dy.data_ptr() % 16:
+            dy = dy.clone()
+        want_word, want_pos, want_type, want_w, want_b = ctx.needs_input_grad[:5]
+
+        def table(want, like):  # dense and zero-filled: the kernels store the rows that occur
+            return torch.zeros(like.shape, dtype=torch.float32, device=dev) if want else None
+
+        dword, dpos, dtype = table(want_word, word), table(want_pos, position), table(want_type, token_type)
+        dgamma = torch.empty(H, dtype=torch.float32, device=dev) if want_w else None
+        dbeta = torch.empty(H, dtype=torch.float32, device=dev) if want_b else None
+        # the saved state is the statistics (and the positions); the backward's rows and partial rows live only as long as this call
+        ws_bytes = L.ance_embed_workspace_bytes(n_rows, H)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+        ws[:stats.numel()].copy_(stats)
+        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        none = (None, None)
+        wk, wp = _sorted(ids) if want_word else none
+        pk, pp = _sorted(positions) if want_pos and positions is not None else none
+        tk, tp = _sorted(types) if want_type and types is not None and a.n_types == 2 else none
+        g = _lib.AnceEmbedGradArgs(dy=dy.data_ptr(), dword=_ptr(dword), dpos=_ptr(dpos), dtype=_ptr(dtype), dgamma=_ptr(dgamma),
+                                   dbeta=_ptr(dbeta), word_keys=_ptr(wk), word_perm=_ptr(wp), pos_keys=_ptr(pk), pos_perm=_ptr(pp),
+                                   type_keys=_ptr(tk), type_perm=_ptr(tp))
+        with torch.cuda.device(dev):
+            _lib.check(L.ance_embed_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_embed_backward")
+        return dword, dpos, dtype, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def _check_table(t, what, H, like=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 2 or t.shape[0] < 1:
+        raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor [n, H]" % what)
+    if t.dtype != torch.float32 and not (torch.is_autocast_enabled() and t.is_floating_point()):  # autocast: cast by _custom_fwd
+        raise _lib.AnceLibraryError("%s must have dtype torch.float32, got %s" % (what, t.dtype))
+    if t.shape[1] != H or (like is not None and t.device != like.device):
+        raise _lib.AnceLibraryError("%s must be [n, %d] on the word table's device, got %r on %s" % (what, H, tuple(t.shape), t.device))
+
+
+def _check_ids(t, what, like, shape=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != like.device:
+        raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor on %s" % (what, like.device))
+    if t.dtype not in (torch.int32, torch.int64):
+        raise _lib.AnceLibraryError("%s must have dtype torch.int32 or torch.int64, got %s" % (what, t.dtype))
+    if t.dim() != 2 or t.numel() == 0 or (shape is not None and t.shape != shape):
+        raise _lib.AnceLibraryError("%s must be [B, L]%s, got %r" % (what, "" if shape is None else " like input_ids", tuple(t.shape)))
+
+
+def bert_embeddings(input_ids, word, position, token_type, ln_weight, ln_bias, eps, token_type_ids=None, position_mode="absolute",
+                    padding_idx=None, dropout_p=0.0, training=True):
+    """dropout(LayerNorm((word[input_ids] + token_type[token_type_ids]) + position[p]) * ln_weight + ln_bias) -> [B, L, H] fp32.
+    input_ids [B, L] int32 or int64 (L <= 512), token_type_ids like it or None (type 0); word [vocab, H], position [max_pos, H],
+    token_type [1 or 2, H] fp32 with H 768 or 1024.  position_mode "absolute": p = the column, L <= max_pos; "roberta": p =
+    padding_idx + the running count of non-pad ids (padding_idx at pads), L + padding_idx + 1 <= max_pos.  padding_idx (None: no
+    such row; required in roberta mode) names the row of the word table -- and in roberta mode of the position table -- whose
+    gradient stays zero.  Ids outside their table are clamped into it.  Gradients for the five parameters, the tables' dense."""
+    if not isinstance(word, torch.Tensor) or word.dim() != 2 or word.shape[1] not in TAIL_WIDTHS:
+        raise _lib.AnceLibraryError("word must be [vocab, H] with H in %r" % (TAIL_WIDTHS,))
+    H = word.shape[1]
+    _check_table(word, "word", H)
+    _check_table(position, "position", H, word)
+    _check_table(token_type, "token_type", H, word)
+    _check_vector(ln_weight, "ln_weight", H, word)
+    _check_vector(ln_bias, "ln_bias", H, word)
+    _check_ids(input_ids, "input_ids", word)
+    if token_type_ids is not None:
+        _check_ids(token_type_ids, "token_type_ids", word, input_ids.shape)
+    if position_mode not in _lib.EMBED_POSITION_MODES:
+        raise _lib.AnceLibraryError("position_mode must be \"absolute\" or \"roberta\", got %r" % (position_mode,))
+    seq_len, vocab, max_pos = input_ids.shape[1], word.shape[0], position.shape[0]
+    pad = -1 if padding_idx is None else int(padding_idx)
+    if seq_len > MAX_SEQ_LEN:
+        raise _lib.AnceLibraryError("input_ids: L = %d is above %d" % (seq_len, MAX_SEQ_LEN))
+    if token_type.shape[0] not in (1, 2):
+        raise _lib.AnceLibraryError("token_type must have 1 or 2 rows, got %d" % token_type.shape[0])
+    if padding_idx is not None and not 0 <= pad < vocab:
+        raise _lib.AnceLibraryError("padding_idx must be in [0, %d), got %r" % (vocab, padding_idx))
+    if position_mode == "roberta":
+        if padding_idx is None:
+            raise _lib.AnceLibraryError("position_mode \"roberta\" needs a padding_idx")
+        if seq_len + pad + 1 > max_pos:
+            raise _lib.AnceLibraryError("position table too small: L + padding_idx + 1 = %d > %d rows" % (seq_len + pad + 1, max_pos))
+    elif seq_len > max_pos:
+        raise _lib.AnceLibraryError("position table too small: L = %d > %d rows" % (seq_len, max_pos))
+    if not 0.0 <= float(dropout_p) < 1.0:
+        raise _lib.AnceLibraryError("dropout_p must be in [0, 1), got %r" % (dropout_p,))
+    if not float(eps) > 0.0:
+        raise _lib.AnceLibraryError("eps must be positive, got %r" % (eps,))
+    return _BertEmbeddings.apply(word, position, token_type, ln_weight, ln_bias, input_ids, token_type_ids, float(eps),
+                                 _lib.EMBED_POSITION_MODES[position_mode], pad, float(dropout_p), bool(training))
+
+
+class BertEmbeddings(torch.nn.Module):
+    """transformers' BertEmbeddings / RobertaEmbeddings with their parameter names -- word_embeddings.weight,
+    position_embeddings.weight, token_type_embeddings.weight, LayerNorm.weight, LayerNorm.bias -- so that the ``embeddings.*`` part of
+    a tower's state dict loads as it is (strict; the position_ids / token_type_ids buffers of recent transformers are not persistent
+    and not in it).  ``forward(input_ids [B, L], token_type_ids=None) -> [B, L, H]`` is one bert_embeddings call.
+    position_mode "roberta" needs pad_token_id; the parameters start as nn.Embedding / nn.LayerNorm initialise them."""
+
+    def __init__(self, vocab_size, hidden_size, max_position_embeddings, type_vocab_size, layer_norm_eps=1e-12, hidden_dropout_prob=0.1,
+                 pad_token_id=None, position_mode="absolute"):
+        super().__init__()
+        if hidden_size not in TAIL_WIDTHS or type_vocab_size not in (1, 2):
+            raise _lib.AnceLibraryError("BertEmbeddings: hidden_size must be 768 or 1024 and type_vocab_size 1 or 2; got %r, %r"
+                                        % (hidden_size, type_vocab_size))
+        if position_mode not in _lib.EMBED_POSITION_MODES or (position_mode == "roberta" and pad_token_id is None):
+            raise _lib.AnceLibraryError("BertEmbeddings: position_mode must be \"absolute\" or \"roberta\" (with a pad_token_id), got %r"
+                                        % (position_mode,))
+        nn = torch.nn
+        self.position_mode, self.pad_token_id = position_mode, pad_token_id
+        self.layer_norm_eps, self.hidden_dropout_prob = float(layer_norm_eps), float(hidden_dropout_prob)
+        self.word_embeddings = nn.Embedding(vocab_size, hidden_size, padding_idx=pad_token_id)
+        self.position_embeddings = nn.Embedding(max_position_embeddings, hidden_size,
+                                                padding_idx=pad_token_id if position_mode == "roberta" else None)
+        self.token_type_embeddings = nn.Embedding(type_vocab_size, hidden_size)
+        self.LayerNorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
+
+    def forward(self, input_ids, token_type_ids=None):
+        return bert_embeddings(input_ids, self.word_embeddings.weight, self.position_embeddings.weight,
+                               self.token_type_embeddings.weight, self.LayerNorm.weight, self.LayerNorm.bias, self.layer_norm_eps,
+                               token_type_ids, self.position_mode, self.pad_token_id, self.hidden_dropout_prob, self.training)

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_* only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_* only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -513,6 +513,96 @@ int ance_layer_tail_forward(const AnceLayerTailArgs *args, void *stream);
 int ance_layer_tail_backward(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads, void *stream);
 int ance_bias_gelu_forward(const AnceBiasGeluArgs *args, void *stream);
 int ance_bias_gelu_backward(const AnceBiasGeluArgs *args, const AnceBiasGeluGradArgs *grads, void *stream);
+
+/* The input end of a trainable tower with its gradients (csrc/embed_train.hip), fp32 throughout: what transformers' eager
+ * BertEmbeddings / RobertaEmbeddings compute, ids -> word + token_type + position -> LayerNorm -> dropout.  T = n_seq * L token rows,
+ * row r = s * L + l; H = 768 or 1024; 1 <= L <= 512; ids and type_ids are int32 [n_seq, L]; y and dy are contiguous [T, H].
+ * Arithmetic, per row:
+ *   id = clamp(ids[r], 0, vocab - 1);  tt = type_ids ? clamp(type_ids[r], 0, n_types - 1) : 0;
+ *   p  = l                                                                     (ANCE_EMBED_POSITION_ABSOLUTE: BERT, DPR)
+ *   p  = padding_idx + (id != padding_idx ? #{t <= l : id(s, t) != padding_idx} : 0)   (ANCE_EMBED_POSITION_ROBERTA:
+ *        create_position_ids_from_input_ids, pads anywhere in the row; counted inside the forward kernel, no extra launch)
+ *   p  = clamp(p, 0, max_pos - 1)
+ *   The clamps are the first thing done with an id, a type id or a position, before an address is formed from it, in the forward
+ *   and in every backward kernel: an out-of-range id is READ AS the nearest valid one (forward bits and gradient row), and nothing
+ *   is reported -- nothing synchronises.  `id != padding_idx` compares the clamped id.
+ *   v = (word[id] + type[tt]) + pos[p] (this association);  mean = sum v / H;  var = sum (v - mean)^2 / H (two passes over the row
+ *   in registers, biased);  rstd = 1.0f / sqrtf(var + eps);  xhat = (v - mean) rstd;  u = xhat o gamma + beta;
+ *   y[r] = keep o u * (1.0f / (1.0f - dropout_p)) when training != 0 and dropout_p > 0, else u.
+ *   backward, given dy:  d = keep o dy / (1 - dropout_p);  g = d o gamma;  dv = rstd (g - mean_H(g) - xhat mean_H(g o xhat));
+ *   dgamma = sum_r d o xhat;  dbeta = sum_r d;  dword[k] = sum of dv over the rows with id k, dpos[k] and dtype[k] likewise.
+ * Dropout: the layer tail's Philox contract above -- key (seed lo32, seed hi32), counter (row lo32, col >> 2, offset lo32, offset
+ * hi32), output word col & 3 decides column col, keep iff word >= floor(dropout_p * 2^32).  seed and offset are host values.
+ * Saved state: mean [T] and rstd [T] in the first S = 2 * roundup(4 * T, 256) bytes of d_workspace (mean at byte 0, rstd at byte
+ * S / 2, as the layer tail lays them out), and in roberta mode positions [T] int32.  ids and type_ids are read again by the backward.
+ * No mask and no [T, H] activation is kept: the backward recomputes v from the tables and regenerates the mask.
+ * Table gradients (dense: dword [vocab, H], dpos [max_pos, H], dtype [n_types, H]; the CALLER zero-fills them, the kernels store only
+ * the rows that occur, with plain vector stores; no atomics anywhere):
+ *   grouping  the caller passes, per table, the keys in the order of a STABLE ascending sort of the T raw int32 keys (word_keys:
+ *             ids; type_keys: type_ids; pos_keys: the saved positions) and the int64 permutation (sorted position j -> row).  The
+ *             kernels clamp the sorted keys (which keeps them sorted) and every row index.  Absolute positions are grouped
+ *             analytically (key p: rows s * L + p, s ascending) and take no arrays; a type table with n_types == 1 or with
+ *             type_ids NULL takes none either: dtype[0] is the column sum of dv over all rows, by the layer tail's partial rows
+ *             and tree.
+ *   order     the sorted positions are cut into aligned chunks of ANCE_EMBED_SEGMENT_CHUNK (ance_embed_segment_chunk returns the
+ *             same number).  A piece is a maximal run of one key inside a chunk; one wave adds a piece's rows in ascending sorted
+ *             position, starting from the first row (no zero is added).  A key whose run crosses chunk boundaries gets its pieces'
+ *             partial rows added in ascending chunk order by one wave in a second launch.  The order is a function of the sorted
+ *             keys alone: the same inputs give the same bits, whatever the grid.  Longest serial chain for a key with n rows:
+ *             about ANCE_EMBED_SEGMENT_CHUNK + n / ANCE_EMBED_SEGMENT_CHUNK row additions.
+ *   padding   rows whose (clamped) id equals padding_idx add nothing to dword -- its row padding_idx keeps the caller's zeros --
+ *             and in roberta mode rows at position padding_idx add nothing to dpos: nn.Embedding(padding_idx=...)'s gradient.
+ *             padding_idx = -1: none (absolute mode only; the type table and the absolute position table never have one).
+ * d_workspace (16-byte aligned), ance_embed_workspace_bytes(T, H) = S + T * H * 4 + n_part * 3 * H * 4 + 3 * n_chunk * 2 * H * 4,
+ * n_part = ceil(T / ANCE_LAYER_TAIL_ROWS_PER_WORKGROUP), n_chunk = ceil(T / ANCE_EMBED_SEGMENT_CHUNK): the statistics; dv [T, H];
+ * the partial rows [n_part][3][H] (dgamma, dbeta, sum dv); per table (word, position, type) the chunks' partial rows
+ * [n_chunk][2][H].  The forward touches and requires only the first S bytes; the backward takes the SAME AnceEmbedArgs (of which it
+ * reads neither y nor beta) and all of the workspace.
+ * Launches: ONE forward.  Backward FOUR: the row kernel, the column-sum tree, the pieces, the joins (all wanted tables ride in the
+ * same two launches); TWO when none of dword, dpos, dtype needs the segmented sum.  The sort that produces the keys is the caller's.
+ * Nothing is read back, nothing synchronises: every call can be captured.
+ * Refuses (ANCE_E_INVALID, before any launch): a null pointer other than type_ids, positions in absolute mode, the gradient
+ * outputs and the keys / permutations of tables not wanted; H outside {768, 1024}; L outside 1 .. 512; n_seq < 1; n_types outside
+ * {1, 2}; a position_mode other than the two; absolute mode with L > max_pos; roberta mode with L + padding_idx + 1 > max_pos or
+ * padding_idx outside 0 .. vocab - 1; dropout_p outside [0, 1); eps <= 0; an unaligned base; a null, unaligned or too small
+ * workspace.  ance_embed_workspace_bytes returns 0 for H outside {768, 1024} or T outside 1 .. 2^31 - 1. */
+#define ANCE_EMBED_SEGMENT_CHUNK 64
+#define ANCE_EMBED_POSITION_ABSOLUTE 0
+#define ANCE_EMBED_POSITION_ROBERTA 1
+typedef struct AnceEmbedArgs {
+    const int32_t *ids;           /* [n_seq, L]                                                   */
+    const int32_t *type_ids;      /* [n_seq, L] or NULL: type 0                                   */
+    const float *word, *pos, *type; /* [vocab, H], [max_pos, H], [n_types, H]                     */
+    const float *gamma, *beta;    /* [H]                                                          */
+    float *y;                     /* [n_seq * L, H]                                               */
+    int32_t *positions;           /* [n_seq * L], roberta mode: written forward, read backward    */
+    int32_t n_seq, L, H;
+    int32_t vocab, max_pos, n_types;
+    int32_t position_mode;        /* ANCE_EMBED_POSITION_*                                        */
+    int32_t padding_idx;          /* -1: none                                                     */
+    float eps;
+    float dropout_p;
+    int32_t training;
+    int32_t reserved;             /* 0 */
+    uint64_t seed, offset;
+    void *d_workspace;
+    size_t workspace_bytes;
+} AnceEmbedArgs;
+typedef struct AnceEmbedGradArgs {
+    const float *dy;              /* [n_seq * L, H]                                               */
+    float *dword, *dpos, *dtype;  /* dense tables, zero-filled by the caller, each nullable       */
+    float *dgamma, *dbeta;        /* [H], each nullable                                           */
+    const int32_t *word_keys;     /* [T] sorted ids; with dword                                   */
+    const int64_t *word_perm;     /* [T] sorted position -> row                                   */
+    const int32_t *pos_keys;      /* sorted saved positions; with dpos in roberta mode            */
+    const int64_t *pos_perm;
+    const int32_t *type_keys;     /* sorted type_ids; with dtype when n_types == 2 and type_ids   */
+    const int64_t *type_perm;
+} AnceEmbedGradArgs;
+int ance_embed_segment_chunk(void);
+size_t ance_embed_workspace_bytes(int64_t n_rows, int H);
+int ance_embed_forward(const AnceEmbedArgs *args, void *stream);
+int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream);
 
 /* Test hook: the SPLIT (fp32-grade) GEMM of the encoder with one of its epilogues.  acc[m][n] = sum_k a[m][k] b[n][k] with
  * a = a_hi + a_lo (b likewise; the lo x lo products are left out); d_a_pair [M, 2K] / d_b_pair [N, 2K] fp16 PAIR ROWS -- 32-column
