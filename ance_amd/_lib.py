@@ -145,6 +145,37 @@ class AnceBiasGeluGradArgs(ctypes.Structure):
                 ("ld_dx", ctypes.c_int32)]
 
 
+class AnceLayerTail16Args(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_layer_tail16_forward / ance_layer_tail16_backward (x and y16 in `dtype`)."""
+    _fields_ = [("x", ctypes.c_void_p), ("res", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
+                ("beta", ctypes.c_void_p), ("y", ctypes.c_void_p), ("y16", ctypes.c_void_p), ("ld_x", ctypes.c_int32),
+                ("ld_res", ctypes.c_int32), ("ld_y", ctypes.c_int32), ("ld_y16", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("n_rows", ctypes.c_int32), ("dtype", ctypes.c_int32), ("eps", ctypes.c_float), ("dropout_p", ctypes.c_float),
+                ("training", ctypes.c_int32), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("d_workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class AnceLayerTail16GradArgs(ctypes.Structure):
+    """include/ance_amd.h: the gradient side of ance_layer_tail16_backward (dy fp32 and dy16 each nullable, one given; every output
+    nullable)."""
+    _fields_ = [("dy", ctypes.c_void_p), ("dy16", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dres", ctypes.c_void_p),
+                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p), ("dbias", ctypes.c_void_p), ("ld_dy", ctypes.c_int32),
+                ("ld_dy16", ctypes.c_int32), ("ld_dx", ctypes.c_int32), ("ld_dres", ctypes.c_int32)]
+
+
+class AnceBiasGelu16Args(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_bias_gelu16_forward / ance_bias_gelu16_backward."""
+    _fields_ = [("x", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p), ("ld_x", ctypes.c_int32),
+                ("ld_y", ctypes.c_int32), ("N", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("d_workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class AnceBiasGelu16GradArgs(ctypes.Structure):
+    """include/ance_amd.h: the gradient side of ance_bias_gelu16_backward."""
+    _fields_ = [("dy", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dbias", ctypes.c_void_p), ("ld_dy", ctypes.c_int32),
+                ("ld_dx", ctypes.c_int32)]
+
+
 class AnceEmbedArgs(ctypes.Structure):
     """include/ance_amd.h: the arguments of ance_embed_forward / ance_embed_backward."""
     _fields_ = [("ids", ctypes.c_void_p), ("type_ids", ctypes.c_void_p), ("word", ctypes.c_void_p), ("pos", ctypes.c_void_p),
@@ -288,6 +319,12 @@ SYMBOLS = {
     "ance_layer_tail_backward": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.POINTER(AnceLayerTailGradArgs), ctypes.c_void_p]),
     "ance_bias_gelu_forward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGeluArgs), ctypes.c_void_p]),
     "ance_bias_gelu_backward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGeluArgs), ctypes.POINTER(AnceBiasGeluGradArgs), ctypes.c_void_p]),
+    "ance_layer_tail16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_bias_gelu16_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_layer_tail16_forward": (ctypes.c_int, [ctypes.POINTER(AnceLayerTail16Args), ctypes.c_void_p]),
+    "ance_layer_tail16_backward": (ctypes.c_int, [ctypes.POINTER(AnceLayerTail16Args), ctypes.POINTER(AnceLayerTail16GradArgs), ctypes.c_void_p]),
+    "ance_bias_gelu16_forward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGelu16Args), ctypes.c_void_p]),
+    "ance_bias_gelu16_backward": (ctypes.c_int, [ctypes.POINTER(AnceBiasGelu16Args), ctypes.POINTER(AnceBiasGelu16GradArgs), ctypes.c_void_p]),
     "ance_embed_segment_chunk": (ctypes.c_int, []),
     "ance_embed_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "ance_embed_forward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p]),

@@ -1,4 +1,4 @@
-// What the row-wise training kernels share (layer_tail.hip, embed_train.hip): one wave owns a row and holds it in registers, lane l
+// What the row-wise training kernels share (layer_tail.hip, layer_tail_half.hip, embed_train.hip): one wave owns a row and holds it in registers, lane l
 // has the float4 at columns 4 (64 i + l), i < width / 256; the row sums are xor butterflies over the 64 lanes (every lane ends with
 // the same bits).  A workgroup is four waves and owns LT_ROWS = 16 consecutive rows, four per wave.
 // Column sums, without atomics: a wave adds its rows' terms per column in registers in ascending row order, the four waves meet in

@@ -14,6 +14,10 @@ Dropout draws its (seed, offset) from ``ance_amd.attention.dropout_state`` -- th
 that every dropout forward, the attention's included, advances by one, so no two calls share a pair.  A call with ``training`` false
 or ``dropout_p == 0`` draws nothing.  Both are HOST values baked into the launch: a captured graph replays the pair it was captured
 with -- the same mask at every replay.  The masks are not torch's.
+
+``precision="half"`` (both functions; ``BertLayer(..., precision="half")``) is the form for ``torch.autocast`` (csrc/layer_tail_half.hip
+behind ance_layer_tail16_* / ance_bias_gelu16_*): the dense outputs go in as fp16 / bf16, the residual stream, ``y`` and every
+parameter gradient stay fp32, and the tail can return a 16-bit copy of ``y`` for the Linears that read it.
 """
 import ctypes
 
@@ -21,7 +25,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .attention import _custom_bwd, _custom_fwd, _rows, attention_padded, dropout_state
+from .attention import (HALF_DTYPES, _check_precision, _custom_bwd, _custom_fwd, _custom_fwd_as_is, _rows, _rows16, attention_padded,
+                        dropout_state)
 
 __all__ = ["dropout_add_layer_norm", "bias_gelu", "BertLayer"]
 
@@ -167,11 +172,163 @@ class _BiasGelu(torch.autograd.Function):
         return dx, dbias
 
 
-def dropout_add_layer_norm(x, bias, residual, weight, beta, eps, dropout_p=0.0, training=True):
+def _matrix16(t):
+    """_matrix for a 16-bit tensor (a row stride must be a multiple of 8 elements)."""
+    if t.dim() > 3:
+        t = t.reshape(-1, t.shape[-1])
+    return _rows16(t)
+
+
+class _DropoutAddLayerNormHalf(torch.autograd.Function):
+    """_DropoutAddLayerNorm with a 16-bit x and an fp32 residual stream (csrc/layer_tail_half.hip): nothing is cast.  Returns y (fp32)
+    or, with want_half, (y, y16); the backward takes whichever of their two gradients exist and sums them in registers."""
+
+    @staticmethod
+    @_custom_fwd_as_is
+    def forward(ctx, x, bias, residual, weight, beta, eps, dropout_p, training, want_half):
+        L = _lib.lib()
+        shape, H = x.shape, x.shape[-1]
+        (x, ld_x), (residual, ld_r) = _matrix16(x), _matrix(residual)
+        bias, weight, beta = _vector(bias), _vector(weight), _vector(beta)
+        n_rows = x.numel() // H
+        if L.ance_layer_tail16_workspace_bytes(n_rows, H) == 0:
+            raise _lib.AnceLibraryError("dropout_add_layer_norm: unsupported shape (rows %d, width %d)" % (n_rows, H))
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        y16 = torch.empty(shape, dtype=x.dtype, device=x.device) if want_half else None
+        stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=x.device)
+        drop = bool(training) and dropout_p > 0.0
+        seed, offset = dropout_state.next_pair(x.device) if drop else (0, 0)
+        args = _lib.AnceLayerTail16Args(x=x.data_ptr(), res=residual.data_ptr(), bias=_ptr(bias), gamma=weight.data_ptr(),
+                                        beta=beta.data_ptr(), y=y.data_ptr(), y16=_ptr(y16), ld_x=ld_x, ld_res=ld_r, ld_y=H, ld_y16=H,
+                                        H=H, n_rows=n_rows, dtype=HALF_DTYPES[x.dtype], eps=float(eps), dropout_p=float(dropout_p),
+                                        training=1 if drop else 0, seed=seed, offset=offset, d_workspace=stats.data_ptr(),
+                                        workspace_bytes=stats.numel() * 4)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_layer_tail16_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_layer_tail16_forward")
+        ctx.save_for_backward(x, residual, bias, weight, stats)
+        ctx.args = args
+        ctx.shape = shape
+        ctx.set_materialize_grads(False)   # a missing gradient stays None: the kernel reads only those that exist
+        return (y, y16) if want_half else y
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dy, dy16=None):
+        L = _lib.lib()
+        x, residual, bias, weight, stats = ctx.saved_tensors
+        if dy is None and dy16 is None:
+            return (None,) * 9
+        a = _lib.AnceLayerTail16Args.from_buffer_copy(ctx.args)  # y, y16 and beta are not touched by the backward
+        H, n_rows = a.H, a.n_rows
+        ld_dy = ld_dy16 = 0
+        if dy is not None:
+            dy, ld_dy = _matrix(dy.to(torch.float32))
+        if dy16 is not None:
+            dy16, ld_dy16 = _matrix16(dy16.to(x.dtype))
+        want_x, want_bias, want_res, want_w, want_b = ctx.needs_input_grad[:5]
+
+        def out(want, shape, dtype=torch.float32):
+            return torch.empty(shape, dtype=dtype, device=x.device) if want else None
+
+        dx, dres = out(want_x, ctx.shape, x.dtype), out(want_res, ctx.shape)
+        dbias, dgamma, dbeta = out(want_bias and bias is not None, (H,)), out(want_w, (H,)), out(want_b, (H,))
+        ws_bytes = L.ance_layer_tail16_workspace_bytes(n_rows, H)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+        ws[:stats.numel()].copy_(stats)
+        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        g = _lib.AnceLayerTail16GradArgs(dy=_ptr(dy), dy16=_ptr(dy16), dx=_ptr(dx), dres=_ptr(dres), dgamma=_ptr(dgamma),
+                                         dbeta=_ptr(dbeta), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dy16=ld_dy16, ld_dx=H, ld_dres=H)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_layer_tail16_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()),
+                       "ance_layer_tail16_backward")
+        return dx, dbias, dres, dgamma, dbeta, None, None, None, None
+
+
+class _BiasGeluHalf(torch.autograd.Function):
+    """_BiasGelu from 16 bits to 16 bits (csrc/layer_tail_half.hip): the saved input is the 16-bit x itself."""
+
+    @staticmethod
+    @_custom_fwd_as_is
+    def forward(ctx, x, bias):
+        L = _lib.lib()
+        shape, N = x.shape, x.shape[-1]
+        x, ld_x = _matrix16(x)
+        bias = _vector(bias)
+        n_rows = x.numel() // N
+        if L.ance_bias_gelu16_workspace_bytes(n_rows, N) == 0:
+            raise _lib.AnceLibraryError("bias_gelu: unsupported shape (rows %d, width %d)" % (n_rows, N))
+        y = torch.empty(shape, dtype=x.dtype, device=x.device)
+        args = _lib.AnceBiasGelu16Args(x=x.data_ptr(), bias=bias.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_y=N, N=N, n_rows=n_rows,
+                                       dtype=HALF_DTYPES[x.dtype], reserved=0, d_workspace=None, workspace_bytes=0)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_bias_gelu16_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_bias_gelu16_forward")
+        ctx.save_for_backward(x, bias)
+        ctx.args = args
+        ctx.shape = shape
+        return y
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dy):
+        L = _lib.lib()
+        x, bias = ctx.saved_tensors
+        a = _lib.AnceBiasGelu16Args.from_buffer_copy(ctx.args)
+        dy, ld_dy = _matrix16(dy.to(x.dtype))
+        want_x, want_bias = ctx.needs_input_grad[:2]
+        dx = torch.empty(ctx.shape, dtype=x.dtype, device=x.device) if want_x else None
+        dbias = torch.empty(a.N, dtype=torch.float32, device=x.device) if want_bias else None
+        ws_bytes = L.ance_bias_gelu16_workspace_bytes(a.n_rows, a.N)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        g = _lib.AnceBiasGelu16GradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=a.N)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ance_bias_gelu16_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()),
+                       "ance_bias_gelu16_backward")
+        return dx, dbias
+
+
+def _half_rows(x, what, widths):
+    """precision="half": x as the 16-bit kernels take it.  fp16 / bf16 go in as they are; an fp32 x is cast to the autocast dtype
+    under autocast (a differentiable cast, as autocast's own) and refused outside it."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor" % what)
+    if x.dtype == torch.float32 and torch.is_autocast_enabled():
+        x = x.to(torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype())
+    if x.dtype not in HALF_DTYPES:
+        raise _lib.AnceLibraryError("%s must have dtype torch.float16 or bfloat16 with precision=\"half\", got %s" % (what, x.dtype))
+    if x.dim() < 2 or x.shape[-1] not in widths:
+        raise _lib.AnceLibraryError("%s must be [.., W] with W in %r, got %r" % (what, widths, tuple(x.shape)))
+    if x.numel() == 0:
+        raise _lib.AnceLibraryError("empty input")
+    return x
+
+
+def _check_fp32(t, what):
+    """precision="half": the residual stream and the parameters stay fp32, under autocast as well (nothing casts them)."""
+    if t is not None and isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+        raise _lib.AnceLibraryError("%s must have dtype torch.float32 with precision=\"half\", got %s" % (what, t.dtype))
+
+
+def dropout_add_layer_norm(x, bias, residual, weight, beta, eps, dropout_p=0.0, training=True, precision="fp32", return_half=False):
     """LayerNorm(dropout(x + bias) + residual) * weight + beta over the last dimension: x, residual [.., H] fp32 with H 768 or 1024
     (views with evenly spaced rows pass as they are, anything else is copied), bias [H] or None, weight, beta [H].  Returns y shaped
-    like x; gradients for x, bias, residual, weight and beta."""
-    _check_rows(x, "x", TAIL_WIDTHS)
+    like x; gradients for x, bias, residual, weight and beta.
+    precision="half" (for ``torch.autocast``): x is fp16 or bf16 and goes in as it is -- the dense output without its bias -- while
+    residual, the parameters and y stay fp32: the residual stream is never rounded to 16 bits.  An fp32 x is cast to the autocast
+    dtype under autocast and refused outside it.  The gradient of x has x's dtype, every other gradient is fp32.
+    ``return_half=True`` returns (y, y16): y16 is y rounded once to x's dtype in the same launch, for the Linears that read y; both
+    are differentiable and the backward sums whichever of their gradients exist in registers."""
+    half = _check_precision(precision)
+    if not half and return_half:
+        raise _lib.AnceLibraryError("return_half needs precision=\"half\"")
+    if half:
+        x = _half_rows(x, "x", TAIL_WIDTHS)
+        for t, what in ((residual, "residual"), (bias, "bias"), (weight, "weight"), (beta, "beta")):
+            _check_fp32(t, what)
+    else:
+        _check_rows(x, "x", TAIL_WIDTHS)
     _check_rows(residual, "residual", TAIL_WIDTHS)
     if residual.shape != x.shape or residual.device != x.device:
         raise _lib.AnceLibraryError("x and residual must be of one shape, on one device")
@@ -183,11 +340,21 @@ def dropout_add_layer_norm(x, bias, residual, weight, beta, eps, dropout_p=0.0, 
         raise _lib.AnceLibraryError("dropout_p must be in [0, 1), got %r" % (dropout_p,))
     if not float(eps) > 0.0:
         raise _lib.AnceLibraryError("eps must be positive, got %r" % (eps,))
+    if half:
+        return _DropoutAddLayerNormHalf.apply(x, bias, residual, weight, beta, float(eps), float(dropout_p), bool(training),
+                                              bool(return_half))
     return _DropoutAddLayerNorm.apply(x, bias, residual, weight, beta, float(eps), float(dropout_p), bool(training))
 
 
-def bias_gelu(x, bias):
-    """gelu(x + bias), the erf form, over [.., N] fp32 with N 3072 or 4096; gradients for x and bias."""
+def bias_gelu(x, bias, precision="fp32"):
+    """gelu(x + bias), the erf form, over [.., N] fp32 with N 3072 or 4096; gradients for x and bias.
+    precision="half": x is fp16 or bf16 (an fp32 x is cast under autocast and refused outside it), bias fp32; y and the gradient of
+    x have x's dtype, the arithmetic is fp32 with one rounding at the store, and the saved input is the 16-bit x."""
+    if _check_precision(precision):
+        x = _half_rows(x, "x", GELU_WIDTHS)
+        _check_fp32(bias, "bias")
+        _check_vector(bias, "bias", x.shape[-1], x)
+        return _BiasGeluHalf.apply(x, bias)
     _check_rows(x, "x", GELU_WIDTHS)
     _check_vector(bias, "bias", x.shape[-1], x)
     return _BiasGelu.apply(x, bias)
@@ -204,17 +371,26 @@ class BertLayer(torch.nn.Module):
     without their bias, which goes into the fused call behind them), attention_padded, two dropout_add_layer_norm and one bias_gelu.
     ``attention_precision="half"`` is for ``torch.autocast``: the fp16 / bf16 Linear outputs enter the attention core as they are and
     ctx goes into attention.output.dense without a cast (attention_padded, precision="half"); with fp32 hidden states outside autocast
-    it raises.  The three row-wise seams stay fp32 either way.
+    it raises.  With it alone the three row-wise seams stay fp32.
+    ``precision="half"`` (implies ``attention_precision="half"``) runs the seams in 16 bits as well and keeps the residual stream in
+    fp32: ``forward(hidden_states, lens, hidden_states_half=None, return_half=False)`` takes the fp32 hidden states (the residual)
+    and, optionally, their 16-bit copy -- otherwise the layer makes that ONE cast itself; the three q / k / v Linears read it, the
+    first tail returns (h, h16) and intermediate.dense reads h16, the GELU runs 16 bits to 16 bits, and the second tail returns the
+    fp32 output, or with ``return_half=True`` (out, out16) for the next layer's ``hidden_states_half``: a stack of layers then runs
+    with no activation cast after the first.  The parameters and their gradients stay fp32.
     Pad rows are computed like any other in the three row-wise seams, as the reference does; the attention core writes zeros there
     (INTEGRATION.md 3i), so a pad row of the output is the LayerNorm tail of zeros, not the reference's value, and never reaches a
     loss."""
 
     def __init__(self, hidden_size, num_attention_heads, intermediate_size, layer_norm_eps=1e-12, hidden_dropout_prob=0.1,
-                 attention_probs_dropout_prob=0.1, attention_precision="fp32"):
+                 attention_probs_dropout_prob=0.1, attention_precision="fp32", precision="fp32"):
         super().__init__()
         if attention_precision not in ("fp32", "half"):
             raise _lib.AnceLibraryError("BertLayer: attention_precision must be \"fp32\" or \"half\", got %r" % (attention_precision,))
-        self.attention_precision = attention_precision
+        if precision not in ("fp32", "half"):
+            raise _lib.AnceLibraryError("BertLayer: precision must be \"fp32\" or \"half\", got %r" % (precision,))
+        self.precision = precision
+        self.attention_precision = "half" if precision == "half" else attention_precision
         if hidden_size not in TAIL_WIDTHS or hidden_size != 64 * num_attention_heads or intermediate_size not in GELU_WIDTHS:
             raise _lib.AnceLibraryError("BertLayer: hidden_size must be 768 (12 heads) or 1024 (16 heads), intermediate_size 3072 or "
                                         "4096; got %r, %r heads, %r" % (hidden_size, num_attention_heads, intermediate_size))
@@ -234,7 +410,35 @@ class BertLayer(torch.nn.Module):
         self.output.dense = nn.Linear(intermediate_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
 
-    def forward(self, hidden_states, lens):
+    def _forward_half(self, hidden_states, lens, hidden_states_half, return_half):
+        F = torch.nn.functional
+        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
+        if not isinstance(hidden_states, torch.Tensor) or hidden_states.dtype != torch.float32:
+            raise _lib.AnceLibraryError("BertLayer(precision=\"half\"): hidden_states is the fp32 residual stream, got %s"
+                                        % (getattr(hidden_states, "dtype", type(hidden_states)),))
+        if hidden_states_half is None:   # the layer's one activation cast
+            hidden_states_half = _half_rows(hidden_states, "hidden_states", TAIL_WIDTHS)
+        elif hidden_states_half.dtype not in HALF_DTYPES or hidden_states_half.shape != hidden_states.shape:
+            raise _lib.AnceLibraryError("hidden_states_half must be the fp16 / bf16 copy of hidden_states, got %s %r"
+                                        % (hidden_states_half.dtype, tuple(hidden_states_half.shape)))
+        q = F.linear(hidden_states_half, att.self.query.weight, att.self.query.bias)
+        k = F.linear(hidden_states_half, att.self.key.weight, att.self.key.bias)
+        v = F.linear(hidden_states_half, att.self.value.weight, att.self.value.bias)
+        ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
+                               precision="half")
+        ln = att.output.LayerNorm
+        h, h16 = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, hidden_states, ln.weight,
+                                        ln.bias, eps, p, self.training, precision="half", return_half=True)
+        t = bias_gelu(F.linear(h16, self.intermediate.dense.weight), self.intermediate.dense.bias, precision="half")
+        ln = self.output.LayerNorm
+        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
+                                      self.training, precision="half", return_half=return_half)
+
+    def forward(self, hidden_states, lens, hidden_states_half=None, return_half=False):
+        if self.precision == "half":
+            return self._forward_half(hidden_states, lens, hidden_states_half, return_half)
+        if hidden_states_half is not None or return_half:
+            raise _lib.AnceLibraryError("BertLayer: hidden_states_half and return_half need precision=\"half\"")
         F = torch.nn.functional
         att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
         q = F.linear(hidden_states, att.self.query.weight, att.self.query.bias)

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_* only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_* only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -513,6 +513,74 @@ int ance_layer_tail_forward(const AnceLayerTailArgs *args, void *stream);
 int ance_layer_tail_backward(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads, void *stream);
 int ance_bias_gelu_forward(const AnceBiasGeluArgs *args, void *stream);
 int ance_bias_gelu_backward(const AnceBiasGeluArgs *args, const AnceBiasGeluGradArgs *grads, void *stream);
+
+/* The same seams with 16-bit matmul-side I/O and an fp32 residual stream (csrc/layer_tail_half.hip): the recipe's --fp16, i.e.
+ * torch.autocast plus a GradScaler.  T = fp16 (dtype ANCE_DTYPE_F16) or bf16 (ANCE_DTYPE_BF16); "rounded" = once, to nearest even,
+ * overflow to +-inf (never clamped: under a GradScaler an overflowing dx must reach found_inf as a non-finite gradient).
+ * Layer tail: x [n_rows, H] is T (the dense output without its bias); res, y, bias, gamma, beta stay fp32.  u = float(x[r]) + bias;
+ *   everything behind the load is the fp32 tail's arithmetic in fp32 -- the same dropout stream (the same (seed, offset, row, col)
+ *   keeps the same element in both precisions), z = d + res, the two-pass LayerNorm, mean / rstd in the workspace.  y is fp32; y16
+ *   (nullable) is the same registers rounded to T, for the Linears that read y: y16 == (T)y bit for bit.
+ *   backward: dy (fp32) and dy16 (T) are each nullable, at least one is given; g = dy + float(dy16) in fp32 registers (the sum
+ *   autograd would otherwise make of the residual's and the Linears' gradients).  dx is T, rounded; dres, dgamma, dbeta, dbias are
+ *   fp32 and every output is nullable.  xhat is recomputed from x, bias, res, the regenerated mask and the saved statistics.
+ *   On an x that holds T values, y, dres, dgamma, dbeta, dbias are the fp32 tail's on float(x), and dx is that dx rounded.
+ * Bias + GELU: x, y, dy, dx [n_rows, N] are T, bias and dbias fp32.  u = float(x[r]) + bias; the erf form and its derivative in fp32
+ *   as above; y and dx rounded; dbias = sum_r of the unrounded dx.  Nothing but x is saved.
+ * Layout: a T matrix has a 16-byte aligned base and a row stride in elements that is a multiple of 8 and at least the width; the
+ * fp32 matrices and vectors are as above.  Lane l of the row's wave holds columns 4 (64 i + l) .. + 3 as in the fp32 kernels: one
+ * 8-byte access of a T row next to one 16-byte access of an fp32 row, one Philox call per four columns.
+ * Workspaces, partial rows, the column-sum tree (so a parameter gradient over the same fp32 terms has the fp32 kernels' summation
+ * order), launch counts (one forward, two backward), no atomics, nothing synchronises, capturable: as above;
+ * ance_layer_tail16_workspace_bytes / ance_bias_gelu16_workspace_bytes equal the fp32 queries.
+ * Refuses what the fp32 calls refuse, a dtype that is neither, a T stride that is not a multiple of 8, and dy == dy16 == NULL. */
+typedef struct AnceLayerTail16Args {
+    const void *x;                /* T [n_rows, ld_x]                                             */
+    const float *res;
+    const float *bias;            /* [H] or NULL                                                  */
+    const float *gamma, *beta;    /* [H]                                                          */
+    float *y;
+    void *y16;                    /* T [n_rows, ld_y16] or NULL                                   */
+    int32_t ld_x, ld_res, ld_y, ld_y16;
+    int32_t H, n_rows;
+    int32_t dtype;                /* ANCE_DTYPE_F16 or ANCE_DTYPE_BF16                            */
+    float eps;
+    float dropout_p;
+    int32_t training;
+    uint64_t seed, offset;
+    void *d_workspace;
+    size_t workspace_bytes;
+} AnceLayerTail16Args;
+typedef struct AnceLayerTail16GradArgs {
+    const float *dy;              /* fp32 or NULL                                                 */
+    const void *dy16;             /* T or NULL; not both NULL                                     */
+    void *dx;                     /* T, nullable                                                  */
+    float *dres;                  /* nullable                                                     */
+    float *dgamma, *dbeta, *dbias; /* [H], each nullable                                          */
+    int32_t ld_dy, ld_dy16, ld_dx, ld_dres;
+} AnceLayerTail16GradArgs;
+typedef struct AnceBiasGelu16Args {
+    const void *x;                /* T                                                            */
+    const float *bias;
+    void *y;                      /* T                                                            */
+    int32_t ld_x, ld_y, N, n_rows;
+    int32_t dtype;                /* ANCE_DTYPE_F16 or ANCE_DTYPE_BF16                            */
+    int32_t reserved;             /* 0 */
+    void *d_workspace;
+    size_t workspace_bytes;
+} AnceBiasGelu16Args;
+typedef struct AnceBiasGelu16GradArgs {
+    const void *dy;               /* T                                                            */
+    void *dx;                     /* T, nullable                                                  */
+    float *dbias;                 /* nullable                                                     */
+    int32_t ld_dy, ld_dx;
+} AnceBiasGelu16GradArgs;
+size_t ance_layer_tail16_workspace_bytes(int64_t n_rows, int H);
+size_t ance_bias_gelu16_workspace_bytes(int64_t n_rows, int N);
+int ance_layer_tail16_forward(const AnceLayerTail16Args *args, void *stream);
+int ance_layer_tail16_backward(const AnceLayerTail16Args *args, const AnceLayerTail16GradArgs *grads, void *stream);
+int ance_bias_gelu16_forward(const AnceBiasGelu16Args *args, void *stream);
+int ance_bias_gelu16_backward(const AnceBiasGelu16Args *args, const AnceBiasGelu16GradArgs *grads, void *stream);
 
 /* The input end of a trainable tower with its gradients (csrc/embed_train.hip), fp32 throughout: what transformers' eager
  * BertEmbeddings / RobertaEmbeddings compute, ids -> word + token_type + position -> LayerNorm -> dropout.  T = n_seq * L token rows,
