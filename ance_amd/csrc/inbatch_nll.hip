@@ -5,7 +5,8 @@
 // Forward, three launches: scores (fp32 FMA GEMM) -> one workgroup per row (max / argmax, log-sum-exp, the row's loss) -> one
 // workgroup that sums the rows.  Backward, three launches: gS -> gq -> gctx.  The sizes are tiny (at most 1024 x 2048 x 1024: 2.1
 // GFMA per product), so the three products share one plain LDS-tiled fp32 kernel: 64 x 64 outputs per workgroup, 4 x 4 per thread,
-// every output an fmaf chain over 16-deep k tiles in ascending k, the tiles' sums added in ascending order.  No atomics, no
+// every output an fmaf chain over 16-deep k tiles in ascending k, the tiles' sums added in fp64 in ascending order and rounded
+// once (a softmax over scores in the hundreds sees what 64 fp32 additions at that magnitude lose).  No atomics, no
 // split-k: the same inputs give the same bits.  HBM traffic: forward reads (nq + nc) d 4 bytes and writes nq nc 4 (the scores stay
 // in the caller's workspace for the backward); backward reads the scores and writes gS once (8 nq nc bytes), reads gS twice and
 // q, ctx once each, writes (nq + nc) d 4.  grad_output is a device scalar: nothing waits for the host.
@@ -24,7 +25,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) gemm_f32_kernel(const float *A, 
     __shared__ float As[TK][TM + 1], Bs[TK][TN + 1];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int m0 = blockIdx.y * TM, n0 = blockIdx.x * TN;
-    float acc[4][4] = {};
+    double acc[4][4] = {};  // the tiles' sums: scores of LayerNorm rows reach 900, where 64 fp32 additions cost 1e-4 -- a softmax sees that
     for (int k0 = 0; k0 < K; k0 += TK) {
 #pragma unroll
         for (int t = 0; t < TM * TK / GEMM_THREADS; ++t) {
@@ -55,7 +56,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) gemm_f32_kernel(const float *A, 
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] += part[i][j];
+            for (int j = 0; j < 4; ++j) acc[i][j] += (double)part[i][j];
         __syncthreads();
     }
 #pragma unroll
@@ -65,7 +66,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) gemm_f32_kernel(const float *A, 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int gn = n0 + tx * 4 + j;
-            if (gn < N) C[(int64_t)gm * N + gn] = acc[i][j];
+            if (gn < N) C[(int64_t)gm * N + gn] = (float)acc[i][j];
         }
     }
 }
@@ -77,8 +78,11 @@ void launch_gemm(const float *A, const float *B, float *C, int M, int N, int K, 
 }
 
 // one workgroup per row: (max, lowest argmax) and sum of exp in a fixed order (thread-strided, xor-shuffle tree, the four waves in order)
-__global__ void __launch_bounds__(256) inbatch_rows_kernel(const float *S, const int64_t *pos, int nc, float *lse, float *loss_rows,
-                                                           int32_t *flags) {
+// The log-sum-exp is kept as its two terms, the row's max and log(sum exp(s - max)): at scores in the hundreds (LayerNorm outputs of
+// 768 / 1024 columns) their sum is only known to ulp(|s|), 6e-5 at 900, and exp(s - (max + log sum)) would carry that as a RELATIVE
+// error into every gradient; (s - max) is exact for the leading scores and the small term is subtracted from it at full precision.
+__global__ void __launch_bounds__(256) inbatch_rows_kernel(const float *S, const int64_t *pos, int nc, float *row_max, float *log_sum,
+                                                           float *loss_rows, int32_t *flags) {
     __shared__ float s_v[4];
     __shared__ int s_i[4];
     const int i = blockIdx.x, tid = threadIdx.x;
@@ -110,11 +114,12 @@ __global__ void __launch_bounds__(256) inbatch_rows_kernel(const float *S, const
     if ((tid & 63) == 0) s_v[tid >> 6] = sum;
     __syncthreads();
     if (tid == 0) {
-        const float l = mx + logf(((s_v[0] + s_v[1]) + s_v[2]) + s_v[3]);
+        const float l = logf(((s_v[0] + s_v[1]) + s_v[2]) + s_v[3]);
         const int64_t p = pos[i];
         const bool ok = p >= 0 && p < (int64_t)nc;
-        lse[i] = l;
-        loss_rows[i] = ok ? l - row[p] : __builtin_nanf("");
+        row_max[i] = mx;
+        log_sum[i] = l;
+        loss_rows[i] = ok ? (mx - row[p]) + l : __builtin_nanf("");
         flags[i] = ok ? (arg == (int)p ? 1 : 0) : 2;  // bit 0: correct, bit 1: index out of range
     }
 }
@@ -145,21 +150,21 @@ __global__ void __launch_bounds__(1024) inbatch_reduce_kernel(const float *loss_
     }
 }
 
-__global__ void __launch_bounds__(256) inbatch_gs_kernel(const float *S, const float *lse, const int64_t *pos, int nq, int nc,
-                                                         const float *grad_output, float *gS) {
+__global__ void __launch_bounds__(256) inbatch_gs_kernel(const float *S, const float *row_max, const float *log_sum, const int64_t *pos,
+                                                         int nq, int nc, const float *grad_output, float *gS) {
     const int i = blockIdx.x;
-    const float s = grad_output[0] / (float)nq, l = lse[i];
+    const float s = grad_output[0] / (float)nq, mx = row_max[i], l = log_sum[i];
     const int64_t p = pos[i];
     const bool ok = p >= 0 && p < (int64_t)nc;
     for (int j = threadIdx.x; j < nc; j += 256) {
         const int64_t o = (int64_t)i * nc + j;
-        const float sm = expf(S[o] - l);
+        const float sm = expf((S[o] - mx) - l);
         gS[o] = ok ? (sm - ((int64_t)j == p ? 1.0f : 0.0f)) * s : __builtin_nanf("");
     }
 }
 
 struct Layout {
-    size_t off_gs, off_lse, off_rows, off_flags, total;
+    size_t off_gs, off_max, off_lse, off_rows, off_flags, total;
 };
 bool in_envelope(int64_t nq, int64_t nc, int d) {
     return nq >= 1 && nq <= 1024 && nc >= nq && nc <= 2048 && d >= 128 && d <= 1024 && d % 4 == 0;
@@ -168,7 +173,8 @@ Layout layout(int64_t nq, int64_t nc) {
     Layout L;
     const size_t mat = align_up(sizeof(float) * (size_t)nq * (size_t)nc, 256), vec = align_up(sizeof(float) * (size_t)nq, 256);
     L.off_gs = mat;
-    L.off_lse = 2 * mat;
+    L.off_max = 2 * mat;
+    L.off_lse = L.off_max + vec;
     L.off_rows = L.off_lse + vec;
     L.off_flags = L.off_rows + vec;
     L.total = L.off_flags + vec;
@@ -204,11 +210,12 @@ extern "C" int ance_inbatch_nll_forward(const float *d_q, const float *d_ctx, co
     if (const char *why = check_common(d_q, d_ctx, d_positive_idx, nq, nc, d, d_workspace, workspace_bytes)) return refuse(fn, why);
     const Layout L = layout(nq, nc);
     char *ws = (char *)d_workspace;
-    float *S = (float *)ws, *lse = (float *)(ws + L.off_lse), *rows = (float *)(ws + L.off_rows);
+    float *S = (float *)ws, *row_max = (float *)(ws + L.off_max), *log_sum = (float *)(ws + L.off_lse), *rows = (float *)(ws + L.off_rows);
     int32_t *flags = (int32_t *)(ws + L.off_flags);
     hipStream_t st = (hipStream_t)stream;
     launch_gemm<true, true>(d_q, d_ctx, S, (int)nq, (int)nc, d, st);
-    hipLaunchKernelGGL(inbatch_rows_kernel, dim3((unsigned)nq), dim3(256), 0, st, (const float *)S, d_positive_idx, (int)nc, lse, rows, flags);
+    hipLaunchKernelGGL(inbatch_rows_kernel, dim3((unsigned)nq), dim3(256), 0, st, (const float *)S, d_positive_idx, (int)nc, row_max, log_sum,
+                       rows, flags);
     hipLaunchKernelGGL(inbatch_reduce_kernel, dim3(1), dim3(1024), 0, st, (const float *)rows, (const int32_t *)flags, (int)nq, d_loss_mean,
                        d_counts);
     return check_launch(fn);
@@ -223,10 +230,11 @@ extern "C" int ance_inbatch_nll_backward(const float *d_q, const float *d_ctx, c
     if (const char *why = check_common(d_q, d_ctx, d_positive_idx, nq, nc, d, d_workspace, workspace_bytes)) return refuse(fn, why);
     const Layout L = layout(nq, nc);
     char *ws = (char *)d_workspace;
-    const float *S = (const float *)ws, *lse = (const float *)(ws + L.off_lse);
+    const float *S = (const float *)ws, *row_max = (const float *)(ws + L.off_max), *log_sum = (const float *)(ws + L.off_lse);
     float *gS = (float *)(ws + L.off_gs);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(inbatch_gs_kernel, dim3((unsigned)nq), dim3(256), 0, st, S, lse, d_positive_idx, (int)nq, (int)nc, d_grad_output, gS);
+    hipLaunchKernelGGL(inbatch_gs_kernel, dim3((unsigned)nq), dim3(256), 0, st, S, row_max, log_sum, d_positive_idx, (int)nq, (int)nc,
+                       d_grad_output, gS);
     launch_gemm<true, false>((const float *)gS, d_ctx, d_gq, (int)nq, d, (int)nc, st);    // gq [nq, d] = gS [nq][nc] . ctx [nc][d]
     launch_gemm<false, false>((const float *)gS, d_q, d_gctx, (int)nc, d, (int)nq, st);   // gctx [nc, d] = gS^T ([nq][nc]) . q [nq][d]
     return check_launch(fn);

@@ -360,6 +360,22 @@ def bias_gelu(x, bias, precision="fp32"):
     return _BiasGelu.apply(x, bias)
 
 
+class _ZeroGradient(torch.autograd.Function):
+    """attention.self.key.bias as the key Linear reads it: the same values, and a gradient of exact zeros.  A bias on the keys adds
+    q_i . b to every score of query row i, a constant along the row that softmax does not see -- with the pad mask and with dropout
+    on the probabilities alike -- so the gradient IS zero; the column sum of dk that autograd would hand back is its rounding
+    noise (measured 1e-7 against query.bias's 0.2, several times the eager expression's own noise: the core takes the row term of
+    the softmax backward from ctx), and LAMB / Adam turn noise into steps of lr."""
+
+    @staticmethod
+    def forward(ctx, bias):
+        return bias.view_as(bias)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return torch.zeros_like(grad)
+
+
 class _Namespace(torch.nn.Module):
     """A module that only holds submodules: the names of transformers' BertLayer, so that its state dict loads as it is."""
 
@@ -378,6 +394,8 @@ class BertLayer(torch.nn.Module):
     first tail returns (h, h16) and intermediate.dense reads h16, the GELU runs 16 bits to 16 bits, and the second tail returns the
     fp32 output, or with ``return_half=True`` (out, out16) for the next layer's ``hidden_states_half``: a stack of layers then runs
     with no activation cast after the first.  The parameters and their gradients stay fp32.
+    attention.self.key.bias gets a gradient of exact zeros (it has none: softmax does not see a constant added to a row of
+    scores), not the rounding noise of the column sum of dk.
     Pad rows are computed like any other in the three row-wise seams, as the reference does; the attention core writes zeros there
     (INTEGRATION.md 3i), so a pad row of the output is the LayerNorm tail of zeros, not the reference's value, and never reaches a
     loss."""
@@ -422,7 +440,7 @@ class BertLayer(torch.nn.Module):
             raise _lib.AnceLibraryError("hidden_states_half must be the fp16 / bf16 copy of hidden_states, got %s %r"
                                         % (hidden_states_half.dtype, tuple(hidden_states_half.shape)))
         q = F.linear(hidden_states_half, att.self.query.weight, att.self.query.bias)
-        k = F.linear(hidden_states_half, att.self.key.weight, att.self.key.bias)
+        k = F.linear(hidden_states_half, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
         v = F.linear(hidden_states_half, att.self.value.weight, att.self.value.bias)
         ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
                                precision="half")
@@ -442,7 +460,7 @@ class BertLayer(torch.nn.Module):
         F = torch.nn.functional
         att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
         q = F.linear(hidden_states, att.self.query.weight, att.self.query.bias)
-        k = F.linear(hidden_states, att.self.key.weight, att.self.key.bias)
+        k = F.linear(hidden_states, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
         v = F.linear(hidden_states, att.self.value.weight, att.self.value.bias)
         ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
                                precision=self.attention_precision)

@@ -320,12 +320,13 @@ int ance_nll_backward(const float *d_q, const float *d_a, const float *d_b, cons
                       int d, int chunks, const float *d_grad_output, float *d_gq, float *d_ga, float *d_gb, void *stream);
 
 /* The DPR trainer's in-batch-negatives objective (csrc/inbatch_nll.hip; drivers/run_ann_dpr.py:356-365 and its evaluate_dev):
- *   scores = q ctx^T [nq, nc] (fp32 FMA, fixed order);  *d_loss_mean = mean_i -log_softmax(scores[i])[positive_idx[i]];
+ *   scores = q ctx^T [nq, nc] (fp32 FMA over 16-deep k tiles, the tiles summed in fp64, fixed order);  *d_loss_mean = mean_i -log_softmax(scores[i])[positive_idx[i]];
  *   d_counts[0] = #{i : argmax_j scores[i][j] == positive_idx[i]} (the lowest j among equal scores);
  *   d_counts[1] = #{i : positive_idx[i] outside [0, nc)}: such an index is never used as an address, the row's loss and the mean
  *   are NaN, the row never counts as correct, and the backward makes that row's part of the gradients NaN.
  * d_q [nq, d], d_ctx [nc, d] fp32; d_positive_idx int64 [nq] on the device; d_counts int64 [2].
- * The scores, the rows' log-sum-exp and gS live in d_workspace (16-byte aligned, ance_inbatch_nll_workspace_bytes; 0: shape not
+ * The scores, the rows' log-sum-exp (as its two terms, the row's max and log sum exp(s - max): exp((s - max) - log sum) keeps its
+ * precision at scores in the hundreds, where exp(s - lse) would be ulp(|s|) off, relatively) and gS live in d_workspace (16-byte aligned, ance_inbatch_nll_workspace_bytes; 0: shape not
  * supported); the backward reads what the forward of the SAME arguments left there and may be repeated.
  * Backward: gS = (softmax(scores) - onehot) *d_grad_output / nq (d_grad_output a DEVICE fp32 scalar); d_gq [nq, d] = gS ctx;
  * d_gctx [nc, d] = gS^T q.  Three launches each way, no atomics: the same inputs give the same bits.

@@ -7,6 +7,7 @@
   embed_eager_fp32   the eager torch fp32 expression on the CPU with the same mask -- F.embedding x 3, (word + type) + position,
                      F.layer_norm, the mask multiply -- and its autograd gradients: the reference whose own distance from fp64
                      sets the tests' bound (attention_train_util.bound)
+  embed_torch_forward   its forward on torch tensors, in the graph: what tests/train_step_util.py chains into a tower
   keep mask          layer_tail_util.tail_keep_mask: the embeddings draw under the layer tail's counter contract
   embed_inputs       seeded tables, LayerNorm parameters and dy
 Ids are taken as the kernels take them: clamped into their table first.
@@ -82,27 +83,35 @@ def embed_fp64(ids, types, word, pos, typ, gamma, beta, eps, dy, mode="absolute"
                 dtype=_scatter(ttc, dv, typ.shape[0]), dgamma=(d * xhat).sum(0), dbeta=d.sum(0), positions=pp)
 
 
+def embed_torch_forward(ids, types, tw, tp, tt, tg, tb, eps, mode="absolute", pad=None, keep=None, p=0.0):
+    """embed_eager_fp32's forward on torch tensors, for chaining: ids, types NumPy [B, L] (types None: zeros), the five parameters
+    tensors, keep a tensor of their dtype shaped like y, or None.  Returns y [B, L, H] in the graph."""
+    import torch
+    F = torch.nn.functional
+    idc = torch.from_numpy(clamp_ids(ids, tw.shape[0])).to(tw.device)
+    ttc = torch.from_numpy(clamp_ids(types, tt.shape[0])).to(tw.device) if types is not None else torch.zeros_like(idc)
+    pc = torch.from_numpy(positions(ids, mode, pad, tw.shape[0], tp.shape[0])).to(tw.device)
+    pad_w = pad if pad is not None and pad >= 0 else None
+    e = F.embedding(idc, tw, padding_idx=pad_w) + F.embedding(ttc, tt)
+    e = e + F.embedding(pc, tp, padding_idx=pad_w if mode == "roberta" else None)
+    y = F.layer_norm(e, (tw.shape[1],), tg, tb, eps)
+    if keep is not None:
+        y = y * keep.reshape(tuple(y.shape)) * _scale(p)
+    return y
+
+
 def embed_eager_fp32(ids, types, word, pos, typ, gamma, beta, eps, dy, mode="absolute", pad=None, keep=None, p=0.0, dtype="float32",
                      backward=True):
     """transformers' eager BertEmbeddings / RobertaEmbeddings expression in torch on the CPU (dtype float64: a check of embed_fp64's
     hand-written backward), the dropout given as a mask.  Same dict as embed_fp64 (y only with backward=False)."""
     import torch
-    F = torch.nn.functional
     dt = getattr(torch, dtype)
     tw, tp, tt, tg, tb = (torch.from_numpy(np.array(t)).to(dt).requires_grad_(backward) for t in (word, pos, typ, gamma, beta))
-    idc = torch.from_numpy(clamp_ids(ids, word.shape[0]))
-    ttc = torch.from_numpy(clamp_ids(types, typ.shape[0])) if types is not None else torch.zeros_like(idc)
-    pc = torch.from_numpy(positions(ids, mode, pad, word.shape[0], pos.shape[0]))
-    pad_w = pad if pad is not None and pad >= 0 else None
-    e = F.embedding(idc, tw, padding_idx=pad_w) + F.embedding(ttc, tt)
-    e = e + F.embedding(pc, tp, padding_idx=pad_w if mode == "roberta" else None)
-    y = F.layer_norm(e, (word.shape[1],), tg, tb, eps)
-    if keep is not None:
-        y = y * torch.from_numpy(keep.reshape(tuple(y.shape))).to(dt) * _scale(p)
+    y = embed_torch_forward(ids, types, tw, tp, tt, tg, tb, eps, mode, pad, None if keep is None else torch.from_numpy(keep).to(dt), p)
     if not backward:
         return dict(y=y.numpy().reshape(-1, word.shape[1]))
     y.backward(torch.from_numpy(np.array(dy)).to(dt).reshape(y.shape))
-    rows = np.unique(idc.numpy())
+    rows = np.unique(clamp_ids(ids, word.shape[0]))
     return dict(y=y.detach().numpy().reshape(-1, word.shape[1]), word_rows=rows, dword=tw.grad.numpy()[rows], dpos=tp.grad.numpy(),
                 dtype=tt.grad.numpy(), dgamma=tg.grad.numpy(), dbeta=tb.grad.numpy())
 

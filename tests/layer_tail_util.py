@@ -6,6 +6,7 @@
                                reference whose own distance from fp64 sets the tests' bound (attention_train_util.bound)
   layer_fp64 / layer_torch     a whole BertLayer as ance_amd.layers.BertLayer composes it (pad rows of the attention's context are
                                zeros), in fp64 NumPy from attention_train_util.attention_fp64 and the two above, and in torch on the CPU
+  layer_torch_forward          layer_torch's forward on torch tensors, in the graph: what tests/train_step_util.py chains into a tower
 """
 import math
 
@@ -182,17 +183,21 @@ def layer_fp64(hs, lens, sd, n_heads, eps, dout, keeps=None, p_attn=0.0, p_hidde
     return dict(g, out=b2["y"].reshape(B, L, H), dhs=dhs.reshape(B, L, H))
 
 
-def layer_torch(hs, lens, sd, n_heads, eps, dout, keeps=None, p_attn=0.0, p_hidden=0.0, dtype="float32"):
-    """The same layer as transformers' eager expressions in torch on the CPU (fp32: the reference of the bound; float64: a check of
-    layer_fp64's hand-written backward), gradients by autograd.  Same dict as layer_fp64."""
+def layer_torch_forward(ths, rows, W, n_heads, eps, keeps=None, p_attn=0.0, p_hidden=0.0, taps=None):
+    """layer_torch's forward on torch tensors, for chaining: ths [B, L, H], rows bool [B, L], W {parameter name: tensor}, keeps three
+    tensors of ths's dtype or None.  Returns out [B, L, H] in the graph.  taps: a list that receives (name, tensor) for the
+    activations ance_amd.layers.BertLayer(precision="half") holds in 16 bits, each with its gradient retained."""
     import torch
     F = torch.nn.functional
-    dt = getattr(torch, dtype)
-    B, L, H = hs.shape
-    rows = torch.from_numpy(A._valid(lens, L))
-    W = {k: torch.from_numpy(np.array(v)).to(dt).requires_grad_(True) for k, v in sd.items()}
-    ths = torch.from_numpy(np.array(hs)).to(dt).requires_grad_(True)
-    ka, k1, k2 = (None if m is None else torch.from_numpy(m).to(dt) for m in (keeps if keeps is not None else (None, None, None)))
+    dt = ths.dtype
+    B, L, H = ths.shape
+    ka, k1, k2 = keeps if keeps is not None else (None, None, None)
+
+    def tap(name, t):
+        if taps is not None:
+            t.retain_grad()
+            taps.append((name, t))
+        return t
 
     def heads(x):
         return x.view(B, L, n_heads, 64).permute(0, 2, 1, 3)
@@ -203,15 +208,30 @@ def layer_torch(hs, lens, sd, n_heads, eps, dout, keeps=None, p_attn=0.0, p_hidd
             u = u * keep.view(B, L, H) * _scale(p_hidden)
         return F.layer_norm(u + res, (H,), W[ln + ".weight"], W[ln + ".bias"], eps)
 
-    q, k, v = (F.linear(ths, W["attention.self.%s.weight" % n], W["attention.self.%s.bias" % n]) for n in ("query", "key", "value"))
+    q, k, v = (tap(n, F.linear(ths, W["attention.self.%s.weight" % n], W["attention.self.%s.bias" % n])) for n in ("query", "key", "value"))
     mask = ((1.0 - rows.to(dt)) * -10000.0)[:, None, None, :]
     probs = torch.softmax(torch.matmul(heads(q), heads(k).transpose(-1, -2)) / math.sqrt(64) + mask, dim=-1)
     if ka is not None:
         probs = probs * ka * _scale(p_attn)
     ctx = torch.matmul(probs, heads(v)).permute(0, 2, 1, 3).contiguous().view(B, L, H) * rows[:, :, None].to(dt)  # pad rows: zeros
-    h = tail(F.linear(ctx, W["attention.output.dense.weight"]), "attention.output.dense", "attention.output.LayerNorm", ths, k1)
-    t = torch_gelu(F.linear(h, W["intermediate.dense.weight"]) + W["intermediate.dense.bias"])
-    out = tail(F.linear(t, W["output.dense.weight"]), "output.dense", "output.LayerNorm", h, k2)
+    ctx = tap("ctx", ctx)
+    h = tail(tap("attention.output.dense", F.linear(ctx, W["attention.output.dense.weight"])), "attention.output.dense",
+             "attention.output.LayerNorm", ths, k1)
+    t = tap("gelu", torch_gelu(tap("intermediate.dense", F.linear(h, W["intermediate.dense.weight"])) + W["intermediate.dense.bias"]))
+    return tail(tap("output.dense", F.linear(t, W["output.dense.weight"])), "output.dense", "output.LayerNorm", h, k2)
+
+
+def layer_torch(hs, lens, sd, n_heads, eps, dout, keeps=None, p_attn=0.0, p_hidden=0.0, dtype="float32"):
+    """The same layer as transformers' eager expressions in torch on the CPU (fp32: the reference of the bound; float64: a check of
+    layer_fp64's hand-written backward), gradients by autograd.  Same dict as layer_fp64."""
+    import torch
+    dt = getattr(torch, dtype)
+    B, L, H = hs.shape
+    rows = torch.from_numpy(A._valid(lens, L))
+    W = {k: torch.from_numpy(np.array(v)).to(dt).requires_grad_(True) for k, v in sd.items()}
+    ths = torch.from_numpy(np.array(hs)).to(dt).requires_grad_(True)
+    keeps = None if keeps is None else tuple(None if m is None else torch.from_numpy(m).to(dt) for m in keeps)
+    out = layer_torch_forward(ths, rows, W, n_heads, eps, keeps, p_attn, p_hidden)
     out.backward(torch.from_numpy(np.array(dout)).to(dt) * rows[:, :, None].to(dt))
     res = {k_: w.grad.numpy() for k_, w in W.items()}
     res.update(out=out.detach().numpy(), dhs=ths.grad.numpy())
