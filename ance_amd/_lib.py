@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("ANCE_AMD_LIB") or os.path.join(_HERE, "libance_amd.so
 CSRC = os.path.join(_HERE, "csrc")
 
 ANCE_OK = 0
+ANCE_E_INVALID = -1  # include/ance_amd.h: a refused argument
 ABI_VERSION = 7
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -329,6 +330,36 @@ SYMBOLS = {
     "ance_embed_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "ance_embed_forward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p]),
     "ance_embed_backward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p]),
+    # the dropout entry points with the device stream {seed, base} (a null stream is the plain call)
+    "ance_attention_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_attention_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.POINTER(AnceAttnGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_attention16_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_attention16_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.POINTER(AnceAttn16GradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_layer_tail_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_layer_tail_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.POINTER(AnceLayerTailGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_layer_tail16_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTail16Args), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_layer_tail16_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTail16Args), ctypes.POINTER(AnceLayerTail16GradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_embed_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_embed_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_dropout_stream_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    # the fused optimizers' resident plans (tables built once into caller-owned host memory; steps that only launch) and the schedule
+    "ance_lamb_plan_table_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "ance_lamb_plan_build": (ctypes.c_int, [ctypes.POINTER(AnceLambTensor), ctypes.c_int, ctypes.POINTER(AnceLambGroup), ctypes.c_void_p,
+                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(ctypes.c_size_t)]),
+    "ance_lamb_step_planned": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "ance_adamw_plan_table_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "ance_adamw_plan_build": (ctypes.c_int, [ctypes.POINTER(AnceAdamwTensor), ctypes.c_int, ctypes.POINTER(AnceLambGroup), ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.POINTER(ctypes.c_size_t)]),
+    "ance_adamw_step_planned": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.c_void_p]),
+    "ance_debug_staging_sends": (ctypes.c_longlong, []),
+    "ance_linear_warmup_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_void_p]),
     "ance_pair_layout": (None, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_float)]),
 }

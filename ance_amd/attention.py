@@ -11,8 +11,13 @@ a sequence of length 0 is skipped.
 
 Dropout: Philox4x32-10 under (seed, offset), stated in include/ance_amd.h.  ``seed`` is ``manual_seed(n)``'s (default:
 ``torch.initial_seed()``, read on the host when first needed); ``offset`` is a per-device call counter that every dropout forward
-advances by one.  The backward gets the forward's pair through the autograd context.  Both are HOST values baked into the launch:
-a captured graph replays the pair it was captured with -- the same mask at every replay.  The masks are not torch's.
+advances by one.  The backward gets the forward's pair through the autograd context.  By default both are HOST values baked into
+the launch: a captured graph replays the pair it was captured with -- the same mask at every replay.  The masks are not torch's.
+
+``dropout_state.to_device()`` opts a device into the device-resident stream: its counter moves into a device tensor {seed, base}
+that every dropout kernel reads at its entry, a call draws under ``base + r`` (r: calls since the last ``advance``), and
+``dropout_state.advance()`` -- once per step, after the backward, inside a captured region -- adds the step's calls to the base.
+Eager code draws the same masks as in host mode; a replayed graph draws the masks of the step it stands for.
 """
 import ctypes
 
@@ -34,31 +39,138 @@ except ImportError:  # pragma: no cover
 __all__ = ["attention_padded", "attention_packed", "lens_from_mask", "manual_seed", "dropout_state"]
 
 
+class _Draw(object):
+    """What one dropout forward draws under and its backward keeps: the host pair ``(seed, offset)``, or -- in device mode --
+    ``stream`` (the device tensor {seed, base}), ``offset`` = the call's index r within the step and the epoch of the stream."""
+    __slots__ = ("state", "dev", "seed", "offset", "stream", "epoch")
+
+    def __init__(self, state, dev, seed, offset, stream, epoch):
+        self.state, self.dev, self.seed, self.offset, self.stream, self.epoch = state, dev, seed, offset, stream, epoch
+
+    def launch(self, name, *structs):
+        """The entry point ``name`` on the current stream, or its ``_dstream`` sibling in device mode.  A backward whose base has
+        moved since its forward (``advance``, ``manual_seed``, ``to_host``) would regenerate another mask: it is refused."""
+        L = _lib.lib()
+        if self.stream is None:
+            _lib.check(getattr(L, name)(*structs, _lib.current_stream_ptr()), name)
+            return
+        if self.state.epochs.get(self.dev) != self.epoch:
+            raise _lib.AnceLibraryError("%s: the device dropout stream has moved since this call's forward (dropout_state.advance, "
+                                        "manual_seed or to_host ran in between): the backward would regenerate another mask; call "
+                                        "advance() once per step, after the backward" % name)
+        name += "_dstream"
+        _lib.check(getattr(L, name)(*structs, ctypes.c_void_p(self.stream.data_ptr()), _lib.current_stream_ptr()), name)
+
+
+def _as_int64(n):
+    return n - (1 << 64) if n >= 1 << 63 else n
+
+
 class _DropoutState:
-    """The seed and the per-device call counters of the dropout stream (host values)."""
+    """The seed and the per-device call counters of the dropout stream.  Host values by default.  After ``to_device`` a device's
+    counter lives in a 2-element int64 device tensor {seed, base}, which every dropout kernel reads at its entry: the effective
+    offset of a call is ``base + r``, r counting the calls since the last ``advance``, so an eager program draws the same masks in
+    both modes whether or not it calls ``advance``, and a captured step that ends with ``advance`` draws the masks of the step it
+    stands for at every replay."""
 
     def __init__(self):
         self.seed = None
-        self.offsets = {}
+        self.offsets = {}   # host mode: calls so far; device mode: r, the calls since the last advance
+        self.streams = {}   # device index -> the device tensor {seed, base} while that device is in device mode
+        self.epochs = {}    # device index -> how often its base has moved under the autograd contexts (advance, manual_seed, to_host)
+        self._tensors = {}  # every tensor ever handed out, kept so that a captured graph's pointer stays valid and is reused
 
-    def manual_seed(self, n):
-        self.seed = int(n) & 0xFFFFFFFFFFFFFFFF
-        self.offsets = {}
-
-    def next_pair(self, device):
+    def _seed(self):
         if self.seed is None:
             self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        dev = device.index if device.index is not None else torch.cuda.current_device()
+        return self.seed
+
+    @staticmethod
+    def _index(device):
+        if device is None:
+            return torch.cuda.current_device()
+        if isinstance(device, int):
+            return device
+        device = torch.device(device)
+        return device.index if device.index is not None else torch.cuda.current_device()
+
+    def _write(self, dev, seed, base):
+        """{seed, base} into the device's tensor: a host-to-device copy, not capturable."""
+        t = self._tensors.get(dev)
+        if t is None:
+            t = self._tensors[dev] = torch.zeros(2, dtype=torch.int64, device=torch.device("cuda", dev))
+            if t.data_ptr() % 16:
+                raise _lib.AnceLibraryError("the device dropout stream must be 16-byte aligned")
+        t.copy_(torch.tensor([_as_int64(seed), _as_int64(base & 0xFFFFFFFFFFFFFFFF)], dtype=torch.int64))
+        return t
+
+    def manual_seed(self, n):
+        """Host mode: as before.  Device mode: rewrites every device tensor to {n, 0} -- a copy from the host, NOT capturable."""
+        self.seed = int(n) & 0xFFFFFFFFFFFFFFFF
+        self.offsets = {}
+        for dev in self.streams:
+            self._write(dev, self.seed, 0)
+            self.epochs[dev] = self.epochs.get(dev, 0) + 1
+
+    def to_device(self, device=None):
+        """Moves ``device``'s counter into its device tensor {seed, calls so far} and returns the tensor.  From then on
+        ``next_pair`` hands out ``(d_stream, r)``.  One small copy from the host: call it before capturing."""
+        dev = self._index(device)
+        if dev not in self.streams:
+            self.streams[dev] = self._write(dev, self._seed(), self.offsets.get(dev, 0))
+            self.offsets[dev] = 0
+            self.epochs[dev] = self.epochs.get(dev, 0) + 1
+        return self.streams[dev]
+
+    def to_host(self, device=None):
+        """``(seed, calls so far)`` of ``device``, read back for checkpointing, and the device is in host mode again (``to_device``
+        returns to the same tensor, so a captured graph stays valid).  ONE SYNCHRONISING READ: off the step path."""
+        dev = self._index(device)
+        if dev in self.streams:
+            seed, base = self.streams.pop(dev).tolist()
+            self.seed = seed & 0xFFFFFFFFFFFFFFFF
+            self.offsets[dev] = (base & 0xFFFFFFFFFFFFFFFF) + self.offsets.get(dev, 0)
+            self.epochs[dev] = self.epochs.get(dev, 0) + 1
+        return self._seed(), self.offsets.get(dev, 0)
+
+    def advance(self, device=None):
+        """Device mode: enqueues ``base += r`` (one one-thread kernel, capturable) and resets r; nothing when r is 0 or in host mode.
+        Once per step, AFTER the backward: a backward that runs behind it is refused (its masks would be another step's)."""
+        dev = self._index(device)
+        r = self.offsets.get(dev, 0)
+        if dev not in self.streams or r == 0:
+            return
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ance_dropout_stream_advance(ctypes.c_void_p(self.streams[dev].data_ptr()), r, _lib.current_stream_ptr()),
+                       "ance_dropout_stream_advance")
+        self.offsets[dev] = 0
+        self.epochs[dev] += 1
+
+    def next_pair(self, device):
+        """Host mode: ``(seed, offset)``; device mode: ``(d_stream, r)``.  Either way the device's call counter grows by one."""
+        seed = self._seed()
+        dev = self._index(device)
         off = self.offsets.get(dev, 0)
         self.offsets[dev] = off + 1
-        return self.seed, off
+        stream = self.streams.get(dev)
+        return (seed, off) if stream is None else (stream, off)
+
+    def draw(self, device):
+        """``next_pair`` as the autograd functions keep it (``_Draw``)."""
+        a, off = self.next_pair(device)
+        dev = self._index(device)
+        if isinstance(a, torch.Tensor):
+            return _Draw(self, dev, 0, off, a, self.epochs[dev])
+        return _Draw(self, dev, a, off, None, 0)
 
 
 dropout_state = _DropoutState()
+_NO_DRAW = _Draw(dropout_state, -1, 0, 0, None, 0)   # a call without dropout
 
 
 def manual_seed(n):
-    """Seeds the dropout stream and resets every device's call counter: the same calls after it give the same bits."""
+    """Seeds the dropout stream and resets every device's call counter: the same calls after it give the same bits.  In device mode
+    (``dropout_state.to_device``) it rewrites the device tensors with a copy from the host, so it cannot be captured."""
     dropout_state.manual_seed(n)
 
 
@@ -168,16 +280,16 @@ class _Attention(torch.autograd.Function):
             raise _lib.AnceLibraryError("attention: unsupported shape (rows %d, heads %d)" % (n_rows, n_heads))
         ws = torch.zeros(ws_bytes // 4, dtype=torch.float32, device=q.device)
         drop = bool(training) and dropout_p > 0.0
-        seed, offset = dropout_state.next_pair(q.device) if drop else (0, 0)
+        draw = dropout_state.draw(q.device) if drop else _NO_DRAW
         args = _lib.AnceAttnTrainArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
                                       ld_ctx=out.shape[-1], d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(),
                                       n_seq=first.numel(), max_seq_len=max_seq_len, n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows,
-                                      dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed, offset=offset,
+                                      dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed, offset=draw.offset,
                                       d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
         with torch.cuda.device(q.device):
-            _lib.check(L.ance_attention_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_attention_forward")
+            draw.launch("ance_attention_forward", ctypes.byref(args))
         ctx.save_for_backward(q, k, v, out, first, lens, ws)
-        ctx.args = args
+        ctx.args, ctx.draw = args, draw
         lse = ws[:n_heads * n_rows].view(n_heads, n_rows)
         ctx.mark_non_differentiable(lse)
         return out, lse
@@ -186,7 +298,6 @@ class _Attention(torch.autograd.Function):
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dctx, _dlse):
-        L = _lib.lib()
         q, k, v, out, first, lens, ws = ctx.saved_tensors
         a = ctx.args
         dctx, ld_d = _rows(dctx.to(torch.float32))
@@ -194,7 +305,7 @@ class _Attention(torch.autograd.Function):
         g = _lib.AnceAttnGradArgs(dctx=dctx.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
                                   ld_dq=dq.stride(-2), ld_dk=dk.stride(-2), ld_dv=dv.stride(-2))
         with torch.cuda.device(q.device):
-            _lib.check(L.ance_attention_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_attention_backward")
+            ctx.draw.launch("ance_attention_backward", ctypes.byref(a), ctypes.byref(g))
         return dq, dk, dv, None, None, None, None, None, None
 
 
@@ -215,16 +326,16 @@ class _AttentionHalf(torch.autograd.Function):
             raise _lib.AnceLibraryError("attention: unsupported shape (rows %d, heads %d)" % (n_rows, n_heads))
         ws = torch.zeros(ws_bytes // 4, dtype=torch.float32, device=q.device)
         drop = bool(training) and dropout_p > 0.0
-        seed, offset = dropout_state.next_pair(q.device) if drop else (0, 0)
+        draw = dropout_state.draw(q.device) if drop else _NO_DRAW
         args = _lib.AnceAttn16Args(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
                                    ld_ctx=out.shape[-1], d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(),
                                    n_seq=first.numel(), max_seq_len=max_seq_len, n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows,
-                                   dtype=HALF_DTYPES[q.dtype], dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed,
-                                   offset=offset, d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+                                   dtype=HALF_DTYPES[q.dtype], dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed,
+                                   offset=draw.offset, d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
         with torch.cuda.device(q.device):
-            _lib.check(L.ance_attention16_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_attention16_forward")
+            draw.launch("ance_attention16_forward", ctypes.byref(args))
         ctx.save_for_backward(q, k, v, out, first, lens, ws)
-        ctx.args = args
+        ctx.args, ctx.draw = args, draw
         lse = ws[:n_heads * n_rows].view(n_heads, n_rows)
         ctx.mark_non_differentiable(lse)
         return out, lse
@@ -233,7 +344,6 @@ class _AttentionHalf(torch.autograd.Function):
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dctx, _dlse):
-        L = _lib.lib()
         q, k, v, out, first, lens, ws = ctx.saved_tensors
         a = ctx.args
         dctx, ld_d = _rows16(dctx.to(q.dtype))
@@ -241,8 +351,7 @@ class _AttentionHalf(torch.autograd.Function):
         g = _lib.AnceAttn16GradArgs(dctx=dctx.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
                                     ld_dq=dq.stride(-2), ld_dk=dk.stride(-2), ld_dv=dv.stride(-2))
         with torch.cuda.device(q.device):
-            _lib.check(L.ance_attention16_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()),
-                       "ance_attention16_backward")
+            ctx.draw.launch("ance_attention16_backward", ctypes.byref(a), ctypes.byref(g))
         return dq, dk, dv, None, None, None, None, None, None
 
 

@@ -34,6 +34,7 @@ struct AdamwDevGroup {
     double lr, beta1, beta2, wd;        // the reference's Python doubles: the step size and the decay factor are formed from these
     float b1, omb1, b2, omb2, eps;      // rounded to fp32 as torch does for a scalar: the moment updates and the denominator
     int32_t has_wd;
+    const double *d_lr;                 // the learning rate as a device fp64 scalar (a resident plan's group with a tensor lr), or null: lr
 };
 struct AdamwScalars {  // per tensor, written by prep
     float neg_ss, decay;
@@ -65,11 +66,12 @@ __global__ void __launch_bounds__(1024) adamw_prep_kernel(const AdamwDevGroup *g
         if (T.numel == 0) continue;  // its step is neither read nor written
         const AdamwDevGroup G = groups[T.group];
         const float t1 = T.step[0] + 1.0f;  // exact up to 2^24 steps
-        double ss = G.lr;
+        const double lr = G.d_lr ? G.d_lr[0] : G.lr;  // the same fp64 value either way, so the same ss and decay
+        double ss = lr;
         if (correct_bias) ss = ss * sqrt(1.0 - pow(G.beta2, (double)t1)) / (1.0 - pow(G.beta1, (double)t1));
         AdamwScalars S;
         S.neg_ss = (float)(-ss);
-        S.decay = (float)(-G.lr * G.wd);
+        S.decay = (float)(-lr * G.wd);
         scalars[t] = S;
         T.step[0] = t1;
     }
@@ -103,8 +105,9 @@ size_t workspace_bytes_for(int n_tensors, int n_groups, int64_t n_chunks, bool c
     return b;
 }
 
-void adamw_group_row(void *row, const AnceLambGroup &a) {
+void adamw_group_row(void *row, const AnceLambGroup &a, const double *d_lr) {
     AdamwDevGroup &G = *(AdamwDevGroup *)row;
+    G.d_lr = d_lr;
     G.lr = a.lr;
     G.beta1 = a.beta1;
     G.beta2 = a.beta2;
@@ -126,6 +129,28 @@ void launch_update(bool unscale, int64_t n_chunks, hipStream_t st, const AdamwDe
     else
         hipLaunchKernelGGL((adamw_update_kernel<CLIP, false>), dim3((unsigned)n_chunks), dim3(THREADS), 0, st, dG, dT, dC, dS, dCoef,
                            (const float *)nullptr, found_inf);
+}
+
+// the launches of a step whose tables stand at the head of ws (layout L): two, or three with the clip
+int adamw_launch(const char *fn, int n_tensors, int64_t n_chunks, const mt::Staged &L, int correct_bias, bool clip, double max_grad_norm,
+                 const float *d_grad_scale, const float *d_found_inf, float *d_grad_norm, int64_t *d_skipped, char *ws, hipStream_t st) {
+    const AdamwDevGroup *dG = (const AdamwDevGroup *)ws;
+    const DevTensor *dT = (const DevTensor *)(ws + L.tensors);
+    const int32_t *dC = (const int32_t *)(ws + L.chunk_tensor);
+    AdamwScalars *dS = (AdamwScalars *)(ws + L.end);
+    if (clip) {
+        double *dGP = (double *)(ws + L.end + align16(sizeof(AdamwScalars) * (size_t)n_tensors));
+        float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
+        mt::launch_gnorm(n_chunks, st, dT, dC, dGP, d_grad_scale);
+        hipLaunchKernelGGL(adamw_prep_kernel<true>, dim3(1), dim3(1024), 0, st, dG, dT, n_tensors, correct_bias ? 1 : 0, dS,
+                           (const double *)dGP, (int)n_chunks, (float)max_grad_norm, d_grad_norm, dCoef, d_found_inf, d_skipped);
+        if (n_chunks > 0) launch_update<true>(d_grad_scale != nullptr, n_chunks, st, dG, dT, dC, dS, dCoef, d_grad_scale, d_found_inf);
+    } else {
+        hipLaunchKernelGGL(adamw_prep_kernel<false>, dim3(1), dim3(1024), 0, st, dG, dT, n_tensors, correct_bias ? 1 : 0, dS,
+                           (const double *)nullptr, 0, 0.0f, (float *)nullptr, (float *)nullptr, d_found_inf, d_skipped);
+        if (n_chunks > 0) launch_update<false>(d_grad_scale != nullptr, n_chunks, st, dG, dT, dC, dS, nullptr, d_grad_scale, d_found_inf);
+    }
+    return check_launch(fn);
 }
 
 }  // namespace
@@ -163,21 +188,51 @@ extern "C" int ance_adamw_step(const AnceAdamwTensor *h_tensors, int n_tensors, 
     char *ws = (char *)d_workspace;
     if (const int e = mt::stage_tables(fn, h_tensors, n_tensors, h_groups, n_groups, sizeof(AdamwDevGroup), adamw_group_row, L, ws, st))
         return e;
-    const AdamwDevGroup *dG = (const AdamwDevGroup *)ws;
-    const DevTensor *dT = (const DevTensor *)(ws + L.tensors);
-    const int32_t *dC = (const int32_t *)(ws + L.chunk_tensor);
-    AdamwScalars *dS = (AdamwScalars *)(ws + L.end);
-    if (clip) {
-        double *dGP = (double *)(ws + L.end + align16(sizeof(AdamwScalars) * (size_t)n_tensors));
-        float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
-        mt::launch_gnorm(n_chunks, st, dT, dC, dGP, d_grad_scale);
-        hipLaunchKernelGGL(adamw_prep_kernel<true>, dim3(1), dim3(1024), 0, st, dG, dT, n_tensors, correct_bias ? 1 : 0, dS,
-                           (const double *)dGP, (int)n_chunks, (float)max_grad_norm, d_grad_norm, dCoef, d_found_inf, d_skipped);
-        if (n_chunks > 0) launch_update<true>(d_grad_scale != nullptr, n_chunks, st, dG, dT, dC, dS, dCoef, d_grad_scale, d_found_inf);
-    } else {
-        hipLaunchKernelGGL(adamw_prep_kernel<false>, dim3(1), dim3(1024), 0, st, dG, dT, n_tensors, correct_bias ? 1 : 0, dS,
-                           (const double *)nullptr, 0, 0.0f, (float *)nullptr, (float *)nullptr, d_found_inf, d_skipped);
-        if (n_chunks > 0) launch_update<false>(d_grad_scale != nullptr, n_chunks, st, dG, dT, dC, dS, nullptr, d_grad_scale, d_found_inf);
-    }
-    return check_launch(fn);
+    return adamw_launch(fn, n_tensors, n_chunks, L, correct_bias, clip, max_grad_norm, d_grad_scale, d_found_inf, d_grad_norm, d_skipped,
+                        ws, st);
+}
+
+// ---- the resident plan (include/ance_amd.h; as lamb.hip's)
+extern "C" size_t ance_adamw_plan_table_bytes(int n_tensors, int n_groups, int64_t total_numel) {
+    using namespace ance;
+    if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
+    const int64_t chunks = mt::max_chunks(n_tensors, total_numel);
+    if (chunks > (int64_t)INT32_MAX) return 0;
+    return mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, chunks).end;
+}
+
+extern "C" int ance_adamw_plan_build(const AnceAdamwTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups,
+                                     const double *const *d_lrs, int n_groups, void *h_tables, size_t h_tables_bytes,
+                                     int64_t *n_chunks_out, size_t *table_bytes_out) {
+    using namespace ance;
+    const char *fn = "ance_adamw_plan_build";
+    if (n_tensors < 1) return mt::refuse(fn, "n_tensors < 1");
+    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
+    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
+    int64_t n_chunks = 0;
+    if (const int e = mt::count_chunks(fn, h_tensors, n_tensors, n_groups, &n_chunks)) return e;
+    if (!h_tables || !n_chunks_out || !table_bytes_out) return mt::refuse(fn, "null pointer");
+    const mt::Staged L = mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, n_chunks);
+    if (h_tables_bytes < L.end) return mt::refuse(fn, "h_tables too small");
+    mt::fill_tables(h_tensors, n_tensors, h_groups, d_lrs, n_groups, sizeof(AdamwDevGroup), adamw_group_row, L, (char *)h_tables);
+    *n_chunks_out = n_chunks;
+    *table_bytes_out = L.end;
+    return ANCE_OK;
+}
+
+extern "C" int ance_adamw_step_planned(int n_tensors, int n_groups, int64_t n_chunks, int correct_bias, double max_grad_norm,
+                                       const float *d_grad_scale, const float *d_found_inf, float *d_grad_norm, int64_t *d_skipped,
+                                       void *d_workspace, size_t workspace_bytes, void *stream) {
+    using namespace ance;
+    const char *fn = "ance_adamw_step_planned";
+    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return mt::refuse(fn, "table sizes out of range");
+    if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
+        return mt::refuse(fn, "max_grad_norm not 0 or a positive finite number");
+    const bool clip = max_grad_norm != 0.0;
+    if (clip && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < workspace_bytes_for(n_tensors, n_groups, n_chunks, clip)) return mt::refuse(fn, "workspace too small");
+    const mt::Staged L = mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, n_chunks);
+    return adamw_launch(fn, n_tensors, n_chunks, L, correct_bias, clip, max_grad_norm, d_grad_scale, d_found_inf, d_grad_norm, d_skipped,
+                        (char *)d_workspace, (hipStream_t)stream);
 }

@@ -47,6 +47,7 @@ struct AttnParams {
     float *lse, *rowdot;  // [n_heads][n_rows] each (workspace)
     uint32_t seed_lo, seed_hi, off_lo, off_hi, keep_thr;
     float keep_scale;
+    const uint64_t *d_stream;  // null, or the device stream {seed, base} (philox.h: drop_stream)
 };
 
 // quad_word and seq_bounds: attention_train.h (shared with the 16-bit core)
@@ -132,10 +133,11 @@ __device__ __forceinline__ void store_row_t(float *dst, const f32x16 acc0, const
     }
 }
 
-template <bool DROP>
+template <int DROP>
 __global__ void __launch_bounds__(AT_THREADS) attn_fwd_kernel(const AttnParams P) {
     __shared__ __attribute__((aligned(16))) float Ks[AT_BLK * AT_LD], Vs[AT_BLK * AT_LD];
     const int s = blockIdx.z, head = blockIdx.y, q0 = blockIdx.x * AT_TILE;
+    const DropStream D = drop_stream<DROP>(P);
     int first;
     const int len = seq_bounds(P, s, &first);
     zero_pad_rows(P, P.ctx_out + 64 * head, P.ld_ctx, first, len, q0, threadIdx.x);
@@ -186,8 +188,8 @@ __global__ void __launch_bounds__(AT_THREADS) attn_fwd_kernel(const AttnParams P
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 uint32_t w[4];
-                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), P.off_lo, P.off_hi,
-                        P.seed_lo, P.seed_hi, w);
+                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), D.off_lo, D.off_hi,
+                        D.seed_lo, D.seed_hi, w);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) sc[4 * a + e] = w[e] >= P.keep_thr ? sc[4 * a + e] : 0.f;
             }
@@ -226,10 +228,11 @@ __global__ void __launch_bounds__(256) attn_rowdot_kernel(const AttnParams P) {
     if (ok && c == 0) P.rowdot[(int64_t)head * P.n_rows + row] = d;
 }
 
-template <bool DROP>
+template <int DROP>
 __global__ void __launch_bounds__(AT_THREADS) attn_dq_kernel(const AttnParams P) {
     __shared__ __attribute__((aligned(16))) float Ks[AT_BLK * AT_LD], Vs[AT_BLK * AT_LD];
     const int s = blockIdx.z, head = blockIdx.y, q0 = blockIdx.x * AT_TILE;
+    const DropStream D = drop_stream<DROP>(P);
     int first;
     const int len = seq_bounds(P, s, &first);
     zero_pad_rows(P, P.dq + 64 * head, P.ld_dq, first, len, q0, threadIdx.x);
@@ -264,8 +267,8 @@ __global__ void __launch_bounds__(AT_THREADS) attn_dq_kernel(const AttnParams P)
         if (DROP) {
 #pragma unroll
             for (int a = 0; a < 4; ++a)
-                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), P.off_lo, P.off_hi,
-                        P.seed_lo, P.seed_hi, w + 4 * a);
+                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), D.off_lo, D.off_hi,
+                        D.seed_lo, D.seed_hi, w + 4 * a);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -280,11 +283,12 @@ __global__ void __launch_bounds__(AT_THREADS) attn_dq_kernel(const AttnParams P)
     if (qok) store_row_t(P.dq + qrow * P.ld_dq + 64 * head, acc0, acc1, half, 0.125f);
 }
 
-template <bool DROP>
+template <int DROP>
 __global__ void __launch_bounds__(AT_THREADS, 2) attn_dkv_kernel(const AttnParams P) {
     __shared__ __attribute__((aligned(16))) float Qs[AT_BLK * AT_LD], Gs[AT_BLK * AT_LD];
     __shared__ __attribute__((aligned(16))) float lse_s[AT_BLK], rd_s[AT_BLK];
     const int s = blockIdx.z, head = blockIdx.y, k0 = blockIdx.x * AT_TILE;
+    const DropStream D = drop_stream<DROP>(P);
     int first;
     const int len = seq_bounds(P, s, &first);
     zero_pad_rows(P, P.dk + 64 * head, P.ld_dk, first, len, k0, threadIdx.x);
@@ -328,8 +332,8 @@ __global__ void __launch_bounds__(AT_THREADS, 2) attn_dkv_kernel(const AttnParam
                 // draws for row c of this group of four rows; every lane then takes word c (its key's) of each row's draw.
                 const int c = lane & 3;  // == kj & 3: k0 and the wave's offset are multiples of 4
                 uint32_t w[4];
-                philox4((uint32_t)(ib + 8 * a + 4 * half + c) * 128u + (uint32_t)(kj >> 2), (uint32_t)(s * P.n_heads + head), P.off_lo,
-                        P.off_hi, P.seed_lo, P.seed_hi, w);
+                philox4((uint32_t)(ib + 8 * a + 4 * half + c) * 128u + (uint32_t)(kj >> 2), (uint32_t)(s * P.n_heads + head), D.off_lo,
+                        D.off_hi, D.seed_lo, D.seed_hi, w);
                 wj[0] = quad_word<0>(w, c);
                 wj[1] = quad_word<1>(w, c);
                 wj[2] = quad_word<2>(w, c);
@@ -389,7 +393,7 @@ const char *check_args(const AnceAttnTrainArgs *a) {
     if (a->workspace_bytes < ws_bytes(a->n_rows, a->n_heads)) return "workspace too small";
     return nullptr;
 }
-AttnParams params(const AnceAttnTrainArgs *a) {
+AttnParams params(const AnceAttnTrainArgs *a, const uint64_t *d_stream) {
     AttnParams P = {};
     P.q = a->q; P.k = a->k; P.v = a->v; P.ctx = a->ctx; P.ctx_out = a->ctx;
     P.ld_q = a->ld_q; P.ld_k = a->ld_k; P.ld_v = a->ld_v; P.ld_ctx = a->ld_ctx;
@@ -399,6 +403,7 @@ AttnParams params(const AnceAttnTrainArgs *a) {
     P.rowdot = (float *)((char *)a->d_workspace + ws_bytes(a->n_rows, a->n_heads) / 2);
     P.seed_lo = (uint32_t)a->seed; P.seed_hi = (uint32_t)(a->seed >> 32);
     P.off_lo = (uint32_t)a->offset; P.off_hi = (uint32_t)(a->offset >> 32);
+    P.d_stream = d_stream;  // given: seed and base come from the device, a->offset is added to the base
     P.keep_thr = (uint32_t)((double)a->dropout_p * 4294967296.0);  // floor(p 2^32), p < 1
     P.keep_scale = 1.0f / (1.0f - a->dropout_p);
     return P;
@@ -413,39 +418,61 @@ extern "C" size_t ance_attention_workspace_bytes(int64_t n_rows, int n_heads) {
     return shape_ok(n_rows, n_heads) ? ws_bytes(n_rows, n_heads) : 0;
 }
 
-extern "C" int ance_attention_forward(const AnceAttnTrainArgs *args, void *stream) {
+static int ance_attention_forward_impl(const char *fn, const AnceAttnTrainArgs *args, const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_attention_forward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_args(args)) return refuse(fn, why);
-    const AttnParams P = params(args);
+    const AttnParams P = params(args, d_stream);
     const dim3 grid((unsigned)((args->max_seq_len + AT_TILE - 1) / AT_TILE), (unsigned)args->n_heads, (unsigned)args->n_seq);
     hipStream_t st = (hipStream_t)stream;
-    if (drops(args)) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(AT_THREADS), 0, st, P);
-    else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(AT_THREADS), 0, st, P);
+    const int mode = drop_mode(drops(args), d_stream);
+    if (mode == DROP_DEVICE) hipLaunchKernelGGL(attn_fwd_kernel<DROP_DEVICE>, grid, dim3(AT_THREADS), 0, st, P);
+    else if (mode == DROP_HOST) hipLaunchKernelGGL(attn_fwd_kernel<DROP_HOST>, grid, dim3(AT_THREADS), 0, st, P);
+    else hipLaunchKernelGGL(attn_fwd_kernel<DROP_NONE>, grid, dim3(AT_THREADS), 0, st, P);
     return check_launch(fn);
 }
 
-extern "C" int ance_attention_backward(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, void *stream) {
+static int ance_attention_backward_impl(const char *fn, const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads,
+                                        const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_attention_backward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_args(args)) return refuse(fn, why);
     if (!grads) return refuse(fn, "null pointer");
     if (const char *why = check_matrix(grads->dctx, grads->ld_dctx, args->n_heads)) return refuse(fn, why);
     if (const char *why = check_matrix(grads->dq, grads->ld_dq, args->n_heads)) return refuse(fn, why);
     if (const char *why = check_matrix(grads->dk, grads->ld_dk, args->n_heads)) return refuse(fn, why);
     if (const char *why = check_matrix(grads->dv, grads->ld_dv, args->n_heads)) return refuse(fn, why);
-    AttnParams P = params(args);
+    AttnParams P = params(args, d_stream);
     P.dctx = grads->dctx; P.dq = grads->dq; P.dk = grads->dk; P.dv = grads->dv;
     P.ld_dctx = grads->ld_dctx; P.ld_dq = grads->ld_dq; P.ld_dk = grads->ld_dk; P.ld_dv = grads->ld_dv;
     const unsigned tiles = (unsigned)((args->max_seq_len + AT_TILE - 1) / AT_TILE), nh = (unsigned)args->n_heads, ns = (unsigned)args->n_seq;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(attn_rowdot_kernel, dim3((unsigned)((args->max_seq_len + 15) / 16), nh, ns), dim3(256), 0, st, P);
-    if (drops(args)) {
-        hipLaunchKernelGGL(attn_dkv_kernel<true>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
-        hipLaunchKernelGGL(attn_dq_kernel<true>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
+    const int mode = drop_mode(drops(args), d_stream);
+    if (mode == DROP_DEVICE) {
+        hipLaunchKernelGGL(attn_dkv_kernel<DROP_DEVICE>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
+        hipLaunchKernelGGL(attn_dq_kernel<DROP_DEVICE>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
+    } else if (mode == DROP_HOST) {
+        hipLaunchKernelGGL(attn_dkv_kernel<DROP_HOST>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
+        hipLaunchKernelGGL(attn_dq_kernel<DROP_HOST>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
     } else {
-        hipLaunchKernelGGL(attn_dkv_kernel<false>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
-        hipLaunchKernelGGL(attn_dq_kernel<false>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
+        hipLaunchKernelGGL(attn_dkv_kernel<DROP_NONE>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
+        hipLaunchKernelGGL(attn_dq_kernel<DROP_NONE>, dim3(tiles, nh, ns), dim3(AT_THREADS), 0, st, P);
     }
     return check_launch(fn);
+}
+
+// The entry points: each with its sibling that takes the device dropout stream (include/ance_amd.h); the plain one passes none.
+extern "C" int ance_attention_forward(const AnceAttnTrainArgs *args, void *stream) {
+    return ance_attention_forward_impl("ance_attention_forward", args, nullptr, stream);
+}
+extern "C" int ance_attention_forward_dstream(const AnceAttnTrainArgs *args, const uint64_t *d_stream, void *stream) {
+    return ance_attention_forward_impl("ance_attention_forward_dstream", args, d_stream, stream);
+}
+extern "C" int ance_attention_backward(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, void *stream) {
+    return ance_attention_backward_impl("ance_attention_backward", args, grads, nullptr, stream);
+}
+extern "C" int ance_attention_backward_dstream(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, const uint64_t *d_stream,
+                                               void *stream) {
+    return ance_attention_backward_impl("ance_attention_backward_dstream", args, grads, d_stream, stream);
 }

@@ -69,6 +69,7 @@ struct AttnParams16 {
     float *lse, *rowdot;  // [n_heads][n_rows] each (workspace)
     uint32_t seed_lo, seed_hi, off_lo, off_hi, keep_thr;
     float keep_scale;
+    const uint64_t *d_stream;  // null, or the device stream {seed, base} (philox.h: drop_stream)
 };
 
 // the one exp of this file: the forward and both backward kernels
@@ -174,11 +175,12 @@ __device__ __forceinline__ void store_row_t(typename X::T *dst, const f32x16 acc
     }
 }
 
-template <class X, bool DROP>
+template <class X, int DROP>
 __global__ void __launch_bounds__(AH_THREADS) attn16_fwd_kernel(const AttnParams16 P) {
     typedef typename X::T T;
     __shared__ __attribute__((aligned(16))) T Ks[AH_BLK * AH_LDR], Vt[64 * AH_LDT];
     const int s = blockIdx.z, head = blockIdx.y, q0 = blockIdx.x * AH_TILE;
+    const DropStream D = drop_stream<DROP>(P);
     int first;
     const int len = seq_bounds(P, s, &first);
     zero_pad_rows<X>(P, (T *)P.ctx_out + 64 * head, P.ld_ctx, first, len, q0, threadIdx.x);
@@ -229,8 +231,8 @@ __global__ void __launch_bounds__(AH_THREADS) attn16_fwd_kernel(const AttnParams
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 uint32_t w[4];
-                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), P.off_lo, P.off_hi,
-                        P.seed_lo, P.seed_hi, w);
+                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), D.off_lo, D.off_hi,
+                        D.seed_lo, D.seed_hi, w);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) sc[4 * a + e] = w[e] >= P.keep_thr ? sc[4 * a + e] : 0.f;
             }
@@ -274,11 +276,12 @@ __global__ void __launch_bounds__(256) attn16_rowdot_kernel(const AttnParams16 P
     if (ok && c == 0) P.rowdot[(int64_t)head * P.n_rows + row] = d;
 }
 
-template <class X, bool DROP>
+template <class X, int DROP>
 __global__ void __launch_bounds__(AH_THREADS) attn16_dq_kernel(const AttnParams16 P) {
     typedef typename X::T T;
     __shared__ __attribute__((aligned(16))) T Ks[AH_BLK * AH_LDR], Vs[AH_BLK * AH_LDR], Kt[64 * AH_LDT];
     const int s = blockIdx.z, head = blockIdx.y, q0 = blockIdx.x * AH_TILE;
+    const DropStream D = drop_stream<DROP>(P);
     int first;
     const int len = seq_bounds(P, s, &first);
     zero_pad_rows<X>(P, (T *)P.dq + 64 * head, P.ld_dq, first, len, q0, threadIdx.x);
@@ -314,8 +317,8 @@ __global__ void __launch_bounds__(AH_THREADS) attn16_dq_kernel(const AttnParams1
         if (DROP) {
 #pragma unroll
             for (int a = 0; a < 4; ++a)
-                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), P.off_lo, P.off_hi,
-                        P.seed_lo, P.seed_hi, w + 4 * a);
+                philox4((uint32_t)qi * 128u + (uint32_t)((jb + 8 * a + 4 * half) >> 2), (uint32_t)(s * P.n_heads + head), D.off_lo, D.off_hi,
+                        D.seed_lo, D.seed_hi, w + 4 * a);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -332,12 +335,13 @@ __global__ void __launch_bounds__(AH_THREADS) attn16_dq_kernel(const AttnParams1
     if (qok) store_row_t<X>((T *)P.dq + qrow * P.ld_dq + 64 * head, acc0, acc1, half, 0.125f);
 }
 
-template <class X, bool DROP>
+template <class X, int DROP>
 __global__ void __launch_bounds__(AH_THREADS) attn16_dkv_kernel(const AttnParams16 P) {
     typedef typename X::T T;
     __shared__ __attribute__((aligned(16))) T Qs[AH_BLK * AH_LDR], Gs[AH_BLK * AH_LDR], Qt[64 * AH_LDT], Gt[64 * AH_LDT];
     __shared__ __attribute__((aligned(16))) float lse_s[AH_BLK], rd_s[AH_BLK];
     const int s = blockIdx.z, head = blockIdx.y, k0 = blockIdx.x * AH_TILE;
+    const DropStream D = drop_stream<DROP>(P);
     int first;
     const int len = seq_bounds(P, s, &first);
     zero_pad_rows<X>(P, (T *)P.dk + 64 * head, P.ld_dk, first, len, k0, threadIdx.x);
@@ -385,8 +389,8 @@ __global__ void __launch_bounds__(AH_THREADS) attn16_dkv_kernel(const AttnParams
                 // draws for row c of this group of four rows; every lane then takes word c (its key's) of each row's draw.
                 const int c = lane & 3;  // == kj & 3: k0 and the wave's offset are multiples of 4
                 uint32_t w[4];
-                philox4((uint32_t)(ib + 8 * a + 4 * half + c) * 128u + (uint32_t)(kj >> 2), (uint32_t)(s * P.n_heads + head), P.off_lo,
-                        P.off_hi, P.seed_lo, P.seed_hi, w);
+                philox4((uint32_t)(ib + 8 * a + 4 * half + c) * 128u + (uint32_t)(kj >> 2), (uint32_t)(s * P.n_heads + head), D.off_lo,
+                        D.off_hi, D.seed_lo, D.seed_hi, w);
                 wj[0] = quad_word<0>(w, c);
                 wj[1] = quad_word<1>(w, c);
                 wj[2] = quad_word<2>(w, c);
@@ -450,7 +454,7 @@ const char *check_args(const AnceAttn16Args *a) {
     if (a->workspace_bytes < ws_bytes(a->n_rows, a->n_heads)) return "workspace too small";
     return nullptr;
 }
-AttnParams16 params(const AnceAttn16Args *a) {
+AttnParams16 params(const AnceAttn16Args *a, const uint64_t *d_stream) {
     AttnParams16 P = {};
     P.q = a->q; P.k = a->k; P.v = a->v; P.ctx = a->ctx; P.ctx_out = a->ctx;
     P.ld_q = a->ld_q; P.ld_k = a->ld_k; P.ld_v = a->ld_v; P.ld_ctx = a->ld_ctx;
@@ -460,6 +464,7 @@ AttnParams16 params(const AnceAttn16Args *a) {
     P.rowdot = (float *)((char *)a->d_workspace + ws_bytes(a->n_rows, a->n_heads) / 2);
     P.seed_lo = (uint32_t)a->seed; P.seed_hi = (uint32_t)(a->seed >> 32);
     P.off_lo = (uint32_t)a->offset; P.off_hi = (uint32_t)(a->offset >> 32);
+    P.d_stream = d_stream;  // given: seed and base come from the device, a->offset is added to the base
     P.keep_thr = (uint32_t)((double)a->dropout_p * 4294967296.0);  // floor(p 2^32), p < 1
     P.keep_scale = 1.0f / (1.0f - a->dropout_p);
     return P;
@@ -469,19 +474,25 @@ bool drops(const AnceAttn16Args *a) { return a->training != 0 && a->dropout_p > 
 template <class X>
 void launch_forward(const AnceAttn16Args *args, const AttnParams16 &P, hipStream_t st) {
     const dim3 grid((unsigned)((args->max_seq_len + AH_TILE - 1) / AH_TILE), (unsigned)args->n_heads, (unsigned)args->n_seq);
-    if (drops(args)) hipLaunchKernelGGL((attn16_fwd_kernel<X, true>), grid, dim3(AH_THREADS), 0, st, P);
-    else hipLaunchKernelGGL((attn16_fwd_kernel<X, false>), grid, dim3(AH_THREADS), 0, st, P);
+    const int mode = drop_mode(drops(args), P.d_stream);
+    if (mode == DROP_DEVICE) hipLaunchKernelGGL((attn16_fwd_kernel<X, DROP_DEVICE>), grid, dim3(AH_THREADS), 0, st, P);
+    else if (mode == DROP_HOST) hipLaunchKernelGGL((attn16_fwd_kernel<X, DROP_HOST>), grid, dim3(AH_THREADS), 0, st, P);
+    else hipLaunchKernelGGL((attn16_fwd_kernel<X, DROP_NONE>), grid, dim3(AH_THREADS), 0, st, P);
 }
 template <class X>
 void launch_backward(const AnceAttn16Args *args, const AttnParams16 &P, hipStream_t st) {
     const unsigned tiles = (unsigned)((args->max_seq_len + AH_TILE - 1) / AH_TILE), nh = (unsigned)args->n_heads, ns = (unsigned)args->n_seq;
     hipLaunchKernelGGL((attn16_rowdot_kernel<X>), dim3((unsigned)((args->max_seq_len + 31) / 32), nh, ns), dim3(256), 0, st, P);
-    if (drops(args)) {
-        hipLaunchKernelGGL((attn16_dkv_kernel<X, true>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
-        hipLaunchKernelGGL((attn16_dq_kernel<X, true>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
+    const int mode = drop_mode(drops(args), P.d_stream);
+    if (mode == DROP_DEVICE) {
+        hipLaunchKernelGGL((attn16_dkv_kernel<X, DROP_DEVICE>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
+        hipLaunchKernelGGL((attn16_dq_kernel<X, DROP_DEVICE>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
+    } else if (mode == DROP_HOST) {
+        hipLaunchKernelGGL((attn16_dkv_kernel<X, DROP_HOST>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
+        hipLaunchKernelGGL((attn16_dq_kernel<X, DROP_HOST>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
     } else {
-        hipLaunchKernelGGL((attn16_dkv_kernel<X, false>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
-        hipLaunchKernelGGL((attn16_dq_kernel<X, false>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
+        hipLaunchKernelGGL((attn16_dkv_kernel<X, DROP_NONE>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
+        hipLaunchKernelGGL((attn16_dq_kernel<X, DROP_NONE>), dim3(tiles, nh, ns), dim3(AH_THREADS), 0, st, P);
     }
 }
 
@@ -493,29 +504,45 @@ extern "C" size_t ance_attention16_workspace_bytes(int64_t n_rows, int n_heads) 
     return shape_ok(n_rows, n_heads) ? ws_bytes(n_rows, n_heads) : 0;
 }
 
-extern "C" int ance_attention16_forward(const AnceAttn16Args *args, void *stream) {
+static int ance_attention16_forward_impl(const char *fn, const AnceAttn16Args *args, const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_attention16_forward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_args(args)) return refuse(fn, why);
-    const AttnParams16 P = params(args);
+    const AttnParams16 P = params(args, d_stream);
     if (args->dtype == ANCE_DTYPE_F16) launch_forward<F16>(args, P, (hipStream_t)stream);
     else launch_forward<BF16>(args, P, (hipStream_t)stream);
     return check_launch(fn);
 }
 
-extern "C" int ance_attention16_backward(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, void *stream) {
+static int ance_attention16_backward_impl(const char *fn, const AnceAttn16Args *args, const AnceAttn16GradArgs *grads,
+                                          const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_attention16_backward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_args(args)) return refuse(fn, why);
     if (!grads) return refuse(fn, "null pointer");
     if (const char *why = check_matrix(grads->dctx, grads->ld_dctx, args->n_heads)) return refuse(fn, why);
     if (const char *why = check_matrix(grads->dq, grads->ld_dq, args->n_heads)) return refuse(fn, why);
     if (const char *why = check_matrix(grads->dk, grads->ld_dk, args->n_heads)) return refuse(fn, why);
     if (const char *why = check_matrix(grads->dv, grads->ld_dv, args->n_heads)) return refuse(fn, why);
-    AttnParams16 P = params(args);
+    AttnParams16 P = params(args, d_stream);
     P.dctx = grads->dctx; P.dq = grads->dq; P.dk = grads->dk; P.dv = grads->dv;
     P.ld_dctx = grads->ld_dctx; P.ld_dq = grads->ld_dq; P.ld_dk = grads->ld_dk; P.ld_dv = grads->ld_dv;
     if (args->dtype == ANCE_DTYPE_F16) launch_backward<F16>(args, P, (hipStream_t)stream);
     else launch_backward<BF16>(args, P, (hipStream_t)stream);
     return check_launch(fn);
+}
+
+// The entry points: each with its sibling that takes the device dropout stream (include/ance_amd.h); the plain one passes none.
+extern "C" int ance_attention16_forward(const AnceAttn16Args *args, void *stream) {
+    return ance_attention16_forward_impl("ance_attention16_forward", args, nullptr, stream);
+}
+extern "C" int ance_attention16_forward_dstream(const AnceAttn16Args *args, const uint64_t *d_stream, void *stream) {
+    return ance_attention16_forward_impl("ance_attention16_forward_dstream", args, d_stream, stream);
+}
+extern "C" int ance_attention16_backward(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, void *stream) {
+    return ance_attention16_backward_impl("ance_attention16_backward", args, grads, nullptr, stream);
+}
+extern "C" int ance_attention16_backward_dstream(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, const uint64_t *d_stream,
+                                                 void *stream) {
+    return ance_attention16_backward_impl("ance_attention16_backward_dstream", args, grads, d_stream, stream);
 }

@@ -31,6 +31,7 @@ struct EmbedParams {
     int L, vocab, max_pos, n_types, roberta, pad;
     float eps, keep_scale;
     uint32_t seed_lo, seed_hi, off_lo, off_hi, keep_thr;
+    const uint64_t *d_stream;  // null, or the device stream {seed, base} (philox.h: drop_stream)
 };
 
 __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
@@ -69,16 +70,17 @@ __device__ __forceinline__ void embed_sum(const EmbedParams &P, int id, int tt, 
 }
 
 // keep bits of four columns (bit e: column 4 c4 + e) under the layer tail's counter contract
-__device__ __forceinline__ uint32_t keep_bits(const EmbedParams &P, int64_t row, int c4) {
+__device__ __forceinline__ uint32_t keep_bits(const EmbedParams &P, const DropStream &D, int64_t row, int c4) {
     uint32_t w[4], k = 0;
-    philox4((uint32_t)row, (uint32_t)c4, P.off_lo, P.off_hi, P.seed_lo, P.seed_hi, w);
+    philox4((uint32_t)row, (uint32_t)c4, D.off_lo, D.off_hi, D.seed_lo, D.seed_hi, w);
 #pragma unroll
     for (int e = 0; e < 4; ++e) k |= (w[e] >= P.keep_thr ? 1u : 0u) << e;
     return k;
 }
 
-template <int NV, bool DROP>
+template <int NV, int DROP>
 __global__ void __launch_bounds__(LT_THREADS) embed_fwd_kernel(const EmbedParams P) {
+    const DropStream D = drop_stream<DROP>(P);
     constexpr float H = (float)(256 * NV);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     f32x4 ga[NV], be[NV];
@@ -109,7 +111,7 @@ __global__ void __launch_bounds__(LT_THREADS) embed_fwd_kernel(const EmbedParams
             const int c4 = 64 * i + lane;
             f32x4 y = z[i] * rstd * ga[i] + be[i];
             if (DROP) {
-                const uint32_t k = keep_bits(P, row, c4);
+                const uint32_t k = keep_bits(P, D, row, c4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) y[e] = (k >> e) & 1u ? y[e] * P.keep_scale : 0.f;
             }
@@ -123,8 +125,9 @@ __global__ void __launch_bounds__(LT_THREADS) embed_fwd_kernel(const EmbedParams
     }
 }
 
-template <int NV, bool DROP>
+template <int NV, int DROP>
 __global__ void __launch_bounds__(LT_THREADS) embed_bwd_kernel(const EmbedParams P) {
+    const DropStream D = drop_stream<DROP>(P);
     __shared__ __attribute__((aligned(16))) f32x4 sm[2 * 3 * NV * 64];
     constexpr float H = (float)(256 * NV);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -149,7 +152,7 @@ __global__ void __launch_bounds__(LT_THREADS) embed_bwd_kernel(const EmbedParams
             const int c4 = 64 * i + lane;
             f32x4 d = load4(gr + 4 * c4);
             if (DROP) {
-                const uint32_t k = keep_bits(P, row, c4);
+                const uint32_t k = keep_bits(P, D, row, c4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) d[e] = (k >> e) & 1u ? d[e] * P.keep_scale : 0.f;
             }
@@ -318,7 +321,7 @@ const char *check_embed(const AnceEmbedArgs *a, bool backward) {
     return check_workspace(a->d_workspace, a->workspace_bytes, backward ? embed_ws_bytes(n_rows, a->H) : stats_bytes(n_rows));
 }
 
-EmbedParams embed_params(const AnceEmbedArgs *a) {
+EmbedParams embed_params(const AnceEmbedArgs *a, const uint64_t *d_stream) {
     EmbedParams P = {};
     const int64_t n_rows = (int64_t)a->n_seq * a->L;
     P.ids = a->ids; P.type_ids = a->type_ids;
@@ -335,43 +338,54 @@ EmbedParams embed_params(const AnceEmbedArgs *a) {
     P.eps = a->eps;
     P.seed_lo = (uint32_t)a->seed; P.seed_hi = (uint32_t)(a->seed >> 32);
     P.off_lo = (uint32_t)a->offset; P.off_hi = (uint32_t)(a->offset >> 32);
+    P.d_stream = d_stream;  // given: seed and base come from the device, a->offset is added to the base
     P.keep_thr = (uint32_t)((double)a->dropout_p * 4294967296.0);  // floor(p 2^32), p < 1
     P.keep_scale = 1.0f / (1.0f - a->dropout_p);
     return P;
 }
 bool drops(const AnceEmbedArgs *a) { return a->training != 0 && a->dropout_p > 0.0f; }
 
+template <int DROP>
+void launch_embed_fwd(int H, dim3 grid, dim3 block, hipStream_t st, const EmbedParams &P) {
+    if (H == 768) hipLaunchKernelGGL((embed_fwd_kernel<3, DROP>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((embed_fwd_kernel<4, DROP>), grid, block, 0, st, P);
+}
+template <int DROP>
+void launch_embed_bwd(int H, dim3 grid, dim3 block, hipStream_t st, const EmbedParams &P) {
+    if (H == 768) hipLaunchKernelGGL((embed_bwd_kernel<3, DROP>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((embed_bwd_kernel<4, DROP>), grid, block, 0, st, P);
+}
+
 }  // namespace
 }  // namespace ance
 
-extern "C" int ance_embed_segment_chunk(void) { return ance::SEG_C; }
+extern "C" int ance_embed_segment_chunk(void) {
+    return ance::SEG_C;
+}
 
 extern "C" size_t ance_embed_workspace_bytes(int64_t n_rows, int H) {
     using namespace ance;
     return rows_ok(n_rows) && (H == 768 || H == 1024) ? embed_ws_bytes(n_rows, H) : 0;
 }
 
-extern "C" int ance_embed_forward(const AnceEmbedArgs *args, void *stream) {
+static int ance_embed_forward_impl(const char *fn, const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_embed_forward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_embed(args, false)) return refuse(fn, why);
-    const EmbedParams P = embed_params(args);
+    const EmbedParams P = embed_params(args, d_stream);
     const dim3 grid((unsigned)n_part(P.n_rows)), block(LT_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    const bool drop = drops(args);
-    if (args->H == 768) {
-        if (drop) hipLaunchKernelGGL((embed_fwd_kernel<3, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((embed_fwd_kernel<3, false>), grid, block, 0, st, P);
-    } else {
-        if (drop) hipLaunchKernelGGL((embed_fwd_kernel<4, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((embed_fwd_kernel<4, false>), grid, block, 0, st, P);
-    }
+    const int mode = drop_mode(drops(args), d_stream);
+    if (mode == DROP_DEVICE) launch_embed_fwd<DROP_DEVICE>(args->H, grid, block, st, P);
+    else if (mode == DROP_HOST) launch_embed_fwd<DROP_HOST>(args->H, grid, block, st, P);
+    else launch_embed_fwd<DROP_NONE>(args->H, grid, block, st, P);
     return check_launch(fn);
 }
 
-extern "C" int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream) {
+static int ance_embed_backward_impl(const char *fn, const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream,
+                                    void *stream) {
     using namespace ance;
-    const char *fn = "ance_embed_backward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_embed(args, true)) return refuse(fn, why);
     if (!grads) return refuse(fn, "null pointer");
     if (const char *why = check_vector(grads->dy)) return refuse(fn, why);
@@ -390,19 +404,15 @@ extern "C" int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGra
     for (const void *p : {(const void *)grads->word_perm, (const void *)grads->pos_perm, (const void *)grads->type_perm})
         if (p && (uintptr_t)p % 8) return refuse(fn, "alignment: a permutation is not 8-byte aligned");
 
-    EmbedParams P = embed_params(args);
+    EmbedParams P = embed_params(args, d_stream);
     P.dy = grads->dy;
     const int H = args->H;
     const dim3 grid((unsigned)n_part(P.n_rows)), block(LT_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    const bool drop = drops(args);
-    if (H == 768) {
-        if (drop) hipLaunchKernelGGL((embed_bwd_kernel<3, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((embed_bwd_kernel<3, false>), grid, block, 0, st, P);
-    } else {
-        if (drop) hipLaunchKernelGGL((embed_bwd_kernel<4, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((embed_bwd_kernel<4, false>), grid, block, 0, st, P);
-    }
+    const int mode = drop_mode(drops(args), d_stream);
+    if (mode == DROP_DEVICE) launch_embed_bwd<DROP_DEVICE>(H, grid, block, st, P);
+    else if (mode == DROP_HOST) launch_embed_bwd<DROP_HOST>(H, grid, block, st, P);
+    else launch_embed_bwd<DROP_NONE>(H, grid, block, st, P);
     // a type table that needs no grouping: every row has type 0, whose gradient is the column sum of dv
     float *dtype0 = grads->dtype && !seg_type ? grads->dtype : nullptr;
     hipLaunchKernelGGL(colsum_tree_kernel, dim3((unsigned)(3 * H / 64)), dim3(256), 0, st, (const float *)P.part,
@@ -429,4 +439,19 @@ extern "C" int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGra
         }
     }
     return check_launch(fn);
+}
+
+// The entry points: each with its sibling that takes the device dropout stream (include/ance_amd.h); the plain one passes none.
+extern "C" int ance_embed_forward(const AnceEmbedArgs *args, void *stream) {
+    return ance_embed_forward_impl("ance_embed_forward", args, nullptr, stream);
+}
+extern "C" int ance_embed_forward_dstream(const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream) {
+    return ance_embed_forward_impl("ance_embed_forward_dstream", args, d_stream, stream);
+}
+extern "C" int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream) {
+    return ance_embed_backward_impl("ance_embed_backward", args, grads, nullptr, stream);
+}
+extern "C" int ance_embed_backward_dstream(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream,
+                                           void *stream) {
+    return ance_embed_backward_impl("ance_embed_backward_dstream", args, grads, d_stream, stream);
 }

@@ -45,7 +45,11 @@ constexpr int LAMB_THREADS = mt::THREADS;
 struct LambDevGroup {
     float b1, omb1, b2, omb2, eps, wd, neg_lr;
     int32_t has_wd;
+    const double *d_lr;  // the learning rate as a device fp64 scalar (a resident plan's group with a tensor lr), or null: neg_lr holds it
 };
+
+// -lr of a group as the fp32 the update multiplies by: the host double, or the device scalar, negated and rounded the same way
+__device__ __forceinline__ float lamb_neg_lr(const LambDevGroup &G) { return G.d_lr ? (float)(-G.d_lr[0]) : G.neg_lr; }
 
 __device__ __forceinline__ float lamb_u(float p, float m, float v, const LambDevGroup &G) {
     float u = m / (sqrtf(v) + G.eps);
@@ -138,7 +142,7 @@ __global__ void __launch_bounds__(LAMB_THREADS) lamb_pass2_kernel(const LambDevG
     const DevTensor T = tensors[t];
     const LambDevGroup G = groups[T.group];
     const float tr = adam ? 1.0f : out[3 * (int64_t)t + 2];
-    const float s = G.neg_lr * tr;  // the reference's -step_size * trust_ratio, an fp32 product
+    const float s = lamb_neg_lr(G) * tr;  // the reference's -step_size * trust_ratio, an fp32 product
     float *a[4];
     const int len = mt::chunk_of(T, a);
     mt::stream_chunk<0b1101, 0b0001>(a, len, T.vec, [&](float(&x)[4]) { x[0] = __builtin_fmaf(s, lamb_u(x[0], x[2], x[3], G), x[0]); });
@@ -153,8 +157,10 @@ size_t workspace_bytes_clipped(int n_tensors, int n_groups, int64_t n_chunks) {
     return workspace_bytes_for(n_tensors, n_groups, n_chunks) + align16(sizeof(double) * (size_t)n_chunks) + 16;
 }
 
-void lamb_group_row(void *row, const AnceLambGroup &a) {  // the reference's Python doubles, rounded to fp32 as torch does for a scalar
+// the reference's Python doubles, rounded to fp32 as torch does for a scalar
+void lamb_group_row(void *row, const AnceLambGroup &a, const double *d_lr) {
     LambDevGroup &G = *(LambDevGroup *)row;
+    G.d_lr = d_lr;
     G.b1 = (float)a.beta1;
     G.omb1 = (float)(1.0 - a.beta1);
     G.b2 = (float)a.beta2;
@@ -178,27 +184,9 @@ void launch_pass1(int64_t n_chunks, hipStream_t st, const LambDevGroup *dG, cons
                        amp.grad_scale, amp.found_inf);
 }
 
-// the body of ance_lamb_step (clip false), ance_lamb_step_clipped (clip true: max_norm, d_grad_norm) and ance_lamb_step_amp (amp);
-// fn: the entry point's name, for the error text
-int lamb_step_impl(const char *fn, const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
-                   float *d_out, void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm,
-                   float *d_grad_norm, const LambAmp &amp) {
-    if (n_tensors < 0) return mt::refuse(fn, "n_tensors < 0");
-    if (n_tensors == 0) return ANCE_OK;
-    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
-    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
-    if (!d_out) return mt::refuse(fn, "null d_out");
-    int64_t n_chunks = 0;
-    if (const int e = mt::count_chunks(fn, h_tensors, n_tensors, n_groups, &n_chunks)) return e;
-    const size_t need = clip ? workspace_bytes_clipped(n_tensors, n_groups, n_chunks) : workspace_bytes_for(n_tensors, n_groups, n_chunks);
-    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
-    if (workspace_bytes < need) return mt::refuse(fn, "workspace too small");
-
-    const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)d_workspace;
-    if (const int e = mt::stage_tables(fn, h_tensors, n_tensors, h_groups, n_groups, sizeof(LambDevGroup), lamb_group_row, L, ws, st))
-        return e;
+// the launches of a step whose tables stand at the head of ws (layout L): three, or five with the clip
+int lamb_launch(const char *fn, int n_tensors, int64_t n_chunks, const mt::Staged &L, int adam, float *d_out, char *ws, hipStream_t st,
+                bool clip, double max_norm, float *d_grad_norm, const LambAmp &amp) {
     const LambDevGroup *dG = (const LambDevGroup *)ws;
     const DevTensor *dT = (const DevTensor *)(ws + L.tensors);
     const int32_t *dC = (const int32_t *)(ws + L.chunk_tensor);
@@ -224,6 +212,38 @@ int lamb_step_impl(const char *fn, const AnceLambTensor *h_tensors, int n_tensor
         hipLaunchKernelGGL(lamb_pass2_kernel, dim3((unsigned)n_chunks), dim3(LAMB_THREADS), 0, st, dG, dT, dC, (const float *)d_out,
                            adam ? 1 : 0, amp.found_inf);
     return check_launch(fn);
+}
+
+// the checks a plan makes of its tables; ANCE_OK with *n_chunks, or a refusal in fn's name
+int lamb_check_tables(const char *fn, const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups,
+                      int64_t *n_chunks) {
+    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
+    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
+    return mt::count_chunks(fn, h_tensors, n_tensors, n_groups, n_chunks);
+}
+
+// the body of ance_lamb_step (clip false), ance_lamb_step_clipped (clip true: max_norm, d_grad_norm) and ance_lamb_step_amp (amp);
+// fn: the entry point's name, for the error text
+int lamb_step_impl(const char *fn, const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
+                   float *d_out, void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm,
+                   float *d_grad_norm, const LambAmp &amp) {
+    if (n_tensors < 0) return mt::refuse(fn, "n_tensors < 0");
+    if (n_tensors == 0) return ANCE_OK;
+    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
+    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
+    if (!d_out) return mt::refuse(fn, "null d_out");
+    int64_t n_chunks = 0;
+    if (const int e = mt::count_chunks(fn, h_tensors, n_tensors, n_groups, &n_chunks)) return e;
+    const size_t need = clip ? workspace_bytes_clipped(n_tensors, n_groups, n_chunks) : workspace_bytes_for(n_tensors, n_groups, n_chunks);
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < need) return mt::refuse(fn, "workspace too small");
+
+    const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)d_workspace;
+    if (const int e = mt::stage_tables(fn, h_tensors, n_tensors, h_groups, n_groups, sizeof(LambDevGroup), lamb_group_row, L, ws, st))
+        return e;
+    return lamb_launch(fn, n_tensors, n_chunks, L, adam, d_out, ws, st, clip, max_norm, d_grad_norm, amp);
 }
 
 }  // namespace
@@ -283,4 +303,55 @@ extern "C" int ance_lamb_step_amp(const AnceLambTensor *h_tensors, int n_tensors
     amp.skipped = d_skipped;
     return lamb_step_impl(fn, h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, clip,
                           max_grad_norm, d_grad_norm, amp);
+}
+
+// ---- the resident plan: the tables are built once on the host, uploaded by the caller to the head of a workspace the plan owns,
+// and every later step only launches (include/ance_amd.h)
+extern "C" size_t ance_lamb_plan_table_bytes(int n_tensors, int n_groups, int64_t total_numel) {
+    using namespace ance;
+    if (n_tensors < 0 || n_groups < 1 || total_numel < 0) return 0;
+    const int64_t chunks = mt::max_chunks(n_tensors, total_numel);
+    if (chunks > (int64_t)INT32_MAX) return 0;
+    return mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, chunks).end;
+}
+
+extern "C" int ance_lamb_plan_build(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups,
+                                    const double *const *d_lrs, int n_groups, void *h_tables, size_t h_tables_bytes,
+                                    int64_t *n_chunks_out, size_t *table_bytes_out) {
+    using namespace ance;
+    const char *fn = "ance_lamb_plan_build";
+    if (n_tensors < 1) return mt::refuse(fn, "n_tensors < 1");
+    int64_t n_chunks = 0;
+    if (const int e = lamb_check_tables(fn, h_tensors, n_tensors, h_groups, n_groups, &n_chunks)) return e;
+    if (!h_tables || !n_chunks_out || !table_bytes_out) return mt::refuse(fn, "null pointer");
+    const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
+    if (h_tables_bytes < L.end) return mt::refuse(fn, "h_tables too small");
+    mt::fill_tables(h_tensors, n_tensors, h_groups, d_lrs, n_groups, sizeof(LambDevGroup), lamb_group_row, L, (char *)h_tables);
+    *n_chunks_out = n_chunks;
+    *table_bytes_out = L.end;
+    return ANCE_OK;
+}
+
+extern "C" int ance_lamb_step_planned(int n_tensors, int n_groups, int64_t n_chunks, int adam, double max_grad_norm,
+                                      const float *d_grad_scale, const float *d_found_inf, const float *d_prev_out, float *d_grad_norm,
+                                      int64_t *d_skipped, float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
+    using namespace ance;
+    const char *fn = "ance_lamb_step_planned";
+    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return mt::refuse(fn, "table sizes out of range");
+    if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
+        return mt::refuse(fn, "max_grad_norm not 0 or a positive finite number");
+    const bool clip = max_grad_norm != 0.0;
+    if (clip && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
+    if (!d_out) return mt::refuse(fn, "null d_out");
+    const size_t need = clip ? workspace_bytes_clipped(n_tensors, n_groups, n_chunks) : workspace_bytes_for(n_tensors, n_groups, n_chunks);
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < need) return mt::refuse(fn, "workspace too small");
+    LambAmp amp;
+    amp.grad_scale = d_grad_scale;
+    amp.found_inf = d_found_inf;
+    amp.prev_out = d_prev_out;
+    amp.skipped = d_skipped;
+    const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
+    return lamb_launch(fn, n_tensors, n_chunks, L, adam, d_out, (char *)d_workspace, (hipStream_t)stream, clip, max_grad_norm, d_grad_norm,
+                       amp);
 }

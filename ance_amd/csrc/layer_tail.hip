@@ -41,11 +41,12 @@ const char *check_tail(const AnceLayerTailArgs *a, bool backward) {
     if (!(a->eps > 0.0f)) return "eps <= 0";
     return check_workspace(a->d_workspace, a->workspace_bytes, backward ? tail_ws_bytes(a->n_rows, a->H) : stats_bytes(a->n_rows));
 }
-TailParams tail_params(const AnceLayerTailArgs *a) {
+TailParams tail_params(const AnceLayerTailArgs *a, const uint64_t *d_stream) {
     TailParams P = {};
     P.x = a->x; P.res = a->res; P.bias = a->bias; P.gamma = a->gamma; P.beta = a->beta; P.y = a->y;
     P.ld_x = a->ld_x; P.ld_res = a->ld_res; P.ld_y = a->ld_y;
     fill_tail_common(P, a);
+    P.d_stream = d_stream;
     return P;
 }
 bool drops(const AnceLayerTailArgs *a) { return a->training != 0 && a->dropout_p > 0.0f; }
@@ -72,7 +73,9 @@ GeluParams gelu_params(const AnceBiasGeluArgs *a) {
 }  // namespace
 }  // namespace ance
 
-extern "C" int ance_layer_tail_rows_per_workgroup(void) { return ance::LT_ROWS; }
+extern "C" int ance_layer_tail_rows_per_workgroup(void) {
+    return ance::LT_ROWS;
+}
 
 extern "C" size_t ance_layer_tail_workspace_bytes(int64_t n_rows, int H) {
     using namespace ance;
@@ -84,18 +87,19 @@ extern "C" size_t ance_bias_gelu_workspace_bytes(int64_t n_rows, int N) {
     return rows_ok(n_rows) && (N == 3072 || N == 4096) ? gelu_ws_bytes(n_rows, N) : 0;
 }
 
-extern "C" int ance_layer_tail_forward(const AnceLayerTailArgs *args, void *stream) {
+static int ance_layer_tail_forward_impl(const char *fn, const AnceLayerTailArgs *args, const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_layer_tail_forward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_tail(args, false)) return refuse(fn, why);
-    const TailParams P = tail_params(args);
+    const TailParams P = tail_params(args, d_stream);
     launch_tail_fwd<F32>(args->H, drops(args), dim3((unsigned)n_part(args->n_rows)), (hipStream_t)stream, P);
     return check_launch(fn);
 }
 
-extern "C" int ance_layer_tail_backward(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads, void *stream) {
+static int ance_layer_tail_backward_impl(const char *fn, const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads,
+                                         const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_layer_tail_backward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_tail(args, true)) return refuse(fn, why);
     if (!grads) return refuse(fn, "null pointer");
     if (const char *why = check_matrix(grads->dy, grads->ld_dy, args->H)) return refuse(fn, why);
@@ -104,7 +108,7 @@ extern "C" int ance_layer_tail_backward(const AnceLayerTailArgs *args, const Anc
     if (const char *why = check_vector(grads->dgamma, true)) return refuse(fn, why);
     if (const char *why = check_vector(grads->dbeta, true)) return refuse(fn, why);
     if (const char *why = check_vector(grads->dbias, true)) return refuse(fn, why);
-    TailParams P = tail_params(args);
+    TailParams P = tail_params(args, d_stream);
     P.dy = grads->dy; P.dx = grads->dx; P.dres = grads->dres;
     P.ld_dy = grads->ld_dy; P.ld_dx = grads->ld_dx; P.ld_dres = grads->ld_dres;
     hipStream_t st = (hipStream_t)stream;
@@ -139,4 +143,19 @@ extern "C" int ance_bias_gelu_backward(const AnceBiasGeluArgs *args, const AnceB
     launch_gelu_bwd<F32>(args->N, dim3((unsigned)n_part(args->n_rows)), st, P);
     launch_gelu_colsum(P.part, args->n_rows, args->N, grads->dbias, st);
     return check_launch(fn);
+}
+
+// The entry points: each with its sibling that takes the device dropout stream (include/ance_amd.h); the plain one passes none.
+extern "C" int ance_layer_tail_forward(const AnceLayerTailArgs *args, void *stream) {
+    return ance_layer_tail_forward_impl("ance_layer_tail_forward", args, nullptr, stream);
+}
+extern "C" int ance_layer_tail_forward_dstream(const AnceLayerTailArgs *args, const uint64_t *d_stream, void *stream) {
+    return ance_layer_tail_forward_impl("ance_layer_tail_forward_dstream", args, d_stream, stream);
+}
+extern "C" int ance_layer_tail_backward(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads, void *stream) {
+    return ance_layer_tail_backward_impl("ance_layer_tail_backward", args, grads, nullptr, stream);
+}
+extern "C" int ance_layer_tail_backward_dstream(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads,
+                                                const uint64_t *d_stream, void *stream) {
+    return ance_layer_tail_backward_impl("ance_layer_tail_backward_dstream", args, grads, d_stream, stream);
 }

@@ -44,11 +44,12 @@ const char *check_tail(const AnceLayerTail16Args *a, bool backward) {
     if (!(a->eps > 0.0f)) return "eps <= 0";
     return check_workspace(a->d_workspace, a->workspace_bytes, backward ? tail_ws_bytes(a->n_rows, a->H) : stats_bytes(a->n_rows));
 }
-TailParams16 tail_params(const AnceLayerTail16Args *a) {
+TailParams16 tail_params(const AnceLayerTail16Args *a, const uint64_t *d_stream) {
     TailParams16 P = {};
     P.x = a->x; P.res = a->res; P.bias = a->bias; P.gamma = a->gamma; P.beta = a->beta; P.y = a->y; P.y16 = a->y16;
     P.ld_x = a->ld_x; P.ld_res = a->ld_res; P.ld_y = a->ld_y; P.ld_y16 = a->ld_y16;
     fill_tail_common(P, a);
+    P.d_stream = d_stream;
     return P;
 }
 bool drops(const AnceLayerTail16Args *a) { return a->training != 0 && a->dropout_p > 0.0f; }
@@ -86,11 +87,11 @@ extern "C" size_t ance_bias_gelu16_workspace_bytes(int64_t n_rows, int N) {
     return rows_ok(n_rows) && (N == 3072 || N == 4096) ? gelu_ws_bytes(n_rows, N) : 0;
 }
 
-extern "C" int ance_layer_tail16_forward(const AnceLayerTail16Args *args, void *stream) {
+static int ance_layer_tail16_forward_impl(const char *fn, const AnceLayerTail16Args *args, const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_layer_tail16_forward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_tail(args, false)) return refuse(fn, why);
-    const TailParams16 P = tail_params(args);
+    const TailParams16 P = tail_params(args, d_stream);
     const dim3 grid((unsigned)n_part(args->n_rows));
     hipStream_t st = (hipStream_t)stream;
     if (args->dtype == ANCE_DTYPE_F16) launch_tail_fwd<F16>(args->H, drops(args), grid, st, P);
@@ -98,9 +99,10 @@ extern "C" int ance_layer_tail16_forward(const AnceLayerTail16Args *args, void *
     return check_launch(fn);
 }
 
-extern "C" int ance_layer_tail16_backward(const AnceLayerTail16Args *args, const AnceLayerTail16GradArgs *grads, void *stream) {
+static int ance_layer_tail16_backward_impl(const char *fn, const AnceLayerTail16Args *args, const AnceLayerTail16GradArgs *grads,
+                                           const uint64_t *d_stream, void *stream) {
     using namespace ance;
-    const char *fn = "ance_layer_tail16_backward";
+    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
     if (const char *why = check_tail(args, true)) return refuse(fn, why);
     if (!grads) return refuse(fn, "null pointer");
     if (!grads->dy && !grads->dy16) return refuse(fn, "null pointer: neither dy nor dy16");
@@ -111,7 +113,7 @@ extern "C" int ance_layer_tail16_backward(const AnceLayerTail16Args *args, const
     if (const char *why = check_vector(grads->dgamma, true)) return refuse(fn, why);
     if (const char *why = check_vector(grads->dbeta, true)) return refuse(fn, why);
     if (const char *why = check_vector(grads->dbias, true)) return refuse(fn, why);
-    TailParams16 P = tail_params(args);
+    TailParams16 P = tail_params(args, d_stream);
     P.dy = grads->dy; P.dy16 = grads->dy16; P.dx = grads->dx; P.dres = grads->dres;
     P.ld_dy = grads->ld_dy; P.ld_dy16 = grads->ld_dy16; P.ld_dx = grads->ld_dx; P.ld_dres = grads->ld_dres;
     const dim3 grid((unsigned)n_part(args->n_rows));
@@ -153,4 +155,19 @@ extern "C" int ance_bias_gelu16_backward(const AnceBiasGelu16Args *args, const A
     else launch_gelu_bwd<BF16>(args->N, grid, st, P);
     launch_gelu_colsum(P.part, args->n_rows, args->N, grads->dbias, st);
     return check_launch(fn);
+}
+
+// The entry points: each with its sibling that takes the device dropout stream (include/ance_amd.h); the plain one passes none.
+extern "C" int ance_layer_tail16_forward(const AnceLayerTail16Args *args, void *stream) {
+    return ance_layer_tail16_forward_impl("ance_layer_tail16_forward", args, nullptr, stream);
+}
+extern "C" int ance_layer_tail16_forward_dstream(const AnceLayerTail16Args *args, const uint64_t *d_stream, void *stream) {
+    return ance_layer_tail16_forward_impl("ance_layer_tail16_forward_dstream", args, d_stream, stream);
+}
+extern "C" int ance_layer_tail16_backward(const AnceLayerTail16Args *args, const AnceLayerTail16GradArgs *grads, void *stream) {
+    return ance_layer_tail16_backward_impl("ance_layer_tail16_backward", args, grads, nullptr, stream);
+}
+extern "C" int ance_layer_tail16_backward_dstream(const AnceLayerTail16Args *args, const AnceLayerTail16GradArgs *grads,
+                                                  const uint64_t *d_stream, void *stream) {
+    return ance_layer_tail16_backward_impl("ance_layer_tail16_backward_dstream", args, grads, d_stream, stream);
 }

@@ -26,6 +26,7 @@ struct TailParams {
     float *mean, *rstd, *part;
     float eps, keep_scale;
     uint32_t seed_lo, seed_hi, off_lo, off_hi, keep_thr;
+    const uint64_t *d_stream;  // null, or the device stream {seed, base} (philox.h: drop_stream)
 };
 
 struct GeluParams {
@@ -46,6 +47,7 @@ struct TailParams16 {
     float *mean, *rstd, *part;
     float eps, keep_scale;
     uint32_t seed_lo, seed_hi, off_lo, off_hi, keep_thr;
+    const uint64_t *d_stream;  // null, or the device stream {seed, base} (philox.h: drop_stream)
 };
 
 struct GeluParams16 {
@@ -97,10 +99,10 @@ __device__ __forceinline__ void store4_t(typename X::T *p, const f32x4 v) {
     else *reinterpret_cast<typename X::V4 *>(p) = v;
 }
 
-// z = keep o (x + bias) / (1 - p) + res of one row, and the row's keep bits (bit e of keep[i]: column 4 (64 i + lane) + e).  The
+// z = keep o (x + bias) / (1 - p) + res of one row under the stream D (resolved once at kernel entry), and the row's keep bits (bit e of keep[i]: column 4 (64 i + lane) + e).  The
 // forward and the backward both come through here, with contraction off: the same bits both times.
-template <class X, int NV, bool DROP>
-__device__ __forceinline__ void tail_z(const typename X::Tail &P, int64_t row, int lane, const f32x4 (&b)[NV], f32x4 (&z)[NV], uint32_t (&keep)[NV]) {
+template <class X, int NV, int DROP>
+__device__ __forceinline__ void tail_z(const typename X::Tail &P, const DropStream &D, int64_t row, int lane, const f32x4 (&b)[NV], f32x4 (&z)[NV], uint32_t (&keep)[NV]) {
 #pragma clang fp contract(off)
     const typename X::T *xr = rows_t<X>(P.x) + row * P.ld_x;
     const float *rr = P.res + row * P.ld_res;
@@ -112,7 +114,7 @@ __device__ __forceinline__ void tail_z(const typename X::Tail &P, int64_t row, i
         keep[i] = 0xfu;
         if (DROP) {
             uint32_t w[4];
-            philox4((uint32_t)row, (uint32_t)c4, P.off_lo, P.off_hi, P.seed_lo, P.seed_hi, w);
+            philox4((uint32_t)row, (uint32_t)c4, D.off_lo, D.off_hi, D.seed_lo, D.seed_hi, w);
             keep[i] = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -125,8 +127,9 @@ __device__ __forceinline__ void tail_z(const typename X::Tail &P, int64_t row, i
     }
 }
 
-template <class X, int NV, bool DROP>
+template <class X, int NV, int DROP>
 __global__ void __launch_bounds__(LT_THREADS) tail_fwd_kernel(const typename X::Tail P) {
+    const DropStream D = drop_stream<DROP>(P);
     constexpr float H = (float)(256 * NV);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     f32x4 b[NV], ga[NV], be[NV];
@@ -139,7 +142,7 @@ __global__ void __launch_bounds__(LT_THREADS) tail_fwd_kernel(const typename X::
         if (row >= P.n_rows) break;  // the same in every lane of the wave
         f32x4 z[NV];
         uint32_t keep[NV];
-        tail_z<X, NV, DROP>(P, row, lane, b, z, keep);
+        tail_z<X, NV, DROP>(P, D, row, lane, b, z, keep);
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) s += (z[i][0] + z[i][1]) + (z[i][2] + z[i][3]);
@@ -167,8 +170,9 @@ __global__ void __launch_bounds__(LT_THREADS) tail_fwd_kernel(const typename X::
     }
 }
 
-template <class X, int NV, bool DROP>
+template <class X, int NV, int DROP>
 __global__ void __launch_bounds__(LT_THREADS) tail_bwd_kernel(const typename X::Tail P) {
+    const DropStream D = drop_stream<DROP>(P);
     __shared__ __attribute__((aligned(16))) f32x4 sm[2 * 3 * NV * 64];
     constexpr float H = (float)(256 * NV);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -184,7 +188,7 @@ __global__ void __launch_bounds__(LT_THREADS) tail_bwd_kernel(const typename X::
         if (row >= P.n_rows) break;  // the same in every lane of the wave
         f32x4 xh[NV], g[NV];
         uint32_t keep[NV];
-        tail_z<X, NV, DROP>(P, row, lane, b, xh, keep);
+        tail_z<X, NV, DROP>(P, D, row, lane, b, xh, keep);
         const float mean = P.mean[row], rstd = P.rstd[row];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -277,28 +281,32 @@ __global__ void __launch_bounds__(LT_THREADS) gelu_bwd_kernel(const typename X::
     write_partial(sm, acc, P.part + (int64_t)blockIdx.x * (256 * NV));
 }
 
-// the launches, by width and dropout
+// the launches, by width and by how the masks are drawn (philox.h: drop_mode)
+template <class X, int DROP>
+void launch_tail_fwd_as(int H, dim3 grid, hipStream_t st, const typename X::Tail &P) {
+    const dim3 block(LT_THREADS);
+    if (H == 768) hipLaunchKernelGGL((tail_fwd_kernel<X, 3, DROP>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((tail_fwd_kernel<X, 4, DROP>), grid, block, 0, st, P);
+}
 template <class X>
 void launch_tail_fwd(int H, bool drop, dim3 grid, hipStream_t st, const typename X::Tail &P) {
+    const int mode = drop_mode(drop, P.d_stream);
+    if (mode == DROP_DEVICE) launch_tail_fwd_as<X, DROP_DEVICE>(H, grid, st, P);
+    else if (mode == DROP_HOST) launch_tail_fwd_as<X, DROP_HOST>(H, grid, st, P);
+    else launch_tail_fwd_as<X, DROP_NONE>(H, grid, st, P);
+}
+template <class X, int DROP>
+void launch_tail_bwd_as(int H, dim3 grid, hipStream_t st, const typename X::Tail &P) {
     const dim3 block(LT_THREADS);
-    if (H == 768) {
-        if (drop) hipLaunchKernelGGL((tail_fwd_kernel<X, 3, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((tail_fwd_kernel<X, 3, false>), grid, block, 0, st, P);
-    } else {
-        if (drop) hipLaunchKernelGGL((tail_fwd_kernel<X, 4, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((tail_fwd_kernel<X, 4, false>), grid, block, 0, st, P);
-    }
+    if (H == 768) hipLaunchKernelGGL((tail_bwd_kernel<X, 3, DROP>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((tail_bwd_kernel<X, 4, DROP>), grid, block, 0, st, P);
 }
 template <class X>
 void launch_tail_bwd(int H, bool drop, dim3 grid, hipStream_t st, const typename X::Tail &P) {
-    const dim3 block(LT_THREADS);
-    if (H == 768) {
-        if (drop) hipLaunchKernelGGL((tail_bwd_kernel<X, 3, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((tail_bwd_kernel<X, 3, false>), grid, block, 0, st, P);
-    } else {
-        if (drop) hipLaunchKernelGGL((tail_bwd_kernel<X, 4, true>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((tail_bwd_kernel<X, 4, false>), grid, block, 0, st, P);
-    }
+    const int mode = drop_mode(drop, P.d_stream);
+    if (mode == DROP_DEVICE) launch_tail_bwd_as<X, DROP_DEVICE>(H, grid, st, P);
+    else if (mode == DROP_HOST) launch_tail_bwd_as<X, DROP_HOST>(H, grid, st, P);
+    else launch_tail_bwd_as<X, DROP_NONE>(H, grid, st, P);
 }
 template <class X>
 void launch_gelu_fwd(int N, dim3 grid, hipStream_t st, const typename X::Gelu &P) {

@@ -183,12 +183,20 @@ inline Staged staged(size_t group_row_bytes, int n_tensors, int n_groups, int64_
     return L;
 }
 
-// the three tables filled in a pinned staging buffer -- group row i by group_row(row, h_groups[i]) -- and sent to d_workspace on
-// st.  ANCE_OK or an error in fn's name
+// a group row's fill: the host hyper-parameters and d_lr, the group's learning rate as a DEVICE fp64 scalar (null: a.lr holds it)
+typedef void (*GroupRowFn)(void *row, const AnceLambGroup &a, const double *d_lr);
+
+// the three tables in the layout L at h (host memory of L.end bytes): group row i by group_row(row, h_groups[i], d_lrs ? d_lrs[i] :
+// null), the DevTensor rows and the chunk map.  Pure host code: what a resident plan keeps and what stage_tables sends
+template <class Host>
+void fill_tables(const Host *h_tensors, int n_tensors, const AnceLambGroup *h_groups, const double *const *d_lrs, int n_groups,
+                 size_t group_row_bytes, GroupRowFn group_row, const Staged &L, char *h);
+
+// fill_tables in a pinned staging buffer of the shared pool, sent to d_workspace on st.  ANCE_OK or an error in fn's name.  Not
+// capturable (the pool queries and waits for events and may allocate): a captured step goes through a resident plan instead
 template <class Host>
 int stage_tables(const char *fn, const Host *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups,
-                 size_t group_row_bytes, void (*group_row)(void *row, const AnceLambGroup &a), const Staged &L, void *d_workspace,
-                 hipStream_t st);
+                 size_t group_row_bytes, GroupRowFn group_row, const Staged &L, void *d_workspace, hipStream_t st);
 
 // gnorm: one workgroup per chunk reads g only; the chunk's sum of g^2 in fp64 -> gpartial[chunk].  grad_scale (nullable): of
 // (g * inv)^2, the fp32 product squared

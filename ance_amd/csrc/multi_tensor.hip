@@ -1,6 +1,7 @@
 // The host side of what the fused multi-tensor optimizer steps share (multi_tensor.h; lamb.hip, adamw.hip): the checks of a host
-// table and its chunk count, the fill of the device tables in a pinned staging buffer and their one copy to the workspace, the pool
-// of those buffers, and the gradient-norm pass in front of a clipped step.
+// table and its chunk count, the fill of the device tables (into a resident plan's own buffer, or into a pinned staging buffer of
+// the pool here with their one copy to the workspace), the pool of those buffers, and the gradient-norm pass in front of a clipped
+// step.
 #include "multi_tensor.h"
 
 #include <mutex>
@@ -26,6 +27,7 @@ struct Staging {
 std::mutex g_stage_mu;
 std::vector<Staging> g_stage;
 unsigned long long g_stage_clock = 0;
+long long g_stage_sends = 0;  // copies sent from the pool since the library was loaded (ance_debug_staging_sends)
 
 // under g_stage_mu; returns the index of a buffer of >= bytes whose previous copy has run, or -1 (out of memory)
 int stage_acquire(size_t bytes) {
@@ -65,6 +67,7 @@ int stage_send(Staging &S, void *d_dst, size_t bytes, hipStream_t st) {
     if (hipEventRecord(S.ev, st) != hipSuccess) return 2;
     S.recorded = true;
     S.last_use = ++g_stage_clock;
+    ++g_stage_sends;
     return 0;
 }
 
@@ -113,20 +116,9 @@ int count_chunks(const char *fn, const Host *h_tensors, int n_tensors, int n_gro
 }
 
 template <class Host>
-int stage_tables(const char *fn, const Host *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups,
-                 size_t group_row_bytes, void (*group_row)(void *row, const AnceLambGroup &a), const Staged &L, void *d_workspace,
-                 hipStream_t st) {
-    char what[96];
-    std::lock_guard<std::mutex> lock(g_stage_mu);
-    const int si = stage_acquire(L.end);
-    if (si < 0) {
-        snprintf(what, sizeof(what), "%s: pinned staging buffer", fn);
-        set_last_error(what);
-        return ANCE_E_NOMEM;
-    }
-    Staging &S = g_stage[si];
-    char *h = (char *)S.h;
-    for (int i = 0; i < n_groups; ++i) group_row(h + group_row_bytes * (size_t)i, h_groups[i]);
+void fill_tables(const Host *h_tensors, int n_tensors, const AnceLambGroup *h_groups, const double *const *d_lrs, int n_groups,
+                 size_t group_row_bytes, GroupRowFn group_row, const Staged &L, char *h) {
+    for (int i = 0; i < n_groups; ++i) group_row(h + group_row_bytes * (size_t)i, h_groups[i], d_lrs ? d_lrs[i] : nullptr);
     DevTensor *T = (DevTensor *)(h + L.tensors);
     int32_t *ct = (int32_t *)(h + L.chunk_tensor);
     int32_t c = 0;
@@ -144,6 +136,21 @@ int stage_tables(const char *fn, const Host *h_tensors, int n_tensors, const Anc
         T[t].vec = ((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) % 16 == 0;
         for (int32_t k = 0; k < T[t].n_chunks; ++k) ct[c++] = t;
     }
+}
+
+template <class Host>
+int stage_tables(const char *fn, const Host *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups,
+                 size_t group_row_bytes, GroupRowFn group_row, const Staged &L, void *d_workspace, hipStream_t st) {
+    char what[96];
+    std::lock_guard<std::mutex> lock(g_stage_mu);
+    const int si = stage_acquire(L.end);
+    if (si < 0) {
+        snprintf(what, sizeof(what), "%s: pinned staging buffer", fn);
+        set_last_error(what);
+        return ANCE_E_NOMEM;
+    }
+    Staging &S = g_stage[si];
+    fill_tables(h_tensors, n_tensors, h_groups, nullptr, n_groups, group_row_bytes, group_row, L, (char *)S.h);
     const int sent = stage_send(S, d_workspace, L.end, st);
     if (!sent) return ANCE_OK;
     snprintf(what, sizeof(what), sent == 1 ? "%s: tables" : "%s: staging event", fn);
@@ -152,10 +159,14 @@ int stage_tables(const char *fn, const Host *h_tensors, int n_tensors, const Anc
 
 template int count_chunks(const char *, const AnceLambTensor *, int, int, int64_t *);
 template int count_chunks(const char *, const AnceAdamwTensor *, int, int, int64_t *);
-template int stage_tables(const char *, const AnceLambTensor *, int, const AnceLambGroup *, int, size_t,
-                          void (*)(void *, const AnceLambGroup &), const Staged &, void *, hipStream_t);
-template int stage_tables(const char *, const AnceAdamwTensor *, int, const AnceLambGroup *, int, size_t,
-                          void (*)(void *, const AnceLambGroup &), const Staged &, void *, hipStream_t);
+template void fill_tables(const AnceLambTensor *, int, const AnceLambGroup *, const double *const *, int, size_t, GroupRowFn,
+                          const Staged &, char *);
+template void fill_tables(const AnceAdamwTensor *, int, const AnceLambGroup *, const double *const *, int, size_t, GroupRowFn,
+                          const Staged &, char *);
+template int stage_tables(const char *, const AnceLambTensor *, int, const AnceLambGroup *, int, size_t, GroupRowFn, const Staged &,
+                          void *, hipStream_t);
+template int stage_tables(const char *, const AnceAdamwTensor *, int, const AnceLambGroup *, int, size_t, GroupRowFn, const Staged &,
+                          void *, hipStream_t);
 
 void launch_gnorm(int64_t n_chunks, hipStream_t st, const DevTensor *tensors, const int32_t *chunk_tensor, double *gpartial,
                   const float *grad_scale) {
@@ -168,3 +179,9 @@ void launch_gnorm(int64_t n_chunks, hipStream_t st, const DevTensor *tensors, co
 
 }  // namespace mt
 }  // namespace ance
+
+// how many table uploads have gone through the shared staging pool: a step through a resident plan adds none
+extern "C" long long ance_debug_staging_sends(void) {
+    std::lock_guard<std::mutex> lock(ance::mt::g_stage_mu);
+    return ance::mt::g_stage_sends;
+}

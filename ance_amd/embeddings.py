@@ -22,7 +22,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .attention import _custom_bwd, _custom_fwd, dropout_state
+from .attention import _NO_DRAW, _custom_bwd, _custom_fwd, dropout_state
 from .layers import TAIL_WIDTHS, _check_vector, _ptr, _stats_floats, _vector
 
 __all__ = ["bert_embeddings", "BertEmbeddings"]
@@ -62,17 +62,17 @@ class _BertEmbeddings(torch.autograd.Function):
         stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=dev)
         positions = torch.empty(n_rows, dtype=torch.int32, device=dev) if mode == 1 else None
         drop = bool(training) and dropout_p > 0.0
-        seed, offset = dropout_state.next_pair(dev) if drop else (0, 0)
+        draw = dropout_state.draw(dev) if drop else _NO_DRAW
         args = _lib.AnceEmbedArgs(ids=ids.data_ptr(), type_ids=_ptr(types), word=word.data_ptr(), pos=position.data_ptr(),
                                   type=token_type.data_ptr(), gamma=weight.data_ptr(), beta=beta.data_ptr(), y=y.data_ptr(),
                                   positions=_ptr(positions), n_seq=n_seq, L=seq_len, H=H, vocab=word.shape[0],
                                   max_pos=position.shape[0], n_types=token_type.shape[0], position_mode=mode, padding_idx=padding_idx,
-                                  eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed, offset=offset,
-                                  d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
+                                  eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed,
+                                  offset=draw.offset, d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
         with torch.cuda.device(dev):
-            _lib.check(L.ance_embed_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_embed_forward")
+            draw.launch("ance_embed_forward", ctypes.byref(args))
         ctx.save_for_backward(word, position, token_type, weight, ids, types, positions, stats)
-        ctx.args = args
+        ctx.args, ctx.draw = args, draw
         return y
 
     @staticmethod
@@ -107,7 +107,7 @@ class _BertEmbeddings(torch.autograd.Function):
                                    dbeta=_ptr(dbeta), word_keys=_ptr(wk), word_perm=_ptr(wp), pos_keys=_ptr(pk), pos_perm=_ptr(pp),
                                    type_keys=_ptr(tk), type_perm=_ptr(tp))
         with torch.cuda.device(dev):
-            _lib.check(L.ance_embed_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_embed_backward")
+            ctx.draw.launch("ance_embed_backward", ctypes.byref(a), ctypes.byref(g))
         return dword, dpos, dtype, dgamma, dbeta, None, None, None, None, None, None, None
 
 

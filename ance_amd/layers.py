@@ -12,8 +12,9 @@ bias) are column sums without atomics: the same inputs give the same bits.
 
 Dropout draws its (seed, offset) from ``ance_amd.attention.dropout_state`` -- the one stream that ``attention.manual_seed`` seeds and
 that every dropout forward, the attention's included, advances by one, so no two calls share a pair.  A call with ``training`` false
-or ``dropout_p == 0`` draws nothing.  Both are HOST values baked into the launch: a captured graph replays the pair it was captured
-with -- the same mask at every replay.  The masks are not torch's.
+or ``dropout_p == 0`` draws nothing.  By default both are HOST values baked into the launch: a captured graph replays the pair it was
+captured with -- the same mask at every replay; ``dropout_state.to_device()`` moves the stream to the device, where a replayed
+step draws the masks of the step it stands for (ance_amd/attention.py).  The masks are not torch's.
 
 ``precision="half"`` (both functions; ``BertLayer(..., precision="half")``) is the form for ``torch.autocast`` (csrc/layer_tail_half.hip
 behind ance_layer_tail16_* / ance_bias_gelu16_*): the dense outputs go in as fp16 / bf16, the residual stream, ``y`` and every
@@ -25,8 +26,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .attention import (HALF_DTYPES, _check_precision, _custom_bwd, _custom_fwd, _custom_fwd_as_is, _rows, _rows16, attention_padded,
-                        dropout_state)
+from .attention import (_NO_DRAW, HALF_DTYPES, _check_precision, _custom_bwd, _custom_fwd, _custom_fwd_as_is, _rows, _rows16,
+                        attention_padded, dropout_state)
 
 __all__ = ["dropout_add_layer_norm", "bias_gelu", "BertLayer"]
 
@@ -91,15 +92,15 @@ class _DropoutAddLayerNorm(torch.autograd.Function):
         y = torch.empty(shape, dtype=torch.float32, device=x.device)
         stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=x.device)
         drop = bool(training) and dropout_p > 0.0
-        seed, offset = dropout_state.next_pair(x.device) if drop else (0, 0)
+        draw = dropout_state.draw(x.device) if drop else _NO_DRAW
         args = _lib.AnceLayerTailArgs(x=x.data_ptr(), res=residual.data_ptr(), bias=_ptr(bias), gamma=weight.data_ptr(),
                                       beta=beta.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_res=ld_r, ld_y=H, H=H, n_rows=n_rows,
-                                      eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=seed, offset=offset,
-                                      d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
+                                      eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed,
+                                      offset=draw.offset, d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
         with torch.cuda.device(x.device):
-            _lib.check(L.ance_layer_tail_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_layer_tail_forward")
+            draw.launch("ance_layer_tail_forward", ctypes.byref(args))
         ctx.save_for_backward(x, residual, bias, weight, stats)
-        ctx.args = args
+        ctx.args, ctx.draw = args, draw
         ctx.shape = shape
         return y
 
@@ -127,7 +128,7 @@ class _DropoutAddLayerNorm(torch.autograd.Function):
         g = _lib.AnceLayerTailGradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dres=_ptr(dres), dgamma=_ptr(dgamma), dbeta=_ptr(dbeta),
                                        dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=H, ld_dres=H)
         with torch.cuda.device(x.device):
-            _lib.check(L.ance_layer_tail_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_layer_tail_backward")
+            ctx.draw.launch("ance_layer_tail_backward", ctypes.byref(a), ctypes.byref(g))
         return dx, dbias, dres, dgamma, dbeta, None, None, None
 
 
@@ -197,16 +198,16 @@ class _DropoutAddLayerNormHalf(torch.autograd.Function):
         y16 = torch.empty(shape, dtype=x.dtype, device=x.device) if want_half else None
         stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=x.device)
         drop = bool(training) and dropout_p > 0.0
-        seed, offset = dropout_state.next_pair(x.device) if drop else (0, 0)
+        draw = dropout_state.draw(x.device) if drop else _NO_DRAW
         args = _lib.AnceLayerTail16Args(x=x.data_ptr(), res=residual.data_ptr(), bias=_ptr(bias), gamma=weight.data_ptr(),
                                         beta=beta.data_ptr(), y=y.data_ptr(), y16=_ptr(y16), ld_x=ld_x, ld_res=ld_r, ld_y=H, ld_y16=H,
                                         H=H, n_rows=n_rows, dtype=HALF_DTYPES[x.dtype], eps=float(eps), dropout_p=float(dropout_p),
-                                        training=1 if drop else 0, seed=seed, offset=offset, d_workspace=stats.data_ptr(),
+                                        training=1 if drop else 0, seed=draw.seed, offset=draw.offset, d_workspace=stats.data_ptr(),
                                         workspace_bytes=stats.numel() * 4)
         with torch.cuda.device(x.device):
-            _lib.check(L.ance_layer_tail16_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_layer_tail16_forward")
+            draw.launch("ance_layer_tail16_forward", ctypes.byref(args))
         ctx.save_for_backward(x, residual, bias, weight, stats)
-        ctx.args = args
+        ctx.args, ctx.draw = args, draw
         ctx.shape = shape
         ctx.set_materialize_grads(False)   # a missing gradient stays None: the kernel reads only those that exist
         return (y, y16) if want_half else y
@@ -240,8 +241,7 @@ class _DropoutAddLayerNormHalf(torch.autograd.Function):
         g = _lib.AnceLayerTail16GradArgs(dy=_ptr(dy), dy16=_ptr(dy16), dx=_ptr(dx), dres=_ptr(dres), dgamma=_ptr(dgamma),
                                          dbeta=_ptr(dbeta), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dy16=ld_dy16, ld_dx=H, ld_dres=H)
         with torch.cuda.device(x.device):
-            _lib.check(L.ance_layer_tail16_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()),
-                       "ance_layer_tail16_backward")
+            ctx.draw.launch("ance_layer_tail16_backward", ctypes.byref(a), ctypes.byref(g))
         return dx, dbias, dres, dgamma, dbeta, None, None, None, None
 
 

@@ -57,10 +57,17 @@ def _ptr(t):
 
 
 class _Call(object):
-    """What ``_FusedOptimizer.step`` hands to a subclass's ``_launch``: the library, the two host tables as the leading arguments
-    of every step entry point (``tab``), the workspace and the stream, the scaler's tensors and what is stepped
+    """What ``_FusedOptimizer.step`` hands to a subclass's ``_launch``: the library, the resident plan (``plan``: its sizes are the
+    leading arguments of every planned entry point, ``tab``), the workspace and the stream, the scaler's tensors and what is stepped
     (``todo``: [(parameter, gradient, group index, state)]; ``group0``: the group of the first of them)."""
-    __slots__ = ("L", "tab", "n", "device", "ws", "stream", "clip", "amp", "grad_scale", "found_inf", "todo", "group0")
+    __slots__ = ("L", "tab", "n", "device", "ws", "stream", "clip", "amp", "grad_scale", "found_inf", "todo", "group0", "plan")
+
+
+class _Plan(object):
+    """The resident plan of a step: ``key`` (everything the device tables hold), ``ws`` (the device workspace the plan owns, the
+    tables at its head), ``pinned`` (the host buffer they were uploaded from: never refilled while the plan lives, so a copy that
+    a graph captured re-reads identical bytes) and the tables' sizes.  ``captured``: built or used while a graph was capturing."""
+    __slots__ = ("key", "ws", "pinned", "n", "n_groups", "n_chunks", "captured", "lr_tensors")
 
 
 class _FusedOptimizer(Optimizer):
@@ -69,6 +76,76 @@ class _FusedOptimizer(Optimizer):
     ``_check_state``), its workspace size and its library call (``_launch``)."""
     _step_supports_amp_scaling = True  # torch.amp.GradScaler.step: attach grad_scale / found_inf and call step() unconditionally
     _STATE_TENSORS = (('exp_avg', " state['exp_avg']"), ('exp_avg_sq', " state['exp_avg_sq']"))   # checked in this order
+    _PINNED_MIN = 65536
+
+    # ---- the resident plan.  The device tables of a step (tensor rows, chunk map, group rows) are built once and live in memory
+    # the plan owns; a step whose key -- every pointer and numel, every group hyper-parameter but a device lr, the clip, amp and
+    # subclass flags -- equals the plan's builds no table, copies nothing and enqueues only its kernels.  Any difference rebuilds.
+    def _plan_init(self):
+        self._plan = None
+        self._kept_plans = []    # plans a captured graph may still refer to: alive as long as the optimizer is
+        self._spare_pinned = None  # allocated outside capture, so that a rebuild during capture allocates no pinned memory
+
+    def invalidate_plan(self):
+        """Drops the resident plan: the next ``step()`` rebuilds it.  Needed only when something the plan cannot see changed.  A
+        graph captured earlier keeps replaying the plan it captured (which stays alive as long as this optimizer does) --
+        re-capturing after ``invalidate_plan()`` is the caller's job."""
+        plan = self._plan
+        if plan is not None and plan.captured:
+            self._kept_plans.append(plan)
+        self._plan = None
+
+    def _take_pinned(self, nbytes, capturing):
+        spare = self._spare_pinned
+        if spare is not None and spare.numel() >= nbytes:
+            buf, self._spare_pinned = spare, None
+        else:
+            size = self._PINNED_MIN
+            while size < nbytes:
+                size <<= 1
+            buf = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        if not capturing and self._spare_pinned is None:
+            self._spare_pinned = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
+        return buf
+
+    def _build_plan(self, key, rows, groups, lrs, c, capturing):
+        L, n_groups = c.L, len(groups)
+        tensors = np.array(rows, dtype=self._TENSOR_DTYPE)
+        gtab = np.array(groups, dtype=_GROUP_DTYPE)
+        total = int(tensors["numel"].sum())
+        need = self._workspace_bytes(c, n_groups, total)
+        table_bytes = getattr(L, self._PLAN + "_plan_table_bytes")(c.n, n_groups, total)
+        if need == 0 or table_bytes == 0:
+            raise _lib.AnceLibraryError("%s: %d tensors of %d elements exceed %s's limits" % (self._name, c.n, total, self._ENTRY))
+        self.invalidate_plan()
+        plan = _Plan()
+        plan.key, plan.n, plan.n_groups, plan.captured = key, c.n, n_groups, capturing
+        plan.lr_tensors = [lr for lr in lrs if lr is not None]   # the plan holds their pointers
+        plan.pinned = self._take_pinned(table_bytes, capturing)
+        plan.ws = torch.empty(need, dtype=torch.uint8, device=c.device)   # torch's allocator: a graph's own pool while capturing
+        d_lrs = None
+        if plan.lr_tensors:
+            d_lrs = (ctypes.c_void_p * n_groups)(*[None if lr is None else lr.data_ptr() for lr in lrs])
+        n_chunks, filled = ctypes.c_int64(0), ctypes.c_size_t(0)
+        _lib.check(getattr(L, self._PLAN + "_plan_build")(tensors.ctypes.data_as(ctypes.POINTER(self._TENSOR_CTYPE)), c.n,
+                                                          gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), d_lrs, n_groups,
+                                                          ctypes.c_void_p(plan.pinned.data_ptr()), plan.pinned.numel(),
+                                                          ctypes.byref(n_chunks), ctypes.byref(filled)), self._PLAN + "_plan_build")
+        plan.n_chunks = n_chunks.value
+        plan.ws[:filled.value].copy_(plan.pinned[:filled.value], non_blocking=True)   # the one upload of the plan's life
+        self._plan = plan
+        self._workspace[c.device] = plan.ws
+        return plan
+
+    def _group_lr(self, gi, group):
+        """(the host lr, None) or (0.0, the device lr): a 0-dim float64 CUDA tensor, as torch's capturable optimizers accept."""
+        lr = group['lr']
+        if not isinstance(lr, torch.Tensor):
+            return float(lr), None
+        if not lr.is_cuda or lr.dtype != torch.float64 or lr.numel() != 1:
+            raise _lib.AnceLibraryError("%s: param_groups[%d]['lr'] as a tensor must be a 0-dim float64 CUDA tensor, got %s %s on %s"
+                                        % (self._name, gi, tuple(lr.shape), lr.dtype, lr.device))
+        return 0.0, lr
 
     def _amp_scalar(self, name, device):
         """optimizer.grad_scale / optimizer.found_inf as GradScaler attaches them: None, or a one-element fp32 tensor on the step's
@@ -104,13 +181,16 @@ class _FusedOptimizer(Optimizer):
                                         % (name, tuple(m.shape), tuple(v.shape), tuple(p.shape)))
 
     def _walk(self):
-        """([(parameter, gradient, group index, its state or None)] of the parameters that have a gradient, the group table, their
-        device).  Checks everything and changes nothing: a refused step leaves no entry in ``self.state`` behind."""
-        todo, groups, device, first_group = [], [], None, None
+        """([(parameter, gradient, group index, its state or None)] of the parameters that have a gradient, the group table, the
+        groups' device learning rates (None where the lr is a host number), their device).  Checks everything and changes nothing:
+        a refused step leaves no entry in ``self.state`` behind."""
+        todo, groups, lrs, device, first_group = [], [], [], None, None
         checked, check_state, state_of = self._checked, self._check_state, self.state.get   # .get: no entry is created
         for gi, group in enumerate(self.param_groups):
             beta1, beta2 = group['betas']
-            groups.append((float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay'])))
+            lr, d_lr = self._group_lr(gi, group)
+            lrs.append(d_lr)
+            groups.append((lr, float(beta1), float(beta2), float(group['eps']), float(group['weight_decay'])))
             group_checked = False
             for pi, p in enumerate(group['params']):
                 if p.grad is None:
@@ -133,7 +213,11 @@ class _FusedOptimizer(Optimizer):
                 if state:
                     check_state(state, name, p, device)
                 todo.append((p, grad, gi, state))
-        return todo, groups, device
+        for gi, lr in enumerate(lrs):
+            if lr is not None and device is not None and lr.device != device:
+                raise _lib.AnceLibraryError("%s: param_groups[%d]['lr'] is on %s, the parameters of this step on %s (mixed devices)"
+                                            % (self._name, gi, lr.device, device))
+        return todo, groups, lrs, device
 
     def step(self, closure=None):
         """One step of every parameter that has a gradient.  Asynchronous: enqueued on the current stream, no host wait -- also
@@ -142,7 +226,7 @@ class _FusedOptimizer(Optimizer):
         if closure is not None:
             loss = closure()
 
-        todo, groups, device = self._walk()
+        todo, groups, lrs, device = self._walk()
         if not todo:
             return loss
         c = _Call()
@@ -158,23 +242,20 @@ class _FusedOptimizer(Optimizer):
         rows = self._rows(todo)
 
         c.L = _lib.lib()
-        tensors = np.array(rows, dtype=self._TENSOR_DTYPE)
-        gtab = np.array(groups, dtype=_GROUP_DTYPE)
-        total = int(tensors["numel"].sum())
         c.n, c.device, c.clip = len(rows), device, self.max_grad_norm is not None
-        need = self._workspace_bytes(c, len(groups), total)
-        if need == 0:
-            raise _lib.AnceLibraryError("%s: %d tensors of %d elements exceed %s's limits" % (self._name, c.n, total, self._ENTRY))
+        key = (rows, groups, [None if lr is None else lr.data_ptr() for lr in lrs], c.clip, c.amp, self._plan_flags(c), device)
+        capturing = torch.cuda.is_current_stream_capturing()
         with torch.cuda.device(device):
-            c.ws = self._workspace.get(device)
-            if c.ws is None or c.ws.numel() < need:
-                c.ws = torch.empty(need, dtype=torch.uint8, device=device)
-                self._workspace[device] = c.ws
+            plan = self._plan
+            if plan is None or plan.key != key:
+                plan = self._build_plan(key, rows, groups, lrs, c, capturing)
+            elif capturing:
+                plan.captured = True
+            c.plan, c.ws = plan, plan.ws
             if c.amp and (self.skipped_steps is None or self.skipped_steps.device != device):
                 self.skipped_steps = torch.zeros((), dtype=torch.int64, device=device)
             c.stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            c.tab = (tensors.ctypes.data_as(ctypes.POINTER(self._TENSOR_CTYPE)), c.n,
-                     gtab.ctypes.data_as(ctypes.POINTER(_lib.AnceLambGroup)), len(groups))
+            c.tab = (plan.n, plan.n_groups, plan.n_chunks)
             self._launch(c)
         return loss
 
@@ -209,12 +290,12 @@ class Lamb(_FusedOptimizer):
     poisons the step.
     """
     _name = "Lamb"  # in front of every AnceLibraryError
-    _ENTRY = "ance_lamb_step"
+    _ENTRY, _PLAN = "ance_lamb_step", "ance_lamb"
     _SPARSE = 'Lamb does not support sparse gradients, consider SparseAdam instad.'
     _TENSOR_DTYPE, _TENSOR_CTYPE = _TENSOR_DTYPE, _lib.AnceLambTensor
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, adam=False, max_grad_norm=None):
-        if not 0.0 <= lr:
+        if not isinstance(lr, torch.Tensor) and not 0.0 <= lr:   # a device lr is not read back: that would be a host wait
             raise ValueError("Invalid learning rate: {}".format(lr))
         if not 0.0 <= eps:
             raise ValueError("Invalid epsilon value: {}".format(eps))
@@ -230,7 +311,11 @@ class Lamb(_FusedOptimizer):
         self.skipped_steps = None
         super(Lamb, self).__init__(params, defaults)
         self._workspace = {}
+        self._plan_init()
         self._prev_out = None  # (out of the last step, the ids of the parameters its rows belong to)
+
+    def _plan_flags(self, c):
+        return bool(self.adam)
 
     def _init_state(self, state, p):
         state['step'] = 0
@@ -250,17 +335,12 @@ class Lamb(_FusedOptimizer):
         L, device, clip = c.L, c.device, c.clip
         stepped = [id(t[0]) for t in c.todo]
         out = torch.empty((c.n, 3), dtype=torch.float32, device=device)
-        tab = c.tab + (1 if self.adam else 0,)
-        tail = (ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), c.stream)
         norm = torch.empty((1,), dtype=torch.float32, device=device) if clip else None
-        if c.amp:
-            prev = self._prev_out[0] if self._prev_out is not None and self._prev_out[1] == stepped else None
-            _lib.check(L.ance_lamb_step_amp(*tab, self.max_grad_norm if clip else 0.0, _ptr(c.grad_scale), _ptr(c.found_inf), _ptr(prev),
-                                            _ptr(norm), _ptr(self.skipped_steps), *tail), "ance_lamb_step_amp")
-        elif clip:
-            _lib.check(L.ance_lamb_step_clipped(*tab, self.max_grad_norm, _ptr(norm), *tail), "ance_lamb_step_clipped")
-        else:
-            _lib.check(L.ance_lamb_step(*tab, *tail), "ance_lamb_step")
+        prev = self._prev_out[0] if c.amp and self._prev_out is not None and self._prev_out[1] == stepped else None
+        _lib.check(L.ance_lamb_step_planned(*c.tab, 1 if self.adam else 0, self.max_grad_norm if clip else 0.0, _ptr(c.grad_scale),
+                                            _ptr(c.found_inf), _ptr(prev), _ptr(norm), _ptr(self.skipped_steps if c.amp else None),
+                                            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), c.stream),
+                   "ance_lamb_step_planned")
         if clip:
             self.last_grad_norm = norm[0]
         self._prev_out = (out, stepped)
@@ -305,13 +385,13 @@ class AdamW(_FusedOptimizer):
     No CPU fallback: every parameter, gradient and state tensor must be a contiguous fp32 tensor on one HIP device.
     """
     _name = "AdamW"
-    _ENTRY = "ance_adamw_step"
+    _ENTRY, _PLAN = "ance_adamw_step", "ance_adamw"
     _SPARSE = 'Adam does not support sparse gradients, please consider SparseAdam instead'
     _TENSOR_DTYPE, _TENSOR_CTYPE = _ADAMW_TENSOR_DTYPE, _lib.AnceAdamwTensor
     _STATE_TENSORS = _FusedOptimizer._STATE_TENSORS + (('step', " state['step']"),)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, max_grad_norm=None):
-        if lr < 0.0:
+        if not isinstance(lr, torch.Tensor) and lr < 0.0:   # a device lr is not read back: that would be a host wait
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if not 0.0 <= betas[0] < 1.0:
             raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
@@ -325,6 +405,10 @@ class AdamW(_FusedOptimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
         super(AdamW, self).__init__(params, defaults)
         self._workspace = {}
+        self._plan_init()
+
+    def _plan_flags(self, c):
+        return bool(c.group0['correct_bias'])
 
     def state_dict(self):
         """The reference's layout: ``step`` a Python int.  One device read for all of them."""
@@ -374,8 +458,77 @@ class AdamW(_FusedOptimizer):
     def _launch(self, c):
         """A skipped step is skipped on the device, its step counts included."""
         norm = torch.empty((1,), dtype=torch.float32, device=c.device) if c.clip else None
-        _lib.check(c.L.ance_adamw_step(*c.tab, 1 if c.group0['correct_bias'] else 0, self.max_grad_norm if c.clip else 0.0, _ptr(c.grad_scale),
-                                       _ptr(c.found_inf), _ptr(norm), _ptr(self.skipped_steps if c.amp else None),
-                                       ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), c.stream), "ance_adamw_step")
+        _lib.check(c.L.ance_adamw_step_planned(*c.tab, 1 if c.group0['correct_bias'] else 0, self.max_grad_norm if c.clip else 0.0,
+                                               _ptr(c.grad_scale), _ptr(c.found_inf), _ptr(norm),
+                                               _ptr(self.skipped_steps if c.amp else None), ctypes.c_void_p(c.ws.data_ptr()),
+                                               c.ws.numel(), c.stream), "ance_adamw_step_planned")
         if c.clip:
             self.last_grad_norm = norm[0]
+
+
+class LinearWarmupSchedule(object):
+    r"""``transformers.get_linear_schedule_with_warmup(optimizer, num_warmup_steps, num_training_steps)`` on the device: the schedule
+    every trainer of the reference steps after ``optimizer.step()`` (drivers/run_ann.py:175,290, run_warmup.py:87,218,
+    run_ann_dpr.py:110,240), with the step count and every group's learning rate in device memory, so that a captured training
+    step carries its schedule and a replay applies the lr of the step it stands for.
+
+    Construction turns every ``param_groups[i]['lr']`` into a 0-dim float64 device tensor (views of one array; ``Lamb`` and ``AdamW``
+    read them at every step with no rebuild of their plan), keeps ``base_lrs`` and applies ``n = 0`` as ``LambdaLR`` does.
+    ``step()`` is ONE launch (csrc/lr_schedule.hip), capturable and without a host wait: ``n += 1``, then
+    ``lr_g = base_g * lambda(n)`` in fp64, ``lambda(n) = n / max(1, warm)`` below ``warm``, else
+    ``max(0, (total - n) / max(1, total - warm))`` -- the values ``LambdaLR`` holds, bit for bit.  The count advances on every call,
+    also after a step the scaler skipped, as the reference's ``scheduler.step()`` does.
+    ``get_last_lr()``, ``state_dict()`` and ``load_state_dict()`` each take one device read: off the step path."""
+
+    def __init__(self, optimizer, num_warmup_steps, num_training_steps, device=None):
+        self.optimizer = optimizer
+        self.num_warmup_steps, self.num_training_steps = int(num_warmup_steps), int(num_training_steps)
+        groups = optimizer.param_groups
+        if device is None:
+            found = [p.device for g in groups for p in g['params']]
+            if not found or not found[0].type == "cuda":
+                raise _lib.AnceLibraryError("LinearWarmupSchedule: the optimizer's parameters must be on a HIP device")
+            device = found[0]
+        self.device = torch.device(device)
+        base = []
+        for g in groups:
+            lr = g.get('initial_lr', g['lr'])
+            base.append(float(lr))   # a tensor lr is read back here, once
+            g.setdefault('initial_lr', base[-1])
+        self.base_lrs = base
+        self._base = torch.tensor(base, dtype=torch.float64, device=self.device)
+        self._lrs = torch.zeros(len(base), dtype=torch.float64, device=self.device)
+        self._n = torch.full((), -1, dtype=torch.int64, device=self.device)
+        for k, g in enumerate(groups):
+            g['lr'] = self._lrs[k]
+        self.step()   # n = 0
+
+    def step(self):
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ance_linear_warmup_step(ctypes.c_void_p(self._n.data_ptr()), ctypes.c_void_p(self._base.data_ptr()),
+                                                          ctypes.c_void_p(self._lrs.data_ptr()), len(self.base_lrs), self.num_warmup_steps,
+                                                          self.num_training_steps, _lib.current_stream_ptr()),
+                       "ance_linear_warmup_step")
+
+    def get_last_lr(self):
+        """The groups' current learning rates as Python floats: one device read."""
+        return self._lrs.tolist()
+
+    def state_dict(self):
+        """``LambdaLR``'s entries that matter: ``last_epoch``, ``base_lrs``, ``_last_lr``.  One device read."""
+        vals = torch.cat([self._n.reshape(1).to(torch.float64), self._lrs]).tolist()
+        return dict(last_epoch=int(vals[0]), base_lrs=list(self.base_lrs), _last_lr=vals[1:],
+                    num_warmup_steps=self.num_warmup_steps, num_training_steps=self.num_training_steps)
+
+    def load_state_dict(self, state_dict):
+        """Takes this class's and ``LambdaLR``'s state dicts: the count and the base lrs; the learning rates follow from them."""
+        base = [float(x) for x in state_dict.get("base_lrs", self.base_lrs)]
+        if len(base) != len(self.base_lrs):
+            raise ValueError("loaded state dict has %d base_lrs, the optimizer %d groups" % (len(base), len(self.base_lrs)))
+        self.num_warmup_steps = int(state_dict.get("num_warmup_steps", self.num_warmup_steps))
+        self.num_training_steps = int(state_dict.get("num_training_steps", self.num_training_steps))
+        self.base_lrs = base
+        self._base.copy_(torch.tensor(base, dtype=torch.float64))
+        self._n.fill_(int(state_dict["last_epoch"]) - 1)
+        self.step()
+

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_* only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -361,6 +361,16 @@ int ance_inbatch_nll_backward(const float *d_q, const float *d_ctx, const int64_
  * Dropout: Philox4x32-10 with key (seed lo32, seed hi32) and counter (i * 128 + (j >> 2), s * n_heads + h, offset lo32, offset
  * hi32) for query i and key j inside sequence s; output word j & 3 decides key j: keep iff word >= floor(dropout_p * 2^32); kept
  * values are scaled by 1.0f / (1.0f - dropout_p).  The backward regenerates the mask from the same (seed, offset).
+ * The device dropout stream (every *_dstream entry point of this header: the attention cores, the layer tails, the embeddings):
+ * d_stream points to a 16-byte aligned DEVICE object {uint64 seed, uint64 base}.  Given one, every kernel of the call draws under
+ * seed = d_stream[0] and offset = d_stream[1] + args->offset (a 64-bit add with carry into the high word); args->seed is ignored and
+ * args->offset is the call's index within the training step.  Key, counter layout, keep threshold and scaling are untouched: a call
+ * with d_stream = {s, b} and args->offset = r produces exactly the bits of the plain call with (seed, offset) = (s, b + r).  The
+ * pair is one uniform 16-byte read at kernel entry, so the values a captured graph bakes in are only the pointer and r: replays
+ * draw under whatever the object holds when they run.  ance_dropout_stream_advance adds n to the base (one thread, an ordinary
+ * 64-bit load, add and store); enqueue it once per step BEHIND the step's backward -- the backward regenerates the forward's masks
+ * from the same object, so the base must not move between them.  A null d_stream is the plain call; one that is not 16-byte
+ * aligned is refused (ANCE_E_INVALID, before any launch).
  * d_workspace (16-byte aligned, ance_attention_workspace_bytes) is the saved state, linear in the rows: the forward leaves the
  * log-sum-exp there as fp32 [n_heads][n_rows] (entry h * n_rows + row; only valid rows are written), the backward reads it, recomputes P
  * from q, k and it, and adds its own [n_heads][n_rows] of dctx . ctx behind it.  Nothing of size L^2 is ever stored.  The backward
@@ -391,6 +401,9 @@ typedef struct AnceAttnGradArgs {
 size_t ance_attention_workspace_bytes(int64_t n_rows, int n_heads); /* 0: n_heads not 12 or 16, or n_rows outside 1 .. 2^31 - 1 */
 int ance_attention_forward(const AnceAttnTrainArgs *args, void *stream);
 int ance_attention_backward(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, void *stream);
+int ance_attention_forward_dstream(const AnceAttnTrainArgs *args, const uint64_t *d_stream, void *stream);
+int ance_attention_backward_dstream(const AnceAttnTrainArgs *args, const AnceAttnGradArgs *grads, const uint64_t *d_stream, void *stream);
+int ance_dropout_stream_advance(uint64_t *d_stream, uint64_t n, void *stream); /* base += n; n = 0 launches nothing */
 
 /* The same core with 16-bit I/O (csrc/attention_train_half.hip): the recipe's --fp16, i.e. torch.autocast plus a GradScaler.  q, k,
  * v, ctx (and dctx, dq, dk, dv) are fp16 (dtype ANCE_DTYPE_F16) or bf16 (ANCE_DTYPE_BF16) row matrices, all of the one type; strides
@@ -434,6 +447,8 @@ typedef struct AnceAttn16GradArgs {
 size_t ance_attention16_workspace_bytes(int64_t n_rows, int n_heads); /* 0: n_heads not 12 or 16, or n_rows outside 1 .. 2^31 - 1 */
 int ance_attention16_forward(const AnceAttn16Args *args, void *stream);
 int ance_attention16_backward(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, void *stream);
+int ance_attention16_forward_dstream(const AnceAttn16Args *args, const uint64_t *d_stream, void *stream); /* the device dropout stream: above */
+int ance_attention16_backward_dstream(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, const uint64_t *d_stream, void *stream);
 
 /* The row-wise seams of a BertLayer with their gradients (csrc/layer_tail.hip), fp32 throughout: what transformers' eager
  * BertSelfOutput.forward / BertOutput.forward compute after their dense matmul (the layer tail), and BertIntermediate.forward after
@@ -512,6 +527,8 @@ size_t ance_layer_tail_workspace_bytes(int64_t n_rows, int H);
 size_t ance_bias_gelu_workspace_bytes(int64_t n_rows, int N);
 int ance_layer_tail_forward(const AnceLayerTailArgs *args, void *stream);
 int ance_layer_tail_backward(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads, void *stream);
+int ance_layer_tail_forward_dstream(const AnceLayerTailArgs *args, const uint64_t *d_stream, void *stream); /* the device dropout stream: ance_attention_* */
+int ance_layer_tail_backward_dstream(const AnceLayerTailArgs *args, const AnceLayerTailGradArgs *grads, const uint64_t *d_stream, void *stream);
 int ance_bias_gelu_forward(const AnceBiasGeluArgs *args, void *stream);
 int ance_bias_gelu_backward(const AnceBiasGeluArgs *args, const AnceBiasGeluGradArgs *grads, void *stream);
 
@@ -580,6 +597,8 @@ size_t ance_layer_tail16_workspace_bytes(int64_t n_rows, int H);
 size_t ance_bias_gelu16_workspace_bytes(int64_t n_rows, int N);
 int ance_layer_tail16_forward(const AnceLayerTail16Args *args, void *stream);
 int ance_layer_tail16_backward(const AnceLayerTail16Args *args, const AnceLayerTail16GradArgs *grads, void *stream);
+int ance_layer_tail16_forward_dstream(const AnceLayerTail16Args *args, const uint64_t *d_stream, void *stream); /* the device dropout stream: ance_attention_* */
+int ance_layer_tail16_backward_dstream(const AnceLayerTail16Args *args, const AnceLayerTail16GradArgs *grads, const uint64_t *d_stream, void *stream);
 int ance_bias_gelu16_forward(const AnceBiasGelu16Args *args, void *stream);
 int ance_bias_gelu16_backward(const AnceBiasGelu16Args *args, const AnceBiasGelu16GradArgs *grads, void *stream);
 
@@ -672,6 +691,8 @@ int ance_embed_segment_chunk(void);
 size_t ance_embed_workspace_bytes(int64_t n_rows, int H);
 int ance_embed_forward(const AnceEmbedArgs *args, void *stream);
 int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream);
+int ance_embed_forward_dstream(const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream); /* the device dropout stream: ance_attention_* */
+int ance_embed_backward_dstream(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream, void *stream);
 
 /* Test hook: the SPLIT (fp32-grade) GEMM of the encoder with one of its epilogues.  acc[m][n] = sum_k a[m][k] b[n][k] with
  * a = a_hi + a_lo (b likewise; the lo x lo products are left out); d_a_pair [M, 2K] / d_b_pair [N, 2K] fp16 PAIR ROWS -- 32-column
@@ -836,6 +857,30 @@ int ance_lamb_step_amp(const AnceLambTensor *h_tensors, int n_tensors, const Anc
                        int64_t *d_skipped,              /* nullable */
                        float *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* The resident plan of a LAMB step: a caller that steps the same tensors again and again builds the device tables ONCE and then only
+ * launches.  ance_lamb_plan_build checks the host tables as ance_lamb_step does and fills h_tables (HOST memory of at least
+ * ance_lamb_plan_table_bytes bytes; pinned memory the caller owns and never refills while the plan lives) with the device layout;
+ * d_lrs (nullable; n_groups entries, each nullable) gives a group's learning rate as a DEVICE fp64 scalar that the kernels read at
+ * every step -- neg_lr = (float)(-*d_lr), the bits of a host lr of the same value -- and h_groups[i].lr is then ignored.  The caller
+ * copies *table_bytes_out bytes of h_tables to the HEAD of a device workspace of ance_lamb_amp_workspace_bytes bytes that the plan
+ * owns (one copy, with its own allocator and on its own stream: a copy captured into a graph re-reads identical bytes), and
+ * ance_lamb_step_planned on that workspace is ance_lamb_step_amp without tables, checks of them, staging or copy: it enqueues only
+ * its kernels (3, or 5 with max_grad_norm != 0), touches no event and allocates nothing, so it can be captured.  The plan is
+ * valid as long as every pointer, numel and hyper-parameter it was built from is (a device lr may change in place). */
+size_t ance_lamb_plan_table_bytes(int n_tensors, int n_groups, int64_t total_numel);
+int ance_lamb_plan_build(const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, const double *const *d_lrs,
+                         int n_groups, void *h_tables, size_t h_tables_bytes, int64_t *n_chunks_out, size_t *table_bytes_out);
+int ance_lamb_step_planned(int n_tensors, int n_groups, int64_t n_chunks, int adam, double max_grad_norm, const float *d_grad_scale,
+                           const float *d_found_inf, const float *d_prev_out, float *d_grad_norm, int64_t *d_skipped, float *d_out,
+                           void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* transformers' get_linear_schedule_with_warmup as one launch on device scalars (csrc/lr_schedule.hip): *d_n += 1, then
+ * d_lrs[g] = d_base_lrs[g] * lambda(*d_n) in fp64 for every group, lambda(n) = n / max(1, warm) below warm, else
+ * max(0, (total - n) / max(1, total - warm)): the values torch.optim.lr_scheduler.LambdaLR holds after its step(), bit for bit.
+ * d_n is a DEVICE int64, the two arrays DEVICE fp64 [n_groups]; the entries of d_lrs are what the plans' d_lrs point to. */
+int ance_linear_warmup_step(int64_t *d_n, const double *d_base_lrs, double *d_lrs, int n_groups, int64_t num_warmup_steps,
+                            int64_t num_training_steps, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused multi-tensor AdamW step (csrc/adamw.hip; transformers 2.3.0 optimization.py AdamW.step, which drivers/run_ann_dpr.py
  * trains with by default and run_ann.py / run_warmup.py with --optimizer adamW).  Per tensor p with gradient g, state m, v, a
@@ -881,6 +926,17 @@ int ance_adamw_step(const AnceAdamwTensor *h_tensors, int n_tensors, const AnceL
                     float *d_grad_norm,              /* required iff max_grad_norm != 0 */
                     int64_t *d_skipped,              /* nullable */
                     void *d_workspace, size_t workspace_bytes, void *stream);
+/* The resident plan of an AdamW step, as ance_lamb_plan_*: h_tables of ance_adamw_plan_table_bytes bytes, a workspace of
+ * ance_adamw_workspace_bytes(.., clip) bytes with the tables at its head, and a step that enqueues only its kernels (2, or 3 with
+ * max_grad_norm != 0).  With a group's d_lr the per-tensor kernel forms ss and -lr wd from *d_lr in fp64 exactly as from the host
+ * double. */
+long long ance_debug_staging_sends(void); /* table uploads through the shared pinned staging pool so far (the unplanned steps') */
+size_t ance_adamw_plan_table_bytes(int n_tensors, int n_groups, int64_t total_numel);
+int ance_adamw_plan_build(const AnceAdamwTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, const double *const *d_lrs,
+                          int n_groups, void *h_tables, size_t h_tables_bytes, int64_t *n_chunks_out, size_t *table_bytes_out);
+int ance_adamw_step_planned(int n_tensors, int n_groups, int64_t n_chunks, int correct_bias, double max_grad_norm,
+                            const float *d_grad_scale, const float *d_found_inf, float *d_grad_norm, int64_t *d_skipped,
+                            void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training batches gathered on the device (csrc/batch_gather.hip): what the reference's loaders build per item in Python
