@@ -97,7 +97,7 @@ class AnceAttnGradArgs(ctypes.Structure):
                 ("ld_dctx", ctypes.c_int32), ("ld_dq", ctypes.c_int32), ("ld_dk", ctypes.c_int32), ("ld_dv", ctypes.c_int32)]
 
 
-ANCE_DTYPE_F16, ANCE_DTYPE_BF16 = 1, 2
+ANCE_DTYPE_F32, ANCE_DTYPE_F16, ANCE_DTYPE_BF16 = 0, 1, 2
 
 
 class AnceAttn16Args(ctypes.Structure):
@@ -335,6 +335,12 @@ SYMBOLS = {
     "ance_attention_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.POINTER(AnceAttnGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "ance_attention16_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.c_void_p, ctypes.c_void_p]),
     "ance_attention16_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.POINTER(AnceAttn16GradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    # the first-query-row core (csrc/attention_row0.hip): AnceAttn16Args with dtype ANCE_DTYPE_F32, _F16 or _BF16
+    "ance_attention_row0_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "ance_attention_row0_forward": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.c_void_p]),
+    "ance_attention_row0_backward": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.POINTER(AnceAttn16GradArgs), ctypes.c_void_p]),
+    "ance_attention_row0_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_attention_row0_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceAttn16Args), ctypes.POINTER(AnceAttn16GradArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "ance_layer_tail_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "ance_layer_tail_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTailArgs), ctypes.POINTER(AnceLayerTailGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "ance_layer_tail16_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTail16Args), ctypes.c_void_p, ctypes.c_void_p]),

@@ -36,7 +36,7 @@ except ImportError:  # pragma: no cover
     _custom_fwd = _amp_fwd(cast_inputs=torch.float32)
     _custom_fwd_as_is = _amp_fwd
 
-__all__ = ["attention_padded", "attention_packed", "lens_from_mask", "manual_seed", "dropout_state"]
+__all__ = ["attention_padded", "attention_packed", "attention_first_row", "lens_from_mask", "manual_seed", "dropout_state"]
 
 
 class _Draw(object):
@@ -392,6 +392,97 @@ def _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training, precisi
     if half:
         return _AttentionHalf.apply(*_half_inputs(q, k, v), first, lens, int(max_seq_len), n_heads, float(dropout_p), bool(training))
     return _Attention.apply(q, k, v, first, lens, int(max_seq_len), n_heads, float(dropout_p), bool(training))
+
+
+def _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, rows, dtype_code):
+    """The forward of both first-row functions (csrc/attention_row0.hip): q0 [B, H], k, v [B, L, H] of one dtype."""
+    L = _lib.lib()
+    (q0, ld_q), (k, ld_k), (v, ld_v) = rows(q0), rows(k), rows(v)
+    B, Lk, H = k.shape
+    out = torch.empty((B, H), dtype=q0.dtype, device=q0.device)
+    ws_bytes = L.ance_attention_row0_workspace_bytes(B, n_heads)
+    if ws_bytes == 0:
+        raise _lib.AnceLibraryError("attention_first_row: unsupported shape (sequences %d, heads %d)" % (B, n_heads))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q0.device)   # (max, sum) per (sequence, head)
+    drop = bool(training) and dropout_p > 0.0
+    draw = dropout_state.draw(q0.device) if drop else _NO_DRAW
+    args = _lib.AnceAttn16Args(q=q0.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
+                               ld_ctx=H, d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(), n_seq=B, max_seq_len=Lk,
+                               n_rows=B * Lk, n_heads=n_heads, seq_rows=Lk, dtype=dtype_code, dropout_p=float(dropout_p),
+                               training=1 if drop else 0, seed=draw.seed, offset=draw.offset, d_workspace=ws.data_ptr(),
+                               workspace_bytes=ws_bytes)
+    with torch.cuda.device(q0.device):
+        draw.launch("ance_attention_row0_forward", ctypes.byref(args))
+    ctx.save_for_backward(q0, k, v, first, lens, ws)
+    ctx.args, ctx.draw = args, draw
+    return out
+
+
+def _first_row_backward(ctx, dctx0, rows):
+    q0, k, v, first, lens, ws = ctx.saved_tensors
+    dctx0, ld_d = rows(dctx0.to(q0.dtype))
+    dq0 = torch.empty(q0.shape, dtype=q0.dtype, device=q0.device)
+    dk, dv = (torch.empty(k.shape, dtype=k.dtype, device=k.device) for _ in range(2))   # the kernel writes every row, pads as zeros
+    g = _lib.AnceAttn16GradArgs(dctx=dctx0.data_ptr(), dq=dq0.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
+                                ld_dq=dq0.shape[-1], ld_dk=dk.shape[-1], ld_dv=dv.shape[-1])
+    with torch.cuda.device(q0.device):
+        ctx.draw.launch("ance_attention_row0_backward", ctypes.byref(ctx.args), ctypes.byref(g))
+    return dq0, dk, dv, None, None, None, None, None
+
+
+class _AttentionFirstRow(torch.autograd.Function):
+    """q0 [B, H], k, v [B, L, H] fp32; first, lens: int32 [B] on the device."""
+
+    @staticmethod
+    @_custom_fwd
+    def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training):
+        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, _rows, _lib.ANCE_DTYPE_F32)
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dctx0):
+        return _first_row_backward(ctx, dctx0, _rows)
+
+
+class _AttentionFirstRowHalf(torch.autograd.Function):
+    """_AttentionFirstRow with fp16 / bf16 rows: nothing is cast, ctx0 and the gradients have the inputs' dtype."""
+
+    @staticmethod
+    @_custom_fwd_as_is
+    def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training):
+        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, _rows16, HALF_DTYPES[q0.dtype])
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dctx0):
+        return _first_row_backward(ctx, dctx0, _rows16)
+
+
+def attention_first_row(q0, k, v, lens, n_heads, dropout_p=0.0, training=True, precision="fp32"):
+    """ctx0 [B, H]: row 0 of ``attention_padded(q, k, v, ...)`` from the first rows' queries alone -- q0 [B, H] (= q[:, 0]), k, v
+    [B, L, H], lens [B] device integers (lens_from_mask), L <= 512.  What a tower's last layer needs when only h[:, 0] is read: one
+    memory-bound pass over k and v per (sequence, head) instead of an L x L core (csrc/attention_row0.hip).  Views with a contiguous
+    last dimension and evenly spaced rows pass as they are (thirds of a fused [B, L, 3H]; hidden[:, 0]).  Gradients for q0, k and v;
+    rows >= lens[b] of dk and dv are zeros; a sequence of length 0 gives a zero ctx0 row and zero gradients.  Under the same (seed,
+    offset) the dropout mask is the full core's query row 0, bit for bit; the call takes one draw of the dropout stream.
+    precision="half": q0, k, v all fp16 or all bf16 (under autocast fp32 ones are cast to the autocast dtype; outside it they are
+    refused); the arithmetic is fp32 and every output is rounded once, at its store.  The default casts to fp32 under autocast and
+    refuses 16-bit inputs outside it."""
+    half = _check_precision(precision)
+    _check_inputs(k, k, v, n_heads, dropout_p, 3, half)
+    _check_inputs(q0, q0, q0, n_heads, dropout_p, 2, half)
+    B, Lk = k.shape[0], k.shape[1]
+    if q0.shape[0] != B or q0.device != k.device:
+        raise _lib.AnceLibraryError("q0 must be [B, H] with k's batch size, on k's device; got %r and %r" % (tuple(q0.shape), tuple(k.shape)))
+    if not 1 <= Lk <= 512:
+        raise _lib.AnceLibraryError("sequence length must be in 1 .. 512, got %d" % Lk)
+    lens = _int32(lens, "lens", B, k.device)
+    first = torch.arange(0, B * Lk, Lk, dtype=torch.int32, device=k.device)
+    if half:
+        return _AttentionFirstRowHalf.apply(*_half_inputs(q0, k, v), first, lens, n_heads, float(dropout_p), bool(training))
+    return _AttentionFirstRow.apply(q0, k, v, first, lens, n_heads, float(dropout_p), bool(training))
 
 
 # _padded / _packed return (ctx, lse): lse is the saved fp32 log-sum-exp [n_heads, rows] (zeros at pad rows), non-differentiable.  It

@@ -27,7 +27,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .attention import (_NO_DRAW, HALF_DTYPES, _check_precision, _custom_bwd, _custom_fwd, _custom_fwd_as_is, _rows, _rows16,
-                        attention_padded, dropout_state)
+                        attention_first_row, attention_padded, dropout_state)
 
 __all__ = ["dropout_add_layer_norm", "bias_gelu", "BertLayer"]
 
@@ -451,6 +451,47 @@ class BertLayer(torch.nn.Module):
         ln = self.output.LayerNorm
         return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
                                       self.training, precision="half", return_half=return_half)
+
+    def forward_first_rows(self, hidden_states, lens, hidden_states_half=None):
+        """``forward(...)[:, 0]`` -- [B, H] fp32 -- for a tower's LAST layer, of which only the first rows are read: the key and the
+        value projections run over all rows, everything else over the B first rows.  q0 = the query Linear of hidden_states[:, 0],
+        attention_first_row, then the three seams on B rows with the residual hidden_states[:, 0] as a strided view.  Three draws of
+        the dropout stream in forward's order; the attention mask is forward's query row 0 bit for bit, the tails' masks are those
+        of a B-row call (row b, not row b * L).  precision="half": the projections read hidden_states_half (or the layer's one cast)
+        and the seams run as in forward."""
+        F = torch.nn.functional
+        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
+        half = self.precision == "half"
+        if not isinstance(hidden_states, torch.Tensor) or hidden_states.dim() != 3:
+            raise _lib.AnceLibraryError("BertLayer.forward_first_rows: hidden_states must be [B, L, H]")
+        if half:
+            if hidden_states.dtype != torch.float32:
+                raise _lib.AnceLibraryError("BertLayer(precision=\"half\"): hidden_states is the fp32 residual stream, got %s"
+                                            % (hidden_states.dtype,))
+            if hidden_states_half is None:   # the layer's one activation cast
+                hidden_states_half = _half_rows(hidden_states, "hidden_states", TAIL_WIDTHS)
+            elif hidden_states_half.dtype not in HALF_DTYPES or hidden_states_half.shape != hidden_states.shape:
+                raise _lib.AnceLibraryError("hidden_states_half must be the fp16 / bf16 copy of hidden_states, got %s %r"
+                                            % (hidden_states_half.dtype, tuple(hidden_states_half.shape)))
+            x = hidden_states_half
+        elif hidden_states_half is not None:
+            raise _lib.AnceLibraryError("BertLayer: hidden_states_half needs precision=\"half\"")
+        else:
+            x = hidden_states
+        prec = dict(precision="half") if half else {}
+        q0 = F.linear(x[:, 0], att.self.query.weight, att.self.query.bias)
+        k = F.linear(x, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
+        v = F.linear(x, att.self.value.weight, att.self.value.bias)
+        ctx0 = attention_first_row(q0, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
+                                   precision=self.attention_precision)
+        ln = att.output.LayerNorm
+        h = dropout_add_layer_norm(F.linear(ctx0, att.output.dense.weight), att.output.dense.bias, hidden_states[:, 0], ln.weight,
+                                   ln.bias, eps, p, self.training, return_half=half, **prec)
+        h, h_in = h if half else (h, h)
+        t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
+        ln = self.output.LayerNorm
+        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
+                                      self.training, **prec)
 
     def forward(self, hidden_states, lens, hidden_states_half=None, return_half=False):
         if self.precision == "half":

@@ -1,0 +1,226 @@
+"""The models a trainer instantiates, assembled from the differentiable pieces: the reference's class names,
+``forward`` signatures and parameter names (model/models.py), so that a trainer changes one import and a reference checkpoint loads.
+
+    RobertaDot_NLL_LN                   roberta.embeddings.*, roberta.encoder.layer.N.*, embeddingHead.*, norm.*     -> [B, 768]
+    RobertaDot_CLF_ANN_NLL_MultiChunk   the same tower; body_emb reshapes [B, C * 512] to [B * C, 512]               -> [B, C, 768]
+    BiEncoder                           question_model.*, ctx_model.* under BertModel's names; no head               -> [B, H]
+
+A tower is ``BertEmbeddings`` -> N - 1 x ``BertLayer.forward`` -> the last layer's ``forward_first_rows``: only h[:, 0] of the last
+layer is ever read, so its query, output and feed-forward Linears and its seams run over the B first rows, and its attention is the
+first-row core (``attention_first_row``).  There is one path; N = 1 is the last layer alone.  One tower call takes 1 + 3 N draws of
+the dropout stream in the order embeddings, then per layer attention, first tail, second tail.  The head is ``F.linear`` +
+``F.layer_norm`` (eps 1e-5), H -> 768 for both widths.  ``precision="half"`` is the form for ``torch.autocast``: the layers chain
+through their 16-bit copies (BertLayer) and the residual stream stays fp32.  Lengths come from ``lens_from_mask``; nothing
+synchronises, so a whole step can be captured.
+
+``use_mean`` is not supported (no shipped recipe sets it).  An all-pad chunk of a MaxP document has length 0: the attention core
+writes zeros for it, so its embedding is the tail of zeros -- finite, NOT the reference's value (which attends uniformly over the
+pads) -- and it receives no gradient; ``nll_loss`` biases it by -9999 before the max, as the reference does, so it never wins.
+"""
+import collections
+
+import torch
+
+from . import _lib
+from .attention import lens_from_mask
+from .embeddings import BertEmbeddings
+from .encoder import count_layers
+from .layers import BertLayer
+from .loss import nll_loss
+
+__all__ = ["TowerConfig", "RobertaDot_NLL_LN", "RobertaDot_CLF_ANN_NLL_MultiChunk", "BiEncoder"]
+
+OUT_DIM, HEAD_EPS = 768, 1e-5
+
+
+class TowerConfig(object):
+    """The attributes of a transformers config that a tower reads, under their names there; any object that has them will do."""
+
+    def __init__(self, vocab_size, hidden_size, num_hidden_layers, intermediate_size, max_position_embeddings, type_vocab_size,
+                 layer_norm_eps, pad_token_id, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, num_attention_heads=None):
+        self.vocab_size, self.hidden_size, self.num_hidden_layers = int(vocab_size), int(hidden_size), int(num_hidden_layers)
+        self.intermediate_size, self.max_position_embeddings = int(intermediate_size), int(max_position_embeddings)
+        self.type_vocab_size, self.layer_norm_eps, self.pad_token_id = int(type_vocab_size), float(layer_norm_eps), int(pad_token_id)
+        self.hidden_dropout_prob, self.attention_probs_dropout_prob = float(hidden_dropout_prob), float(attention_probs_dropout_prob)
+        self.num_attention_heads = self.hidden_size // 64 if num_attention_heads is None else int(num_attention_heads)
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix, roberta, dropout=0.1):
+        """The shape of the tower under ``prefix``, inferred as ance_amd/encoder.py infers it; RoBERTa: eps 1e-5, pad id 1; BERT:
+        eps 1e-12, pad id 0."""
+        n = count_layers(sd, prefix)
+        if n == 0:
+            raise KeyError("no '%sencoder.layer.*' weights in state dict" % prefix)
+        e = prefix + "embeddings."
+        word, pos, types = (sd[e + k + "_embeddings.weight"] for k in ("word", "position", "token_type"))
+        return cls(word.shape[0], word.shape[1], n, sd[prefix + "encoder.layer.0.intermediate.dense.weight"].shape[0], pos.shape[0],
+                   types.shape[0], 1e-5 if roberta else 1e-12, 1 if roberta else 0, dropout, dropout)
+
+
+class _Layers(torch.nn.Module):
+    def __init__(self, layers):
+        super().__init__()
+        self.layer = torch.nn.ModuleList(layers)
+
+
+class _Tower(torch.nn.Module):
+    """embeddings.*, encoder.layer.N.* as BertModel / RobertaModel name them; ``forward`` returns the last layer's first rows."""
+
+    def __init__(self, config, position_mode, precision):
+        super().__init__()
+        c = config
+        if c.num_hidden_layers < 1:
+            raise _lib.AnceLibraryError("a tower needs at least one layer")
+        self.precision = precision
+        self.embeddings = BertEmbeddings(c.vocab_size, c.hidden_size, c.max_position_embeddings, c.type_vocab_size, c.layer_norm_eps,
+                                         c.hidden_dropout_prob, c.pad_token_id, position_mode)
+        self.encoder = _Layers([BertLayer(c.hidden_size, c.num_attention_heads, c.intermediate_size, c.layer_norm_eps,
+                                          c.hidden_dropout_prob, c.attention_probs_dropout_prob, precision=precision)
+                                for _ in range(c.num_hidden_layers)])
+
+    def forward(self, input_ids, attention_mask, token_type_ids=None):
+        if attention_mask is None:
+            raise _lib.AnceLibraryError("attention_mask is required: the lengths come from it")
+        lens = lens_from_mask(attention_mask)
+        h = self.embeddings(input_ids, token_type_ids)
+        layers = self.encoder.layer
+        if self.precision == "half":   # chained through the 16-bit copy: one activation cast in the whole tower
+            h16 = None
+            for layer in layers[:-1]:
+                h, h16 = layer(h, lens, hidden_states_half=h16, return_half=True)
+            return layers[-1].forward_first_rows(h, lens, hidden_states_half=h16)
+        for layer in layers[:-1]:
+            h = layer(h, lens)
+        return layers[-1].forward_first_rows(h, lens)
+
+
+def _never_used(key):
+    """The tensors the reference's classes carry but never use: the poolers, RobertaForSequenceClassification's classifier and the
+    position_ids buffers of later transformers."""
+    return ".pooler." in key or key.startswith("classifier.") or key.endswith(".position_ids")
+
+
+class _Checkpointed(torch.nn.Module):
+    """Loading and re-emitting a reference checkpoint."""
+
+    def load_reference_state_dict(self, sd):
+        """Strict on every used name; the tensors the reference carries but never uses (``*.pooler.*``, ``classifier.*``,
+        ``*.position_ids``) are set aside for ``reference_state_dict``; any other unknown key is refused."""
+        used = set(self.state_dict().keys())
+        unknown = [k for k in sd if k not in used and not _never_used(k)]
+        if unknown:
+            raise KeyError("unexpected keys in state dict: %s ..." % unknown[:4])
+        missing = [k for k in self.state_dict() if k not in sd]
+        if missing:
+            raise KeyError("missing weights: %s ..." % missing[:4])
+        self.load_state_dict(collections.OrderedDict((k, torch.as_tensor(v)) for k, v in sd.items() if k in used), strict=True)
+        self._set_aside = collections.OrderedDict((k, torch.as_tensor(v).detach().clone()) for k, v in sd.items() if k not in used)
+        return self
+
+    def reference_state_dict(self):
+        """``state_dict()`` (detached) plus the set-aside tensors: a loaded checkpoint round-trips, and ``Encoder(...)`` builds from
+        it with no renaming."""
+        out = collections.OrderedDict((k, v.detach()) for k, v in self.state_dict().items())
+        out.update(getattr(self, "_set_aside", {}))
+        return out
+
+
+class RobertaDot_NLL_LN(_Checkpointed):
+    """model/models.py: RobertaDot_NLL_LN (FirstP): ``norm(embeddingHead(roberta(ids)[0][:, 0]))``, NLL over (query, positive,
+    negative) triplets.  ``config``: a transformers RobertaConfig or a TowerConfig."""
+
+    def __init__(self, config, model_argobj=None, precision="fp32"):
+        super().__init__()
+        if model_argobj is not None and getattr(model_argobj, "use_mean", False):
+            raise _lib.AnceLibraryError("use_mean is not supported: the last layer computes the first rows only")
+        self.use_mean = False
+        self.roberta = _Tower(config, "roberta", precision)
+        self.embeddingHead = torch.nn.Linear(config.hidden_size, OUT_DIM)
+        self.norm = torch.nn.LayerNorm(OUT_DIM, eps=HEAD_EPS)
+
+    @classmethod
+    def from_state_dict(cls, sd, precision="fp32", dropout=0.1):
+        model = cls(TowerConfig.from_state_dict(sd, "roberta.", True, dropout), precision=precision)
+        return model.to(sd["embeddingHead.weight"].device).load_reference_state_dict(sd)
+
+    def _head(self, first_rows):
+        F = torch.nn.functional
+        e = F.linear(first_rows, self.embeddingHead.weight, self.embeddingHead.bias)
+        return F.layer_norm(e.float(), (OUT_DIM,), self.norm.weight, self.norm.bias, HEAD_EPS)
+
+    def query_emb(self, input_ids, attention_mask):
+        return self._head(self.roberta(input_ids, attention_mask))
+
+    def body_emb(self, input_ids, attention_mask):
+        return self.query_emb(input_ids, attention_mask)
+
+    def _loss(self, q, a, b, attention_mask_a, attention_mask_b):
+        return nll_loss(q, a, b)
+
+    def forward(self, query_ids, attention_mask_q, input_ids_a=None, attention_mask_a=None, input_ids_b=None, attention_mask_b=None,
+                is_query=True):
+        if input_ids_b is None and is_query:
+            return self.query_emb(query_ids, attention_mask_q)
+        if input_ids_b is None:
+            return self.body_emb(query_ids, attention_mask_q)
+        q = self.query_emb(query_ids, attention_mask_q)
+        a = self.body_emb(input_ids_a, attention_mask_a)
+        b = self.body_emb(input_ids_b, attention_mask_b)
+        return (self._loss(q, a, b, attention_mask_a, attention_mask_b),)
+
+
+class RobertaDot_CLF_ANN_NLL_MultiChunk(RobertaDot_NLL_LN):
+    """model/models.py: RobertaDot_CLF_ANN_NLL_MultiChunk (MaxP): a document is C chunks of ``base_len`` = 512 tokens, its score the
+    max over the chunks; an all-pad chunk is biased by -9999 (module docstring: its embedding is finite, not the reference's)."""
+
+    def __init__(self, config, model_argobj=None, precision="fp32"):
+        super().__init__(config, model_argobj, precision)
+        self.base_len = 512
+
+    def body_emb(self, input_ids, attention_mask):
+        B, full = input_ids.shape
+        C = full // self.base_len
+        if C < 1 or C * self.base_len != full:
+            raise _lib.AnceLibraryError("body_emb: the document length %d is not a multiple of base_len = %d" % (full, self.base_len))
+        e = self._head(self.roberta(input_ids.reshape(B * C, full // C), attention_mask.reshape(B * C, full // C)))
+        return e.reshape(B, C, OUT_DIM)
+
+    @staticmethod
+    def chunk_mask(attention_mask, n_chunks):
+        """[B, C] fp32: the first attention-mask entry of every chunk, as NLL_MultiChunk.forward reads it."""
+        return attention_mask.reshape(attention_mask.shape[0], n_chunks, -1)[:, :, 0].float()
+
+    def _loss(self, q, a, b, attention_mask_a, attention_mask_b):
+        C = a.shape[1]
+        return nll_loss(q, a, b, self.chunk_mask(attention_mask_a, C), self.chunk_mask(attention_mask_b, C))
+
+
+class BiEncoder(_Checkpointed):
+    """model/models.py: BiEncoder (DPR): two BERT towers under BertModel's names (absolute positions, two token types, eps 1e-12),
+    no head: an embedding is the last layer's first row.  ``forward`` with a negative returns ``(loss,)`` over the triplets; without
+    one it returns ``(q_embs, a_embs)``, which the trainer feeds to ``ance_amd.loss.biencoder_nll_loss``.  ``config``: a transformers
+    BertConfig or a TowerConfig, for both towers."""
+
+    def __init__(self, config, precision="fp32"):
+        super().__init__()
+        self.question_model = _Tower(config, "absolute", precision)
+        self.ctx_model = _Tower(config, "absolute", precision)
+
+    @classmethod
+    def from_state_dict(cls, sd, precision="fp32", dropout=0.1):
+        model = cls(TowerConfig.from_state_dict(sd, "question_model.", False, dropout), precision=precision)
+        return model.to(sd["question_model.embeddings.word_embeddings.weight"].device).load_reference_state_dict(sd)
+
+    def query_emb(self, input_ids, attention_mask):
+        return self.question_model(input_ids, attention_mask)
+
+    def body_emb(self, input_ids, attention_mask):
+        return self.ctx_model(input_ids, attention_mask)
+
+    def forward(self, query_ids, attention_mask_q, input_ids_a=None, attention_mask_a=None, input_ids_b=None, attention_mask_b=None):
+        q = self.query_emb(query_ids, attention_mask_q)
+        a = self.body_emb(input_ids_a, attention_mask_a)
+        if input_ids_b is None:
+            return (q, a)
+        b = self.body_emb(input_ids_b, attention_mask_b)
+        return (nll_loss(q, a, b),)

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_* only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -449,6 +449,32 @@ int ance_attention16_forward(const AnceAttn16Args *args, void *stream);
 int ance_attention16_backward(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, void *stream);
 int ance_attention16_forward_dstream(const AnceAttn16Args *args, const uint64_t *d_stream, void *stream); /* the device dropout stream: above */
 int ance_attention16_backward_dstream(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, const uint64_t *d_stream, void *stream);
+
+/* The same core for the FIRST query row of every sequence (csrc/attention_row0.hip): what the last layer of a tower needs when only
+ * h[:, 0] is read.  The calls take AnceAttn16Args / AnceAttn16GradArgs with these meanings: dtype is ANCE_DTYPE_F32, _F16 or _BF16,
+ * the type of every row in memory; q, ctx, dctx and dq are [n_seq, 64 n_heads] matrices, row s belonging to sequence s (q its first
+ * row's query, ctx its first row's context); k, v, dk, dv are the [n_rows, 64 n_heads] matrices of the full core, sequence s being
+ * rows d_seq_first[s] .. + d_seq_len[s] - 1 with the full core's clamps.  Strides are in elements, multiples of a 16-byte piece (4
+ * fp32, 8 16-bit elements), at least 64 n_heads; bases 16-byte aligned.  Per sequence s and head h, q0 = q[s]:
+ *   t_j = 0.125f * (q0 . K_j) for j < len;  m = max_j t_j;  l = sum_j expf(t_j - m);  P_j = expf(t_j - m) / l;
+ *   P'_j = keep_j ? P_j * (1.0f / (1.0f - p)) : 0 under dropout, else P_j;  ctx[s] = sum_j P'_j V_j;
+ *   backward: dP_j = keep_j ? (dctx[s] . V_j) * (1.0f / (1.0f - p)) : 0;  D = sum_j dP_j P_j;  dS_j = P_j (dP_j - D);
+ *   dq[s] = 0.125f sum_j dS_j K_j;  dK_j = 0.125f dS_j q0;  dV_j = P'_j dctx[s].
+ * All arithmetic is fp32 whatever the dtype; every output element is rounded once at its store (to nearest even, overflow to +-inf);
+ * P is never rounded.  seq_rows > 0: rows len .. seq_rows - 1 of the sequence in dk and dv are WRITTEN AS ZEROS by the backward (every
+ * valid row of dk and dv is written too: no pre-zeroing); seq_rows = 0: only the valid rows are written.  A sequence of length <= 0
+ * gets a zero ctx[s] and a zero dq[s].  Dropout is the full core's query row i = 0 of sequence s, bit for bit: counter (j >> 2,
+ * s * n_heads + h, offset lo32, offset hi32), word j & 3; the _dstream forms as above.  d_workspace
+ * (ance_attention_row0_workspace_bytes) is the saved state: fp32 (m, l) per (sequence, head), entry 2 (s n_heads + h).  One launch
+ * forward, one backward, one workgroup per (sequence, head), no atomics, every sum in a fixed order: the same inputs give the same
+ * bits.  The grid is sized from n_seq and n_heads; nothing is read back -- both calls can be captured.  Refuses what the 16-bit core
+ * refuses (with the stride rule above), before any launch. */
+#define ANCE_DTYPE_F32 0
+size_t ance_attention_row0_workspace_bytes(int64_t n_seq, int n_heads); /* 0: n_heads not 12 or 16, or n_seq outside 1 .. 65535 */
+int ance_attention_row0_forward(const AnceAttn16Args *args, void *stream);
+int ance_attention_row0_backward(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, void *stream);
+int ance_attention_row0_forward_dstream(const AnceAttn16Args *args, const uint64_t *d_stream, void *stream);
+int ance_attention_row0_backward_dstream(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, const uint64_t *d_stream, void *stream);
 
 /* The row-wise seams of a BertLayer with their gradients (csrc/layer_tail.hip), fp32 throughout: what transformers' eager
  * BertSelfOutput.forward / BertOutput.forward compute after their dense matmul (the layer tail), and BertIntermediate.forward after
