@@ -1,4 +1,4 @@
-"""The trainers' self-attention core, differentiable (csrc/attention_train.hip behind ance_attention_forward / _backward).
+"""The trainers' self-attention core, differentiable (csrc/attention_train_kernels.h behind ance_attention_forward / _backward).
 
 What transformers' eager ``BertSelfAttention.forward`` computes between its three Linear outputs and ``context_layer``, for
 right-padded sequences and heads of width 64: scores * 0.125, softmax over the valid keys in fp32, dropout on the probabilities,
@@ -183,25 +183,16 @@ def lens_from_mask(attention_mask):
     return (attention_mask != 0).sum(dim=1, dtype=torch.int32)
 
 
-def _rows(t):
-    """A [.., H] fp32 CUDA tensor as a row matrix: (tensor to keep alive, row stride).  A view whose rows are evenly spaced passes as
-    it is; anything else is copied."""
+def _rows(t, piece=4):
+    """A [.., H] CUDA tensor as a row matrix: (tensor to keep alive, row stride).  The kernels read 16-byte pieces, so a row stride
+    must be a multiple of ``piece`` elements: 4 for fp32, 8 for a 16-bit dtype.  A view whose rows are evenly spaced passes as it is;
+    anything else is copied."""
     if t.dim() == 3:
-        if t.stride(2) != 1 or t.stride(0) != t.size(1) * t.stride(1) or t.stride(1) % 4 or t.stride(1) < t.size(2) or t.data_ptr() % 16:
+        if t.stride(2) != 1 or t.stride(0) != t.size(1) * t.stride(1) or t.stride(1) % piece or t.stride(1) < t.size(2) \
+                or t.data_ptr() % 16:
             t = t.contiguous()
         return t, t.stride(1)
-    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.size(1) or t.data_ptr() % 16:
-        t = t.contiguous()
-    return t, t.stride(0)
-
-
-def _rows16(t):
-    """_rows for a 16-bit tensor: the kernels read 16-byte pieces, so a row stride must be a multiple of 8 elements."""
-    if t.dim() == 3:
-        if t.stride(2) != 1 or t.stride(0) != t.size(1) * t.stride(1) or t.stride(1) % 8 or t.stride(1) < t.size(2) or t.data_ptr() % 16:
-            t = t.contiguous()
-        return t, t.stride(1)
-    if t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.size(1) or t.data_ptr() % 16:
+    if t.stride(1) != 1 or t.stride(0) % piece or t.stride(0) < t.size(1) or t.data_ptr() % 16:
         t = t.contiguous()
     return t, t.stride(0)
 
@@ -263,96 +254,77 @@ def _grads_like(q, k, v, zero):
     return tuple(t.zero_() for t in out) if zero else out
 
 
+def _core_forward(ctx, q, k, v, first, lens, max_seq_len, n_heads, dropout_p, training, half):
+    """The forward of both full-core functions (csrc/attention_train_kernels.h): q, k, v [B, L, H] or [T, H] of one dtype -- fp32, or
+    with ``half`` fp16 / bf16."""
+    L = _lib.lib()
+    piece, entry = (8, "ance_attention16") if half else (4, "ance_attention")
+    (q, ld_q), (k, ld_k), (v, ld_v) = _rows(q, piece), _rows(k, piece), _rows(v, piece)
+    n_rows = q.numel() // q.shape[-1]
+    # padded form: the kernels write the pad rows' zeros themselves; packed form: rows that no sequence covers stay zero
+    seq_rows = max_seq_len if q.dim() == 3 else 0
+    out = (torch.empty if seq_rows else torch.zeros)(q.shape, dtype=q.dtype, device=q.device)
+    ws_bytes = getattr(L, entry + "_workspace_bytes")(n_rows, n_heads)
+    if ws_bytes == 0:
+        raise _lib.AnceLibraryError("attention: unsupported shape (rows %d, heads %d)" % (n_rows, n_heads))
+    ws = torch.zeros(ws_bytes // 4, dtype=torch.float32, device=q.device)
+    drop = bool(training) and dropout_p > 0.0
+    draw = dropout_state.draw(q.device) if drop else _NO_DRAW
+    common = dict(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
+                  ld_ctx=out.shape[-1], d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(), n_seq=first.numel(),
+                  max_seq_len=max_seq_len, n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows, dropout_p=float(dropout_p),
+                  training=1 if drop else 0, seed=draw.seed, offset=draw.offset, d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
+    args = _lib.AnceAttn16Args(dtype=HALF_DTYPES[q.dtype], **common) if half else _lib.AnceAttnTrainArgs(**common)
+    with torch.cuda.device(q.device):
+        draw.launch(entry + "_forward", ctypes.byref(args))
+    ctx.save_for_backward(q, k, v, out, first, lens, ws)
+    ctx.args, ctx.draw = args, draw
+    lse = ws[:n_heads * n_rows].view(n_heads, n_rows)
+    ctx.mark_non_differentiable(lse)
+    return out, lse
+
+
+def _core_backward(ctx, dctx, half):
+    q, k, v, out, first, lens, ws = ctx.saved_tensors
+    a = ctx.args
+    dctx, ld_d = _rows(dctx.to(q.dtype), 8 if half else 4)
+    dq, dk, dv = _grads_like(q, k, v, zero=a.seq_rows == 0)
+    g = (_lib.AnceAttn16GradArgs if half else _lib.AnceAttnGradArgs)(
+        dctx=dctx.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d, ld_dq=dq.stride(-2),
+        ld_dk=dk.stride(-2), ld_dv=dv.stride(-2))
+    with torch.cuda.device(q.device):
+        ctx.draw.launch("ance_attention16_backward" if half else "ance_attention_backward", ctypes.byref(a), ctypes.byref(g))
+    return dq, dk, dv, None, None, None, None, None, None
+
+
 class _Attention(torch.autograd.Function):
-    """q, k, v: [B, L, H] or [T, H]; first, lens: int32 [n_seq] on the device."""
+    """q, k, v: [B, L, H] or [T, H] fp32 (autocast casts them); first, lens: int32 [n_seq] on the device."""
 
     @staticmethod
     @_custom_fwd
     def forward(ctx, q, k, v, first, lens, max_seq_len, n_heads, dropout_p, training):
-        L = _lib.lib()
-        (q, ld_q), (k, ld_k), (v, ld_v) = _rows(q), _rows(k), _rows(v)
-        n_rows = q.numel() // q.shape[-1]
-        # padded form: the kernels write the pad rows' zeros themselves; packed form: rows that no sequence covers stay zero
-        seq_rows = max_seq_len if q.dim() == 3 else 0
-        out = (torch.empty if seq_rows else torch.zeros)(q.shape, dtype=torch.float32, device=q.device)
-        ws_bytes = L.ance_attention_workspace_bytes(n_rows, n_heads)
-        if ws_bytes == 0:
-            raise _lib.AnceLibraryError("attention: unsupported shape (rows %d, heads %d)" % (n_rows, n_heads))
-        ws = torch.zeros(ws_bytes // 4, dtype=torch.float32, device=q.device)
-        drop = bool(training) and dropout_p > 0.0
-        draw = dropout_state.draw(q.device) if drop else _NO_DRAW
-        args = _lib.AnceAttnTrainArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
-                                      ld_ctx=out.shape[-1], d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(),
-                                      n_seq=first.numel(), max_seq_len=max_seq_len, n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows,
-                                      dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed, offset=draw.offset,
-                                      d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
-        with torch.cuda.device(q.device):
-            draw.launch("ance_attention_forward", ctypes.byref(args))
-        ctx.save_for_backward(q, k, v, out, first, lens, ws)
-        ctx.args, ctx.draw = args, draw
-        lse = ws[:n_heads * n_rows].view(n_heads, n_rows)
-        ctx.mark_non_differentiable(lse)
-        return out, lse
+        return _core_forward(ctx, q, k, v, first, lens, max_seq_len, n_heads, dropout_p, training, False)
 
     @staticmethod
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dctx, _dlse):
-        q, k, v, out, first, lens, ws = ctx.saved_tensors
-        a = ctx.args
-        dctx, ld_d = _rows(dctx.to(torch.float32))
-        dq, dk, dv = _grads_like(q, k, v, zero=a.seq_rows == 0)
-        g = _lib.AnceAttnGradArgs(dctx=dctx.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
-                                  ld_dq=dq.stride(-2), ld_dk=dk.stride(-2), ld_dv=dv.stride(-2))
-        with torch.cuda.device(q.device):
-            ctx.draw.launch("ance_attention_backward", ctypes.byref(a), ctypes.byref(g))
-        return dq, dk, dv, None, None, None, None, None, None
+        return _core_backward(ctx, dctx, False)
 
 
 class _AttentionHalf(torch.autograd.Function):
-    """_Attention with fp16 / bf16 rows (csrc/attention_train_half.hip): nothing is cast, ctx and the gradients have the inputs' dtype,
-    the log-sum-exp stays fp32."""
+    """_Attention with fp16 / bf16 rows: nothing is cast, ctx and the gradients have the inputs' dtype, the log-sum-exp stays fp32."""
 
     @staticmethod
     @_custom_fwd_as_is
     def forward(ctx, q, k, v, first, lens, max_seq_len, n_heads, dropout_p, training):
-        L = _lib.lib()
-        (q, ld_q), (k, ld_k), (v, ld_v) = _rows16(q), _rows16(k), _rows16(v)
-        n_rows = q.numel() // q.shape[-1]
-        seq_rows = max_seq_len if q.dim() == 3 else 0
-        out = (torch.empty if seq_rows else torch.zeros)(q.shape, dtype=q.dtype, device=q.device)
-        ws_bytes = L.ance_attention16_workspace_bytes(n_rows, n_heads)
-        if ws_bytes == 0:
-            raise _lib.AnceLibraryError("attention: unsupported shape (rows %d, heads %d)" % (n_rows, n_heads))
-        ws = torch.zeros(ws_bytes // 4, dtype=torch.float32, device=q.device)
-        drop = bool(training) and dropout_p > 0.0
-        draw = dropout_state.draw(q.device) if drop else _NO_DRAW
-        args = _lib.AnceAttn16Args(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
-                                   ld_ctx=out.shape[-1], d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(),
-                                   n_seq=first.numel(), max_seq_len=max_seq_len, n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows,
-                                   dtype=HALF_DTYPES[q.dtype], dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed,
-                                   offset=draw.offset, d_workspace=ws.data_ptr(), workspace_bytes=ws_bytes)
-        with torch.cuda.device(q.device):
-            draw.launch("ance_attention16_forward", ctypes.byref(args))
-        ctx.save_for_backward(q, k, v, out, first, lens, ws)
-        ctx.args, ctx.draw = args, draw
-        lse = ws[:n_heads * n_rows].view(n_heads, n_rows)
-        ctx.mark_non_differentiable(lse)
-        return out, lse
+        return _core_forward(ctx, q, k, v, first, lens, max_seq_len, n_heads, dropout_p, training, True)
 
     @staticmethod
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dctx, _dlse):
-        q, k, v, out, first, lens, ws = ctx.saved_tensors
-        a = ctx.args
-        dctx, ld_d = _rows16(dctx.to(q.dtype))
-        dq, dk, dv = _grads_like(q, k, v, zero=a.seq_rows == 0)
-        g = _lib.AnceAttn16GradArgs(dctx=dctx.data_ptr(), dq=dq.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
-                                    ld_dq=dq.stride(-2), ld_dk=dk.stride(-2), ld_dv=dv.stride(-2))
-        with torch.cuda.device(q.device):
-            ctx.draw.launch("ance_attention16_backward", ctypes.byref(a), ctypes.byref(g))
-        return dq, dk, dv, None, None, None, None, None, None
+        return _core_backward(ctx, dctx, True)
 
 
 def _half_inputs(q, k, v):
@@ -394,10 +366,10 @@ def _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training, precisi
     return _Attention.apply(q, k, v, first, lens, int(max_seq_len), n_heads, float(dropout_p), bool(training))
 
 
-def _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, rows, dtype_code):
+def _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, piece, dtype_code):
     """The forward of both first-row functions (csrc/attention_row0.hip): q0 [B, H], k, v [B, L, H] of one dtype."""
     L = _lib.lib()
-    (q0, ld_q), (k, ld_k), (v, ld_v) = rows(q0), rows(k), rows(v)
+    (q0, ld_q), (k, ld_k), (v, ld_v) = _rows(q0, piece), _rows(k, piece), _rows(v, piece)
     B, Lk, H = k.shape
     out = torch.empty((B, H), dtype=q0.dtype, device=q0.device)
     ws_bytes = L.ance_attention_row0_workspace_bytes(B, n_heads)
@@ -418,9 +390,9 @@ def _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training,
     return out
 
 
-def _first_row_backward(ctx, dctx0, rows):
+def _first_row_backward(ctx, dctx0, piece):
     q0, k, v, first, lens, ws = ctx.saved_tensors
-    dctx0, ld_d = rows(dctx0.to(q0.dtype))
+    dctx0, ld_d = _rows(dctx0.to(q0.dtype), piece)
     dq0 = torch.empty(q0.shape, dtype=q0.dtype, device=q0.device)
     dk, dv = (torch.empty(k.shape, dtype=k.dtype, device=k.device) for _ in range(2))   # the kernel writes every row, pads as zeros
     g = _lib.AnceAttn16GradArgs(dctx=dctx0.data_ptr(), dq=dq0.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
@@ -436,13 +408,13 @@ class _AttentionFirstRow(torch.autograd.Function):
     @staticmethod
     @_custom_fwd
     def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training):
-        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, _rows, _lib.ANCE_DTYPE_F32)
+        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, 4, _lib.ANCE_DTYPE_F32)
 
     @staticmethod
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dctx0):
-        return _first_row_backward(ctx, dctx0, _rows)
+        return _first_row_backward(ctx, dctx0, 4)
 
 
 class _AttentionFirstRowHalf(torch.autograd.Function):
@@ -451,13 +423,13 @@ class _AttentionFirstRowHalf(torch.autograd.Function):
     @staticmethod
     @_custom_fwd_as_is
     def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training):
-        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, _rows16, HALF_DTYPES[q0.dtype])
+        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, 8, HALF_DTYPES[q0.dtype])
 
     @staticmethod
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dctx0):
-        return _first_row_backward(ctx, dctx0, _rows16)
+        return _first_row_backward(ctx, dctx0, 8)
 
 
 def attention_first_row(q0, k, v, lens, n_heads, dropout_p=0.0, training=True, precision="fp32"):

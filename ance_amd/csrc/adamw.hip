@@ -170,18 +170,18 @@ extern "C" int ance_adamw_step(const AnceAdamwTensor *h_tensors, int n_tensors, 
     using namespace ance;
     const char *fn = "ance_adamw_step";
     if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
-        return mt::refuse(fn, "max_grad_norm not 0 or a positive finite number");
+        return refuse(fn, "max_grad_norm not 0 or a positive finite number");
     const bool clip = max_grad_norm != 0.0;
-    if (clip && n_tensors > 0 && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
-    if (n_tensors < 0) return mt::refuse(fn, "n_tensors < 0");
+    if (clip && n_tensors > 0 && !d_grad_norm) return refuse(fn, "null d_grad_norm");
+    if (n_tensors < 0) return refuse(fn, "n_tensors < 0");
     if (n_tensors == 0) return ANCE_OK;
-    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
-    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
+    if (!h_tensors || !h_groups) return refuse(fn, "null table");
+    if (n_groups < 1) return refuse(fn, "n_groups < 1");
     int64_t n_chunks = 0;
     if (const int e = mt::count_chunks(fn, h_tensors, n_tensors, n_groups, &n_chunks)) return e;
     const size_t need = workspace_bytes_for(n_tensors, n_groups, n_chunks, clip);
-    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
-    if (workspace_bytes < need) return mt::refuse(fn, "workspace too small");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < need) return refuse(fn, "workspace too small");
 
     const mt::Staged L = mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, n_chunks);
     hipStream_t st = (hipStream_t)stream;
@@ -206,14 +206,14 @@ extern "C" int ance_adamw_plan_build(const AnceAdamwTensor *h_tensors, int n_ten
                                      int64_t *n_chunks_out, size_t *table_bytes_out) {
     using namespace ance;
     const char *fn = "ance_adamw_plan_build";
-    if (n_tensors < 1) return mt::refuse(fn, "n_tensors < 1");
-    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
-    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
+    if (n_tensors < 1) return refuse(fn, "n_tensors < 1");
+    if (!h_tensors || !h_groups) return refuse(fn, "null table");
+    if (n_groups < 1) return refuse(fn, "n_groups < 1");
     int64_t n_chunks = 0;
     if (const int e = mt::count_chunks(fn, h_tensors, n_tensors, n_groups, &n_chunks)) return e;
-    if (!h_tables || !n_chunks_out || !table_bytes_out) return mt::refuse(fn, "null pointer");
+    if (!h_tables || !n_chunks_out || !table_bytes_out) return refuse(fn, "null pointer");
     const mt::Staged L = mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, n_chunks);
-    if (h_tables_bytes < L.end) return mt::refuse(fn, "h_tables too small");
+    if (h_tables_bytes < L.end) return refuse(fn, "h_tables too small");
     mt::fill_tables(h_tensors, n_tensors, h_groups, d_lrs, n_groups, sizeof(AdamwDevGroup), adamw_group_row, L, (char *)h_tables);
     *n_chunks_out = n_chunks;
     *table_bytes_out = L.end;
@@ -225,13 +225,13 @@ extern "C" int ance_adamw_step_planned(int n_tensors, int n_groups, int64_t n_ch
                                        void *d_workspace, size_t workspace_bytes, void *stream) {
     using namespace ance;
     const char *fn = "ance_adamw_step_planned";
-    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return mt::refuse(fn, "table sizes out of range");
+    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return refuse(fn, "table sizes out of range");
     if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
-        return mt::refuse(fn, "max_grad_norm not 0 or a positive finite number");
+        return refuse(fn, "max_grad_norm not 0 or a positive finite number");
     const bool clip = max_grad_norm != 0.0;
-    if (clip && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
-    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
-    if (workspace_bytes < workspace_bytes_for(n_tensors, n_groups, n_chunks, clip)) return mt::refuse(fn, "workspace too small");
+    if (clip && !d_grad_norm) return refuse(fn, "null d_grad_norm");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < workspace_bytes_for(n_tensors, n_groups, n_chunks, clip)) return refuse(fn, "workspace too small");
     const mt::Staged L = mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, n_chunks);
     return adamw_launch(fn, n_tensors, n_chunks, L, correct_bias, clip, max_grad_norm, d_grad_scale, d_found_inf, d_grad_norm, d_skipped,
                         (char *)d_workspace, (hipStream_t)stream);

@@ -6,7 +6,7 @@
 //   backward: t_j, P_j by the SAME expressions from the saved (m, l);  dP_j = keep_j ? (dctx0 . V_j) * keep_scale : 0;
 //             D = sum_j dP_j P_j;  dS_j = P_j (dP_j - D);  dq0 = 0.125f sum_j dS_j K_j;  dK_j = 0.125f dS_j q0;  dV_j = P'_j dctx0;
 //             rows len <= j < seq_rows of dK and dV are written as zeros; a sequence of length 0 writes a zero ctx0 and a zero dq0.
-//   Dropout: the full core's row i = 0 (attention_train.hip): Philox4x32-10, key (seed lo, seed hi), counter (j >> 2, s * n_heads + h,
+//   Dropout: the full core's row i = 0 (attention_train_kernels.h): Philox4x32-10, key (seed lo, seed hi), counter (j >> 2, s * n_heads + h,
 //             offset lo, offset hi), word j & 3, keep iff word >= keep_thr.
 // T = fp32, fp16 or bf16 is the type of the rows in memory only: all arithmetic is fp32, and every output element is rounded once at
 // its store (to nearest even, overflow to +-inf: the plain conversion).  P is never rounded: there is no matrix operand here.
@@ -18,9 +18,7 @@
 // over j is ascending in each group, then ascending over the groups; the workgroup's max / sum is an xor tree per wave, then the
 // four waves in order.  No atomics: the same inputs give the same bits.  The grid comes from n_heads and n_seq; the lengths are
 // read on the device; nothing waits for the host.
-#include "common.h"
-#include "philox.h"
-#include "attention_train.h"
+#include "attention_common.h"
 
 namespace ance {
 namespace {
@@ -289,54 +287,6 @@ __global__ void __launch_bounds__(R0_THREADS) row0_bwd_kernel(const Row0Params P
     weighted_rows<X>(part, t, P.k, P.ld_k, first, len, head, P.dq, P.ld_dq, s, 0.125f, tid);  // dq0 = 0.125 sum_j dS_j K_j
 }
 
-int refuse(const char *fn, const char *why) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: invalid argument (%s)", fn, why);
-    set_last_error(buf);
-    return ANCE_E_INVALID;
-}
-bool shape_ok(int64_t n_seq, int n_heads) { return n_seq >= 1 && n_seq <= 65535 && (n_heads == 12 || n_heads == 16); }
-size_t ws_bytes(int64_t n_seq, int n_heads) { return align_up(2 * sizeof(float) * (size_t)n_seq * (size_t)n_heads, 256); }
-const char *check_matrix(const void *p, int ld, int n_heads, int dtype) {
-    if (!p) return "null pointer";
-    if ((uintptr_t)p % 16) return "alignment: a base is not 16-byte aligned";
-    if (ld % (dtype == ANCE_DTYPE_F32 ? 4 : 8) != 0 || ld < 64 * n_heads) return "stride: not a multiple of a 16-byte piece or below 64 * n_heads";
-    return nullptr;
-}
-const char *check_args(const AnceAttn16Args *a) {
-    if (!a) return "null pointer";
-    if (a->dtype != ANCE_DTYPE_F32 && a->dtype != ANCE_DTYPE_F16 && a->dtype != ANCE_DTYPE_BF16) return "dtype not ANCE_DTYPE_F32, _F16 or _BF16";
-    if (a->n_heads != 12 && a->n_heads != 16) return "n_heads not 12 or 16";
-    if (a->max_seq_len < 1 || a->max_seq_len > R0_MAX_LEN) return "max_seq_len outside 1 .. 512";
-    if (a->n_seq < 1 || a->n_seq > 65535) return "n_seq outside 1 .. 65535";
-    if (a->n_rows < 1) return "n_rows < 1";
-    if (a->seq_rows < 0 || a->seq_rows > a->max_seq_len) return "seq_rows outside 0 .. max_seq_len";
-    if (!a->d_seq_first || !a->d_seq_len) return "null pointer";
-    if (const char *why = check_matrix(a->q, a->ld_q, a->n_heads, a->dtype)) return why;
-    if (const char *why = check_matrix(a->k, a->ld_k, a->n_heads, a->dtype)) return why;
-    if (const char *why = check_matrix(a->v, a->ld_v, a->n_heads, a->dtype)) return why;
-    if (const char *why = check_matrix(a->ctx, a->ld_ctx, a->n_heads, a->dtype)) return why;
-    if (!(a->dropout_p >= 0.0f && a->dropout_p < 1.0f)) return "dropout_p outside [0, 1)";
-    if (!a->d_workspace || (uintptr_t)a->d_workspace % 16) return "null or unaligned workspace";
-    if (a->workspace_bytes < ws_bytes(a->n_seq, a->n_heads)) return "workspace too small";
-    return nullptr;
-}
-Row0Params params(const AnceAttn16Args *a, const uint64_t *d_stream) {
-    Row0Params P = {};
-    P.q = a->q; P.k = a->k; P.v = a->v; P.ctx = a->ctx;
-    P.ld_q = a->ld_q; P.ld_k = a->ld_k; P.ld_v = a->ld_v; P.ld_ctx = a->ld_ctx;
-    P.seq_first = a->d_seq_first; P.seq_len = a->d_seq_len;
-    P.max_seq_len = a->max_seq_len; P.n_rows = a->n_rows; P.n_heads = a->n_heads; P.seq_rows = a->seq_rows;
-    P.ml = (float *)a->d_workspace;
-    P.seed_lo = (uint32_t)a->seed; P.seed_hi = (uint32_t)(a->seed >> 32);
-    P.off_lo = (uint32_t)a->offset; P.off_hi = (uint32_t)(a->offset >> 32);
-    P.d_stream = d_stream;  // given: seed and base come from the device, a->offset is added to the base
-    P.keep_thr = (uint32_t)((double)a->dropout_p * 4294967296.0);  // floor(p 2^32), p < 1
-    P.keep_scale = 1.0f / (1.0f - a->dropout_p);
-    return P;
-}
-bool drops(const AnceAttn16Args *a) { return a->training != 0 && a->dropout_p > 0.0f; }
-
 template <class X, bool BWD>
 void launch(const AnceAttn16Args *args, const Row0Params &P, hipStream_t st) {
     const dim3 grid((unsigned)args->n_heads, (unsigned)args->n_seq), block(R0_THREADS);
@@ -358,50 +308,37 @@ void launch_typed(const AnceAttn16Args *args, const Row0Params &P, hipStream_t s
     else launch<R0F32, BWD>(args, P, st);
 }
 
+size_t ws_bytes(int64_t n_seq, int n_heads) { return align_up(2 * sizeof(float) * (size_t)n_seq * (size_t)n_heads, 256); }
+
+// an entry point: attention_call with all three dtypes and the workspace as (max, sum) per (sequence, head)
+template <bool BWD>
+int call(const char *fn, const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, const uint64_t *d_stream, void *stream) {
+    const AttnRules rules = {1u << ANCE_DTYPE_F32 | 1u << ANCE_DTYPE_F16 | 1u << ANCE_DTYPE_BF16, "dtype not ANCE_DTYPE_F32, _F16 or _BF16",
+                             args ? ws_bytes(args->n_seq, args->n_heads) : 0};
+    return attention_call<Row0Params>(fn, rules, args, BWD, grads, d_stream, [&](Row0Params P) {
+        P.ml = (float *)args->d_workspace;
+        launch_typed<BWD>(args, P, (hipStream_t)stream);
+    });
+}
+
 }  // namespace
 }  // namespace ance
 
 extern "C" size_t ance_attention_row0_workspace_bytes(int64_t n_seq, int n_heads) {
-    using namespace ance;
-    return shape_ok(n_seq, n_heads) ? ws_bytes(n_seq, n_heads) : 0;
-}
-
-static int ance_attention_row0_forward_impl(const char *fn, const AnceAttn16Args *args, const uint64_t *d_stream, void *stream) {
-    using namespace ance;
-    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
-    if (const char *why = check_args(args)) return refuse(fn, why);
-    launch_typed<false>(args, params(args, d_stream), (hipStream_t)stream);
-    return check_launch(fn);
-}
-
-static int ance_attention_row0_backward_impl(const char *fn, const AnceAttn16Args *args, const AnceAttn16GradArgs *grads,
-                                             const uint64_t *d_stream, void *stream) {
-    using namespace ance;
-    if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
-    if (const char *why = check_args(args)) return refuse(fn, why);
-    if (!grads) return refuse(fn, "null pointer");
-    if (const char *why = check_matrix(grads->dctx, grads->ld_dctx, args->n_heads, args->dtype)) return refuse(fn, why);
-    if (const char *why = check_matrix(grads->dq, grads->ld_dq, args->n_heads, args->dtype)) return refuse(fn, why);
-    if (const char *why = check_matrix(grads->dk, grads->ld_dk, args->n_heads, args->dtype)) return refuse(fn, why);
-    if (const char *why = check_matrix(grads->dv, grads->ld_dv, args->n_heads, args->dtype)) return refuse(fn, why);
-    Row0Params P = params(args, d_stream);
-    P.dctx = grads->dctx; P.dq = grads->dq; P.dk = grads->dk; P.dv = grads->dv;
-    P.ld_dctx = grads->ld_dctx; P.ld_dq = grads->ld_dq; P.ld_dk = grads->ld_dk; P.ld_dv = grads->ld_dv;
-    launch_typed<true>(args, P, (hipStream_t)stream);
-    return check_launch(fn);
+    return ance::shape_ok(n_seq, 65535, n_heads) ? ance::ws_bytes(n_seq, n_heads) : 0;
 }
 
 // The entry points: each with its sibling that takes the device dropout stream (include/ance_amd.h); the plain one passes none.
 extern "C" int ance_attention_row0_forward(const AnceAttn16Args *args, void *stream) {
-    return ance_attention_row0_forward_impl("ance_attention_row0_forward", args, nullptr, stream);
+    return ance::call<false>("ance_attention_row0_forward", args, nullptr, nullptr, stream);
 }
 extern "C" int ance_attention_row0_forward_dstream(const AnceAttn16Args *args, const uint64_t *d_stream, void *stream) {
-    return ance_attention_row0_forward_impl("ance_attention_row0_forward_dstream", args, d_stream, stream);
+    return ance::call<false>("ance_attention_row0_forward_dstream", args, nullptr, d_stream, stream);
 }
 extern "C" int ance_attention_row0_backward(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, void *stream) {
-    return ance_attention_row0_backward_impl("ance_attention_row0_backward", args, grads, nullptr, stream);
+    return ance::call<true>("ance_attention_row0_backward", args, grads, nullptr, stream);
 }
 extern "C" int ance_attention_row0_backward_dstream(const AnceAttn16Args *args, const AnceAttn16GradArgs *grads, const uint64_t *d_stream,
                                                     void *stream) {
-    return ance_attention_row0_backward_impl("ance_attention_row0_backward_dstream", args, grads, d_stream, stream);
+    return ance::call<true>("ance_attention_row0_backward_dstream", args, grads, d_stream, stream);
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <float.h>
+#include <stdio.h>
 
 #include "../../include/ance_amd.h"
 
@@ -16,6 +17,13 @@ namespace ance {
 
 void set_last_error(const char *msg);
 int check_launch(const char *what);
+// an entry point's refusal: "<fn>: invalid argument (<why>)" as the last error, ANCE_E_INVALID as the status
+inline int refuse(const char *fn, const char *why) {
+    char buf[200];
+    snprintf(buf, sizeof(buf), "%s: invalid argument (%s)", fn, why);
+    set_last_error(buf);
+    return ANCE_E_INVALID;
+}
 
 // ---- optional per-kernel timing with HIP events on the launch stream (bench.py's roofline) ----
 enum ProfCat {

@@ -180,12 +180,6 @@ Layout layout(int64_t nq, int64_t nc) {
     L.total = L.off_flags + vec;
     return L;
 }
-int refuse(const char *fn, const char *why) {
-    char buf[160];
-    snprintf(buf, sizeof(buf), "%s: invalid argument (%s)", fn, why);
-    set_last_error(buf);
-    return ANCE_E_INVALID;
-}
 const char *check_common(const void *q, const void *ctx, const void *pos, int64_t nq, int64_t nc, int d, const void *ws, size_t ws_bytes) {
     if (!q || !ctx || !pos) return "null pointer";
     if (!in_envelope(nq, nc, d)) return "shape outside 1 <= nq <= 1024, nq <= nc <= 2048, 128 <= d <= 1024, d % 4 == 0";

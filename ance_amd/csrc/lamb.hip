@@ -217,8 +217,8 @@ int lamb_launch(const char *fn, int n_tensors, int64_t n_chunks, const mt::Stage
 // the checks a plan makes of its tables; ANCE_OK with *n_chunks, or a refusal in fn's name
 int lamb_check_tables(const char *fn, const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups,
                       int64_t *n_chunks) {
-    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
-    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
+    if (!h_tensors || !h_groups) return refuse(fn, "null table");
+    if (n_groups < 1) return refuse(fn, "n_groups < 1");
     return mt::count_chunks(fn, h_tensors, n_tensors, n_groups, n_chunks);
 }
 
@@ -227,16 +227,16 @@ int lamb_check_tables(const char *fn, const AnceLambTensor *h_tensors, int n_ten
 int lamb_step_impl(const char *fn, const AnceLambTensor *h_tensors, int n_tensors, const AnceLambGroup *h_groups, int n_groups, int adam,
                    float *d_out, void *d_workspace, size_t workspace_bytes, void *stream, bool clip, double max_norm,
                    float *d_grad_norm, const LambAmp &amp) {
-    if (n_tensors < 0) return mt::refuse(fn, "n_tensors < 0");
+    if (n_tensors < 0) return refuse(fn, "n_tensors < 0");
     if (n_tensors == 0) return ANCE_OK;
-    if (!h_tensors || !h_groups) return mt::refuse(fn, "null table");
-    if (n_groups < 1) return mt::refuse(fn, "n_groups < 1");
-    if (!d_out) return mt::refuse(fn, "null d_out");
+    if (!h_tensors || !h_groups) return refuse(fn, "null table");
+    if (n_groups < 1) return refuse(fn, "n_groups < 1");
+    if (!d_out) return refuse(fn, "null d_out");
     int64_t n_chunks = 0;
     if (const int e = mt::count_chunks(fn, h_tensors, n_tensors, n_groups, &n_chunks)) return e;
     const size_t need = clip ? workspace_bytes_clipped(n_tensors, n_groups, n_chunks) : workspace_bytes_for(n_tensors, n_groups, n_chunks);
-    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
-    if (workspace_bytes < need) return mt::refuse(fn, "workspace too small");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < need) return refuse(fn, "workspace too small");
 
     const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
     hipStream_t st = (hipStream_t)stream;
@@ -276,8 +276,8 @@ extern "C" int ance_lamb_step_clipped(const AnceLambTensor *h_tensors, int n_ten
                                       size_t workspace_bytes, void *stream) {
     using namespace ance;
     const char *fn = "ance_lamb_step_clipped";
-    if (!(max_grad_norm > 0.0) || !(max_grad_norm < (double)INFINITY)) return mt::refuse(fn, "max_grad_norm not a positive finite number");
-    if (n_tensors > 0 && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
+    if (!(max_grad_norm > 0.0) || !(max_grad_norm < (double)INFINITY)) return refuse(fn, "max_grad_norm not a positive finite number");
+    if (n_tensors > 0 && !d_grad_norm) return refuse(fn, "null d_grad_norm");
     return lamb_step_impl(fn, h_tensors, n_tensors, h_groups, n_groups, adam, d_out, d_workspace, workspace_bytes, stream, true,
                           max_grad_norm, d_grad_norm, LambAmp());
 }
@@ -293,9 +293,9 @@ extern "C" int ance_lamb_step_amp(const AnceLambTensor *h_tensors, int n_tensors
     using namespace ance;
     const char *fn = "ance_lamb_step_amp";
     if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
-        return mt::refuse(fn, "max_grad_norm not 0 or a positive finite number");
+        return refuse(fn, "max_grad_norm not 0 or a positive finite number");
     const bool clip = max_grad_norm != 0.0;
-    if (clip && n_tensors > 0 && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
+    if (clip && n_tensors > 0 && !d_grad_norm) return refuse(fn, "null d_grad_norm");
     LambAmp amp;
     amp.grad_scale = d_grad_scale;
     amp.found_inf = d_found_inf;
@@ -320,12 +320,12 @@ extern "C" int ance_lamb_plan_build(const AnceLambTensor *h_tensors, int n_tenso
                                     int64_t *n_chunks_out, size_t *table_bytes_out) {
     using namespace ance;
     const char *fn = "ance_lamb_plan_build";
-    if (n_tensors < 1) return mt::refuse(fn, "n_tensors < 1");
+    if (n_tensors < 1) return refuse(fn, "n_tensors < 1");
     int64_t n_chunks = 0;
     if (const int e = lamb_check_tables(fn, h_tensors, n_tensors, h_groups, n_groups, &n_chunks)) return e;
-    if (!h_tables || !n_chunks_out || !table_bytes_out) return mt::refuse(fn, "null pointer");
+    if (!h_tables || !n_chunks_out || !table_bytes_out) return refuse(fn, "null pointer");
     const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
-    if (h_tables_bytes < L.end) return mt::refuse(fn, "h_tables too small");
+    if (h_tables_bytes < L.end) return refuse(fn, "h_tables too small");
     mt::fill_tables(h_tensors, n_tensors, h_groups, d_lrs, n_groups, sizeof(LambDevGroup), lamb_group_row, L, (char *)h_tables);
     *n_chunks_out = n_chunks;
     *table_bytes_out = L.end;
@@ -337,15 +337,15 @@ extern "C" int ance_lamb_step_planned(int n_tensors, int n_groups, int64_t n_chu
                                       int64_t *d_skipped, float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
     using namespace ance;
     const char *fn = "ance_lamb_step_planned";
-    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return mt::refuse(fn, "table sizes out of range");
+    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return refuse(fn, "table sizes out of range");
     if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
-        return mt::refuse(fn, "max_grad_norm not 0 or a positive finite number");
+        return refuse(fn, "max_grad_norm not 0 or a positive finite number");
     const bool clip = max_grad_norm != 0.0;
-    if (clip && !d_grad_norm) return mt::refuse(fn, "null d_grad_norm");
-    if (!d_out) return mt::refuse(fn, "null d_out");
+    if (clip && !d_grad_norm) return refuse(fn, "null d_grad_norm");
+    if (!d_out) return refuse(fn, "null d_out");
     const size_t need = clip ? workspace_bytes_clipped(n_tensors, n_groups, n_chunks) : workspace_bytes_for(n_tensors, n_groups, n_chunks);
-    if (!d_workspace || (uintptr_t)d_workspace % 16) return mt::refuse(fn, "null or unaligned workspace");
-    if (workspace_bytes < need) return mt::refuse(fn, "workspace too small");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < need) return refuse(fn, "workspace too small");
     LambAmp amp;
     amp.grad_scale = d_grad_scale;
     amp.found_inf = d_found_inf;

@@ -162,9 +162,6 @@ inline int64_t max_chunks(int n_tensors, int64_t total_numel) {  // >= the sum o
     return (int64_t)n_tensors + total_numel / CHUNK;
 }
 
-// "<fn>: invalid argument (<why>)" -> the last error; returns ANCE_E_INVALID
-int refuse(const char *fn, const char *why);
-
 // every row of a host table checked (Host: AnceLambTensor or AnceAdamwTensor) and the chunks of the call counted -> *n_chunks;
 // ANCE_OK or a refusal in fn's name
 template <class Host>

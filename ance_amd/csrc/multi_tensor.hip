@@ -91,12 +91,6 @@ __global__ void __launch_bounds__(THREADS) gnorm_kernel(const DevTensor *tensors
 
 }  // namespace
 
-int refuse(const char *fn, const char *why) {
-    char buf[160];
-    snprintf(buf, sizeof(buf), "%s: invalid argument (%s)", fn, why);
-    set_last_error(buf);
-    return ANCE_E_INVALID;
-}
 
 template <class Host>
 int count_chunks(const char *fn, const Host *h_tensors, int n_tensors, int n_groups, int64_t *n_chunks) {

@@ -108,12 +108,6 @@ __global__ void __launch_bounds__(256) colsum_tree_kernel(const float *part, int
     }
 }
 
-inline int refuse(const char *fn, const char *why) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: invalid argument (%s)", fn, why);
-    set_last_error(buf);
-    return ANCE_E_INVALID;
-}
 inline bool rows_ok(int64_t n_rows) { return n_rows >= 1 && n_rows <= 0x7fffffff; }
 inline size_t n_part(int64_t n_rows) { return (size_t)((n_rows + LT_ROWS - 1) / LT_ROWS); }
 inline size_t stats_bytes(int64_t n_rows) { return 2 * align_up(sizeof(float) * (size_t)n_rows, 256); }

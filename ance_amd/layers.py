@@ -26,7 +26,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .attention import (_NO_DRAW, HALF_DTYPES, _check_precision, _custom_bwd, _custom_fwd, _custom_fwd_as_is, _rows, _rows16,
+from .attention import (_NO_DRAW, HALF_DTYPES, _check_precision, _custom_bwd, _custom_fwd, _custom_fwd_as_is, _rows,
                         attention_first_row, attention_padded, dropout_state)
 
 __all__ = ["dropout_add_layer_norm", "bias_gelu", "BertLayer"]
@@ -177,7 +177,7 @@ def _matrix16(t):
     """_matrix for a 16-bit tensor (a row stride must be a multiple of 8 elements)."""
     if t.dim() > 3:
         t = t.reshape(-1, t.shape[-1])
-    return _rows16(t)
+    return _rows(t, 8)
 
 
 class _DropoutAddLayerNormHalf(torch.autograd.Function):

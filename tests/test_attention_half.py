@@ -64,12 +64,12 @@ def test_rows16_accepts_strides_that_are_multiples_of_8():
     from ance_amd import attention as T
     fused = torch.zeros(2, 8, 3 * 768, dtype=torch.float16)
     for t in (fused[..., :768], fused[..., 768:1536], fused[..., 1536:]):
-        kept, ld = T._rows16(t)
+        kept, ld = T._rows(t, 8)
         assert ld == 3 * 768 and kept.data_ptr() == t.data_ptr()          # a view passes as it is
     odd = torch.zeros(2, 8, 768 + 4, dtype=torch.float16)[..., :768]     # stride 772: a multiple of 4, not of 8
-    kept, ld = T._rows16(odd)
+    kept, ld = T._rows(odd, 8)
     assert ld == 768 and kept.is_contiguous()
-    kept, ld = T._rows16(torch.zeros(16, 776, dtype=torch.bfloat16)[:, :768])
+    kept, ld = T._rows(torch.zeros(16, 776, dtype=torch.bfloat16)[:, :768], 8)
     assert ld == 776
 
 
