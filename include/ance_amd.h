@@ -463,9 +463,11 @@ int ance_attention16_backward_dstream(const AnceAttn16Args *args, const AnceAttn
  * All arithmetic is fp32 whatever the dtype; every output element is rounded once at its store (to nearest even, overflow to +-inf);
  * P is never rounded.  seq_rows > 0: rows len .. seq_rows - 1 of the sequence in dk and dv are WRITTEN AS ZEROS by the backward (every
  * valid row of dk and dv is written too: no pre-zeroing); seq_rows = 0: only the valid rows are written.  A sequence of length <= 0
- * gets a zero ctx[s] and a zero dq[s].  Dropout is the full core's query row i = 0 of sequence s, bit for bit: counter (j >> 2,
- * s * n_heads + h, offset lo32, offset hi32), word j & 3; the _dstream forms as above.  d_workspace
- * (ance_attention_row0_workspace_bytes) is the saved state: fp32 (m, l) per (sequence, head), entry 2 (s n_heads + h).  One launch
+ * gets a zero ctx[s] and a zero dq[s].  A sequence whose first row lies outside [0, n_rows) is treated as one of length 0 that owns
+ * no rows: ctx[s] and dq[s] are written as zeros and nothing of dk or dv is touched, in both forms (a negative length with a first
+ * row inside is an empty sequence: seq_rows > 0 zeroes the rows it owns, clamped to n_rows).  Dropout is the full core's query row
+ * i = 0 of sequence s, bit for bit: counter (j >> 2, s * n_heads + h, offset lo32, offset hi32), word j & 3; the _dstream forms as
+ * above.  d_workspace (ance_attention_row0_workspace_bytes) is the saved state: fp32 (m, l) per (sequence, head), entry 2 (s n_heads + h).  One launch
  * forward, one backward, one workgroup per (sequence, head), no atomics, every sum in a fixed order: the same inputs give the same
  * bits.  The grid is sized from n_seq and n_heads; nothing is read back -- both calls can be captured.  Refuses what the 16-bit core
  * refuses (with the stride rule above), before any launch. */

@@ -243,6 +243,69 @@ def test_packed_form_leaves_uncovered_rows_alone():
     HU.check("C ABI packed, stride 776", got, want, ref, dtype)
 
 
+def test_padded_form_zeroes_its_pad_rows_and_leaves_the_rest_alone():
+    """The padded_rule twin of the test above, in bf16 (seq_rows = L): the pad rows of the 31-row sequence and the rows of the empty
+    one are written as exact zeros by the call itself into sentinel-filled ctx, dq, dk and dv -- up to an n_rows that ends inside the
+    buffer, 40 rows into the empty sequence: nothing at or behind it is touched.  Guard rows, the stride's unused columns and the
+    NaN-filled workspace's guards keep their bits; a length above max_seq_len is clamped; descriptors that start outside [0, n_rows)
+    touch nothing.  The guards are wide enough for a kernel without its clamps to stay inside the buffers."""
+    import ctypes
+    from ance_amd import _lib
+    L_ = _lib.lib()
+    dtype, SENT, NAN32 = torch.bfloat16, 0x7FCB, 0x7FC00ABC   # NaNs with a recognisable payload
+    (q, k, v, g, ln), want, ref, _ = _seeded("layouts", LAYOUT_LENS, 12, LAYOUT_L, 1.0, 0.0, 0, 0, "bf16")
+    B, Lq, H, G, ld = len(ln), LAYOUT_L, 768, 64, 768 + 8
+    all_rows, n_rows = B * Lq, 2 * Lq + 40
+    valid = (np.arange(Lq)[None, :] < ln[:, None]).reshape(-1)
+    inside = np.arange(all_rows) < n_rows
+    # a first row at n_rows + 7 with seq_rows = 96 rows behind it, and one at -3, stay inside the guards even without clamps
+    assert n_rows + 7 + Lq <= all_rows + G and 3 <= G and 200 <= all_rows + G
+
+    def guarded(x=None):
+        buf = torch.full((all_rows + 2 * G, ld), SENT, dtype=torch.int16, device=DEV).view(dtype)
+        if x is not None:
+            buf[G:G + all_rows, :H] = _dev(x.reshape(all_rows, H), dtype)
+        return buf
+
+    ins = dict(q=guarded(q), k=guarded(k), v=guarded(v), dctx=guarded(np.where(valid.reshape(B, Lq)[:, :, None], g, np.float32("nan"))))
+    before = {n: t.view(torch.int16).clone() for n, t in ins.items()}
+    outs = dict(ctx=guarded(), dq=guarded(), dk=guarded(), dv=guarded())
+    ws_bytes = L_.ance_attention16_workspace_bytes(n_rows, 12)
+    ws = torch.full((ws_bytes // 4 + 2 * 64,), NAN32, dtype=torch.int32, device=DEV).view(torch.float32)
+    first = _dev(np.array([0, Lq, 2 * Lq, n_rows + 7, -3], np.int32))
+    lens = _dev(np.array([200, 31, 0, 50, 20], np.int32))   # 200 is clamped to max_seq_len; the last two start outside [0, n_rows)
+    P = lambda t: t[G:].data_ptr()  # noqa: E731
+    a = _lib.AnceAttn16Args(q=P(ins["q"]), k=P(ins["k"]), v=P(ins["v"]), ctx=P(outs["ctx"]), ld_q=ld, ld_k=ld, ld_v=ld, ld_ctx=ld,
+                            d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(), n_seq=5, max_seq_len=Lq, n_rows=n_rows,
+                            n_heads=12, seq_rows=Lq, dtype=_lib.ANCE_DTYPE_BF16, dropout_p=0.0, training=1, seed=0, offset=0,
+                            d_workspace=ws[64:].data_ptr(), workspace_bytes=ws_bytes)
+    gr = _lib.AnceAttn16GradArgs(dctx=P(ins["dctx"]), dq=P(outs["dq"]), dk=P(outs["dk"]), dv=P(outs["dv"]), ld_dctx=ld, ld_dq=ld,
+                                 ld_dk=ld, ld_dv=ld)
+    st = _lib.current_stream_ptr()
+    _lib.check(L_.ance_attention16_forward(ctypes.byref(a), st), "forward")
+    _lib.check(L_.ance_attention16_backward(ctypes.byref(a), ctypes.byref(gr), st), "backward")
+    torch.cuda.synchronize()
+    got = {}
+    for n, buf in outs.items():
+        bits = buf.view(torch.int16).cpu().numpy()
+        assert np.all(bits[:G] == SENT) and np.all(bits[G + all_rows:] == SENT), n + ": guard rows"
+        assert np.all(bits[:, H:] == SENT), n + ": columns past 64 n_heads"
+        body = bits[G:G + all_rows, :H]
+        assert np.all(body[~valid & inside] == 0), n + ": pad rows below n_rows are written as +0.0"
+        assert np.all(body[~inside] == SENT), n + ": nothing at or behind n_rows is touched"
+        x = np.zeros((all_rows, H), np.float32)
+        x[valid] = _np(buf)[G:G + all_rows, :H][valid]
+        assert np.all(np.isfinite(x)), n
+        got[n] = x.reshape(B, Lq, H)
+    for n, t in ins.items():
+        assert torch.equal(t.view(torch.int16), before[n]), n + " has changed"
+    wbits = ws.view(torch.int32).cpu().numpy()
+    assert np.all(wbits[:64] == NAN32) and np.all(wbits[64 + ws_bytes // 4:] == NAN32), "workspace guards"
+    got["lse"] = np.zeros((12, all_rows), np.float32)
+    got["lse"][:, :n_rows] = np.where(valid[None, :n_rows], _np(ws)[64:64 + 12 * n_rows].reshape(12, n_rows), 0)
+    HU.check("C ABI padded bf16, stride 776", got, want, ref, dtype)
+
+
 # ---------------------------------------------------------------------------------------------------------------- 7. determinism
 @pytest.mark.parametrize("dt", BOTH)
 def test_deterministic_capturable_and_never_synchronises(dt):

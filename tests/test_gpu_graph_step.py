@@ -93,6 +93,23 @@ def _attention_case(form, precision, p):
     return fn
 
 
+def _first_row_case(precision, p):
+    """The first-row core on the padded case's shape: q0 [3, 768], k, v [3, 40, 768]; ctx0 and the three gradients."""
+    from ance_amd.attention import attention_first_row
+    lens, L, H = (33, 5, 1), 40, 768
+    dt = torch.float32 if precision == "fp32" else HALF[precision]
+    q0, d = _rand("row0.q", (len(lens), H), 1.0, dt), _rand("row0.d", (len(lens), H), 1.0, dt)
+    k, v = (_rand("row0." + n, (len(lens), L, H), 1.0, dt) for n in "kv")
+    lens_t = torch.tensor(lens, dtype=torch.int32, device=DEV)
+
+    def fn():
+        a, b, c = (t.clone().requires_grad_(True) for t in (q0, k, v))
+        out = attention_first_row(a, b, c, lens_t, 12, p, True, precision="fp32" if precision == "fp32" else "half")
+        out.backward(d)
+        return [out.detach(), a.grad, b.grad, c.grad]
+    return fn
+
+
 def _tail_case(H, precision, p, rows=17):
     from ance_amd.layers import dropout_add_layer_norm
     dt = torch.float32 if precision == "fp32" else HALF[precision]
@@ -123,6 +140,7 @@ def _embed_case(p, rows=17, H=768):
 
 ENTRY_POINTS = (
     [("attention %s %s" % (f, pr), lambda p, f=f, pr=pr: _attention_case(f, pr, p)) for f in ("padded", "packed") for pr in ("fp32", "fp16", "bf16")]
+    + [("first row %s" % pr, lambda p, pr=pr: _first_row_case(pr, p)) for pr in ("fp32", "fp16", "bf16")]
     + [("tail %d %s" % (H, pr), lambda p, H=H, pr=pr: _tail_case(H, pr, p)) for H in (768, 1024) for pr in ("fp32", "fp16", "bf16")]
     + [("embeddings", lambda p: _embed_case(p))])
 
@@ -155,6 +173,8 @@ def test_unaligned_stream_is_refused_and_nothing_is_launched():
              ("ance_attention_backward_dstream", (ctypes.byref(_lib.AnceAttnTrainArgs()), ctypes.byref(_lib.AnceAttnGradArgs()))),
              ("ance_attention16_forward_dstream", (ctypes.byref(_lib.AnceAttn16Args()),)),
              ("ance_attention16_backward_dstream", (ctypes.byref(_lib.AnceAttn16Args()), ctypes.byref(_lib.AnceAttn16GradArgs()))),
+             ("ance_attention_row0_forward_dstream", (ctypes.byref(_lib.AnceAttn16Args()),)),
+             ("ance_attention_row0_backward_dstream", (ctypes.byref(_lib.AnceAttn16Args()), ctypes.byref(_lib.AnceAttn16GradArgs()))),
              ("ance_layer_tail_forward_dstream", (ctypes.byref(_lib.AnceLayerTailArgs()),)),
              ("ance_layer_tail_backward_dstream", (ctypes.byref(_lib.AnceLayerTailArgs()), ctypes.byref(_lib.AnceLayerTailGradArgs()))),
              ("ance_layer_tail16_forward_dstream", (ctypes.byref(_lib.AnceLayerTail16Args()),)),
