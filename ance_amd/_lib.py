@@ -197,6 +197,22 @@ class AnceEmbedGradArgs(ctypes.Structure):
                 ("type_perm", ctypes.c_void_p)]
 
 
+class AncePackArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_pack_tokens."""
+    _fields_ = [("ids", ctypes.c_void_p), ("type_ids", ctypes.c_void_p), ("d_seq_len", ctypes.c_void_p), ("d_seq_off", ctypes.c_void_p),
+                ("d_seq_kept", ctypes.c_void_p), ("d_dropped", ctypes.c_void_p), ("packed_ids", ctypes.c_void_p),
+                ("packed_type_ids", ctypes.c_void_p), ("packed_positions", ctypes.c_void_p), ("n_seq", ctypes.c_int32),
+                ("L", ctypes.c_int32), ("rows", ctypes.c_int32), ("position_mode", ctypes.c_int32), ("padding_idx", ctypes.c_int32),
+                ("vocab", ctypes.c_int32), ("max_pos", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AnceFirstRowsArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_first_rows_gather / ance_first_rows_scatter."""
+    _fields_ = [("rows_matrix", ctypes.c_void_p), ("first", ctypes.c_void_p), ("d_seq_off", ctypes.c_void_p),
+                ("d_seq_kept", ctypes.c_void_p), ("ld_rows", ctypes.c_int32), ("ld_first", ctypes.c_int32), ("n_seq", ctypes.c_int32),
+                ("rows", ctypes.c_int32), ("H", ctypes.c_int32), ("dtype", ctypes.c_int32)]
+
+
 # include/ance_amd.h: ANCE_EMBED_SEGMENT_CHUNK (the library states the same number through ance_embed_segment_chunk), ANCE_EMBED_POSITION_*
 EMBED_SEGMENT_CHUNK = 64
 EMBED_POSITION_MODES = {"absolute": 0, "roberta": 1}
@@ -347,6 +363,14 @@ SYMBOLS = {
     "ance_layer_tail16_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceLayerTail16Args), ctypes.POINTER(AnceLayerTail16GradArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "ance_embed_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "ance_embed_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    # packed token rows of a fixed capacity (csrc/pack_rows.hip) and the embeddings over rows with given positions
+    "ance_pack_tokens": (ctypes.c_int, [ctypes.POINTER(AncePackArgs), ctypes.c_void_p]),
+    "ance_embed_rows_forward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p]),
+    "ance_embed_rows_backward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p]),
+    "ance_embed_rows_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_embed_rows_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "ance_first_rows_gather": (ctypes.c_int, [ctypes.POINTER(AnceFirstRowsArgs), ctypes.c_void_p]),
+    "ance_first_rows_scatter": (ctypes.c_int, [ctypes.POINTER(AnceFirstRowsArgs), ctypes.c_void_p]),
     "ance_dropout_stream_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     # the fused optimizers' resident plans (tables built once into caller-owned host memory; steps that only launch) and the schedule
     "ance_lamb_plan_table_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),

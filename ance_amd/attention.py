@@ -36,7 +36,8 @@ except ImportError:  # pragma: no cover
     _custom_fwd = _amp_fwd(cast_inputs=torch.float32)
     _custom_fwd_as_is = _amp_fwd
 
-__all__ = ["attention_padded", "attention_packed", "attention_first_row", "lens_from_mask", "manual_seed", "dropout_state"]
+__all__ = ["attention_padded", "attention_packed", "attention_first_row", "attention_first_row_packed", "lens_from_mask",
+           "manual_seed", "dropout_state"]
 
 
 class _Draw(object):
@@ -366,11 +367,13 @@ def _packed(q, k, v, seq_off, max_seq_len, n_heads, dropout_p, training, precisi
     return _Attention.apply(q, k, v, first, lens, int(max_seq_len), n_heads, float(dropout_p), bool(training))
 
 
-def _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, piece, dtype_code):
-    """The forward of both first-row functions (csrc/attention_row0.hip): q0 [B, H], k, v [B, L, H] of one dtype."""
+def _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, max_seq_len, piece, dtype_code):
+    """The forward of both first-row functions (csrc/attention_row0.hip): q0 [B, H], k, v of one dtype -- [B, L, H] (the padded form,
+    max_seq_len = L) or [R, H] (the packed form: seq_rows = 0, nothing outside the valid rows is written)."""
     L = _lib.lib()
     (q0, ld_q), (k, ld_k), (v, ld_v) = _rows(q0, piece), _rows(k, piece), _rows(v, piece)
-    B, Lk, H = k.shape
+    B, H = q0.shape
+    Lk, n_rows, seq_rows = max_seq_len, k.numel() // H, max_seq_len if k.dim() == 3 else 0
     out = torch.empty((B, H), dtype=q0.dtype, device=q0.device)
     ws_bytes = L.ance_attention_row0_workspace_bytes(B, n_heads)
     if ws_bytes == 0:
@@ -380,7 +383,7 @@ def _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training,
     draw = dropout_state.draw(q0.device) if drop else _NO_DRAW
     args = _lib.AnceAttn16Args(q=q0.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), ctx=out.data_ptr(), ld_q=ld_q, ld_k=ld_k, ld_v=ld_v,
                                ld_ctx=H, d_seq_first=first.data_ptr(), d_seq_len=lens.data_ptr(), n_seq=B, max_seq_len=Lk,
-                               n_rows=B * Lk, n_heads=n_heads, seq_rows=Lk, dtype=dtype_code, dropout_p=float(dropout_p),
+                               n_rows=n_rows, n_heads=n_heads, seq_rows=seq_rows, dtype=dtype_code, dropout_p=float(dropout_p),
                                training=1 if drop else 0, seed=draw.seed, offset=draw.offset, d_workspace=ws.data_ptr(),
                                workspace_bytes=ws_bytes)
     with torch.cuda.device(q0.device):
@@ -394,12 +397,14 @@ def _first_row_backward(ctx, dctx0, piece):
     q0, k, v, first, lens, ws = ctx.saved_tensors
     dctx0, ld_d = _rows(dctx0.to(q0.dtype), piece)
     dq0 = torch.empty(q0.shape, dtype=q0.dtype, device=q0.device)
-    dk, dv = (torch.empty(k.shape, dtype=k.dtype, device=k.device) for _ in range(2))   # the kernel writes every row, pads as zeros
+    # padded form: the kernel writes every row, pads as zeros; packed form: rows that no sequence covers stay zero
+    make = torch.empty if ctx.args.seq_rows else torch.zeros
+    dk, dv = (make(k.shape, dtype=k.dtype, device=k.device) for _ in range(2))
     g = _lib.AnceAttn16GradArgs(dctx=dctx0.data_ptr(), dq=dq0.data_ptr(), dk=dk.data_ptr(), dv=dv.data_ptr(), ld_dctx=ld_d,
                                 ld_dq=dq0.shape[-1], ld_dk=dk.shape[-1], ld_dv=dv.shape[-1])
     with torch.cuda.device(q0.device):
         ctx.draw.launch("ance_attention_row0_backward", ctypes.byref(ctx.args), ctypes.byref(g))
-    return dq0, dk, dv, None, None, None, None, None
+    return dq0, dk, dv, None, None, None, None, None, None
 
 
 class _AttentionFirstRow(torch.autograd.Function):
@@ -407,8 +412,8 @@ class _AttentionFirstRow(torch.autograd.Function):
 
     @staticmethod
     @_custom_fwd
-    def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training):
-        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, 4, _lib.ANCE_DTYPE_F32)
+    def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, max_seq_len):
+        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, max_seq_len, 4, _lib.ANCE_DTYPE_F32)
 
     @staticmethod
     @_custom_bwd
@@ -422,8 +427,8 @@ class _AttentionFirstRowHalf(torch.autograd.Function):
 
     @staticmethod
     @_custom_fwd_as_is
-    def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training):
-        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, 8, HALF_DTYPES[q0.dtype])
+    def forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, max_seq_len):
+        return _first_row_forward(ctx, q0, k, v, first, lens, n_heads, dropout_p, training, max_seq_len, 8, HALF_DTYPES[q0.dtype])
 
     @staticmethod
     @_custom_bwd
@@ -453,8 +458,30 @@ def attention_first_row(q0, k, v, lens, n_heads, dropout_p=0.0, training=True, p
     lens = _int32(lens, "lens", B, k.device)
     first = torch.arange(0, B * Lk, Lk, dtype=torch.int32, device=k.device)
     if half:
-        return _AttentionFirstRowHalf.apply(*_half_inputs(q0, k, v), first, lens, n_heads, float(dropout_p), bool(training))
-    return _AttentionFirstRow.apply(q0, k, v, first, lens, n_heads, float(dropout_p), bool(training))
+        return _AttentionFirstRowHalf.apply(*_half_inputs(q0, k, v), first, lens, n_heads, float(dropout_p), bool(training), Lk)
+    return _AttentionFirstRow.apply(q0, k, v, first, lens, n_heads, float(dropout_p), bool(training), Lk)
+
+
+def attention_first_row_packed(q0, k, v, seq_off, max_seq_len, n_heads, dropout_p=0.0, training=True, precision="fp32"):
+    """``attention_first_row`` over packed rows: q0 [B, H] (the query of every sequence's first row), k, v [R, H], sequence s being
+    rows seq_off[s] .. seq_off[s + 1] - 1 (seq_off: device integers [B + 1]), each at most max_seq_len <= 512 rows.  ctx0 [B, H];
+    gradients for q0, k and v, of which dk and dv are zero at every row that no sequence covers.  A sequence of length 0 (an empty
+    or a dropped one of ``pack_tokens``) gives a zero ctx0 row and zero gradients.  The dropout mask of sequence s is the padded
+    call's, bit for bit, under the same (seed, offset).  precision: as attention_first_row."""
+    half = _check_precision(precision)
+    _check_inputs(k, k, v, n_heads, dropout_p, 2, half)
+    _check_inputs(q0, q0, q0, n_heads, dropout_p, 2, half)
+    if not 1 <= int(max_seq_len) <= 512:
+        raise _lib.AnceLibraryError("max_seq_len must be in 1 .. 512, got %r" % (max_seq_len,))
+    B = q0.shape[0]
+    if q0.device != k.device or not isinstance(seq_off, torch.Tensor) or seq_off.dim() != 1 or seq_off.numel() != B + 1:
+        raise _lib.AnceLibraryError("q0 must be [B, H] on k's device and seq_off a device integer tensor [B + 1]")
+    off = _int32(seq_off, "seq_off", B + 1, k.device)
+    first, lens = off[:-1].contiguous(), (off[1:] - off[:-1]).contiguous()
+    if half:
+        return _AttentionFirstRowHalf.apply(*_half_inputs(q0, k, v), first, lens, n_heads, float(dropout_p), bool(training),
+                                            int(max_seq_len))
+    return _AttentionFirstRow.apply(q0, k, v, first, lens, n_heads, float(dropout_p), bool(training), int(max_seq_len))
 
 
 # _padded / _packed return (ctx, lse): lse is the saved fp32 log-sum-exp [n_heads, rows] (zeros at pad rows), non-differentiable.  It

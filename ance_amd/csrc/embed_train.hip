@@ -9,6 +9,8 @@
 //             partial rows of dgamma = sum d o xhat, dbeta = sum d and sum dv per 16-row workgroup, then row_kernels.h's tree
 //             table gradients: dTable[key] = sum of dv over the rows with that key, a segmented sum over the rows in the order of a
 //             STABLE sort of the keys (see seg_piece_kernel below).  No atomics.
+//   rows forms  (ance_embed_rows_*: packed rows, pack_rows.hip) the same kernels over T rows with L = 1 whose position is the CALLER's
+//             positions[row], read in both directions; dpos then always goes through the sorted keys
 // One wave owns a token row, as in layer_tail.hip; the reductions, the partial rows and the tree are row_kernels.h's.
 #include "common.h"
 #include "philox.h"
@@ -29,6 +31,7 @@ struct EmbedParams {
     int *positions;
     int64_t n_rows;
     int L, vocab, max_pos, n_types, roberta, pad;
+    int given;  // the rows forms (ance_embed_rows_*): the position of a row is positions[row], in both directions
     float eps, keep_scale;
     uint32_t seed_lo, seed_hi, off_lo, off_hi, keep_thr;
     const uint64_t *d_stream;  // null, or the device stream {seed, base} (philox.h: drop_stream)
@@ -38,12 +41,15 @@ __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n
 
 // (id, tt, p) of a row, each clamped into its table before anything is addressed with it.  FWD: the roberta position is counted from
 // the sequence's prefix; otherwise it is read back from the saved buffer (and clamped again: the buffer is memory like any other).
+// given (the rows forms): the caller's positions are read, forward and backward, and the forward writes none.
 template <bool FWD>
 __device__ __forceinline__ void row_keys(const EmbedParams &P, int64_t row, int lane, int &id, int &tt, int &p) {
     id = clampi(P.ids[row], P.vocab);
     tt = P.type_ids ? clampi(P.type_ids[row], P.n_types) : 0;
     const int l = (int)(row % P.L);
-    if (!P.roberta) {
+    if (P.given) {
+        p = clampi(P.positions[row], P.max_pos);
+    } else if (!P.roberta) {
         p = clampi(l, P.max_pos);
     } else if (FWD) {
         const int *seq = P.ids + (row - l);
@@ -120,7 +126,7 @@ __global__ void __launch_bounds__(LT_THREADS) embed_fwd_kernel(const EmbedParams
         if (lane == 0) {
             P.mean[row] = mean;
             P.rstd[row] = rstd;
-            if (P.roberta) P.positions[row] = p;
+            if (P.roberta && !P.given) P.positions[row] = p;
         }
     }
 }
@@ -288,14 +294,20 @@ const char *check_ints(const void *p, bool nullable = false) {
     return nullptr;
 }
 
-const char *check_embed(const AnceEmbedArgs *a, bool backward) {
+const char *check_embed(const AnceEmbedArgs *a, bool backward, bool rows = false) {
     if (!a) return "null pointer";
     if (a->H != 768 && a->H != 1024) return "width H not 768 or 1024";
+    if (rows && a->L != 1) return "the rows form takes L = 1: n_seq is the number of rows";
     if (a->L < 1 || a->L > 512) return "L outside 1 .. 512";
     if (a->n_seq < 1 || (int64_t)a->n_seq * a->L > 0x7fffffff) return "n_seq < 1 or more than 2^31 - 1 rows";
     if (a->vocab < 1 || a->max_pos < 1) return "an empty table";
     if (a->n_types != 1 && a->n_types != 2) return "n_types not 1 or 2";
-    if (a->position_mode == ANCE_EMBED_POSITION_ABSOLUTE) {
+    if (rows) {  // the positions are given: the mode only says whether the position table has a padding row
+        if (a->position_mode != ANCE_EMBED_POSITION_ABSOLUTE && a->position_mode != ANCE_EMBED_POSITION_ROBERTA) return "position_mode not 0 or 1";
+        const int lo = a->position_mode == ANCE_EMBED_POSITION_ROBERTA ? 0 : -1;
+        if (a->padding_idx < lo || a->padding_idx >= a->vocab) return "padding_idx outside its range";
+        if (const char *why = check_ints(a->positions)) return why;
+    } else if (a->position_mode == ANCE_EMBED_POSITION_ABSOLUTE) {
         if (a->L > a->max_pos) return "absolute positions: L > max_pos";
         if (a->padding_idx < -1 || a->padding_idx >= a->vocab) return "padding_idx outside -1 .. vocab - 1";
     } else if (a->position_mode == ANCE_EMBED_POSITION_ROBERTA) {
@@ -321,7 +333,7 @@ const char *check_embed(const AnceEmbedArgs *a, bool backward) {
     return check_workspace(a->d_workspace, a->workspace_bytes, backward ? embed_ws_bytes(n_rows, a->H) : stats_bytes(n_rows));
 }
 
-EmbedParams embed_params(const AnceEmbedArgs *a, const uint64_t *d_stream) {
+EmbedParams embed_params(const AnceEmbedArgs *a, const uint64_t *d_stream, bool rows = false) {
     EmbedParams P = {};
     const int64_t n_rows = (int64_t)a->n_seq * a->L;
     P.ids = a->ids; P.type_ids = a->type_ids;
@@ -329,7 +341,8 @@ EmbedParams embed_params(const AnceEmbedArgs *a, const uint64_t *d_stream) {
     P.y = a->y; P.positions = a->positions;
     P.n_rows = n_rows;
     P.L = a->L; P.vocab = a->vocab; P.max_pos = a->max_pos; P.n_types = a->n_types;
-    P.roberta = a->position_mode == ANCE_EMBED_POSITION_ROBERTA; P.pad = a->padding_idx;
+    P.roberta = !rows && a->position_mode == ANCE_EMBED_POSITION_ROBERTA; P.pad = a->padding_idx;
+    P.given = rows ? 1 : 0;
     char *ws = (char *)a->d_workspace;
     P.mean = (float *)ws;
     P.rstd = (float *)(ws + stats_bytes(n_rows) / 2);
@@ -368,11 +381,11 @@ extern "C" size_t ance_embed_workspace_bytes(int64_t n_rows, int H) {
     return rows_ok(n_rows) && (H == 768 || H == 1024) ? embed_ws_bytes(n_rows, H) : 0;
 }
 
-static int ance_embed_forward_impl(const char *fn, const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream) {
+static int ance_embed_forward_impl(const char *fn, const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream, bool rows = false) {
     using namespace ance;
     if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
-    if (const char *why = check_embed(args, false)) return refuse(fn, why);
-    const EmbedParams P = embed_params(args, d_stream);
+    if (const char *why = check_embed(args, false, rows)) return refuse(fn, why);
+    const EmbedParams P = embed_params(args, d_stream, rows);
     const dim3 grid((unsigned)n_part(P.n_rows)), block(LT_THREADS);
     hipStream_t st = (hipStream_t)stream;
     const int mode = drop_mode(drops(args), d_stream);
@@ -383,10 +396,10 @@ static int ance_embed_forward_impl(const char *fn, const AnceEmbedArgs *args, co
 }
 
 static int ance_embed_backward_impl(const char *fn, const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream,
-                                    void *stream) {
+                                    void *stream, bool rows = false) {
     using namespace ance;
     if (!stream_aligned(d_stream)) return refuse(fn, "alignment: d_stream is not 16-byte aligned");
-    if (const char *why = check_embed(args, true)) return refuse(fn, why);
+    if (const char *why = check_embed(args, true, rows)) return refuse(fn, why);
     if (!grads) return refuse(fn, "null pointer");
     if (const char *why = check_vector(grads->dy)) return refuse(fn, why);
     for (const float *p : {(const float *)grads->dword, (const float *)grads->dpos, (const float *)grads->dtype,
@@ -397,14 +410,14 @@ static int ance_embed_backward_impl(const char *fn, const AnceEmbedArgs *args, c
     const bool seg_word = grads->dword != nullptr, seg_pos = grads->dpos != nullptr;
     const bool seg_type = grads->dtype != nullptr && args->n_types == 2 && args->type_ids != nullptr;
     if (seg_word && (!grads->word_keys || !grads->word_perm)) return refuse(fn, "null pointer: dword without word_keys / word_perm");
-    if (seg_pos && roberta && (!grads->pos_keys || !grads->pos_perm)) return refuse(fn, "null pointer: dpos without pos_keys / pos_perm");
+    if (seg_pos && (roberta || rows) && (!grads->pos_keys || !grads->pos_perm)) return refuse(fn, "null pointer: dpos without pos_keys / pos_perm");
     if (seg_type && (!grads->type_keys || !grads->type_perm)) return refuse(fn, "null pointer: dtype without type_keys / type_perm");
     for (const void *p : {(const void *)grads->word_keys, (const void *)grads->pos_keys, (const void *)grads->type_keys})
         if (const char *why = check_ints(p, true)) return refuse(fn, why);
     for (const void *p : {(const void *)grads->word_perm, (const void *)grads->pos_perm, (const void *)grads->type_perm})
         if (p && (uintptr_t)p % 8) return refuse(fn, "alignment: a permutation is not 8-byte aligned");
 
-    EmbedParams P = embed_params(args, d_stream);
+    EmbedParams P = embed_params(args, d_stream, rows);
     P.dy = grads->dy;
     const int H = args->H;
     const dim3 grid((unsigned)n_part(P.n_rows)), block(LT_THREADS);
@@ -424,8 +437,9 @@ static int ance_embed_backward_impl(const char *fn, const AnceEmbedArgs *args, c
         char *seg = (char *)P.part + part_bytes(P.n_rows, H);
         const size_t sb = seg_bytes(P.n_rows, H);
         if (seg_word) S.t[0] = SegTable{grads->word_keys, grads->word_perm, grads->dword, (float *)seg, 1, args->vocab, args->padding_idx, 0, 0};
-        if (seg_pos && roberta)
-            S.t[1] = SegTable{grads->pos_keys, grads->pos_perm, grads->dpos, (float *)(seg + sb), 1, args->max_pos, args->padding_idx, 0, 0};
+        if (seg_pos && (roberta || rows))  // rows: sorted keys in absolute mode too (a row is no longer s * L + p), and no padding row there
+            S.t[1] = SegTable{grads->pos_keys, grads->pos_perm, grads->dpos, (float *)(seg + sb), 1, args->max_pos,
+                              roberta ? args->padding_idx : -1, 0, 0};
         else if (seg_pos)
             S.t[1] = SegTable{nullptr, nullptr, grads->dpos, (float *)(seg + sb), 2, args->L, -1, args->n_seq, args->L};
         if (seg_type) S.t[2] = SegTable{grads->type_keys, grads->type_perm, grads->dtype, (float *)(seg + 2 * sb), 1, 2, -1, 0, 0};
@@ -454,4 +468,19 @@ extern "C" int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGra
 extern "C" int ance_embed_backward_dstream(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream,
                                            void *stream) {
     return ance_embed_backward_impl("ance_embed_backward_dstream", args, grads, d_stream, stream);
+}
+
+// The rows forms: n_seq rows (L = 1) whose positions are the caller's (include/ance_amd.h) -- the same kernels, the same launches.
+extern "C" int ance_embed_rows_forward(const AnceEmbedArgs *args, void *stream) {
+    return ance_embed_forward_impl("ance_embed_rows_forward", args, nullptr, stream, true);
+}
+extern "C" int ance_embed_rows_forward_dstream(const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream) {
+    return ance_embed_forward_impl("ance_embed_rows_forward_dstream", args, d_stream, stream, true);
+}
+extern "C" int ance_embed_rows_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream) {
+    return ance_embed_backward_impl("ance_embed_rows_backward", args, grads, nullptr, stream, true);
+}
+extern "C" int ance_embed_rows_backward_dstream(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream,
+                                                void *stream) {
+    return ance_embed_backward_impl("ance_embed_rows_backward_dstream", args, grads, d_stream, stream, true);
 }

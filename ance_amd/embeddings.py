@@ -24,8 +24,9 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from .attention import _NO_DRAW, _custom_bwd, _custom_fwd, dropout_state
 from .layers import TAIL_WIDTHS, _check_vector, _ptr, _stats_floats, _vector
+from .packing import PackedTokens
 
-__all__ = ["bert_embeddings", "BertEmbeddings"]
+__all__ = ["bert_embeddings", "bert_embeddings_packed", "BertEmbeddings"]
 
 MAX_SEQ_LEN = 512
 
@@ -111,6 +112,69 @@ class _BertEmbeddings(torch.autograd.Function):
         return dword, dpos, dtype, dgamma, dbeta, None, None, None, None, None, None, None
 
 
+class _BertEmbeddingsRows(torch.autograd.Function):
+    """_BertEmbeddings over R packed rows whose positions are given (ance_embed_rows_*): ids, types, positions int32 [R]."""
+
+    @staticmethod
+    @_custom_fwd
+    def forward(ctx, word, position, token_type, weight, beta, ids, types, positions, eps, mode, padding_idx, dropout_p, training):
+        L = _lib.lib()
+        word, position, token_type = _table(word), _table(position), _table(token_type)
+        weight, beta = _vector(weight), _vector(beta)
+        H, n_rows, dev = word.shape[1], ids.numel(), word.device
+        if L.ance_embed_workspace_bytes(n_rows, H) == 0:
+            raise _lib.AnceLibraryError("bert_embeddings_packed: unsupported shape (rows %d, width %d)" % (n_rows, H))
+        y = torch.empty((n_rows, H), dtype=torch.float32, device=dev)
+        stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=dev)
+        drop = bool(training) and dropout_p > 0.0
+        draw = dropout_state.draw(dev) if drop else _NO_DRAW
+        args = _lib.AnceEmbedArgs(ids=ids.data_ptr(), type_ids=_ptr(types), word=word.data_ptr(), pos=position.data_ptr(),
+                                  type=token_type.data_ptr(), gamma=weight.data_ptr(), beta=beta.data_ptr(), y=y.data_ptr(),
+                                  positions=positions.data_ptr(), n_seq=n_rows, L=1, H=H, vocab=word.shape[0],
+                                  max_pos=position.shape[0], n_types=token_type.shape[0], position_mode=mode, padding_idx=padding_idx,
+                                  eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed,
+                                  offset=draw.offset, d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
+        with torch.cuda.device(dev):
+            draw.launch("ance_embed_rows_forward", ctypes.byref(args))
+        ctx.save_for_backward(word, position, token_type, weight, ids, types, positions, stats)
+        ctx.args, ctx.draw = args, draw
+        return y
+
+    @staticmethod
+    @_custom_bwd
+    @once_differentiable
+    def backward(ctx, dy):
+        L = _lib.lib()
+        word, position, token_type, weight, ids, types, positions, stats = ctx.saved_tensors
+        a = _lib.AnceEmbedArgs.from_buffer_copy(ctx.args)  # y and beta are not touched by the backward
+        H, n_rows, dev = a.H, a.n_seq, word.device
+        dy = dy.to(torch.float32).contiguous()
+        if dy.data_ptr() % 16:
+            dy = dy.clone()
+        want_word, want_pos, want_type, want_w, want_b = ctx.needs_input_grad[:5]
+
+        def table(want, like):  # dense and zero-filled: the kernels store the rows that occur
+            return torch.zeros(like.shape, dtype=torch.float32, device=dev) if want else None
+
+        dword, dpos, dtype = table(want_word, word), table(want_pos, position), table(want_type, token_type)
+        dgamma = torch.empty(H, dtype=torch.float32, device=dev) if want_w else None
+        dbeta = torch.empty(H, dtype=torch.float32, device=dev) if want_b else None
+        ws_bytes = L.ance_embed_workspace_bytes(n_rows, H)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+        ws[:stats.numel()].copy_(stats)
+        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        none = (None, None)
+        wk, wp = _sorted(ids) if want_word else none
+        pk, pp = _sorted(positions) if want_pos else none   # in absolute mode too: a packed row is not s * L + p
+        tk, tp = _sorted(types) if want_type and types is not None and a.n_types == 2 else none
+        g = _lib.AnceEmbedGradArgs(dy=dy.data_ptr(), dword=_ptr(dword), dpos=_ptr(dpos), dtype=_ptr(dtype), dgamma=_ptr(dgamma),
+                                   dbeta=_ptr(dbeta), word_keys=_ptr(wk), word_perm=_ptr(wp), pos_keys=_ptr(pk), pos_perm=_ptr(pp),
+                                   type_keys=_ptr(tk), type_perm=_ptr(tp))
+        with torch.cuda.device(dev):
+            ctx.draw.launch("ance_embed_rows_backward", ctypes.byref(a), ctypes.byref(g))
+        return dword, dpos, dtype, dgamma, dbeta, None, None, None, None, None, None, None, None
+
+
 def _check_table(t, what, H, like=None):
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 2 or t.shape[0] < 1:
         raise _lib.AnceLibraryError("%s must be a CUDA(HIP) tensor [n, H]" % what)
@@ -173,6 +237,43 @@ def bert_embeddings(input_ids, word, position, token_type, ln_weight, ln_bias, e
                                  _lib.EMBED_POSITION_MODES[position_mode], pad, float(dropout_p), bool(training))
 
 
+def bert_embeddings_packed(packed, word, position, token_type, ln_weight, ln_bias, eps, position_mode="absolute", padding_idx=None,
+                           dropout_p=0.0, training=True):
+    """``bert_embeddings`` over the R rows of a ``PackedTokens`` (``ance_amd.packing.pack_tokens`` with the same position_mode and
+    padding_idx, which formed the positions) -> [R, H] fp32.  A row that a sequence covers has the bits of the padded call's row
+    (dropout aside); a slack row is the embedding of a pad token: finite, and read by nothing that reaches a loss.  The dropout
+    counter's row is the PACKED row index, so the masks are those of an R-row call.  The position table's gradient goes through the
+    sorted positions in both modes; its padding row (roberta) and the word table's get no gradient, as in ``bert_embeddings``."""
+    if not isinstance(packed, PackedTokens):
+        raise _lib.AnceLibraryError("bert_embeddings_packed: packed must be a PackedTokens (ance_amd.packing.pack_tokens)")
+    if not isinstance(word, torch.Tensor) or word.dim() != 2 or word.shape[1] not in TAIL_WIDTHS:
+        raise _lib.AnceLibraryError("word must be [vocab, H] with H in %r" % (TAIL_WIDTHS,))
+    H = word.shape[1]
+    _check_table(word, "word", H)
+    _check_table(position, "position", H, word)
+    _check_table(token_type, "token_type", H, word)
+    _check_vector(ln_weight, "ln_weight", H, word)
+    _check_vector(ln_bias, "ln_bias", H, word)
+    if packed.ids.device != word.device:
+        raise _lib.AnceLibraryError("the packed batch must be on the word table's device")
+    if position_mode not in _lib.EMBED_POSITION_MODES:
+        raise _lib.AnceLibraryError("position_mode must be \"absolute\" or \"roberta\", got %r" % (position_mode,))
+    vocab = word.shape[0]
+    pad = -1 if padding_idx is None else int(padding_idx)
+    if token_type.shape[0] not in (1, 2):
+        raise _lib.AnceLibraryError("token_type must have 1 or 2 rows, got %d" % token_type.shape[0])
+    if padding_idx is not None and not 0 <= pad < vocab:
+        raise _lib.AnceLibraryError("padding_idx must be in [0, %d), got %r" % (vocab, padding_idx))
+    if position_mode == "roberta" and padding_idx is None:
+        raise _lib.AnceLibraryError("position_mode \"roberta\" needs a padding_idx")
+    if not 0.0 <= float(dropout_p) < 1.0:
+        raise _lib.AnceLibraryError("dropout_p must be in [0, 1), got %r" % (dropout_p,))
+    if not float(eps) > 0.0:
+        raise _lib.AnceLibraryError("eps must be positive, got %r" % (eps,))
+    return _BertEmbeddingsRows.apply(word, position, token_type, ln_weight, ln_bias, packed.ids, packed.type_ids, packed.positions,
+                                     float(eps), _lib.EMBED_POSITION_MODES[position_mode], pad, float(dropout_p), bool(training))
+
+
 class BertEmbeddings(torch.nn.Module):
     """transformers' BertEmbeddings / RobertaEmbeddings with their parameter names -- word_embeddings.weight,
     position_embeddings.weight, token_type_embeddings.weight, LayerNorm.weight, LayerNorm.bias -- so that the ``embeddings.*`` part of
@@ -202,3 +303,15 @@ class BertEmbeddings(torch.nn.Module):
         return bert_embeddings(input_ids, self.word_embeddings.weight, self.position_embeddings.weight,
                                self.token_type_embeddings.weight, self.LayerNorm.weight, self.LayerNorm.bias, self.layer_norm_eps,
                                token_type_ids, self.position_mode, self.pad_token_id, self.hidden_dropout_prob, self.training)
+
+    def pack(self, input_ids, lens, rows, token_type_ids=None, dropped=None):
+        """``pack_tokens`` with this module's position mode, padding index and table sizes."""
+        from .packing import pack_tokens
+        return pack_tokens(input_ids, lens, rows, token_type_ids, self.position_mode, self.pad_token_id,
+                           self.word_embeddings.num_embeddings, self.position_embeddings.num_embeddings, dropped)
+
+    def forward_packed(self, packed):
+        """[R, H] fp32 over the rows of a PackedTokens made by ``pack`` (one bert_embeddings_packed call)."""
+        return bert_embeddings_packed(packed, self.word_embeddings.weight, self.position_embeddings.weight,
+                                      self.token_type_embeddings.weight, self.LayerNorm.weight, self.LayerNorm.bias, self.layer_norm_eps,
+                                      self.position_mode, self.pad_token_id, self.hidden_dropout_prob, self.training)

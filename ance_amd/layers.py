@@ -27,7 +27,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .attention import (_NO_DRAW, HALF_DTYPES, _check_precision, _custom_bwd, _custom_fwd, _custom_fwd_as_is, _rows,
-                        attention_first_row, attention_padded, dropout_state)
+                        attention_first_row, attention_first_row_packed, attention_packed, attention_padded, dropout_state)
+from .packing import PackedTokens, first_rows
 
 __all__ = ["dropout_add_layer_norm", "bias_gelu", "BertLayer"]
 
@@ -487,6 +488,76 @@ class BertLayer(torch.nn.Module):
         ln = att.output.LayerNorm
         h = dropout_add_layer_norm(F.linear(ctx0, att.output.dense.weight), att.output.dense.bias, hidden_states[:, 0], ln.weight,
                                    ln.bias, eps, p, self.training, return_half=half, **prec)
+        h, h_in = h if half else (h, h)
+        t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
+        ln = self.output.LayerNorm
+        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
+                                      self.training, **prec)
+
+    def _packed_inputs(self, hidden_states, packed, hidden_states_half, what):
+        """The checks of the packed forms; returns the rows the projections read (the 16-bit copy with precision="half")."""
+        if not isinstance(packed, PackedTokens):
+            raise _lib.AnceLibraryError("BertLayer.%s: packed must be a PackedTokens (ance_amd.packing.pack_tokens)" % what)
+        if not isinstance(hidden_states, torch.Tensor) or hidden_states.dim() != 2 or hidden_states.shape[0] != packed.rows:
+            raise _lib.AnceLibraryError("BertLayer.%s: hidden_states must be [R, H] with the packed batch's R = %d rows" % (what, packed.rows))
+        if self.precision != "half":
+            if hidden_states_half is not None:
+                raise _lib.AnceLibraryError("BertLayer: hidden_states_half and return_half need precision=\"half\"")
+            return hidden_states
+        if hidden_states.dtype != torch.float32:
+            raise _lib.AnceLibraryError("BertLayer(precision=\"half\"): hidden_states is the fp32 residual stream, got %s"
+                                        % (hidden_states.dtype,))
+        if hidden_states_half is None:   # the layer's one activation cast
+            return _half_rows(hidden_states, "hidden_states", TAIL_WIDTHS)
+        if hidden_states_half.dtype not in HALF_DTYPES or hidden_states_half.shape != hidden_states.shape:
+            raise _lib.AnceLibraryError("hidden_states_half must be the fp16 / bf16 copy of hidden_states, got %s %r"
+                                        % (hidden_states_half.dtype, tuple(hidden_states_half.shape)))
+        return hidden_states_half
+
+    def forward_packed(self, hidden_states, packed, hidden_states_half=None, return_half=False):
+        """``forward`` over the R rows of a PackedTokens: hidden_states [R, H] fp32 -> [R, H] fp32 (precision="half": with
+        ``hidden_states_half`` / ``return_half`` as in forward).  The statements are forward's with attention_packed in place of
+        attention_padded: the Linears and the seams run over R rows instead of B * L.  The attention's dropout mask is forward's
+        bit for bit; the tails' masks are those of an R-row call.  A slack row (one that no sequence covers) is computed like any
+        other by the seams, from a zero context: finite, and never read by a kept sequence; its gradient is exactly zero."""
+        F = torch.nn.functional
+        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
+        half = self.precision == "half"
+        if return_half and not half:
+            raise _lib.AnceLibraryError("BertLayer: hidden_states_half and return_half need precision=\"half\"")
+        x = self._packed_inputs(hidden_states, packed, hidden_states_half, "forward_packed")
+        prec = dict(precision="half") if half else {}
+        q = F.linear(x, att.self.query.weight, att.self.query.bias)
+        k = F.linear(x, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
+        v = F.linear(x, att.self.value.weight, att.self.value.bias)
+        ctx = attention_packed(q, k, v, packed.seq_off, packed.max_seq_len, self.num_attention_heads, self.attention_probs_dropout_prob,
+                               self.training, precision=self.attention_precision)
+        ln = att.output.LayerNorm
+        h = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, hidden_states, ln.weight, ln.bias,
+                                   eps, p, self.training, return_half=half, **prec)
+        h, h_in = h if half else (h, h)
+        t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
+        ln = self.output.LayerNorm
+        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
+                                      self.training, return_half=return_half, **prec)
+
+    def forward_first_rows_packed(self, hidden_states, packed, hidden_states_half=None):
+        """``forward_first_rows`` over the R rows of a PackedTokens -> [B, H] fp32: ``first_rows`` in place of ``x[:, 0]`` and
+        attention_first_row_packed in place of attention_first_row.  An empty sequence's row is the tails of a zero residual and a
+        zero context; a DROPPED sequence's row is NaN (first_rows), which is how an overflow of the capacity reaches the loss."""
+        F = torch.nn.functional
+        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
+        half = self.precision == "half"
+        x = self._packed_inputs(hidden_states, packed, hidden_states_half, "forward_first_rows_packed")
+        prec = dict(precision="half") if half else {}
+        q0 = F.linear(first_rows(x, packed), att.self.query.weight, att.self.query.bias)
+        k = F.linear(x, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
+        v = F.linear(x, att.self.value.weight, att.self.value.bias)
+        ctx0 = attention_first_row_packed(q0, k, v, packed.seq_off, packed.max_seq_len, self.num_attention_heads,
+                                          self.attention_probs_dropout_prob, self.training, precision=self.attention_precision)
+        ln = att.output.LayerNorm
+        h = dropout_add_layer_norm(F.linear(ctx0, att.output.dense.weight), att.output.dense.bias, first_rows(hidden_states, packed),
+                                   ln.weight, ln.bias, eps, p, self.training, return_half=half, **prec)
         h, h_in = h if half else (h, h)
         t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
         ln = self.output.LayerNorm

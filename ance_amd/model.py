@@ -16,6 +16,16 @@ synchronises, so a whole step can be captured.
 ``use_mean`` is not supported (no shipped recipe sets it).  An all-pad chunk of a MaxP document has length 0: the attention core
 writes zeros for it, so its embedding is the tail of zeros -- finite, NOT the reference's value (which attends uniformly over the
 pads) -- and it receives no gradient; ``nll_loss`` biases it by -9999 before the max, as the reference does, so it never wins.
+
+Packed rows: ``model.set_packed_rows(query=Rq, body=Rb)`` makes the towers pack their padded ``[B, L]`` input
+into R token rows (``ance_amd.packing``) and run every layer over those instead of B * L; ``None`` (the default) is the padded path
+above, bit for bit; an int is a fixed capacity (what a captured step needs), ``"exact"`` reads the batch's total back and
+synchronises.  ``forward``, ``query_emb`` and ``body_emb`` keep their signatures, and a tower call still takes 1 + 3 N draws in the
+same order.  A sequence that does not fit the capacity is dropped: its embedding is NaN, and ``model.packed_dropped`` -- a 0-dim
+int64 device tensor (created on the first packed call, not part of ``state_dict()``) that every packed tower call adds to -- counts
+it.  MaxP packs its B * C chunks; an all-pad chunk is an EMPTY sequence there, whose embedding is the last layer's tails of a zero
+residual and a zero context: finite, NOT the padded path's value (which is the tail of the pad token's hidden state), without a
+gradient, and under the -9999 bias it never wins either.
 """
 import collections
 
@@ -78,10 +88,27 @@ class _Tower(torch.nn.Module):
                                           c.hidden_dropout_prob, c.attention_probs_dropout_prob, precision=precision)
                                 for _ in range(c.num_hidden_layers)])
 
-    def forward(self, input_ids, attention_mask, token_type_ids=None):
+    def _forward_packed(self, input_ids, lens, token_type_ids, rows, dropped):
+        """The tower over R packed rows: pack (two launches, no draw), the embeddings, N - 1 layers, the last layer's first rows."""
+        packed = self.embeddings.pack(input_ids, lens, rows, token_type_ids, dropped)
+        h = self.embeddings.forward_packed(packed)
+        layers = self.encoder.layer
+        if self.precision == "half":
+            h16 = None
+            for layer in layers[:-1]:
+                h, h16 = layer.forward_packed(h, packed, hidden_states_half=h16, return_half=True)
+            return layers[-1].forward_first_rows_packed(h, packed, hidden_states_half=h16)
+        for layer in layers[:-1]:
+            h = layer.forward_packed(h, packed)
+        return layers[-1].forward_first_rows_packed(h, packed)
+
+    def forward(self, input_ids, attention_mask, token_type_ids=None, packed_rows=None, dropped=None):
+        """packed_rows: None (the padded path), an int capacity or "exact"; dropped: the counter a packed call adds to."""
         if attention_mask is None:
             raise _lib.AnceLibraryError("attention_mask is required: the lengths come from it")
         lens = lens_from_mask(attention_mask)
+        if packed_rows is not None:
+            return self._forward_packed(input_ids, lens, token_type_ids, packed_rows, dropped)
         h = self.embeddings(input_ids, token_type_ids)
         layers = self.encoder.layer
         if self.precision == "half":   # chained through the 16-bit copy: one activation cast in the whole tower
@@ -100,8 +127,37 @@ def _never_used(key):
     return ".pooler." in key or key.startswith("classifier.") or key.endswith(".position_ids")
 
 
+def _check_packed_rows(rows, what):
+    if rows is None or rows == "exact":
+        return rows
+    if isinstance(rows, bool) or not isinstance(rows, int) or rows < 1:
+        raise _lib.AnceLibraryError("set_packed_rows: %s must be None, \"exact\" or an int capacity >= 1, got %r" % (what, rows))
+    return rows
+
+
 class _Checkpointed(torch.nn.Module):
-    """Loading and re-emitting a reference checkpoint."""
+    """Loading and re-emitting a reference checkpoint; the packed-rows setting of the towers."""
+
+    _packed_rows = (None, None)
+    packed_dropped = None
+
+    def set_packed_rows(self, query=None, body=None):
+        """The token-row capacity of the query tower's and of the body tower's calls: None (padded, the default), "exact" (the
+        batch's total, read back: synchronises) or an int.  A body capacity counts the rows of ONE body_emb call (MaxP: of its
+        B * C chunks).  Returns self."""
+        self._packed_rows = (_check_packed_rows(query, "query"), _check_packed_rows(body, "body"))
+        dev = next(self.parameters()).device
+        if dev.type == "cuda" and (self.packed_dropped is None or self.packed_dropped.device != dev):
+            self.packed_dropped = torch.zeros((), dtype=torch.int64, device=dev)   # here, not inside a step: a captured step only adds
+        return self
+
+    def _tower(self, tower, which, input_ids, attention_mask):
+        rows = self._packed_rows[which]
+        if rows is None:
+            return tower(input_ids, attention_mask)
+        if self.packed_dropped is None or self.packed_dropped.device != input_ids.device:   # a plain attribute: not in state_dict()
+            self.packed_dropped = torch.zeros((), dtype=torch.int64, device=input_ids.device)
+        return tower(input_ids, attention_mask, packed_rows=rows, dropped=self.packed_dropped)
 
     def load_reference_state_dict(self, sd):
         """Strict on every used name; the tensors the reference carries but never uses (``*.pooler.*``, ``classifier.*``,
@@ -149,10 +205,10 @@ class RobertaDot_NLL_LN(_Checkpointed):
         return F.layer_norm(e.float(), (OUT_DIM,), self.norm.weight, self.norm.bias, HEAD_EPS)
 
     def query_emb(self, input_ids, attention_mask):
-        return self._head(self.roberta(input_ids, attention_mask))
+        return self._head(self._tower(self.roberta, 0, input_ids, attention_mask))
 
     def body_emb(self, input_ids, attention_mask):
-        return self.query_emb(input_ids, attention_mask)
+        return self._head(self._tower(self.roberta, 1, input_ids, attention_mask))
 
     def _loss(self, q, a, b, attention_mask_a, attention_mask_b):
         return nll_loss(q, a, b)
@@ -182,7 +238,7 @@ class RobertaDot_CLF_ANN_NLL_MultiChunk(RobertaDot_NLL_LN):
         C = full // self.base_len
         if C < 1 or C * self.base_len != full:
             raise _lib.AnceLibraryError("body_emb: the document length %d is not a multiple of base_len = %d" % (full, self.base_len))
-        e = self._head(self.roberta(input_ids.reshape(B * C, full // C), attention_mask.reshape(B * C, full // C)))
+        e = self._head(self._tower(self.roberta, 1, input_ids.reshape(B * C, full // C), attention_mask.reshape(B * C, full // C)))
         return e.reshape(B, C, OUT_DIM)
 
     @staticmethod
@@ -212,10 +268,10 @@ class BiEncoder(_Checkpointed):
         return model.to(sd["question_model.embeddings.word_embeddings.weight"].device).load_reference_state_dict(sd)
 
     def query_emb(self, input_ids, attention_mask):
-        return self.question_model(input_ids, attention_mask)
+        return self._tower(self.question_model, 0, input_ids, attention_mask)
 
     def body_emb(self, input_ids, attention_mask):
-        return self.ctx_model(input_ids, attention_mask)
+        return self._tower(self.ctx_model, 1, input_ids, attention_mask)
 
     def forward(self, query_ids, attention_mask_q, input_ids_a=None, attention_mask_a=None, input_ids_b=None, attention_mask_b=None):
         q = self.query_emb(query_ids, attention_mask_q)

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_* only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_*, ance_pack_tokens, ance_embed_rows_*, ance_first_rows_* only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -721,6 +721,77 @@ int ance_embed_forward(const AnceEmbedArgs *args, void *stream);
 int ance_embed_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream);
 int ance_embed_forward_dstream(const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream); /* the device dropout stream: ance_attention_* */
 int ance_embed_backward_dstream(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream, void *stream);
+
+/* Packed token rows of a fixed capacity (csrc/pack_rows.hip; the rows forms of the embeddings: csrc/embed_train.hip).  A right-padded
+ * batch ids [n_seq, L] with device lengths becomes R = `rows` token rows that hold the sequences back to back; R is the CALLER's
+ * capacity, a host value that fixes every shape and grid, while the number of rows in use lives on the device only.  Nothing is
+ * read back, nothing synchronises, there are no atomics, and the same inputs give the same bits: every call here can be captured.
+ *
+ * ance_pack_tokens -- the plan and the packed keys, TWO launches whatever the inputs (the plan: one workgroup; the fill):
+ *   len_s  = clamp(d_seq_len[s], 0, L);  off_s = len_0 + .. + len_{s-1};  sequence s is KEPT iff off_s + len_s <= R.  off_s + len_s
+ *            never decreases with s, so the dropped sequences are a suffix; T = the rows of the kept ones.
+ *   d_seq_off [n_seq + 1]  off_s for a kept sequence; T for every dropped one and for the last entry -- the differences are the
+ *            kept lengths and 0 for a dropped sequence, which is what ance_attention_* take as the packed form
+ *   d_seq_kept [n_seq]     len_s, or -1 for a dropped sequence
+ *   d_dropped              int64 on the device: the call ADDS the number of dropped sequences (one thread, a plain load and store)
+ *   packed row off_s + l, l < len_s, of a kept sequence: packed_ids = ids[s, l] as it is; packed_type_ids = type_ids[s, l] (only when
+ *            type_ids is given); packed_positions = ance_embed_forward's p of (s, l), its clamps included: l, or padding_idx + (id !=
+ *            padding_idx ? #{t <= l : id(s, t) != padding_idx} : 0) over the ids clamped into the vocabulary, then clamp(p, 0, max_pos - 1)
+ *   slack rows T .. R - 1: id padding_idx (0 when it is -1), type 0, position padding_idx in roberta mode and 0 otherwise
+ *   No row >= R of a packed array is written whatever d_seq_len holds, and every offset read back from memory is clamped first.
+ *   Refuses (ANCE_E_INVALID, before any launch): a null pointer other than type_ids / packed_type_ids (type_ids given needs
+ *   packed_type_ids); an integer array not 4-byte aligned, d_dropped not 8-byte aligned; n_seq outside 1 .. 65535; L outside
+ *   1 .. 512; rows < 1; vocab or max_pos < 1; a position_mode other than the two; padding_idx outside -1 .. vocab - 1 (roberta:
+ *   0 .. vocab - 1).
+ *
+ * ance_embed_rows_forward / _backward (+ _dstream) -- ance_embed_* over T = n_seq rows with L = 1 whose positions are GIVEN:
+ *   AnceEmbedArgs.positions [n_seq] is read in both directions (clamped into the table) and never written; position_mode only
+ *   says whether the position table has a padding row (roberta: positions equal to padding_idx add nothing to dpos; absolute:
+ *   none).  dpos ALWAYS goes through the sorted keys (pos_keys / pos_perm are required with dpos in both modes: a row is no longer
+ *   s * L + p).  Everything else is ance_embed_*'s, by the same kernels: the arithmetic, the dropout counter (the row is the PACKED
+ *   row index), the saved state, the workspace (ance_embed_workspace_bytes(n_seq, H)), the launch counts, the padding rule of
+ *   dword, the order of every sum.  Refuses what ance_embed_* refuse, L != 1 and null positions; max_pos is not tied to L.
+ *
+ * ance_first_rows_gather / _scatter -- the first row of every sequence out of a row matrix [R, H] and its backward; H = 768 or 1024,
+ *   dtype ANCE_DTYPE_F32, _F16 or _BF16, 16-byte pieces, one wave per sequence, ONE launch each:
+ *   gather   first[s] = rows_matrix[d_seq_off[s]] when d_seq_kept[s] > 0; zeros when it is 0 (an empty sequence); a QUIET NaN in
+ *            every element when it is negative (a dropped sequence: it must not go unnoticed, and nothing may wait for the host)
+ *   scatter  rows_matrix[d_seq_off[s]] = first[s] for every s with d_seq_kept[s] > 0 -- distinct rows, one owner each, plain vector
+ *            stores; nothing else is written: the CALLER zero-fills rows_matrix.
+ *   d_seq_off is clamped into [0, rows - 1] before a row is addressed.  Refuses a null or unaligned pointer, H, dtype, n_seq outside
+ *   1 .. 65535, rows < 1, a stride that is not a multiple of a 16-byte piece or below H. */
+typedef struct AncePackArgs {
+    const int32_t *ids;           /* [n_seq, L]                                                   */
+    const int32_t *type_ids;      /* [n_seq, L] or NULL                                           */
+    const int32_t *d_seq_len;     /* [n_seq] on the device                                        */
+    int32_t *d_seq_off;           /* [n_seq + 1] out                                              */
+    int32_t *d_seq_kept;          /* [n_seq] out                                                  */
+    int64_t *d_dropped;           /* device counter, added to                                     */
+    int32_t *packed_ids;          /* [rows] out                                                   */
+    int32_t *packed_type_ids;     /* [rows] out, with type_ids                                    */
+    int32_t *packed_positions;    /* [rows] out                                                   */
+    int32_t n_seq, L, rows;
+    int32_t position_mode;        /* ANCE_EMBED_POSITION_*                                        */
+    int32_t padding_idx;          /* -1: none                                                     */
+    int32_t vocab, max_pos;
+    int32_t reserved;             /* 0 */
+} AncePackArgs;
+typedef struct AnceFirstRowsArgs {
+    void *rows_matrix;            /* [rows, H]: read by the gather, written by the scatter        */
+    void *first;                  /* [n_seq, H]: written by the gather, read by the scatter       */
+    const int32_t *d_seq_off;     /* [n_seq + 1] (the last entry is not read)                     */
+    const int32_t *d_seq_kept;    /* [n_seq]                                                      */
+    int32_t ld_rows, ld_first;    /* row strides in elements                                      */
+    int32_t n_seq, rows, H;
+    int32_t dtype;                /* ANCE_DTYPE_*                                                 */
+} AnceFirstRowsArgs;
+int ance_pack_tokens(const AncePackArgs *args, void *stream);
+int ance_embed_rows_forward(const AnceEmbedArgs *args, void *stream);
+int ance_embed_rows_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream);
+int ance_embed_rows_forward_dstream(const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream);
+int ance_embed_rows_backward_dstream(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, const uint64_t *d_stream, void *stream);
+int ance_first_rows_gather(const AnceFirstRowsArgs *args, void *stream);
+int ance_first_rows_scatter(const AnceFirstRowsArgs *args, void *stream);
 
 /* Test hook: the SPLIT (fp32-grade) GEMM of the encoder with one of its epilogues.  acc[m][n] = sum_k a[m][k] b[n][k] with
  * a = a_hi + a_lo (b likewise; the lo x lo products are left out); d_a_pair [M, 2K] / d_b_pair [N, 2K] fp16 PAIR ROWS -- 32-column
