@@ -213,6 +213,16 @@ class AnceFirstRowsArgs(ctypes.Structure):
                 ("rows", ctypes.c_int32), ("H", ctypes.c_int32), ("dtype", ctypes.c_int32)]
 
 
+class AncePackedGatherSegment(ctypes.Structure):
+    """include/ance_amd.h: one segment (tower) of ance_gather_batch_packed."""
+    _fields_ = [("d_records", ctypes.c_void_p), ("n_records", ctypes.c_int64), ("d_index", ctypes.c_void_p),
+                ("n_index", ctypes.c_int64), ("d_cum", ctypes.c_void_p), ("packed_ids", ctypes.c_void_p),
+                ("packed_positions", ctypes.c_void_p), ("d_seq_off", ctypes.c_void_p), ("d_seq_kept", ctypes.c_void_p),
+                ("d_dropped", ctypes.c_void_p), ("L", ctypes.c_int32), ("chunk_len", ctypes.c_int32), ("rows", ctypes.c_int32),
+                ("position_mode", ctypes.c_int32), ("padding_idx", ctypes.c_int32), ("vocab", ctypes.c_int32),
+                ("max_pos", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 # include/ance_amd.h: ANCE_EMBED_SEGMENT_CHUNK (the library states the same number through ance_embed_segment_chunk), ANCE_EMBED_POSITION_*
 EMBED_SEGMENT_CHUNK = 64
 EMBED_POSITION_MODES = {"absolute": 0, "roberta": 1}
@@ -323,6 +333,10 @@ SYMBOLS = {
                                                  ctypes.c_size_t, ctypes.c_void_p]),
     "ance_gather_batch": (ctypes.c_int, [ctypes.POINTER(AnceGatherSegment), ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                          ctypes.c_void_p]),
+    "ance_record_lengths": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "ance_gather_batch_packed": (ctypes.c_int, [ctypes.POINTER(AncePackedGatherSegment), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
     "ance_attention_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "ance_attention_forward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.c_void_p]),
     "ance_attention_backward": (ctypes.c_int, [ctypes.POINTER(AnceAttnTrainArgs), ctypes.POINTER(AnceAttnGradArgs), ctypes.c_void_p]),

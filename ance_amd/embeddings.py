@@ -24,7 +24,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from .attention import _NO_DRAW, _custom_bwd, _custom_fwd, dropout_state
 from .layers import TAIL_WIDTHS, _check_vector, _ptr, _stats_floats, _vector
-from .packing import PackedTokens
+from .packing import PackedTokens, PackRule
 
 __all__ = ["bert_embeddings", "bert_embeddings_packed", "BertEmbeddings"]
 
@@ -310,8 +310,14 @@ class BertEmbeddings(torch.nn.Module):
         return pack_tokens(input_ids, lens, rows, token_type_ids, self.position_mode, self.pad_token_id,
                            self.word_embeddings.num_embeddings, self.position_embeddings.num_embeddings, dropped)
 
+    @property
+    def pack_rule(self):
+        """The ``PackRule`` of ``pack``: what a PackedTokens for this module must have been made under."""
+        return PackRule.of(self.position_mode, self.pad_token_id, self.word_embeddings.num_embeddings,
+                           self.position_embeddings.num_embeddings)
+
     def forward_packed(self, packed):
-        """[R, H] fp32 over the rows of a PackedTokens made by ``pack`` (one bert_embeddings_packed call)."""
+        """[R, H] fp32 over the rows of a PackedTokens made under ``pack_rule`` (one bert_embeddings_packed call)."""
         return bert_embeddings_packed(packed, self.word_embeddings.weight, self.position_embeddings.weight,
                                       self.token_type_embeddings.weight, self.LayerNorm.weight, self.LayerNorm.bias, self.layer_norm_eps,
                                       self.position_mode, self.pad_token_id, self.hidden_dropout_prob, self.training)

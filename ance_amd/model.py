@@ -26,6 +26,12 @@ int64 device tensor (created on the first packed call, not part of ``state_dict(
 it.  MaxP packs its B * C chunks; an all-pad chunk is an EMPTY sequence there, whose embedding is the last layer's tails of a zero
 residual and a zero context: finite, NOT the padded path's value (which is the tail of the pad token's hidden state), without a
 gradient, and under the -9999 bias it never wins either.
+
+Packed batches: every place that takes a tower's ``input_ids`` also takes a ``PackedTokens`` with
+``attention_mask=None`` -- what ``TrainingBatches.packed(model)`` yields -- and runs the same packed tower on it as it is: no
+``lens_from_mask``, no pack.  ``model.packed_dropped`` adds the batch's own count.  The batch must have been made under the tower's
+rule (position mode, pad id, table sizes: ``tower.embeddings.pack_rule``); another rule is refused on the host.  MaxP reads its
+chunk mask from ``seq_kept != 0``: a dropped chunk counts as present, so its NaN reaches the loss.
 """
 import collections
 
@@ -37,6 +43,7 @@ from .embeddings import BertEmbeddings
 from .encoder import count_layers
 from .layers import BertLayer
 from .loss import nll_loss
+from .packing import PackedTokens
 
 __all__ = ["TowerConfig", "RobertaDot_NLL_LN", "RobertaDot_CLF_ANN_NLL_MultiChunk", "BiEncoder"]
 
@@ -89,8 +96,19 @@ class _Tower(torch.nn.Module):
                                 for _ in range(c.num_hidden_layers)])
 
     def _forward_packed(self, input_ids, lens, token_type_ids, rows, dropped):
-        """The tower over R packed rows: pack (two launches, no draw), the embeddings, N - 1 layers, the last layer's first rows."""
-        packed = self.embeddings.pack(input_ids, lens, rows, token_type_ids, dropped)
+        """The tower over R packed rows: pack (two launches, no draw), then ``_run_packed``."""
+        return self._run_packed(self.embeddings.pack(input_ids, lens, rows, token_type_ids, dropped))
+
+    def _check_packed(self, packed):
+        want = self.embeddings.pack_rule
+        if packed.rule != want:
+            raise _lib.AnceLibraryError("the packed batch was made under %r, this tower's rule is %r" % (packed.rule, want))
+        dev = self.embeddings.word_embeddings.weight.device
+        if packed.ids.device != dev:
+            raise _lib.AnceLibraryError("the packed batch is on %s, the tower on %s" % (packed.ids.device, dev))
+
+    def _run_packed(self, packed):
+        """The embeddings, N - 1 layers and the last layer's first rows over the R rows of a PackedTokens."""
         h = self.embeddings.forward_packed(packed)
         layers = self.encoder.layer
         if self.precision == "half":
@@ -103,7 +121,13 @@ class _Tower(torch.nn.Module):
         return layers[-1].forward_first_rows_packed(h, packed)
 
     def forward(self, input_ids, attention_mask, token_type_ids=None, packed_rows=None, dropped=None):
-        """packed_rows: None (the padded path), an int capacity or "exact"; dropped: the counter a packed call adds to."""
+        """packed_rows: None (the padded path), an int capacity or "exact"; dropped: the counter a packed call adds to.  A
+        PackedTokens as input_ids (attention_mask None) is run as it is."""
+        if isinstance(input_ids, PackedTokens):
+            if attention_mask is not None or token_type_ids is not None:
+                raise _lib.AnceLibraryError("a PackedTokens carries its lengths: attention_mask and token_type_ids must be None")
+            self._check_packed(input_ids)
+            return self._run_packed(input_ids)
         if attention_mask is None:
             raise _lib.AnceLibraryError("attention_mask is required: the lengths come from it")
         lens = lens_from_mask(attention_mask)
@@ -151,13 +175,25 @@ class _Checkpointed(torch.nn.Module):
             self.packed_dropped = torch.zeros((), dtype=torch.int64, device=dev)   # here, not inside a step: a captured step only adds
         return self
 
+    def _dropped_counter(self, dev):
+        if self.packed_dropped is None or self.packed_dropped.device != dev:   # a plain attribute: not in state_dict()
+            self.packed_dropped = torch.zeros((), dtype=torch.int64, device=dev)
+        return self.packed_dropped
+
+    def towers(self):
+        """(the query tower, the body tower)."""
+        raise NotImplementedError
+
     def _tower(self, tower, which, input_ids, attention_mask):
+        if isinstance(input_ids, PackedTokens):
+            tower._check_packed(input_ids)   # before the counter moves
+            out = tower(input_ids, attention_mask)
+            self._dropped_counter(input_ids.ids.device).add_(input_ids.dropped)
+            return out
         rows = self._packed_rows[which]
         if rows is None:
             return tower(input_ids, attention_mask)
-        if self.packed_dropped is None or self.packed_dropped.device != input_ids.device:   # a plain attribute: not in state_dict()
-            self.packed_dropped = torch.zeros((), dtype=torch.int64, device=input_ids.device)
-        return tower(input_ids, attention_mask, packed_rows=rows, dropped=self.packed_dropped)
+        return tower(input_ids, attention_mask, packed_rows=rows, dropped=self._dropped_counter(input_ids.device))
 
     def load_reference_state_dict(self, sd):
         """Strict on every used name; the tensors the reference carries but never uses (``*.pooler.*``, ``classifier.*``,
@@ -204,16 +240,19 @@ class RobertaDot_NLL_LN(_Checkpointed):
         e = F.linear(first_rows, self.embeddingHead.weight, self.embeddingHead.bias)
         return F.layer_norm(e.float(), (OUT_DIM,), self.norm.weight, self.norm.bias, HEAD_EPS)
 
-    def query_emb(self, input_ids, attention_mask):
+    def towers(self):
+        return self.roberta, self.roberta
+
+    def query_emb(self, input_ids, attention_mask=None):
         return self._head(self._tower(self.roberta, 0, input_ids, attention_mask))
 
-    def body_emb(self, input_ids, attention_mask):
+    def body_emb(self, input_ids, attention_mask=None):
         return self._head(self._tower(self.roberta, 1, input_ids, attention_mask))
 
-    def _loss(self, q, a, b, attention_mask_a, attention_mask_b):
+    def _loss(self, q, a, b, mask_a, mask_b):
         return nll_loss(q, a, b)
 
-    def forward(self, query_ids, attention_mask_q, input_ids_a=None, attention_mask_a=None, input_ids_b=None, attention_mask_b=None,
+    def forward(self, query_ids, attention_mask_q=None, input_ids_a=None, attention_mask_a=None, input_ids_b=None, attention_mask_b=None,
                 is_query=True):
         if input_ids_b is None and is_query:
             return self.query_emb(query_ids, attention_mask_q)
@@ -222,7 +261,8 @@ class RobertaDot_NLL_LN(_Checkpointed):
         q = self.query_emb(query_ids, attention_mask_q)
         a = self.body_emb(input_ids_a, attention_mask_a)
         b = self.body_emb(input_ids_b, attention_mask_b)
-        return (self._loss(q, a, b, attention_mask_a, attention_mask_b),)
+        packed = isinstance(input_ids_a, PackedTokens)   # a packed batch is its own mask
+        return (self._loss(q, a, b, input_ids_a if packed else attention_mask_a, input_ids_b if packed else attention_mask_b),)
 
 
 class RobertaDot_CLF_ANN_NLL_MultiChunk(RobertaDot_NLL_LN):
@@ -233,7 +273,13 @@ class RobertaDot_CLF_ANN_NLL_MultiChunk(RobertaDot_NLL_LN):
         super().__init__(config, model_argobj, precision)
         self.base_len = 512
 
-    def body_emb(self, input_ids, attention_mask):
+    def body_emb(self, input_ids, attention_mask=None):
+        if isinstance(input_ids, PackedTokens):
+            C = input_ids.chunks
+            if input_ids.max_seq_len != self.base_len or input_ids.n_seq % C:
+                raise _lib.AnceLibraryError("body_emb: a packed document batch must hold chunks of base_len = %d tokens, got %d"
+                                            % (self.base_len, input_ids.max_seq_len))
+            return self._head(self._tower(self.roberta, 1, input_ids, attention_mask)).reshape(-1, C, OUT_DIM)
         B, full = input_ids.shape
         C = full // self.base_len
         if C < 1 or C * self.base_len != full:
@@ -243,12 +289,15 @@ class RobertaDot_CLF_ANN_NLL_MultiChunk(RobertaDot_NLL_LN):
 
     @staticmethod
     def chunk_mask(attention_mask, n_chunks):
-        """[B, C] fp32: the first attention-mask entry of every chunk, as NLL_MultiChunk.forward reads it."""
+        """[B, C] fp32: the first attention-mask entry of every chunk, as NLL_MultiChunk.forward reads it.  Of a PackedTokens:
+        ``seq_kept != 0`` -- the same values for kept chunks; a dropped chunk counts as present, so its NaN reaches the loss."""
+        if isinstance(attention_mask, PackedTokens):
+            return (attention_mask.seq_kept != 0).reshape(-1, n_chunks).float()
         return attention_mask.reshape(attention_mask.shape[0], n_chunks, -1)[:, :, 0].float()
 
-    def _loss(self, q, a, b, attention_mask_a, attention_mask_b):
+    def _loss(self, q, a, b, mask_a, mask_b):
         C = a.shape[1]
-        return nll_loss(q, a, b, self.chunk_mask(attention_mask_a, C), self.chunk_mask(attention_mask_b, C))
+        return nll_loss(q, a, b, self.chunk_mask(mask_a, C), self.chunk_mask(mask_b, C))
 
 
 class BiEncoder(_Checkpointed):
@@ -267,13 +316,16 @@ class BiEncoder(_Checkpointed):
         model = cls(TowerConfig.from_state_dict(sd, "question_model.", False, dropout), precision=precision)
         return model.to(sd["question_model.embeddings.word_embeddings.weight"].device).load_reference_state_dict(sd)
 
-    def query_emb(self, input_ids, attention_mask):
+    def towers(self):
+        return self.question_model, self.ctx_model
+
+    def query_emb(self, input_ids, attention_mask=None):
         return self._tower(self.question_model, 0, input_ids, attention_mask)
 
-    def body_emb(self, input_ids, attention_mask):
+    def body_emb(self, input_ids, attention_mask=None):
         return self._tower(self.ctx_model, 1, input_ids, attention_mask)
 
-    def forward(self, query_ids, attention_mask_q, input_ids_a=None, attention_mask_a=None, input_ids_b=None, attention_mask_b=None):
+    def forward(self, query_ids, attention_mask_q=None, input_ids_a=None, attention_mask_a=None, input_ids_b=None, attention_mask_b=None):
         q = self.query_emb(query_ids, attention_mask_q)
         a = self.body_emb(input_ids_a, attention_mask_a)
         if input_ids_b is None:

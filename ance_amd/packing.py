@@ -13,6 +13,7 @@ sequences are a suffix of the batch) is DROPPED: it owns no rows, ``seq_kept`` i
 ``rows="exact"`` reads the total back (``int(lens.sum())``, at least 1): ONE SYNCHRONISATION per call.  It is for eager use and for
 tests; a captured step needs an int.
 """
+import collections
 import ctypes
 
 import torch
@@ -21,22 +22,35 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from .attention import HALF_DTYPES, _custom_bwd, _custom_fwd_as_is, _int32, _rows
 
-__all__ = ["PackedTokens", "pack_tokens", "first_rows"]
+__all__ = ["PackedTokens", "PackRule", "pack_tokens", "first_rows"]
 
 MAX_SEQ_LEN, MAX_SEQS = 512, 65535
 ROW_DTYPES = dict(HALF_DTYPES)
 ROW_DTYPES[torch.float32] = _lib.ANCE_DTYPE_F32
 
 
-class PackedTokens(object):
-    """What ``pack_tokens`` returns.  Device tensors: ``ids``, ``type_ids`` (or None), ``positions`` -- int32 [R]; ``seq_off`` int32
-    [B + 1] (a dropped sequence's entry is the total T, so the differences are the kept lengths); ``seq_kept`` int32 [B] (the kept
-    length, -1: dropped); ``dropped`` int64 0-dim, the counter the call added to.  Host ints: ``rows`` = R, ``max_seq_len`` = L."""
-    __slots__ = ("ids", "type_ids", "positions", "seq_off", "seq_kept", "rows", "max_seq_len", "dropped")
+class PackRule(collections.namedtuple("PackRule", "position_mode padding_idx vocab max_pos")):
+    """The rule a packed batch's positions were formed under: position_mode ("absolute" / "roberta"), padding_idx (-1: none) and the
+    two table sizes the clamps used (2^31 - 1: no clamp).  A tower takes only batches made under its own rule."""
+    __slots__ = ()
 
-    def __init__(self, ids, type_ids, positions, seq_off, seq_kept, rows, max_seq_len, dropped):
+    @classmethod
+    def of(cls, position_mode, padding_idx, vocab_size, max_position):
+        return cls(position_mode, -1 if padding_idx is None else int(padding_idx), 0x7fffffff if vocab_size is None else int(vocab_size),
+                   0x7fffffff if max_position is None else int(max_position))
+
+
+class PackedTokens(object):
+    """What ``pack_tokens`` and the packed gather (``ance_amd.batches.PackedBatches``) return.  Device tensors: ``ids``, ``type_ids``
+    (or None), ``positions`` -- int32 [R]; ``seq_off`` int32 [B + 1] (a dropped sequence's entry is the total T, so the differences
+    are the kept lengths); ``seq_kept`` int32 [B] (the kept length, -1: dropped); ``dropped`` int64 0-dim: the counter ``pack_tokens``
+    added to, or this batch's own count from the packed gather.  Host values: ``rows`` = R, ``max_seq_len`` = L, ``rule`` (a
+    ``PackRule``: what the positions were formed under), ``chunks`` (sequences per item: 1, or C for a MaxP document batch)."""
+    __slots__ = ("ids", "type_ids", "positions", "seq_off", "seq_kept", "rows", "max_seq_len", "dropped", "rule", "chunks")
+
+    def __init__(self, ids, type_ids, positions, seq_off, seq_kept, rows, max_seq_len, dropped, rule=None, chunks=1):
         self.ids, self.type_ids, self.positions, self.seq_off, self.seq_kept = ids, type_ids, positions, seq_off, seq_kept
-        self.rows, self.max_seq_len, self.dropped = rows, max_seq_len, dropped
+        self.rows, self.max_seq_len, self.dropped, self.rule, self.chunks = rows, max_seq_len, dropped, rule, chunks
 
     @property
     def n_seq(self):
@@ -97,7 +111,8 @@ def pack_tokens(input_ids, lens, rows, token_type_ids=None, position_mode="absol
                              position_mode=_lib.EMBED_POSITION_MODES[position_mode], padding_idx=pad, vocab=vocab, max_pos=max_pos)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().ance_pack_tokens(ctypes.byref(args), _lib.current_stream_ptr()), "ance_pack_tokens")
-    return PackedTokens(out_ids, out_types, out_pos, seq_off, seq_kept, rows, L, dropped)
+    return PackedTokens(out_ids, out_types, out_pos, seq_off, seq_kept, rows, L, dropped,
+                        PackRule.of(position_mode, padding_idx, vocab_size, max_position))
 
 
 def _first_rows_args(rows_matrix, ld_rows, first, packed):

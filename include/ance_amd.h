@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_*, ance_pack_tokens, ance_embed_rows_*, ance_first_rows_* only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_*, ance_pack_tokens, ance_embed_rows_*, ance_first_rows_*, ance_record_lengths, ance_gather_batch_packed only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -1068,6 +1068,58 @@ typedef struct AnceGatherSegment {
     int32_t L, mask_rule, type_rule, reserved;
 } AnceGatherSegment;
 int ance_gather_batch(const AnceGatherSegment *h_segs, int n_segs, int64_t first, int64_t B, int width, void *stream);
+
+/* Packed batches straight from the token caches (csrc/batch_gather_packed.hip): the gather above followed by ance_pack_tokens in
+ * every tower, as ONE launch for all towers, with the scan of the lengths moved to the time the pass's plan is made.
+ *
+ * ance_record_lengths -- int32 d_out [n_records, L / chunk_len], once per cache: entry (r, c) is the length of chunk c of record r.
+ *   rule ANCE_GATHER_MASK_LENGTH: len = min(bswap(header), L), chunk c gets clamp(len - c chunk_len, 0, chunk_len);
+ *   ANCE_GATHER_MASK_NONZERO: the number of non-zero ids in the chunk (what the lengths of the DPR loaders' mask are, holes
+ *   included).  chunk_len == L is the ordinary one-sequence record.  Refuses (ANCE_E_INVALID, before any launch): a null or not
+ *   4-byte aligned pointer; n_records < 1; L < 1; chunk_len outside 1 .. 512 or not dividing L; an unknown rule.
+ *
+ * ance_gather_batch_packed -- a segment is one tower's share of a batch of B items, each C = L / chunk_len sequences:
+ *   d_cum      int64 [n_index * C + 1], made with the plan: the exclusive running sum of the sequence lengths (ance_record_lengths
+ *              of the records d_index names) in item-then-chunk order.  Sequence s = item * C + c of the batch, s0 = first * C:
+ *              off_s = cum[s0 + s] - cum[s0], len_s = clamp(cum[s0 + s + 1] - cum[s0 + s], 0, chunk_len), KEPT iff
+ *              off_s + len_s <= rows.  off_s + len_s never decreases, so the dropped sequences are a suffix; T = the rows in use.
+ *   outputs    packed_ids, packed_positions [rows]; d_seq_off [B C + 1]; d_seq_kept [B C]; d_dropped: exactly what ance_pack_tokens
+ *              writes for the padded batch the segment stands for -- the ids as they are, the positions with their clamps, off_s and
+ *              len_s for a kept sequence, T and -1 for a dropped one, T in the last entry, the slack rows T .. rows - 1 as stated
+ *              there -- EXCEPT d_dropped, which is STORED, not added to: this batch's number of dropped sequences, by the one lane
+ *              of the grid that also stores T (no read-modify-write: the segments share a grid).  No token types are produced.
+ *              Every byte of the five outputs is written on every call, and no row >= rows ever.
+ *   position_mode, padding_idx, vocab, max_pos   as in AncePackArgs
+ *   first, d_first   the first item of the batch; with d_first != NULL it is read from that int64 device scalar when the kernel
+ *              starts and `first` is ignored (a cursor that lives on the device: the call can be captured and replayed).  The item
+ *              is clamped into [0, n_index] and every read of d_cum and d_index stays inside them whatever the scalar holds; an
+ *              item at or beyond n_index is C empty sequences (kept with length 0 if they fit) and reads no record.
+ *   The record index is clamped into [0, n_records) and every offset into [0, rows] before an address is formed.
+ * ONE launch for all segments; no copy, no allocation, no synchronisation, no atomics.  Refuses (ANCE_E_INVALID, before any launch): a
+ * null table or pointer (d_first aside); n_segs outside 1..3; B < 1; without d_first: first < 0 or first + B past n_index; L < 1;
+ * chunk_len outside 1 .. 512 or not dividing L; B C above 65535; n_records < 1; n_index < 0; rows < 1; vocab or max_pos < 1; a
+ * position_mode other than the two; padding_idx outside -1 .. vocab - 1 (roberta: 0 .. vocab - 1); d_records or an int32 output not
+ * 4-byte aligned; d_index, d_cum, d_dropped or d_first not 8-byte aligned. */
+typedef struct AncePackedGatherSegment {
+    const void *d_records;
+    int64_t n_records;
+    const int64_t *d_index;
+    int64_t n_index;
+    const int64_t *d_cum;         /* [n_index * (L / chunk_len) + 1]                              */
+    int32_t *packed_ids;          /* [rows] out                                                   */
+    int32_t *packed_positions;    /* [rows] out                                                   */
+    int32_t *d_seq_off;           /* [B * (L / chunk_len) + 1] out                                */
+    int32_t *d_seq_kept;          /* [B * (L / chunk_len)] out                                    */
+    int64_t *d_dropped;           /* out: this batch's dropped sequences (stored)                 */
+    int32_t L, chunk_len, rows;
+    int32_t position_mode;        /* ANCE_EMBED_POSITION_*                                        */
+    int32_t padding_idx;          /* -1: none                                                     */
+    int32_t vocab, max_pos;
+    int32_t reserved;             /* 0 */
+} AncePackedGatherSegment;
+int ance_record_lengths(const void *d_records, int64_t n_records, int L, int chunk_len, int rule, int32_t *d_out, void *stream);
+int ance_gather_batch_packed(const AncePackedGatherSegment *h_segs, int n_segs, int64_t first, int64_t B, const int64_t *d_first,
+                             void *stream);
 
 /* Re-reads every ANCE_* tuning knob from the environment (they are otherwise read once per process).  For tests and
  * sweeps that change a knob between two calls; not thread-safe against concurrent searches. */
