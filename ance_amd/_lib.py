@@ -206,6 +206,14 @@ class AncePackArgs(ctypes.Structure):
                 ("vocab", ctypes.c_int32), ("max_pos", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class AncePackByIdArgs(ctypes.Structure):
+    """include/ance_amd.h: the arguments of ance_pack_tokens_by_id."""
+    _fields_ = [("ids", ctypes.c_void_p), ("d_seq_len", ctypes.c_void_p), ("d_seq_off", ctypes.c_void_p),
+                ("d_seq_kept", ctypes.c_void_p), ("d_dropped", ctypes.c_void_p), ("packed_ids", ctypes.c_void_p),
+                ("packed_positions", ctypes.c_void_p), ("n_seq", ctypes.c_int32), ("L", ctypes.c_int32), ("rows", ctypes.c_int32),
+                ("padding_idx", ctypes.c_int32), ("vocab", ctypes.c_int32), ("max_pos", ctypes.c_int32)]
+
+
 class AnceFirstRowsArgs(ctypes.Structure):
     """include/ance_amd.h: the arguments of ance_first_rows_gather / ance_first_rows_scatter."""
     _fields_ = [("rows_matrix", ctypes.c_void_p), ("first", ctypes.c_void_p), ("d_seq_off", ctypes.c_void_p),
@@ -379,6 +387,7 @@ SYMBOLS = {
     "ance_embed_backward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
     # packed token rows of a fixed capacity (csrc/pack_rows.hip) and the embeddings over rows with given positions
     "ance_pack_tokens": (ctypes.c_int, [ctypes.POINTER(AncePackArgs), ctypes.c_void_p]),
+    "ance_pack_tokens_by_id": (ctypes.c_int, [ctypes.POINTER(AncePackByIdArgs), ctypes.c_void_p]),
     "ance_embed_rows_forward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p]),
     "ance_embed_rows_backward": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.POINTER(AnceEmbedGradArgs), ctypes.c_void_p]),
     "ance_embed_rows_forward_dstream": (ctypes.c_int, [ctypes.POINTER(AnceEmbedArgs), ctypes.c_void_p, ctypes.c_void_p]),

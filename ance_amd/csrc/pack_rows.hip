@@ -9,6 +9,9 @@
 //             pieces, whatever the element type.
 // Every offset read back from memory is clamped into [0, R] before a row is addressed with it, and no row >= R is ever written.
 // No atomics: the dropped-sequence counter is one thread's plain read, add and store.
+// By id (ance_pack_tokens_by_id): the lengths are not given but counted -- a wave per sequence ballots id != pad over all L columns
+// (-1 for a sequence that BEGINS with the pad id) -- the plan treats -1 as a dropped sequence of no rows that keeps its running
+// offset, and the fill walks all L columns and sends every non-pad id to row off + its rank among them: three launches.
 #include "common.h"
 
 namespace ance {
@@ -26,6 +29,9 @@ struct PackParams {
 
 __device__ __forceinline__ int clamp_to(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// BY_ID: a length of -1 (a sequence that begins with the pad id) scans as 0 rows, is dropped (seq_kept -1, counted) and, unlike a
+// sequence dropped for capacity, keeps its own running offset in seq_off while that is <= R: -2 marks it between the two loops.
+template <bool BY_ID>
 __global__ void __launch_bounds__(PLAN_THREADS) pack_plan_kernel(const PackParams P) {
     __shared__ int wave_tot[PLAN_WAVES];
     __shared__ int red[2][PLAN_WAVES];
@@ -33,7 +39,9 @@ __global__ void __launch_bounds__(PLAN_THREADS) pack_plan_kernel(const PackParam
     int carry = 0, used = 0, n_drop = 0;  // carry: the same in every thread; used, n_drop: this thread's share
     for (int s0 = 0; s0 < P.n_seq; s0 += PLAN_THREADS) {
         const int s = s0 + (int)threadIdx.x;
-        const int len = s < P.n_seq ? clamp_to(P.seq_len[s], 0, P.L) : 0;
+        const int given = s < P.n_seq ? P.seq_len[s] : 0;
+        const bool lead = BY_ID && given < 0;
+        const int len = clamp_to(given, 0, P.L);
         int inc = len;  // the inclusive scan inside the wave
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -53,9 +61,9 @@ __global__ void __launch_bounds__(PLAN_THREADS) pack_plan_kernel(const PackParam
         const int off = carry + before + inc - len;
         const bool kept = off + len <= P.rows;  // at most 65535 * 512 rows: no overflow
         if (s < P.n_seq) {
-            P.seq_kept[s] = kept ? len : -1;
-            if (kept) {
-                P.seq_off[s] = off;
+            P.seq_kept[s] = kept && !lead ? len : (kept ? -2 : -1);
+            if (kept) P.seq_off[s] = off;
+            if (kept && !lead) {
                 used = off + len;  // the thread's sequences ascend, and so do their ends
             } else {
                 ++n_drop;
@@ -81,8 +89,11 @@ __global__ void __launch_bounds__(PLAN_THREADS) pack_plan_kernel(const PackParam
         T = T > red[0][w] ? T : red[0][w];
         dropped += red[1][w];
     }
-    for (int s = (int)threadIdx.x; s < P.n_seq; s += PLAN_THREADS)
-        if (P.seq_kept[s] < 0) P.seq_off[s] = T;  // the thread's own store above: s has the same owner in both loops
+    for (int s = (int)threadIdx.x; s < P.n_seq; s += PLAN_THREADS) {  // the thread's own stores above: s has the same owner in both loops
+        const int k = P.seq_kept[s];
+        if (BY_ID && k == -2) P.seq_kept[s] = -1;
+        else if (k < 0) P.seq_off[s] = T;
+    }
     if (threadIdx.x == 0) {
         P.seq_off[P.n_seq] = T;
         *P.dropped = *P.dropped + dropped;
@@ -126,6 +137,55 @@ __global__ void __launch_bounds__(FILL_THREADS) pack_fill_kernel(const PackParam
             P.out_ids[row] = raw;
             if (P.out_types) P.out_types[row] = tsrc[l];
             P.out_pos[row] = clamp_to(p, 0, P.max_pos - 1);
+        }
+    }
+}
+
+// d_seq_len[s] = #{l < L : ids[s, l] != pad}, or -1 when ids[s, 0] == pad (an all-pad row included): a wave per sequence, one ballot
+// per 64 columns.
+__global__ void __launch_bounds__(FILL_THREADS) pack_count_by_id_kernel(const int *ids, int *seq_len, int n_seq, int L, int pad) {
+    const int lane = threadIdx.x & 63, s = (int)blockIdx.x * FILL_WAVES + (threadIdx.x >> 6);
+    if (s >= n_seq) return;
+    const int *src = ids + (size_t)s * L;
+    int count = 0;
+    for (int l0 = 0; l0 < L; l0 += 64) {
+        const int l = l0 + lane;
+        count += __builtin_popcountll(__ballot(l < L && src[l] != pad));
+    }
+    if (lane == 0) seq_len[s] = src[0] == pad ? -1 : count;
+}
+
+// pack_fill_kernel by id: the wave of a kept sequence walks ALL L columns; a non-pad id goes to row off + rank, rank = the non-pad
+// ids before it (the ballot's prefix popcount plus the carry of the earlier rounds), with position pad + 1 + rank.
+__global__ void __launch_bounds__(FILL_THREADS) pack_fill_by_id_kernel(const PackParams P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((int)blockIdx.x >= P.seq_blocks) {  // the slack rows
+        const int T = clamp_to(P.seq_off[P.n_seq], 0, P.rows);
+        const long long row = (long long)((int)blockIdx.x - P.seq_blocks) * FILL_THREADS + threadIdx.x;
+        if (row >= T && row < P.rows) {
+            P.out_ids[row] = P.pad;
+            P.out_pos[row] = P.pad;
+        }
+        return;
+    }
+    const int s = (int)blockIdx.x * FILL_WAVES + wave;
+    if (s >= P.n_seq) return;
+    const int len = clamp_to(P.seq_kept[s], -1, P.L);
+    if (len <= 0) return;
+    const int off = clamp_to(P.seq_off[s], 0, P.rows);
+    const int *src = P.ids + (size_t)s * P.L;
+    int count = 0;  // the non-pad ids in the columns before this round's
+    for (int l0 = 0; l0 < P.L; l0 += 64) {
+        const int l = l0 + lane;
+        const int raw = l < P.L ? src[l] : P.pad;
+        const bool tok = raw != P.pad;
+        const u64 b = __ballot(tok);
+        const int rank = count + __builtin_popcountll(b & ((1ull << lane) - 1));  // columns 0 .. l - 1
+        count += __builtin_popcountll(b);
+        const long long row = (long long)off + rank;
+        if (tok && rank < len && row < P.rows) {  // rank < len: the plan's count is the bound, whatever the ids hold by now
+            P.out_ids[row] = raw;
+            P.out_pos[row] = clamp_to(P.pad + 1 + rank, 0, P.max_pos - 1);
         }
     }
 }
@@ -232,9 +292,42 @@ extern "C" int ance_pack_tokens(const AncePackArgs *a, void *stream) {
     P.vocab = a->vocab; P.max_pos = a->max_pos;
     P.seq_blocks = (a->n_seq + FILL_WAVES - 1) / FILL_WAVES;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(pack_plan_kernel, dim3(1), dim3(PLAN_THREADS), 0, st, P);
+    hipLaunchKernelGGL(pack_plan_kernel<false>, dim3(1), dim3(PLAN_THREADS), 0, st, P);
     const unsigned slack_blocks = (unsigned)(((int64_t)a->rows + FILL_THREADS - 1) / FILL_THREADS);
     hipLaunchKernelGGL(pack_fill_kernel, dim3((unsigned)P.seq_blocks + slack_blocks), dim3(FILL_THREADS), 0, st, P);
+    return check_launch(fn);
+}
+
+extern "C" int ance_pack_tokens_by_id(const AncePackByIdArgs *a, void *stream) {
+    using namespace ance;
+    const char *fn = "ance_pack_tokens_by_id";
+    if (!a) return refuse(fn, "null pointer");
+    if (a->n_seq < 1 || a->n_seq > 65535) return refuse(fn, "n_seq outside 1 .. 65535");
+    if (a->L < 1 || a->L > 512) return refuse(fn, "L outside 1 .. 512");
+    if (a->rows < 1) return refuse(fn, "rows < 1");
+    if (a->vocab < 1 || a->max_pos < 1) return refuse(fn, "an empty table");
+    if (a->padding_idx < 0 || a->padding_idx >= a->vocab) return refuse(fn, "padding_idx outside 0 .. vocab - 1");
+    for (const void *p : {(const void *)a->ids, (const void *)a->d_seq_len, (const void *)a->d_seq_off, (const void *)a->d_seq_kept,
+                          (const void *)a->packed_ids, (const void *)a->packed_positions})
+        if (const char *why = check_ints4(p)) return refuse(fn, why);
+    if (!a->d_dropped) return refuse(fn, "null pointer");
+    if ((uintptr_t)a->d_dropped % 8) return refuse(fn, "alignment: d_dropped is not 8-byte aligned");
+
+    PackParams P = {};
+    P.ids = a->ids; P.seq_len = a->d_seq_len;
+    P.seq_off = a->d_seq_off; P.seq_kept = a->d_seq_kept;
+    P.out_ids = a->packed_ids; P.out_pos = a->packed_positions;
+    P.dropped = (long long *)a->d_dropped;
+    P.n_seq = a->n_seq; P.L = a->L; P.rows = a->rows;
+    P.roberta = 1; P.pad = a->padding_idx;
+    P.vocab = a->vocab; P.max_pos = a->max_pos;
+    P.seq_blocks = (a->n_seq + FILL_WAVES - 1) / FILL_WAVES;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(pack_count_by_id_kernel, dim3((unsigned)P.seq_blocks), dim3(FILL_THREADS), 0, st, a->ids, a->d_seq_len, a->n_seq,
+                       a->L, a->padding_idx);
+    hipLaunchKernelGGL(pack_plan_kernel<true>, dim3(1), dim3(PLAN_THREADS), 0, st, P);
+    const unsigned slack_blocks = (unsigned)(((int64_t)a->rows + FILL_THREADS - 1) / FILL_THREADS);
+    hipLaunchKernelGGL(pack_fill_by_id_kernel, dim3((unsigned)P.seq_blocks + slack_blocks), dim3(FILL_THREADS), 0, st, P);
     return check_launch(fn);
 }
 

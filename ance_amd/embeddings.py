@@ -26,7 +26,7 @@ from .attention import _NO_DRAW, _custom_bwd, _custom_fwd, dropout_state
 from .layers import TAIL_WIDTHS, _check_vector, _ptr, _stats_floats, _vector
 from .packing import PackedTokens, PackRule
 
-__all__ = ["bert_embeddings", "bert_embeddings_packed", "BertEmbeddings"]
+__all__ = ["bert_embeddings", "bert_embeddings_packed", "BertEmbeddings", "SeedEmbeddings"]
 
 MAX_SEQ_LEN = 512
 
@@ -321,3 +321,53 @@ class BertEmbeddings(torch.nn.Module):
         return bert_embeddings_packed(packed, self.word_embeddings.weight, self.position_embeddings.weight,
                                       self.token_type_embeddings.weight, self.LayerNorm.weight, self.LayerNorm.bias, self.layer_norm_eps,
                                       self.position_mode, self.pad_token_id, self.hidden_dropout_prob, self.training)
+
+
+class _Table(object):
+    """What BertEmbeddings' methods read of a table that is not an nn.Embedding of its own."""
+    __slots__ = ("weight",)
+
+    def __init__(self, weight):
+        self.weight = weight
+
+
+class SeedEmbeddings(BertEmbeddings):
+    """The input end of the SEED-Encoder's tower (fairseq's TransformerSentenceEncoder with num_segments = 0) under ITS parameter
+    names -- embed_tokens.weight, embed_positions.weight, emb_layer_norm.weight / .bias -- so that ``named_parameters()`` and
+    ``state_dict()`` are the reference's.  The arithmetic is BertEmbeddings' in roberta mode, unchanged: ``word_embeddings``,
+    ``position_embeddings`` and ``LayerNorm`` are the three modules under their other names (properties, not registered twice), and
+    the segment table is a non-persistent zero buffer [1, H] without a gradient -- ``(word + 0) + position`` is the same sum.
+    There is no padded ``forward``: the tower masks keys by id, which only a batch packed by id (``pack``: ``pack_tokens_by_id``,
+    rule "seed") expresses.  ``max_positions`` is the reference's: the position table has max_positions + padding_idx + 1 rows."""
+
+    def __init__(self, vocab_size, hidden_size, max_positions, padding_idx=1, layer_norm_eps=1e-5, dropout=0.1):
+        torch.nn.Module.__init__(self)
+        if hidden_size not in TAIL_WIDTHS:
+            raise _lib.AnceLibraryError("SeedEmbeddings: hidden_size must be 768 or 1024, got %r" % (hidden_size,))
+        if padding_idx is None or not 0 <= int(padding_idx) < vocab_size:
+            raise _lib.AnceLibraryError("SeedEmbeddings: padding_idx must be in [0, %d), got %r" % (vocab_size, padding_idx))
+        nn = torch.nn
+        self.position_mode, self.pad_token_id = "roberta", int(padding_idx)
+        self.layer_norm_eps, self.hidden_dropout_prob = float(layer_norm_eps), float(dropout)
+        self.embed_tokens = nn.Embedding(vocab_size, hidden_size, padding_idx=self.pad_token_id)
+        self.embed_positions = nn.Embedding(max_positions + self.pad_token_id + 1, hidden_size, padding_idx=self.pad_token_id)
+        self.emb_layer_norm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
+        self.register_buffer("no_segment", torch.zeros(1, hidden_size), persistent=False)
+
+    word_embeddings = property(lambda self: self.embed_tokens)
+    position_embeddings = property(lambda self: self.embed_positions)
+    LayerNorm = property(lambda self: self.emb_layer_norm)
+    token_type_embeddings = property(lambda self: _Table(self.no_segment))
+
+    def forward(self, input_ids, token_type_ids=None):
+        raise _lib.AnceLibraryError("SeedEmbeddings has no padded form: pack by id (pack) and call forward_packed")
+
+    def pack(self, input_ids, rows, dropped=None):
+        """``pack_tokens_by_id`` with this module's padding index and table sizes."""
+        from .packing import pack_tokens_by_id
+        return pack_tokens_by_id(input_ids, rows, self.pad_token_id, self.embed_tokens.num_embeddings,
+                                 self.embed_positions.num_embeddings, dropped)
+
+    @property
+    def pack_rule(self):
+        return PackRule.of("seed", self.pad_token_id, self.embed_tokens.num_embeddings, self.embed_positions.num_embeddings)

@@ -583,3 +583,45 @@ class BertLayer(torch.nn.Module):
         ln = self.output.LayerNorm
         return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
                                       self.training)
+
+
+class _Names(object):
+    """A plain holder of attributes (not an nn.Module: what it holds is registered elsewhere, under other names)."""
+
+    def __init__(*args, **kw):   # no named first parameter: "self" is one of the attribute names (attention.self)
+        args[0].__dict__.update(kw)
+
+
+class SeedLayer(BertLayer):
+    """fairseq's post-LayerNorm TransformerSentenceEncoderLayer -- the SEED-Encoder's -- under ITS submodule names: self_attn.q_proj /
+    k_proj / v_proj / out_proj, self_attn_layer_norm, fc1, fc2, final_layer_norm, so that ``named_parameters()`` and
+    ``state_dict()`` are the reference's.  The layer is BertLayer's in arithmetic (q scaled by 1/8, attention-probability dropout,
+    dropout on the attention output and on fc2's output, erf-GELU, eps 1e-5; activation_dropout = 0), and the forward text IS
+    BertLayer's: ``attention``, ``intermediate`` and ``output`` are plain holders that name the same eight modules the way BertLayer's
+    methods read them, registered once, under fairseq's names.  self_attn.k_proj.bias gets attention.self.key.bias's exact-zero
+    gradient."""
+
+    def __init__(self, hidden_size, num_attention_heads, intermediate_size, layer_norm_eps=1e-5, dropout=0.1, attention_dropout=0.1,
+                 precision="fp32"):
+        torch.nn.Module.__init__(self)
+        if precision not in ("fp32", "half"):
+            raise _lib.AnceLibraryError("SeedLayer: precision must be \"fp32\" or \"half\", got %r" % (precision,))
+        self.precision = self.attention_precision = precision
+        if hidden_size not in TAIL_WIDTHS or hidden_size != 64 * num_attention_heads or intermediate_size not in GELU_WIDTHS:
+            raise _lib.AnceLibraryError("SeedLayer: hidden_size must be 768 (12 heads) or 1024 (16 heads), intermediate_size 3072 or "
+                                        "4096; got %r, %r heads, %r" % (hidden_size, num_attention_heads, intermediate_size))
+        nn = torch.nn
+        self.num_attention_heads, self.layer_norm_eps = num_attention_heads, float(layer_norm_eps)
+        self.hidden_dropout_prob, self.attention_probs_dropout_prob = float(dropout), float(attention_dropout)
+        self.self_attn = _Namespace()
+        for name in ("k_proj", "v_proj", "q_proj", "out_proj"):   # the reference's order of registration
+            setattr(self.self_attn, name, nn.Linear(hidden_size, hidden_size))
+        self.self_attn_layer_norm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
+        self.fc1 = nn.Linear(hidden_size, intermediate_size)
+        self.fc2 = nn.Linear(intermediate_size, hidden_size)
+        self.final_layer_norm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
+        a = self.self_attn
+        self.attention = _Names(output=_Names(dense=a.out_proj, LayerNorm=self.self_attn_layer_norm),
+                                **{"self": _Names(query=a.q_proj, key=a.k_proj, value=a.v_proj)})
+        self.intermediate = _Names(dense=self.fc1)
+        self.output = _Names(dense=self.fc2, LayerNorm=self.final_layer_norm)

@@ -4,6 +4,7 @@
     RobertaDot_NLL_LN                   roberta.embeddings.*, roberta.encoder.layer.N.*, embeddingHead.*, norm.*     -> [B, 768]
     RobertaDot_CLF_ANN_NLL_MultiChunk   the same tower; body_emb reshapes [B, C * 512] to [B * C, 512]               -> [B, C, 768]
     BiEncoder                           question_model.*, ctx_model.* under BertModel's names; no head               -> [B, H]
+    SEEDEncoderDot_NLL_LN               seed_encoder.encoder.sentence_encoder.* under fairseq's names, embeddingHead.*, norm.*   -> [B, 768]
 
 A tower is ``BertEmbeddings`` -> N - 1 x ``BertLayer.forward`` -> the last layer's ``forward_first_rows``: only h[:, 0] of the last
 layer is ever read, so its query, output and feed-forward Linears and its seams run over the B first rows, and its attention is the
@@ -32,6 +33,15 @@ Packed batches: every place that takes a tower's ``input_ids
 ``lens_from_mask``, no pack.  ``model.packed_dropped`` adds the batch's own count.  The batch must have been made under the tower's
 rule (position mode, pad id, table sizes: ``tower.embeddings.pack_rule``); another rule is refused on the host.  MaxP reads its
 chunk mask from ``seq_kept != 0``: a dropped chunk counts as present, so its NaN reaches the loss.
+
+SEED-Encoder: the reference's tower masks every key whose id is the pad id, inside a record too, zeroes those
+rows' embeddings and counts positions past them, so a pad row feeds nothing into a first row or a parameter gradient: leaving the
+pad tokens out before the tower is exact.  ``SEEDEncoderDot_NLL_LN`` therefore has ONE path, the packed one: every call packs by id
+(``pack_tokens_by_id``, three launches) into a capacity of B * L rows of that call -- under which nothing is dropped for capacity --
+or what ``set_packed_rows`` says; ``attention_mask`` is accepted and ignored, as in the reference.  A sequence that BEGINS with the
+pad id is dropped (NaN embedding, counted in ``packed_dropped``): its first row would not be its first token.  Not covered:
+``PackedBatches`` / the device cursor for SEED (the padded ``TrainingBatches`` gather feeds the model), MaxP (the reference has no
+SEED MaxP class), a non-zero activation_dropout.
 """
 import collections
 
@@ -39,13 +49,13 @@ import torch
 
 from . import _lib
 from .attention import lens_from_mask
-from .embeddings import BertEmbeddings
+from .embeddings import BertEmbeddings, SeedEmbeddings
 from .encoder import count_layers
-from .layers import BertLayer
+from .layers import BertLayer, SeedLayer, _Names, _Namespace
 from .loss import nll_loss
 from .packing import PackedTokens
 
-__all__ = ["TowerConfig", "RobertaDot_NLL_LN", "RobertaDot_CLF_ANN_NLL_MultiChunk", "BiEncoder"]
+__all__ = ["TowerConfig", "RobertaDot_NLL_LN", "RobertaDot_CLF_ANN_NLL_MultiChunk", "BiEncoder", "SEEDEncoderDot_NLL_LN"]
 
 OUT_DIM, HEAD_EPS = 768, 1e-5
 
@@ -80,6 +90,28 @@ class _Layers(torch.nn.Module):
         self.layer = torch.nn.ModuleList(layers)
 
 
+def _check_packed_batch(embeddings, packed):
+    want = embeddings.pack_rule
+    if packed.rule != want:
+        raise _lib.AnceLibraryError("the packed batch was made under %r, this tower's rule is %r" % (packed.rule, want))
+    dev = embeddings.word_embeddings.weight.device
+    if packed.ids.device != dev:
+        raise _lib.AnceLibraryError("the packed batch is on %s, the tower on %s" % (packed.ids.device, dev))
+
+
+def _run_packed_rows(embeddings, layers, precision, packed):
+    """The embeddings, N - 1 layers and the last layer's first rows over the R rows of a PackedTokens."""
+    h = embeddings.forward_packed(packed)
+    if precision == "half":
+        h16 = None
+        for layer in layers[:-1]:
+            h, h16 = layer.forward_packed(h, packed, hidden_states_half=h16, return_half=True)
+        return layers[-1].forward_first_rows_packed(h, packed, hidden_states_half=h16)
+    for layer in layers[:-1]:
+        h = layer.forward_packed(h, packed)
+    return layers[-1].forward_first_rows_packed(h, packed)
+
+
 class _Tower(torch.nn.Module):
     """embeddings.*, encoder.layer.N.* as BertModel / RobertaModel name them; ``forward`` returns the last layer's first rows."""
 
@@ -100,25 +132,10 @@ class _Tower(torch.nn.Module):
         return self._run_packed(self.embeddings.pack(input_ids, lens, rows, token_type_ids, dropped))
 
     def _check_packed(self, packed):
-        want = self.embeddings.pack_rule
-        if packed.rule != want:
-            raise _lib.AnceLibraryError("the packed batch was made under %r, this tower's rule is %r" % (packed.rule, want))
-        dev = self.embeddings.word_embeddings.weight.device
-        if packed.ids.device != dev:
-            raise _lib.AnceLibraryError("the packed batch is on %s, the tower on %s" % (packed.ids.device, dev))
+        _check_packed_batch(self.embeddings, packed)
 
     def _run_packed(self, packed):
-        """The embeddings, N - 1 layers and the last layer's first rows over the R rows of a PackedTokens."""
-        h = self.embeddings.forward_packed(packed)
-        layers = self.encoder.layer
-        if self.precision == "half":
-            h16 = None
-            for layer in layers[:-1]:
-                h, h16 = layer.forward_packed(h, packed, hidden_states_half=h16, return_half=True)
-            return layers[-1].forward_first_rows_packed(h, packed, hidden_states_half=h16)
-        for layer in layers[:-1]:
-            h = layer.forward_packed(h, packed)
-        return layers[-1].forward_first_rows_packed(h, packed)
+        return _run_packed_rows(self.embeddings, self.encoder.layer, self.precision, packed)
 
     def forward(self, input_ids, attention_mask, token_type_ids=None, packed_rows=None, dropped=None):
         """packed_rows: None (the padded path), an int capacity or "exact"; dropped: the counter a packed call adds to.  A
@@ -164,6 +181,7 @@ class _Checkpointed(torch.nn.Module):
 
     _packed_rows = (None, None)
     packed_dropped = None
+    _never_used = staticmethod(_never_used)
 
     def set_packed_rows(self, query=None, body=None):
         """The token-row capacity of the query tower's and of the body tower's calls: None (padded, the default), "exact" (the
@@ -199,7 +217,7 @@ class _Checkpointed(torch.nn.Module):
         """Strict on every used name; the tensors the reference carries but never uses (``*.pooler.*``, ``classifier.*``,
         ``*.position_ids``) are set aside for ``reference_state_dict``; any other unknown key is refused."""
         used = set(self.state_dict().keys())
-        unknown = [k for k in sd if k not in used and not _never_used(k)]
+        unknown = [k for k in sd if k not in used and not self._never_used(k)]
         if unknown:
             raise KeyError("unexpected keys in state dict: %s ..." % unknown[:4])
         missing = [k for k in self.state_dict() if k not in sd]
@@ -332,3 +350,114 @@ class BiEncoder(_Checkpointed):
             return (q, a)
         b = self.body_emb(input_ids_b, attention_mask_b)
         return (nll_loss(q, a, b),)
+
+
+class _SeedSentenceEncoder(SeedEmbeddings):
+    """fairseq's TransformerSentenceEncoder as the SEED-Encoder configures it, under its names: embed_tokens, embed_positions,
+    layers.N.*, emb_layer_norm (in the reference's order).  ``forward`` packs by id and returns the last layer's first rows."""
+
+    def __init__(self, vocab_size, hidden_size, n_layers, n_heads, ffn_size, max_positions, padding_idx, dropout, attention_dropout,
+                 precision):
+        super().__init__(vocab_size, hidden_size, max_positions, padding_idx, HEAD_EPS, dropout)
+        if n_layers < 1:
+            raise _lib.AnceLibraryError("a tower needs at least one layer")
+        self.precision = precision
+        self.layers = torch.nn.ModuleList([SeedLayer(hidden_size, n_heads, ffn_size, HEAD_EPS, dropout, attention_dropout, precision)
+                                           for _ in range(n_layers)])
+        self._modules["emb_layer_norm"] = self._modules.pop("emb_layer_norm")   # after the layers, as the reference registers it
+
+    def _check_packed(self, packed):
+        _check_packed_batch(self, packed)
+
+    def forward(self, input_ids, attention_mask=None, packed_rows=None, dropped=None):
+        """input_ids [B, L] (packed by id into packed_rows rows, None: B * L) or a PackedTokens under the "seed" rule (run as it is);
+        attention_mask is ignored: the keys are masked by id."""
+        if isinstance(input_ids, PackedTokens):
+            self._check_packed(input_ids)
+            packed = input_ids
+        else:
+            if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2 or input_ids.numel() == 0:
+                raise _lib.AnceLibraryError("input_ids must be a CUDA(HIP) int32 or int64 tensor [B, L]")
+            packed = self.pack(input_ids, input_ids.numel() if packed_rows is None else packed_rows, dropped)
+        return _run_packed_rows(self, self.layers, self.precision, packed)
+
+
+def _seed_never_used(key):
+    return key.startswith("classification_heads.")
+
+
+class SEEDEncoderDot_NLL_LN(RobertaDot_NLL_LN):
+    """model/models.py: SEEDEncoderDot_NLL_LN: ``norm(embeddingHead(seed_encoder.encoder(ids)[:, 0]))`` over fairseq's post-LayerNorm
+    sentence encoder, NLL over (query, positive, negative) triplets; body_emb is query_emb.  ``config``: the reference's
+    SEEDEncoderConfig or any object with its attribute names (pad_token_id, vocab_size, encoder_layers, encoder_embed_dim,
+    encoder_ffn_embed_dim, encoder_attention_heads, dropout, attention_dropout, activation_dropout, encoder_layerdrop,
+    max_positions, activation_fn, quant_noise_pq).  The tower has one path, packed by id (module docstring).
+    ``classification_heads.*``, which the reference carries and never uses, is set aside on loading and re-emitted."""
+
+    _never_used = staticmethod(_seed_never_used)
+
+    def __init__(self, config, model_argobj=None, precision="fp32"):
+        _Checkpointed.__init__(self)
+        c = config
+        if model_argobj is not None and getattr(model_argobj, "use_mean", False):
+            raise _lib.AnceLibraryError("use_mean is not supported: the last layer computes the first rows only")
+        if float(getattr(c, "activation_dropout", 0.0)) != 0.0:
+            raise _lib.AnceLibraryError("activation_dropout = %r is not supported: the GELU and fc2 are fused without a dropout between "
+                                        "them (the shipped configs set 0.0)" % (c.activation_dropout,))
+        if float(getattr(c, "encoder_layerdrop", 0.0)) != 0.0:
+            raise _lib.AnceLibraryError("encoder_layerdrop = %r is not supported: every layer runs" % (c.encoder_layerdrop,))
+        if float(getattr(c, "quant_noise_pq", 0.0)) != 0.0:
+            raise _lib.AnceLibraryError("quant_noise_pq = %r is not supported" % (c.quant_noise_pq,))
+        if getattr(c, "activation_fn", "gelu") != "gelu":
+            raise _lib.AnceLibraryError("activation_fn = %r is not supported: the feed-forward seam is the erf GELU" % (c.activation_fn,))
+        if (c.encoder_embed_dim, c.encoder_attention_heads, c.encoder_ffn_embed_dim) != (768, 12, 3072):
+            raise _lib.AnceLibraryError("encoder_embed_dim = %r with %r heads and encoder_ffn_embed_dim = %r is not supported: the "
+                                        "SEED-Encoder is 768 wide with 12 heads and a feed-forward width of 3072"
+                                        % (c.encoder_embed_dim, c.encoder_attention_heads, c.encoder_ffn_embed_dim))
+        self.use_mean = False
+        self.seed_encoder = _Namespace()
+        self.seed_encoder.encoder = _Namespace()
+        self.seed_encoder.encoder.sentence_encoder = _SeedSentenceEncoder(
+            int(c.vocab_size), int(c.encoder_embed_dim), int(c.encoder_layers), int(c.encoder_attention_heads),
+            int(c.encoder_ffn_embed_dim), int(c.max_positions), int(c.pad_token_id), float(c.dropout), float(c.attention_dropout), precision)
+        self.embeddingHead = torch.nn.Linear(c.encoder_embed_dim, OUT_DIM)
+        self.norm = torch.nn.LayerNorm(OUT_DIM, eps=HEAD_EPS)
+
+    @classmethod
+    def from_state_dict(cls, sd, precision="fp32", dropout=0.1):
+        """The shape of the tower from the weights themselves; pad id 1, as in the reference's config."""
+        from .encoder import SEED_PREFIX
+        word, pos = sd[SEED_PREFIX + "embed_tokens.weight"], sd[SEED_PREFIX + "embed_positions.weight"]
+        n = 0
+        while "%slayers.%d.fc1.weight" % (SEED_PREFIX, n) in sd:
+            n += 1
+        if n == 0:
+            raise KeyError("no '%slayers.*' weights in state dict" % SEED_PREFIX)
+        H, pad = int(word.shape[1]), 1
+        config = _Names(pad_token_id=pad, vocab_size=int(word.shape[0]), encoder_layers=n, encoder_embed_dim=H,
+                        encoder_ffn_embed_dim=int(sd[SEED_PREFIX + "layers.0.fc1.weight"].shape[0]), encoder_attention_heads=H // 64,
+                        dropout=dropout, attention_dropout=dropout, activation_dropout=0.0, encoder_layerdrop=0.0,
+                        max_positions=int(pos.shape[0]) - pad - 1, activation_fn="gelu", quant_noise_pq=0.0)
+        model = cls(config, precision=precision)
+        return model.to(sd["embeddingHead.weight"].device).load_reference_state_dict(sd)
+
+    @property
+    def sentence_encoder(self):
+        return self.seed_encoder.encoder.sentence_encoder
+
+    def towers(self):
+        return self.sentence_encoder, self.sentence_encoder
+
+    def _tower(self, tower, which, input_ids, attention_mask):
+        if isinstance(input_ids, PackedTokens):
+            tower._check_packed(input_ids)   # before the counter moves
+            out = tower(input_ids)
+            self._dropped_counter(input_ids.ids.device).add_(input_ids.dropped)
+            return out
+        return tower(input_ids, None, packed_rows=self._packed_rows[which], dropped=self._dropped_counter(input_ids.device))
+
+    def query_emb(self, input_ids, attention_mask=None):
+        return self._head(self._tower(self.sentence_encoder, 0, input_ids, attention_mask))
+
+    def body_emb(self, input_ids, attention_mask=None):
+        return self._head(self._tower(self.sentence_encoder, 1, input_ids, attention_mask))

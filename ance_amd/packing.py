@@ -12,6 +12,12 @@ sequences are a suffix of the batch) is DROPPED: it owns no rows, ``seq_kept`` i
 
 ``rows="exact"`` reads the total back (``int(lens.sum())``, at least 1): ONE SYNCHRONISATION per call.  It is for eager use and for
 tests; a captured step needs an int.
+
+    packed = pack_tokens_by_id(input_ids, rows, padding_idx, vocab_size, max_position)          # the SEED-Encoder's rule
+
+packs by ID instead of by length (ance_pack_tokens_by_id, three launches): every id equal to ``padding_idx`` is left out wherever it
+sits, and the positions count the ids that stay.  A sequence that BEGINS with the pad id is dropped like one that does not fit (its
+first row would not be its first token), but keeps its place in ``seq_off``, so its neighbours are untouched.
 """
 import collections
 import ctypes
@@ -22,7 +28,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from .attention import HALF_DTYPES, _custom_bwd, _custom_fwd_as_is, _int32, _rows
 
-__all__ = ["PackedTokens", "PackRule", "pack_tokens", "first_rows"]
+__all__ = ["PackedTokens", "PackRule", "pack_tokens", "pack_tokens_by_id", "first_rows"]
 
 MAX_SEQ_LEN, MAX_SEQS = 512, 65535
 ROW_DTYPES = dict(HALF_DTYPES)
@@ -30,8 +36,9 @@ ROW_DTYPES[torch.float32] = _lib.ANCE_DTYPE_F32
 
 
 class PackRule(collections.namedtuple("PackRule", "position_mode padding_idx vocab max_pos")):
-    """The rule a packed batch's positions were formed under: position_mode ("absolute" / "roberta"), padding_idx (-1: none) and the
-    two table sizes the clamps used (2^31 - 1: no clamp).  A tower takes only batches made under its own rule."""
+    """The rule a packed batch's positions were formed under: position_mode ("absolute" / "roberta"; "seed": packed by id, which only
+    ``pack_tokens_by_id`` makes), padding_idx (-1: none) and the two table sizes the clamps used (2^31 - 1: no clamp).  A tower takes
+    only batches made under its own rule."""
     __slots__ = ()
 
     @classmethod
@@ -113,6 +120,56 @@ def pack_tokens(input_ids, lens, rows, token_type_ids=None, position_mode="absol
         _lib.check(_lib.lib().ance_pack_tokens(ctypes.byref(args), _lib.current_stream_ptr()), "ance_pack_tokens")
     return PackedTokens(out_ids, out_types, out_pos, seq_off, seq_kept, rows, L, dropped,
                         PackRule.of(position_mode, padding_idx, vocab_size, max_position))
+
+
+def pack_tokens_by_id(input_ids, rows, padding_idx, vocab_size=None, max_position=None, dropped=None):
+    """``pack_tokens`` for a batch whose pad ids may sit anywhere in a row, in three launches: input_ids [B, L] (B <= 65535, L <= 512),
+    rows an int capacity >= 1 or "exact" (synchronises once, on the count's result; at least 1), padding_idx the id to leave out.
+    Positions are ``padding_idx + 1 + rank`` among the ids that stay, clamped into ``max_position`` rows (None: no clamp).  A
+    sequence that begins with the pad id is dropped whatever the capacity (``seq_kept`` -1, counted in ``dropped``, NaN from
+    ``first_rows``) and owns no rows.  Returns a PackedTokens without type ids under the rule ("seed", padding_idx, ...)."""
+    ids = _ids_matrix(input_ids, "input_ids")
+    B, L = ids.shape
+    dev = ids.device
+    if B > MAX_SEQS or L > MAX_SEQ_LEN:
+        raise _lib.AnceLibraryError("input_ids: at most %d sequences of at most %d tokens, got %r" % (MAX_SEQS, MAX_SEQ_LEN, (B, L)))
+    vocab = 0x7fffffff if vocab_size is None else int(vocab_size)
+    max_pos = 0x7fffffff if max_position is None else int(max_position)
+    if padding_idx is None or isinstance(padding_idx, bool) or not 0 <= int(padding_idx) < vocab:
+        raise _lib.AnceLibraryError("padding_idx must be in [0, %d), got %r" % (vocab, padding_idx))
+    pad = int(padding_idx)
+    exact = isinstance(rows, str)
+    if exact:
+        if rows != "exact":
+            raise _lib.AnceLibraryError("rows must be an int capacity or \"exact\", got %r" % (rows,))
+        rows = 1   # the plan of this call is thrown away: only the count is read
+    rows = int(rows)
+    if not 1 <= rows <= 0x7fffffff:
+        raise _lib.AnceLibraryError("rows must be in 1 .. 2^31 - 1, got %r" % (rows,))
+    if dropped is None:
+        dropped = torch.zeros((), dtype=torch.int64, device=dev)
+    elif not isinstance(dropped, torch.Tensor) or dropped.dtype != torch.int64 or dropped.numel() != 1 or dropped.device != dev:
+        raise _lib.AnceLibraryError("dropped must be a one-element int64 tensor on %s" % (dev,))
+    lens = torch.empty(B, dtype=torch.int32, device=dev)
+    seq_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    seq_kept = torch.empty(B, dtype=torch.int32, device=dev)
+
+    def launch(rows, counter):
+        out_ids = torch.empty(rows, dtype=torch.int32, device=dev)
+        out_pos = torch.empty(rows, dtype=torch.int32, device=dev)
+        args = _lib.AncePackByIdArgs(ids=ids.data_ptr(), d_seq_len=lens.data_ptr(), d_seq_off=seq_off.data_ptr(),
+                                     d_seq_kept=seq_kept.data_ptr(), d_dropped=counter.data_ptr(), packed_ids=out_ids.data_ptr(),
+                                     packed_positions=out_pos.data_ptr(), n_seq=B, L=L, rows=rows, padding_idx=pad, vocab=vocab,
+                                     max_pos=max_pos)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ance_pack_tokens_by_id(ctypes.byref(args), _lib.current_stream_ptr()), "ance_pack_tokens_by_id")
+        return out_ids, out_pos
+
+    if exact:
+        launch(1, torch.zeros((), dtype=torch.int64, device=dev))   # the count alone matters; the caller's counter is not touched
+        rows = max(1, int(lens.clamp(min=0).sum()))   # the one synchronisation
+    out_ids, out_pos = launch(rows, dropped)
+    return PackedTokens(out_ids, None, out_pos, seq_off, seq_kept, rows, L, dropped, PackRule.of("seed", pad, vocab_size, max_position))
 
 
 def _first_rows_args(rows_matrix, ld_rows, first, packed):

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_*, ance_pack_tokens, ance_embed_rows_*, ance_first_rows_*, ance_record_lengths, ance_gather_batch_packed only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_*, ance_pack_tokens, ance_embed_rows_*, ance_first_rows_*, ance_record_lengths, ance_gather_batch_packed, ance_pack_tokens_by_id only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -744,6 +744,24 @@ int ance_embed_backward_dstream(const AnceEmbedArgs *args, const AnceEmbedGradAr
  *   1 .. 512; rows < 1; vocab or max_pos < 1; a position_mode other than the two; padding_idx outside -1 .. vocab - 1 (roberta:
  *   0 .. vocab - 1).
  *
+ * ance_pack_tokens_by_id -- the same outputs (without type ids) for a batch whose pad tokens may sit ANYWHERE in a row, the SEED-Encoder's
+ *   rule: every id equal to padding_idx is left out, inside a record too, and the positions count the ids that stay.  THREE launches
+ *   whatever the inputs -- count (a wave per sequence, one ballot per 64 columns), the plan above over the counted lengths, fill (a wave
+ *   per kept sequence walks all L columns) -- no atomics, nothing read back, capturable.
+ *   d_seq_len [n_seq]      WRITTEN by the call: #{l < L : ids[s, l] != padding_idx} (the raw ids are compared), or -1 when
+ *            ids[s, 0] == padding_idx (a LEADING pad; an all-pad row included): the first row of such a sequence would not be its
+ *            first token, so it is DROPPED whatever the capacity: it scans as 0 rows, d_seq_kept = -1, d_dropped grows by one, and
+ *            d_seq_off keeps its own running offset (while that is <= R), so d_seq_off stays non-decreasing and the neighbours'
+ *            differences stay their lengths; ance_first_rows_gather hands out NaN for it.  Capacity overflow is ance_pack_tokens':
+ *            a suffix of the batch gets d_seq_kept = -1 and d_seq_off = T.
+ *   packed row off_s + r of a kept sequence, r = the rank of column l among the sequence's non-pad columns: packed_ids = ids[s, l] as
+ *            it is; packed_positions = clamp(padding_idx + 1 + r, 0, max_pos - 1).  Slack rows T .. R - 1: id and position padding_idx.
+ *   For sequences that begin with a non-pad id (whose ids inside the vocabulary do not clamp onto padding_idx) every output equals,
+ *   bit for bit, ance_pack_tokens' in roberta mode on the batch with each row's non-pad ids moved to the front and d_seq_len their
+ *   counts.  No row >= R is written, and every offset read back from memory is clamped into [0, R] first.
+ *   Refuses (ANCE_E_INVALID, before any launch): a null pointer; an integer array not 4-byte aligned, d_dropped not 8-byte aligned;
+ *   n_seq outside 1 .. 65535; L outside 1 .. 512; rows < 1; vocab or max_pos < 1; padding_idx outside 0 .. vocab - 1.
+ *
  * ance_embed_rows_forward / _backward (+ _dstream) -- ance_embed_* over T = n_seq rows with L = 1 whose positions are GIVEN:
  *   AnceEmbedArgs.positions [n_seq] is read in both directions (clamped into the table) and never written; position_mode only
  *   says whether the position table has a padding row (roberta: positions equal to padding_idx add nothing to dpos; absolute:
@@ -785,7 +803,20 @@ typedef struct AnceFirstRowsArgs {
     int32_t n_seq, rows, H;
     int32_t dtype;                /* ANCE_DTYPE_*                                                 */
 } AnceFirstRowsArgs;
+typedef struct AncePackByIdArgs {
+    const int32_t *ids;           /* [n_seq, L]                                                   */
+    int32_t *d_seq_len;           /* [n_seq] on the device, WRITTEN: the non-pad counts, -1: a leading pad */
+    int32_t *d_seq_off;           /* [n_seq + 1] out                                              */
+    int32_t *d_seq_kept;          /* [n_seq] out                                                  */
+    int64_t *d_dropped;           /* device counter, added to                                     */
+    int32_t *packed_ids;          /* [rows] out                                                   */
+    int32_t *packed_positions;    /* [rows] out                                                   */
+    int32_t n_seq, L, rows;
+    int32_t padding_idx;          /* 0 .. vocab - 1                                               */
+    int32_t vocab, max_pos;
+} AncePackByIdArgs;
 int ance_pack_tokens(const AncePackArgs *args, void *stream);
+int ance_pack_tokens_by_id(const AncePackByIdArgs *args, void *stream);
 int ance_embed_rows_forward(const AnceEmbedArgs *args, void *stream);
 int ance_embed_rows_backward(const AnceEmbedArgs *args, const AnceEmbedGradArgs *grads, void *stream);
 int ance_embed_rows_forward_dstream(const AnceEmbedArgs *args, const uint64_t *d_stream, void *stream);
