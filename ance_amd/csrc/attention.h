@@ -20,6 +20,7 @@ size_t attention_lds_bytes(int max_seq_len, int n_waves);
 // query of sequence s is row s of the Q columns (the compact [CLS] projection of the encoder's tail), its output row ctx_pair[s]
 int launch_attention_split(const float *qkv, _Float16 *ctx_pair, const int4 *desc, int n_seq, int n_heads, int max_seq_len,
                            int cls_only, hipStream_t stream);
+void reload_attention_knobs();  // re-read ANCE_ATTN_TWO_PASS (ance_reload_env)
 int launch_attention(const AttnArgs &args, int n_seq, int max_seq_len, hipStream_t stream);
 
 }  // namespace ance

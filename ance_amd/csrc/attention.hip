@@ -253,6 +253,7 @@ __global__ void __launch_bounds__(64 * NW, 3) attention_kernel(const AttnArgs A)
 // unscaled lo halves, see common.h) and every product is three MFMAs:
 //     S^T = 2^-11 (K_hi Q_lo'^T + K_lo' Q_hi^T) + K_hi Q_hi^T          (Q carries log2(e) / 8: the softmax runs on exp2)
 //     O^T = 2^-11 (V_hi P_lo'^T + V_lo' P_hi^T) + V_hi P_hi^T          (two accumulator sets, combined once at the end)
+// Sequences of <= 128 tokens (at most 4 key blocks, all staged) take the two-pass softmax instead (split_attend_two_pass, below).
 // LDS: 4 x keys x 64 halves = 64 KB at 128 keys, 128 KB at 256; longer sequences stage their keys 256 at a time (the
 // online softmax iterates key blocks anyway) and re-stage them for every pass of 128 queries.  Replaces the vector-unit kernel of
 // precise32.h (launch_attention32, now the fp32 mode's only) at 8 x the speed for the lengths of config 2.
@@ -287,9 +288,120 @@ __device__ __forceinline__ void permlane32_swap(float &x, float &y) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x), "+v"(y));
 }
 
+constexpr float SPLIT_SC = 2048.0f, SPLIT_SI = 1.0f / 2048.0f;  // lo' = (v - hi) 2^11
+
+// The staged panel of one (sequence, head): K hi | lo' [keys][64] chunk-swizzled, V hi | lo' [keys][VS] row-major (vswz)
+struct SplitPanel {
+    const _Float16 *Kh, *Kl, *Vh, *Vl;
+};
+
+// S^T of key block kb of the staged panel against this wave's 32 queries: 8 cross MFMAs, 2^-11, 4 hi x hi MFMAs.
+// st[r] = score(key 32 kb + (r & 3) + 8 (r >> 2) + 4 g, query i) in the log2 domain; not masked.
+__device__ __forceinline__ f32x16 split_scores(const SplitPanel &P, const f16x8 (&qh)[4], const f16x8 (&ql)[4], int kb, int g, int i) {
+    const int krow = kb * 32 + i;
+    const int ksw = (krow >> 1) & 7;
+    f32x16 st = {0};
+    f16x8 kfh[4];
+#pragma unroll
+    for (int sx = 0; sx < 4; ++sx) {
+        kfh[sx] = *reinterpret_cast<const f16x8 *>(P.Kh + krow * HD + (((4 * g + sx) ^ ksw) * 8));
+        const f16x8 kfl = *reinterpret_cast<const f16x8 *>(P.Kl + krow * HD + (((4 * g + sx) ^ ksw) * 8));
+        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[sx], ql[sx], st, 0, 0, 0);
+        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfl, qh[sx], st, 0, 0, 0);
+    }
+    st *= SPLIT_SI;
+#pragma unroll
+    for (int sx = 0; sx < 4; ++sx) st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[sx], qh[sx], st, 0, 0, 0);
+    return st;
+}
+
+// O^T += V^T P^T for key block kb of the staged panel: P split into (hi, lo'), six MFMAs per 16-key half.
+__device__ __forceinline__ void split_pv(const SplitPanel &P, const float (&p)[16], int kb, int l, f32x16 &om0, f32x16 &om1, f32x16 &oc0,
+                                         f32x16 &oc1) {
+    const int g = l >> 5, i = l & 31;
+#pragma unroll
+    for (int uu = 0; uu < 2; ++uu) {
+        const f16x4 h0 = cvt_f16x4_pinned(f32x4{p[8 * uu], p[8 * uu + 1], p[8 * uu + 2], p[8 * uu + 3]});
+        const f16x4 h1 = cvt_f16x4_pinned(f32x4{p[8 * uu + 4], p[8 * uu + 5], p[8 * uu + 6], p[8 * uu + 7]});
+        f16x8 ph, pl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ph[j] = h0[j]; ph[4 + j] = h1[j];
+            pl[j] = (_Float16)((p[8 * uu + j] - (float)h0[j]) * SPLIT_SC);
+            pl[4 + j] = (_Float16)((p[8 * uu + 4 + j] - (float)h1[j]) * SPLIT_SC);
+        }
+        const int kcol = kb * 32 + 16 * uu + 4 * g;
+        // V^T fragment of head dims row .. (lane i), keys kcol + {0..3, 8..11}
+        auto vfrag = [&](const _Float16 *V, int row) {
+            // lane q of a 16-lane group points at key kcol + q / 4, dims (row - i) + 16 (lane / 16 % 2) + 4 (q % 4) .. + 3
+            // (keys key and key + 8 share bit 1: one swizzle for both reads)
+            const int q = l & 15, key = kcol + (q >> 2);
+            const _Float16 *vp = V + key * VS + vswz(key, (row - i) + 16 * ((l >> 4) & 1) + 4 * (q & 3));
+            const f16x4 a = lds_read_tr16(vp), b = lds_read_tr16(vp + 8 * VS);
+            return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        };
+        const f16x8 v0h = vfrag(P.Vh, i), v1h = vfrag(P.Vh, i + 32), v0l = vfrag(P.Vl, i), v1l = vfrag(P.Vl, i + 32);
+        oc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0h, pl, oc0, 0, 0, 0);
+        oc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0l, ph, oc0, 0, 0, 0);
+        oc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1h, pl, oc1, 0, 0, 0);
+        oc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1l, ph, oc1, 0, 0, 0);
+        om0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0h, ph, om0, 0, 0, 0);
+        om1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1h, ph, om1, 0, 0, 0);
+    }
+}
+
+// TWO-PASS softmax for a sequence whose keys are all staged and whose score strip fits the registers (NKB = Tk / 32 <= 4 key blocks:
+// 16 NKB registers per lane).  Pass A computes every block's scores -- the same MFMAs, in the same order, and the same masking as the
+// online form, so the score bits are the same -- and the query's maximum; pass B exponentiates against that final maximum, block by block
+// in ascending order.  Nothing is ever rescaled: no alpha = exp2(m_run - m_new), no alpha products on the four accumulator sets and on
+// l_run, and no block's exponentials wait for the previous block's maximum.  st[] is indexed by unrolled constants only (registers).
+// NKB = 1: the online form's alpha is exp2(-inf) = 0 on zero accumulators -- the same bits.  NKB >= 2: fewer roundings.
+template <int NKB>
+__device__ __forceinline__ void split_attend_two_pass(const SplitPanel &P, const f16x8 (&qh)[4], const f16x8 (&ql)[4], int T, int l,
+                                                      f32x16 &om0, f32x16 &om1, f32x16 &oc0, f32x16 &oc1, float &l_run) {
+    const int g = l >> 5, i = l & 31;
+    f32x16 st[NKB];
+    float m = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+        st[kb] = split_scores(P, qh, ql, kb, g, i);
+        if (kb == NKB - 1 && NKB * 32 > T) {  // only the last block holds keys >= T
+            const int left = T - (kb * 32 + 4 * g);  // valid keys from this lane group's first one on
+#pragma unroll
+            for (int r = 0; r < 16; ++r) st[kb][r] = (r & 3) + 8 * (r >> 2) < left ? st[kb][r] : -INFINITY;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m = fmaxf(m, st[kb][r]);
+    }
+    m = fmaxf(m, __shfl_xor(m, 32));  // finite: key 0 is always real
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+        float psum = 0.0f;
+        float p[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = __builtin_amdgcn_exp2f(st[kb][r] - m);
+            psum += p[r];
+        }
+        l_run += psum;
+        split_pv(P, p, kb, l, om0, om1, oc0, oc1);
+    }
+}
+
+// ANCE_ATTN_TWO_PASS: 1 (default) = the sequences of <= 128 tokens take the two-pass softmax above; 0 = the online form everywhere
+// (same-box A/B, tests/test_gpu_attention_two_pass.py).  Read once per process, ance_reload_env re-reads it.
+int g_attn_two_pass = -1;
+int attn_two_pass_mode() {
+    if (g_attn_two_pass < 0) {
+        const char *e = getenv("ANCE_ATTN_TWO_PASS");
+        g_attn_two_pass = (e && e[0] == '0') ? 0 : 1;
+    }
+    return g_attn_two_pass;
+}
+
 template <int NW>
 __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float *qkv, _Float16 *ctx_pair, const int4 *desc, int n_heads,
-                                                                     int cls_only, int kchunk) {
+                                                                     int cls_only, int kchunk, int two_pass_on) {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     const int u = blockIdx.x / n_heads;
     const int h = blockIdx.x - u * n_heads;
@@ -307,11 +419,12 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
     const int w = tid >> 6, l = tid & 63, g = l >> 5, i = l & 31;
     constexpr int NT = 64 * NW;
     const int ld = 3 * n_heads * HD;
-    constexpr float SC = 2048.0f, SI = 1.0f / 2048.0f;
+    constexpr float SC = SPLIT_SC, SI = SPLIT_SI;
+    const SplitPanel P = {Kh, Kl, Vh, Vl};
     // ---- stage K (rows = keys) and V^T (rows = head dims) of keys [k0, k0 + kc), split on the way; keys >= T are zeros ----
     // UNR rounds of loads are issued before the first one is consumed: a sequence's K / V panel then costs one HBM latency, not
     // one per round (4 rounds at 128 keys).  The chunked path (T > 256) stages under live accumulators and keeps UNR = 1.
-    auto stage = [&](int k0, auto unr_tag) {
+    auto stage = [&](int k0, auto unr_tag) __attribute__((always_inline)) {
         constexpr int UNR = decltype(unr_tag)::value;
         for (int e0 = tid; e0 < kc * 8; e0 += UNR * NT) {
             f32x4 kv[UNR][4];
@@ -358,9 +471,16 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
         }
     };
     const bool single = Tk <= kc;  // one chunk: staged once (inside the first query pass, behind its Q loads), shared by every pass
+    // two-pass softmax (split_attend_two_pass) for up to 4 key blocks: by the sequence's own length alone (Tk <= 128 is always one
+    // chunk: kchunk >= the launch's longest Tk), whatever the launch's max_seq_len, batch mates, head count or cls_only
+    const bool two_pass = two_pass_on && Tk <= 128;
     const int q_end = cls_only ? 1 : T;
     const float qscale = 0.125f * 1.44269504088896340736f;
-    for (int qp0 = 0; qp0 < q_end; qp0 += 32 * NW) {  // query pass: 32 queries per wave (uniform loop: the barriers below)
+    // One query pass: 32 queries per wave.  tp_tag: the two-pass form -- a sequence of <= 128 tokens is one pass of <= 128 queries, so
+    // that form sits in no loop (inside the pass loop the compiler hoists every instantiation's invariants out of it and holds them
+    // in registers across the whole kernel: spills at 4 key blocks).
+    auto query_pass = [&](int qp0, auto tp_tag) __attribute__((always_inline)) {
+        constexpr bool TP = decltype(tp_tag)::value;
         const int qb0 = qp0 + w * 32;
         const bool active = qb0 < q_end;
         // Q fragments (B operand: lane (query i, group g) holds head dims 32 g + 8 sx .. + 8), scaled, then split
@@ -391,82 +511,51 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
         }
         float m_run = -INFINITY, l_run = 0.0f;
         f32x16 om0 = {0}, om1 = {0}, oc0 = {0}, oc1 = {0};
-        for (int k0 = 0; k0 < Tk; k0 += kc) {
-            if (!single) {
-                __syncthreads();  // the previous chunk (or pass) is no longer read
-                stage(k0, std::integral_constant<int, 1>{});
-                __syncthreads();
+        if constexpr (TP) {  // the panel is staged (single), no barrier below
+            if (!active) return;
+            switch (Tk >> 5) {
+            case 1: split_attend_two_pass<1>(P, qh, ql, T, l, om0, om1, oc0, oc1, l_run); break;
+            case 2: split_attend_two_pass<2>(P, qh, ql, T, l, om0, om1, oc0, oc1, l_run); break;
+            case 3: split_attend_two_pass<3>(P, qh, ql, T, l, om0, om1, oc0, oc1, l_run); break;
+            default: split_attend_two_pass<4>(P, qh, ql, T, l, om0, om1, oc0, oc1, l_run); break;
             }
-            if (!active) continue;
-            const int nkb = min(kc, Tk - k0) >> 5;
-            for (int kb = 0; kb < nkb; ++kb) {
-                const int krow = kb * 32 + i;
-                const int ksw = (krow >> 1) & 7;
-                f32x16 st = {0};
-                f16x8 kfh[4];
-#pragma unroll
-                for (int sx = 0; sx < 4; ++sx) {
-                    kfh[sx] = *reinterpret_cast<const f16x8 *>(Kh + krow * HD + (((4 * g + sx) ^ ksw) * 8));
-                    const f16x8 kfl = *reinterpret_cast<const f16x8 *>(Kl + krow * HD + (((4 * g + sx) ^ ksw) * 8));
-                    st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[sx], ql[sx], st, 0, 0, 0);
-                    st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfl, qh[sx], st, 0, 0, 0);
+        } else {
+            for (int k0 = 0; k0 < Tk; k0 += kc) {
+                if (!single) {
+                    __syncthreads();  // the previous chunk (or pass) is no longer read
+                    stage(k0, std::integral_constant<int, 1>{});
+                    __syncthreads();
                 }
-                st *= SI;
+                if (!active) continue;
+                const int nkb = min(kc, Tk - k0) >> 5;
+                for (int kb = 0; kb < nkb; ++kb) {
+                    f32x16 st = split_scores(P, qh, ql, kb, g, i);
+                    const int key_base = k0 + kb * 32 + 4 * g;
+                    float bm = -INFINITY;
 #pragma unroll
-                for (int sx = 0; sx < 4; ++sx) st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[sx], qh[sx], st, 0, 0, 0);
-                const int key_base = k0 + kb * 32 + 4 * g;
-                float bm = -INFINITY;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = key_base + (r & 3) + 8 * (r >> 2);
-                    if (k0 + kb * 32 + 32 > T) st[r] = key < T ? st[r] : -INFINITY;  // only the last block holds keys >= T
-                    bm = fmaxf(bm, st[r]);
-                }
-                bm = fmaxf(bm, __shfl_xor(bm, 32));
-                const float m_new = fmaxf(m_run, bm);   // finite: key 0 of block 0 is always real
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-                float psum = 0.0f;
-                float p[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    p[r] = __builtin_amdgcn_exp2f(st[r] - m_new);
-                    psum += p[r];
-                }
-                l_run = l_run * alpha + psum;
-                m_run = m_new;
-                om0 *= alpha; om1 *= alpha; oc0 *= alpha; oc1 *= alpha;
-#pragma unroll
-                for (int uu = 0; uu < 2; ++uu) {
-                    const f16x4 h0 = cvt_f16x4_pinned(f32x4{p[8 * uu], p[8 * uu + 1], p[8 * uu + 2], p[8 * uu + 3]});
-                    const f16x4 h1 = cvt_f16x4_pinned(f32x4{p[8 * uu + 4], p[8 * uu + 5], p[8 * uu + 6], p[8 * uu + 7]});
-                    f16x8 ph, pl;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        ph[j] = h0[j]; ph[4 + j] = h1[j];
-                        pl[j] = (_Float16)((p[8 * uu + j] - (float)h0[j]) * SC);
-                        pl[4 + j] = (_Float16)((p[8 * uu + 4 + j] - (float)h1[j]) * SC);
+                    for (int r = 0; r < 16; ++r) {
+                        const int key = key_base + (r & 3) + 8 * (r >> 2);
+                        if (k0 + kb * 32 + 32 > T) st[r] = key < T ? st[r] : -INFINITY;  // only the last block holds keys >= T
+                        bm = fmaxf(bm, st[r]);
                     }
-                    const int kcol = kb * 32 + 16 * uu + 4 * g;
-                    // V^T fragment of head dims row .. (lane i), keys kcol + {0..3, 8..11}
-                    auto vfrag = [&](const _Float16 *V, int row) {
-                        // lane q of a 16-lane group points at key kcol + q / 4, dims (row - i) + 16 (lane / 16 % 2) + 4 (q % 4) .. + 3
-                        // (keys key and key + 8 share bit 1: one swizzle for both reads)
-                        const int q = l & 15, key = kcol + (q >> 2);
-                        const _Float16 *vp = V + key * VS + vswz(key, (row - i) + 16 * ((l >> 4) & 1) + 4 * (q & 3));
-                        const f16x4 a = lds_read_tr16(vp), b = lds_read_tr16(vp + 8 * VS);
-                        return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-                    };
-                    const f16x8 v0h = vfrag(Vh, i), v1h = vfrag(Vh, i + 32), v0l = vfrag(Vl, i), v1l = vfrag(Vl, i + 32);
-                    oc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0h, pl, oc0, 0, 0, 0);
-                    oc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0l, ph, oc0, 0, 0, 0);
-                    oc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1h, pl, oc1, 0, 0, 0);
-                    oc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1l, ph, oc1, 0, 0, 0);
-                    om0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0h, ph, om0, 0, 0, 0);
-                    om1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1h, ph, om1, 0, 0, 0);
+                    bm = fmaxf(bm, __shfl_xor(bm, 32));
+                    const float m_new = fmaxf(m_run, bm);   // finite: key 0 of block 0 is always real
+                    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+                    float psum = 0.0f;
+                    float p[16];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        p[r] = __builtin_amdgcn_exp2f(st[r] - m_new);
+                        psum += p[r];
+                    }
+                    l_run = l_run * alpha + psum;
+                    m_run = m_new;
+                    om0 *= alpha; om1 *= alpha; oc0 *= alpha; oc1 *= alpha;
+                    split_pv(P, p, kb, l, om0, om1, oc0, oc1);
                 }
             }
+            if (!active) return;
         }
-        if (!active) continue;
         const float l_tot = l_run + __shfl_xor(l_run, 32);
         const float inv = 1.0f / l_tot;
         {
@@ -505,10 +594,17 @@ __global__ void __launch_bounds__(64 * NW, 2) attention_split_kernel(const float
                 }
             }
         }
+    };
+    if (two_pass) {  // uniform
+        query_pass(0, std::true_type{});
+    } else {
+        for (int qp0 = 0; qp0 < q_end; qp0 += 32 * NW) query_pass(qp0, std::false_type{});  // uniform loop: the barriers inside
     }
 }
 
 }  // namespace
+
+void reload_attention_knobs() { g_attn_two_pass = -1; }
 
 size_t attention_split_lds_bytes(int max_seq_len) {
     const int Tk = (max_seq_len + 31) & ~31;
@@ -535,7 +631,7 @@ int launch_attention_split(const float *qkv, _Float16 *ctx_pair, const int4 *des
         if (tracked) __atomic_store_n(&attr_set[dev], lds, __ATOMIC_RELEASE);
     }
     hipLaunchKernelGGL((attention_split_kernel<4>), dim3((unsigned)n_seq * n_heads), dim3(256), lds, st, qkv, ctx_pair, desc, n_heads,
-                       cls_only, kchunk);
+                       cls_only, kchunk, attn_two_pass_mode());
     return ANCE_OK;
 }
 

@@ -360,6 +360,7 @@ using namespace ance;
 
 namespace ance {
 void reload_gemm_knobs();  // gemm256_f16.hip
+void reload_attention_knobs();  // attention.hip
 }
 
 extern "C" void ance_debug_search_stamps(void *d_stamps) { ance::set_fast_stamps(reinterpret_cast<unsigned long long *>(d_stamps)); }
@@ -379,6 +380,7 @@ extern "C" void ance_reload_env(void) {
     g_search_exact = -1;
     ance::reload_fast_knobs();
     ance::reload_gemm_knobs();
+    ance::reload_attention_knobs();
 }
 
 static size_t scan_workspace_bytes(int64_t n, int64_t nq, int k) {

@@ -237,7 +237,10 @@ typedef struct AnceEncoder AnceEncoder;
  *   ANCE_ENCODER_STREAMS=n   internal streams / activation sets (1 or 2, default 2)
  *   ANCE_CLS_TAIL=0          the full last layer instead of the CLS-only tail (bit-identical: the tail's reference; per handle)
  *   ANCE_GEMM_STREAM=0       the launch-per-tile split GEMM for QKV and FFN1 instead of the persistent streaming one
- *                            (bit-identical: the streaming kernel's reference; read once per process, ance_reload_env re-reads) */
+ *                            (bit-identical: the streaming kernel's reference; read once per process, ance_reload_env re-reads)
+ *   ANCE_ATTN_TWO_PASS=0     the online softmax for every sequence in the split attention instead of the two-pass form for
+ *                            sequences of <= 128 tokens (same bits up to 32 tokens, rounding only above; A/B; read once per process,
+ *                            ance_reload_env re-reads) */
 size_t ance_encoder_weight_bytes(const AnceEncoderDesc *desc);
 size_t ance_encoder_workspace_bytes(const AnceEncoderDesc *desc);
 
