@@ -1,5 +1,6 @@
 // The kernels of the BertLayer's row-wise seams, once, for both precisions of their matmul-side I/O (layer_tail.hip: X = F32, fp32
-// throughout; layer_tail_half.hip: X = F16 / BF16, 16-bit x / dx / y16 / dy16 around an fp32 residual stream).  The arithmetic behind
+// throughout; layer_tail_half.hip: X = F16 / BF16, 16-bit x / dx / y16 / dy16 around an fp32 residual stream), behind the one host
+// front end of layer_tail_common.h, which fills the parameter blocks and picks X at the launch.  The arithmetic behind
 // the load and in front of the store is one text, so on an x that holds 16-bit values the 16-bit tail's fp32 outputs are the fp32
 // tail's bits.  The organisation (one wave per row, lane l at columns 4 (64 i + l) .. + 3, 16 rows per workgroup, partial rows, the
 // column-sum tree) is row_kernels.h's; the contracts are include/ance_amd.h's.
@@ -331,20 +332,6 @@ inline void launch_gelu_colsum(const float *part, int64_t n_rows, int N, float *
 
 inline size_t tail_ws_bytes(int64_t n_rows, int H) { return stats_bytes(n_rows) + n_part(n_rows) * 3 * (size_t)H * sizeof(float); }
 inline size_t gelu_ws_bytes(int64_t n_rows, int N) { return n_part(n_rows) * (size_t)N * sizeof(float); }
-
-// the fields that every tail parameter block derives from the call's arguments the same way
-template <class P_, class A_>
-void fill_tail_common(P_ &P, const A_ *a) {
-    P.n_rows = a->n_rows;
-    P.mean = (float *)a->d_workspace;
-    P.rstd = (float *)((char *)a->d_workspace + stats_bytes(a->n_rows) / 2);
-    P.part = (float *)((char *)a->d_workspace + stats_bytes(a->n_rows));
-    P.eps = a->eps;
-    P.seed_lo = (uint32_t)a->seed; P.seed_hi = (uint32_t)(a->seed >> 32);
-    P.off_lo = (uint32_t)a->offset; P.off_hi = (uint32_t)(a->offset >> 32);
-    P.keep_thr = (uint32_t)((double)a->dropout_p * 4294967296.0);  // floor(p 2^32), p < 1
-    P.keep_scale = 1.0f / (1.0f - a->dropout_p);
-}
 
 }  // namespace
 }  // namespace ance

@@ -19,6 +19,9 @@ step draws the masks of the step it stands for (ance_amd/attention.py).  The mas
 ``precision="half"`` (both functions; ``BertLayer(..., precision="half")``) is the form for ``torch.autocast`` (csrc/layer_tail_half.hip
 behind ance_layer_tail16_* / ance_bias_gelu16_*): the dense outputs go in as fp16 / bf16, the residual stream, ``y`` and every
 parameter gradient stay fp32, and the tail can return a 16-bit copy of ``y`` for the Linears that read it.
+
+Both precisions of a seam share one forward and one backward body (``_tail_forward`` ... ``_gelu_backward``, taking ``half``), and
+the four forms of ``BertLayer`` -- all rows or first rows, padded or packed -- share one forward text (``BertLayer._layer``).
 """
 import ctypes
 
@@ -55,11 +58,12 @@ def _check_vector(t, what, width, like, optional=False):
         raise _lib.AnceLibraryError("%s must have dtype torch.float32, got %s" % (what, t.dtype))
 
 
-def _matrix(t):
-    """[.., W] as (tensor to keep alive, row stride): 2- and 3-dimensional views with evenly spaced rows pass as they are."""
+def _matrix(t, piece=4):
+    """[.., W] as (tensor to keep alive, row stride): 2- and 3-dimensional views with evenly spaced rows pass as they are.  piece:
+    the elements of a 16-byte piece of a row, which the row stride must be a multiple of (4 for fp32, 8 for a 16-bit tensor)."""
     if t.dim() > 3:
         t = t.reshape(-1, t.shape[-1])
-    return _rows(t)
+    return _rows(t, piece)
 
 
 def _vector(t):
@@ -79,106 +83,148 @@ def _stats_floats(n_rows):
     return 2 * ((4 * n_rows + 255) // 256 * 256) // 4
 
 
+# per precision (indexed by half): the elements of a 16-byte piece of x, the names of the workspace query, the forward and the backward
+# entry, the argument and the gradient struct -- written out once here, so that a call looks nothing up but the library's attribute
+_TAIL = ((4, "ance_layer_tail_workspace_bytes", "ance_layer_tail_forward", "ance_layer_tail_backward",
+          _lib.AnceLayerTailArgs, _lib.AnceLayerTailGradArgs),
+         (8, "ance_layer_tail16_workspace_bytes", "ance_layer_tail16_forward", "ance_layer_tail16_backward",
+          _lib.AnceLayerTail16Args, _lib.AnceLayerTail16GradArgs))
+_GELU = ((4, "ance_bias_gelu_workspace_bytes", "ance_bias_gelu_forward", "ance_bias_gelu_backward",
+          _lib.AnceBiasGeluArgs, _lib.AnceBiasGeluGradArgs),
+         (8, "ance_bias_gelu16_workspace_bytes", "ance_bias_gelu16_forward", "ance_bias_gelu16_backward",
+          _lib.AnceBiasGelu16Args, _lib.AnceBiasGelu16GradArgs))
+
+
+def _tail_forward(ctx, x, bias, residual, weight, beta, eps, dropout_p, training, half, want_half=False):
+    """The forward of both tail Functions: x fp32, or with ``half`` fp16 / bf16 as it is (nothing is cast); residual fp32.  Returns
+    (y, y16), y16 None unless ``want_half``."""
+    L = _lib.lib()
+    piece, ws_query, forward, _, Args, _ = _TAIL[half]
+    shape, H = x.shape, x.shape[-1]
+    (x, ld_x), (residual, ld_r) = _matrix(x, piece), _matrix(residual)
+    bias, weight, beta = _vector(bias), _vector(weight), _vector(beta)
+    n_rows = x.numel() // H
+    if getattr(L, ws_query)(n_rows, H) == 0:
+        raise _lib.AnceLibraryError("dropout_add_layer_norm: unsupported shape (rows %d, width %d)" % (n_rows, H))
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    y16 = torch.empty(shape, dtype=x.dtype, device=x.device) if want_half else None
+    stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=x.device)
+    drop = bool(training) and dropout_p > 0.0
+    draw = dropout_state.draw(x.device) if drop else _NO_DRAW
+    args = Args(x=x.data_ptr(), res=residual.data_ptr(), bias=_ptr(bias), gamma=weight.data_ptr(), beta=beta.data_ptr(), y=y.data_ptr(),
+                ld_x=ld_x, ld_res=ld_r, ld_y=H, H=H, n_rows=n_rows, eps=float(eps), dropout_p=float(dropout_p),
+                training=1 if drop else 0, seed=draw.seed, offset=draw.offset, d_workspace=stats.data_ptr(),
+                workspace_bytes=stats.numel() * 4)
+    if half:   # the fields only the 16-bit struct has
+        args.y16, args.ld_y16, args.dtype = _ptr(y16), H, HALF_DTYPES[x.dtype]
+    with torch.cuda.device(x.device):
+        draw.launch(forward, ctypes.byref(args))
+    ctx.save_for_backward(x, residual, bias, weight, stats)
+    ctx.args, ctx.draw = args, draw
+    ctx.shape = shape
+    return y, y16
+
+
+def _tail_backward(ctx, dy, dy16, half):
+    """The backward of both tail Functions -> (dx, dbias, dres, dgamma, dbeta): dx in x's dtype, the rest fp32.  With ``half``, dy
+    and dy16 may each be None (not both)."""
+    L = _lib.lib()
+    piece, ws_query, _, backward, Args, GradArgs = _TAIL[half]
+    x, residual, bias, weight, stats = ctx.saved_tensors
+    a = Args.from_buffer_copy(ctx.args)  # y, y16 and beta are not touched by the backward
+    H, n_rows = a.H, a.n_rows
+    ld_dy = ld_dy16 = 0
+    if dy is not None:
+        dy, ld_dy = _matrix(dy.to(torch.float32))
+    if dy16 is not None:
+        dy16, ld_dy16 = _matrix(dy16.to(x.dtype), piece)
+    want_x, want_bias, want_res, want_w, want_b = ctx.needs_input_grad[:5]
+
+    def out(want, shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=x.device) if want else None
+
+    dx, dres = out(want_x, ctx.shape, x.dtype), out(want_res, ctx.shape)
+    dbias, dgamma, dbeta = out(want_bias and bias is not None, (H,)), out(want_w, (H,)), out(want_b, (H,))
+    # the saved state is the statistics alone; the backward's partial rows live only as long as this call
+    ws_bytes = getattr(L, ws_query)(n_rows, H)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    ws[:stats.numel()].copy_(stats)
+    a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    g = GradArgs(dy=_ptr(dy), dx=_ptr(dx), dres=_ptr(dres), dgamma=_ptr(dgamma), dbeta=_ptr(dbeta), dbias=_ptr(dbias), ld_dy=ld_dy,
+                 ld_dx=H, ld_dres=H)
+    if half:
+        g.dy16, g.ld_dy16 = _ptr(dy16), ld_dy16
+    with torch.cuda.device(x.device):
+        ctx.draw.launch(backward, ctypes.byref(a), ctypes.byref(g))
+    return dx, dbias, dres, dgamma, dbeta
+
+
+def _gelu_forward(ctx, x, bias, half):
+    """The forward of both GELU Functions: y has x's dtype, and the saved input is x itself."""
+    L = _lib.lib()
+    piece, ws_query, forward, _, Args, _ = _GELU[half]
+    shape, N = x.shape, x.shape[-1]
+    x, ld_x = _matrix(x, piece)
+    bias = _vector(bias)
+    n_rows = x.numel() // N
+    if getattr(L, ws_query)(n_rows, N) == 0:
+        raise _lib.AnceLibraryError("bias_gelu: unsupported shape (rows %d, width %d)" % (n_rows, N))
+    y = torch.empty(shape, dtype=x.dtype, device=x.device)
+    args = Args(x=x.data_ptr(), bias=bias.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_y=N, N=N, n_rows=n_rows, d_workspace=None,
+                workspace_bytes=0)
+    if half:
+        args.dtype = HALF_DTYPES[x.dtype]
+    with torch.cuda.device(x.device):
+        _lib.check(getattr(L, forward)(ctypes.byref(args), _lib.current_stream_ptr()), forward)
+    ctx.save_for_backward(x, bias)
+    ctx.args = args
+    ctx.shape = shape
+    return y
+
+
+def _gelu_backward(ctx, dy, half):
+    """The backward of both GELU Functions -> (dx, dbias): dx in x's dtype, dbias fp32."""
+    L = _lib.lib()
+    piece, ws_query, _, backward, Args, GradArgs = _GELU[half]
+    x, bias = ctx.saved_tensors
+    a = Args.from_buffer_copy(ctx.args)
+    dy, ld_dy = _matrix(dy.to(x.dtype), piece)
+    want_x, want_bias = ctx.needs_input_grad[:2]
+    dx = torch.empty(ctx.shape, dtype=x.dtype, device=x.device) if want_x else None
+    dbias = torch.empty(a.N, dtype=torch.float32, device=x.device) if want_bias else None
+    ws_bytes = getattr(L, ws_query)(a.n_rows, a.N)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    g = GradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=a.N)
+    with torch.cuda.device(x.device):
+        _lib.check(getattr(L, backward)(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), backward)
+    return dx, dbias
+
+
 class _DropoutAddLayerNorm(torch.autograd.Function):
     @staticmethod
     @_custom_fwd
     def forward(ctx, x, bias, residual, weight, beta, eps, dropout_p, training):
-        L = _lib.lib()
-        shape, H = x.shape, x.shape[-1]
-        (x, ld_x), (residual, ld_r) = _matrix(x), _matrix(residual)
-        bias, weight, beta = _vector(bias), _vector(weight), _vector(beta)
-        n_rows = x.numel() // H
-        if L.ance_layer_tail_workspace_bytes(n_rows, H) == 0:
-            raise _lib.AnceLibraryError("dropout_add_layer_norm: unsupported shape (rows %d, width %d)" % (n_rows, H))
-        y = torch.empty(shape, dtype=torch.float32, device=x.device)
-        stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=x.device)
-        drop = bool(training) and dropout_p > 0.0
-        draw = dropout_state.draw(x.device) if drop else _NO_DRAW
-        args = _lib.AnceLayerTailArgs(x=x.data_ptr(), res=residual.data_ptr(), bias=_ptr(bias), gamma=weight.data_ptr(),
-                                      beta=beta.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_res=ld_r, ld_y=H, H=H, n_rows=n_rows,
-                                      eps=float(eps), dropout_p=float(dropout_p), training=1 if drop else 0, seed=draw.seed,
-                                      offset=draw.offset, d_workspace=stats.data_ptr(), workspace_bytes=stats.numel() * 4)
-        with torch.cuda.device(x.device):
-            draw.launch("ance_layer_tail_forward", ctypes.byref(args))
-        ctx.save_for_backward(x, residual, bias, weight, stats)
-        ctx.args, ctx.draw = args, draw
-        ctx.shape = shape
-        return y
+        return _tail_forward(ctx, x, bias, residual, weight, beta, eps, dropout_p, training, False)[0]
 
     @staticmethod
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dy):
-        L = _lib.lib()
-        x, residual, bias, weight, stats = ctx.saved_tensors
-        a = _lib.AnceLayerTailArgs.from_buffer_copy(ctx.args)  # y and beta are not touched by the backward
-        H, n_rows = a.H, a.n_rows
-        dy, ld_dy = _matrix(dy.to(torch.float32))
-        want_x, want_bias, want_res, want_w, want_b = ctx.needs_input_grad[:5]
-
-        def out(want, shape):
-            return torch.empty(shape, dtype=torch.float32, device=x.device) if want else None
-
-        dx, dres = out(want_x, ctx.shape), out(want_res, ctx.shape)
-        dbias, dgamma, dbeta = out(want_bias and bias is not None, (H,)), out(want_w, (H,)), out(want_b, (H,))
-        # the saved state is the statistics alone; the backward's partial rows live only as long as this call
-        ws_bytes = L.ance_layer_tail_workspace_bytes(n_rows, H)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-        ws[:stats.numel()].copy_(stats)
-        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
-        g = _lib.AnceLayerTailGradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dres=_ptr(dres), dgamma=_ptr(dgamma), dbeta=_ptr(dbeta),
-                                       dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=H, ld_dres=H)
-        with torch.cuda.device(x.device):
-            ctx.draw.launch("ance_layer_tail_backward", ctypes.byref(a), ctypes.byref(g))
-        return dx, dbias, dres, dgamma, dbeta, None, None, None
+        return _tail_backward(ctx, dy, None, False) + (None, None, None)
 
 
 class _BiasGelu(torch.autograd.Function):
     @staticmethod
     @_custom_fwd
     def forward(ctx, x, bias):
-        L = _lib.lib()
-        shape, N = x.shape, x.shape[-1]
-        x, ld_x = _matrix(x)
-        bias = _vector(bias)
-        n_rows = x.numel() // N
-        if L.ance_bias_gelu_workspace_bytes(n_rows, N) == 0:
-            raise _lib.AnceLibraryError("bias_gelu: unsupported shape (rows %d, width %d)" % (n_rows, N))
-        y = torch.empty(shape, dtype=torch.float32, device=x.device)
-        args = _lib.AnceBiasGeluArgs(x=x.data_ptr(), bias=bias.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_y=N, N=N, n_rows=n_rows,
-                                     d_workspace=None, workspace_bytes=0)
-        with torch.cuda.device(x.device):
-            _lib.check(L.ance_bias_gelu_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_bias_gelu_forward")
-        ctx.save_for_backward(x, bias)
-        ctx.args = args
-        ctx.shape = shape
-        return y
+        return _gelu_forward(ctx, x, bias, False)
 
     @staticmethod
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dy):
-        L = _lib.lib()
-        x, bias = ctx.saved_tensors
-        a = _lib.AnceBiasGeluArgs.from_buffer_copy(ctx.args)
-        dy, ld_dy = _matrix(dy.to(torch.float32))
-        want_x, want_bias = ctx.needs_input_grad[:2]
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=x.device) if want_x else None
-        dbias = torch.empty(a.N, dtype=torch.float32, device=x.device) if want_bias else None
-        ws_bytes = L.ance_bias_gelu_workspace_bytes(a.n_rows, a.N)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
-        g = _lib.AnceBiasGeluGradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=a.N)
-        with torch.cuda.device(x.device):
-            _lib.check(L.ance_bias_gelu_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()), "ance_bias_gelu_backward")
-        return dx, dbias
-
-
-def _matrix16(t):
-    """_matrix for a 16-bit tensor (a row stride must be a multiple of 8 elements)."""
-    if t.dim() > 3:
-        t = t.reshape(-1, t.shape[-1])
-    return _rows(t, 8)
+        return _gelu_backward(ctx, dy, False)
 
 
 class _DropoutAddLayerNormHalf(torch.autograd.Function):
@@ -188,28 +234,7 @@ class _DropoutAddLayerNormHalf(torch.autograd.Function):
     @staticmethod
     @_custom_fwd_as_is
     def forward(ctx, x, bias, residual, weight, beta, eps, dropout_p, training, want_half):
-        L = _lib.lib()
-        shape, H = x.shape, x.shape[-1]
-        (x, ld_x), (residual, ld_r) = _matrix16(x), _matrix(residual)
-        bias, weight, beta = _vector(bias), _vector(weight), _vector(beta)
-        n_rows = x.numel() // H
-        if L.ance_layer_tail16_workspace_bytes(n_rows, H) == 0:
-            raise _lib.AnceLibraryError("dropout_add_layer_norm: unsupported shape (rows %d, width %d)" % (n_rows, H))
-        y = torch.empty(shape, dtype=torch.float32, device=x.device)
-        y16 = torch.empty(shape, dtype=x.dtype, device=x.device) if want_half else None
-        stats = torch.empty(_stats_floats(n_rows), dtype=torch.float32, device=x.device)
-        drop = bool(training) and dropout_p > 0.0
-        draw = dropout_state.draw(x.device) if drop else _NO_DRAW
-        args = _lib.AnceLayerTail16Args(x=x.data_ptr(), res=residual.data_ptr(), bias=_ptr(bias), gamma=weight.data_ptr(),
-                                        beta=beta.data_ptr(), y=y.data_ptr(), y16=_ptr(y16), ld_x=ld_x, ld_res=ld_r, ld_y=H, ld_y16=H,
-                                        H=H, n_rows=n_rows, dtype=HALF_DTYPES[x.dtype], eps=float(eps), dropout_p=float(dropout_p),
-                                        training=1 if drop else 0, seed=draw.seed, offset=draw.offset, d_workspace=stats.data_ptr(),
-                                        workspace_bytes=stats.numel() * 4)
-        with torch.cuda.device(x.device):
-            draw.launch("ance_layer_tail16_forward", ctypes.byref(args))
-        ctx.save_for_backward(x, residual, bias, weight, stats)
-        ctx.args, ctx.draw = args, draw
-        ctx.shape = shape
+        y, y16 = _tail_forward(ctx, x, bias, residual, weight, beta, eps, dropout_p, training, True, want_half)
         ctx.set_materialize_grads(False)   # a missing gradient stays None: the kernel reads only those that exist
         return (y, y16) if want_half else y
 
@@ -217,33 +242,9 @@ class _DropoutAddLayerNormHalf(torch.autograd.Function):
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dy, dy16=None):
-        L = _lib.lib()
-        x, residual, bias, weight, stats = ctx.saved_tensors
         if dy is None and dy16 is None:
             return (None,) * 9
-        a = _lib.AnceLayerTail16Args.from_buffer_copy(ctx.args)  # y, y16 and beta are not touched by the backward
-        H, n_rows = a.H, a.n_rows
-        ld_dy = ld_dy16 = 0
-        if dy is not None:
-            dy, ld_dy = _matrix(dy.to(torch.float32))
-        if dy16 is not None:
-            dy16, ld_dy16 = _matrix16(dy16.to(x.dtype))
-        want_x, want_bias, want_res, want_w, want_b = ctx.needs_input_grad[:5]
-
-        def out(want, shape, dtype=torch.float32):
-            return torch.empty(shape, dtype=dtype, device=x.device) if want else None
-
-        dx, dres = out(want_x, ctx.shape, x.dtype), out(want_res, ctx.shape)
-        dbias, dgamma, dbeta = out(want_bias and bias is not None, (H,)), out(want_w, (H,)), out(want_b, (H,))
-        ws_bytes = L.ance_layer_tail16_workspace_bytes(n_rows, H)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-        ws[:stats.numel()].copy_(stats)
-        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
-        g = _lib.AnceLayerTail16GradArgs(dy=_ptr(dy), dy16=_ptr(dy16), dx=_ptr(dx), dres=_ptr(dres), dgamma=_ptr(dgamma),
-                                         dbeta=_ptr(dbeta), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dy16=ld_dy16, ld_dx=H, ld_dres=H)
-        with torch.cuda.device(x.device):
-            ctx.draw.launch("ance_layer_tail16_backward", ctypes.byref(a), ctypes.byref(g))
-        return dx, dbias, dres, dgamma, dbeta, None, None, None, None
+        return _tail_backward(ctx, dy, dy16, True) + (None, None, None, None)
 
 
 class _BiasGeluHalf(torch.autograd.Function):
@@ -252,42 +253,13 @@ class _BiasGeluHalf(torch.autograd.Function):
     @staticmethod
     @_custom_fwd_as_is
     def forward(ctx, x, bias):
-        L = _lib.lib()
-        shape, N = x.shape, x.shape[-1]
-        x, ld_x = _matrix16(x)
-        bias = _vector(bias)
-        n_rows = x.numel() // N
-        if L.ance_bias_gelu16_workspace_bytes(n_rows, N) == 0:
-            raise _lib.AnceLibraryError("bias_gelu: unsupported shape (rows %d, width %d)" % (n_rows, N))
-        y = torch.empty(shape, dtype=x.dtype, device=x.device)
-        args = _lib.AnceBiasGelu16Args(x=x.data_ptr(), bias=bias.data_ptr(), y=y.data_ptr(), ld_x=ld_x, ld_y=N, N=N, n_rows=n_rows,
-                                       dtype=HALF_DTYPES[x.dtype], reserved=0, d_workspace=None, workspace_bytes=0)
-        with torch.cuda.device(x.device):
-            _lib.check(L.ance_bias_gelu16_forward(ctypes.byref(args), _lib.current_stream_ptr()), "ance_bias_gelu16_forward")
-        ctx.save_for_backward(x, bias)
-        ctx.args = args
-        ctx.shape = shape
-        return y
+        return _gelu_forward(ctx, x, bias, True)
 
     @staticmethod
     @_custom_bwd
     @once_differentiable
     def backward(ctx, dy):
-        L = _lib.lib()
-        x, bias = ctx.saved_tensors
-        a = _lib.AnceBiasGelu16Args.from_buffer_copy(ctx.args)
-        dy, ld_dy = _matrix16(dy.to(x.dtype))
-        want_x, want_bias = ctx.needs_input_grad[:2]
-        dx = torch.empty(ctx.shape, dtype=x.dtype, device=x.device) if want_x else None
-        dbias = torch.empty(a.N, dtype=torch.float32, device=x.device) if want_bias else None
-        ws_bytes = L.ance_bias_gelu16_workspace_bytes(a.n_rows, a.N)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-        a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
-        g = _lib.AnceBiasGelu16GradArgs(dy=dy.data_ptr(), dx=_ptr(dx), dbias=_ptr(dbias), ld_dy=ld_dy, ld_dx=a.N)
-        with torch.cuda.device(x.device):
-            _lib.check(L.ance_bias_gelu16_backward(ctypes.byref(a), ctypes.byref(g), _lib.current_stream_ptr()),
-                       "ance_bias_gelu16_backward")
-        return dx, dbias
+        return _gelu_backward(ctx, dy, True)
 
 
 def _half_rows(x, what, widths):
@@ -381,6 +353,14 @@ class _Namespace(torch.nn.Module):
     """A module that only holds submodules: the names of transformers' BertLayer, so that its state dict loads as it is."""
 
 
+def _all_rows(t):
+    return t
+
+
+def _first_of_padded(t):
+    return t[:, 0]
+
+
 class BertLayer(torch.nn.Module):
     """transformers' BertLayer (2.3.0 modeling_bert.py; RoBERTa's towers run the same class) for right-padded batches, with the same
     submodule and parameter names: attention.self.query / key / value, attention.output.dense / LayerNorm, intermediate.dense,
@@ -399,7 +379,9 @@ class BertLayer(torch.nn.Module):
     scores), not the rounding noise of the column sum of dk.
     Pad rows are computed like any other in the three row-wise seams, as the reference does; the attention core writes zeros there
     (INTEGRATION.md 3i), so a pad row of the output is the LayerNorm tail of zeros, not the reference's value, and never reaches a
-    loss."""
+    loss.
+    The four forms -- ``forward``, ``forward_first_rows``, ``forward_packed``, ``forward_first_rows_packed`` -- are their own checks
+    in front of ONE forward text, ``_layer``."""
 
     def __init__(self, hidden_size, num_attention_heads, intermediate_size, layer_norm_eps=1e-12, hidden_dropout_prob=0.1,
                  attention_probs_dropout_prob=0.1, attention_precision="fp32", precision="fp32"):
@@ -429,29 +411,56 @@ class BertLayer(torch.nn.Module):
         self.output.dense = nn.Linear(intermediate_size, hidden_size)
         self.output.LayerNorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
 
-    def _forward_half(self, hidden_states, lens, hidden_states_half, return_half):
-        F = torch.nn.functional
-        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
+    def _projection_rows(self, hidden_states, hidden_states_half, return_half=False):
+        """The checks of (hidden_states, hidden_states_half, return_half) that every form makes; returns the rows the projections
+        read: hidden_states itself, or with precision="half" its 16-bit copy (the one given, or the layer's one activation cast)."""
+        if self.precision != "half":
+            if hidden_states_half is not None or return_half:
+                raise _lib.AnceLibraryError("BertLayer: hidden_states_half and return_half need precision=\"half\"")
+            return hidden_states
         if not isinstance(hidden_states, torch.Tensor) or hidden_states.dtype != torch.float32:
             raise _lib.AnceLibraryError("BertLayer(precision=\"half\"): hidden_states is the fp32 residual stream, got %s"
                                         % (getattr(hidden_states, "dtype", type(hidden_states)),))
         if hidden_states_half is None:   # the layer's one activation cast
-            hidden_states_half = _half_rows(hidden_states, "hidden_states", TAIL_WIDTHS)
-        elif hidden_states_half.dtype not in HALF_DTYPES or hidden_states_half.shape != hidden_states.shape:
+            return _half_rows(hidden_states, "hidden_states", TAIL_WIDTHS)
+        if hidden_states_half.dtype not in HALF_DTYPES or hidden_states_half.shape != hidden_states.shape:
             raise _lib.AnceLibraryError("hidden_states_half must be the fp16 / bf16 copy of hidden_states, got %s %r"
                                         % (hidden_states_half.dtype, tuple(hidden_states_half.shape)))
-        q = F.linear(hidden_states_half, att.self.query.weight, att.self.query.bias)
-        k = F.linear(hidden_states_half, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
-        v = F.linear(hidden_states_half, att.self.value.weight, att.self.value.bias)
-        ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
-                               precision="half")
+        return hidden_states_half
+
+    def _check_packed(self, hidden_states, packed, what):
+        if not isinstance(packed, PackedTokens):
+            raise _lib.AnceLibraryError("BertLayer.%s: packed must be a PackedTokens (ance_amd.packing.pack_tokens)" % what)
+        if not isinstance(hidden_states, torch.Tensor) or hidden_states.dim() != 2 or hidden_states.shape[0] != packed.rows:
+            raise _lib.AnceLibraryError("BertLayer.%s: hidden_states must be [R, H] with the packed batch's R = %d rows" % (what, packed.rows))
+
+    def _layer(self, x, residual, rows, attention, return_half=False):
+        """The forward text of every form.  x: the rows the key and value projections read (``_projection_rows``); residual: the
+        fp32 hidden states; rows: what the query projection and the seams run over -- all rows (identity) or the sequences' first
+        rows (``t[:, 0]``, ``first_rows(t, packed)``), applied to x and to residual; attention(q, k, v): the core's call of the
+        form.  Three draws of the dropout stream in training: attention, first tail, second tail."""
+        F = torch.nn.functional
+        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
+        half = self.precision == "half"
+        prec = dict(precision="half") if half else {}
+        q = F.linear(rows(x), att.self.query.weight, att.self.query.bias)
+        k = F.linear(x, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
+        v = F.linear(x, att.self.value.weight, att.self.value.bias)
+        ctx = attention(q, k, v)
         ln = att.output.LayerNorm
-        h, h16 = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, hidden_states, ln.weight,
-                                        ln.bias, eps, p, self.training, precision="half", return_half=True)
-        t = bias_gelu(F.linear(h16, self.intermediate.dense.weight), self.intermediate.dense.bias, precision="half")
+        h = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, rows(residual), ln.weight, ln.bias,
+                                   eps, p, self.training, return_half=half, **prec)
+        h, h_in = h if half else (h, h)   # half: (h, h16), and intermediate.dense reads the 16-bit copy
+        t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
         ln = self.output.LayerNorm
         return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
-                                      self.training, precision="half", return_half=return_half)
+                                      self.training, return_half=return_half, **prec)
+
+    def forward(self, hidden_states, lens, hidden_states_half=None, return_half=False):
+        x = self._projection_rows(hidden_states, hidden_states_half, return_half)
+        return self._layer(x, hidden_states, _all_rows, lambda q, k, v: attention_padded(
+            q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
+            precision=self.attention_precision), return_half)
 
     def forward_first_rows(self, hidden_states, lens, hidden_states_half=None):
         """``forward(...)[:, 0]`` -- [B, H] fp32 -- for a tower's LAST layer, of which only the first rows are read: the key and the
@@ -460,59 +469,12 @@ class BertLayer(torch.nn.Module):
         the dropout stream in forward's order; the attention mask is forward's query row 0 bit for bit, the tails' masks are those
         of a B-row call (row b, not row b * L).  precision="half": the projections read hidden_states_half (or the layer's one cast)
         and the seams run as in forward."""
-        F = torch.nn.functional
-        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
-        half = self.precision == "half"
         if not isinstance(hidden_states, torch.Tensor) or hidden_states.dim() != 3:
             raise _lib.AnceLibraryError("BertLayer.forward_first_rows: hidden_states must be [B, L, H]")
-        if half:
-            if hidden_states.dtype != torch.float32:
-                raise _lib.AnceLibraryError("BertLayer(precision=\"half\"): hidden_states is the fp32 residual stream, got %s"
-                                            % (hidden_states.dtype,))
-            if hidden_states_half is None:   # the layer's one activation cast
-                hidden_states_half = _half_rows(hidden_states, "hidden_states", TAIL_WIDTHS)
-            elif hidden_states_half.dtype not in HALF_DTYPES or hidden_states_half.shape != hidden_states.shape:
-                raise _lib.AnceLibraryError("hidden_states_half must be the fp16 / bf16 copy of hidden_states, got %s %r"
-                                            % (hidden_states_half.dtype, tuple(hidden_states_half.shape)))
-            x = hidden_states_half
-        elif hidden_states_half is not None:
-            raise _lib.AnceLibraryError("BertLayer: hidden_states_half needs precision=\"half\"")
-        else:
-            x = hidden_states
-        prec = dict(precision="half") if half else {}
-        q0 = F.linear(x[:, 0], att.self.query.weight, att.self.query.bias)
-        k = F.linear(x, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
-        v = F.linear(x, att.self.value.weight, att.self.value.bias)
-        ctx0 = attention_first_row(q0, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
-                                   precision=self.attention_precision)
-        ln = att.output.LayerNorm
-        h = dropout_add_layer_norm(F.linear(ctx0, att.output.dense.weight), att.output.dense.bias, hidden_states[:, 0], ln.weight,
-                                   ln.bias, eps, p, self.training, return_half=half, **prec)
-        h, h_in = h if half else (h, h)
-        t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
-        ln = self.output.LayerNorm
-        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
-                                      self.training, **prec)
-
-    def _packed_inputs(self, hidden_states, packed, hidden_states_half, what):
-        """The checks of the packed forms; returns the rows the projections read (the 16-bit copy with precision="half")."""
-        if not isinstance(packed, PackedTokens):
-            raise _lib.AnceLibraryError("BertLayer.%s: packed must be a PackedTokens (ance_amd.packing.pack_tokens)" % what)
-        if not isinstance(hidden_states, torch.Tensor) or hidden_states.dim() != 2 or hidden_states.shape[0] != packed.rows:
-            raise _lib.AnceLibraryError("BertLayer.%s: hidden_states must be [R, H] with the packed batch's R = %d rows" % (what, packed.rows))
-        if self.precision != "half":
-            if hidden_states_half is not None:
-                raise _lib.AnceLibraryError("BertLayer: hidden_states_half and return_half need precision=\"half\"")
-            return hidden_states
-        if hidden_states.dtype != torch.float32:
-            raise _lib.AnceLibraryError("BertLayer(precision=\"half\"): hidden_states is the fp32 residual stream, got %s"
-                                        % (hidden_states.dtype,))
-        if hidden_states_half is None:   # the layer's one activation cast
-            return _half_rows(hidden_states, "hidden_states", TAIL_WIDTHS)
-        if hidden_states_half.dtype not in HALF_DTYPES or hidden_states_half.shape != hidden_states.shape:
-            raise _lib.AnceLibraryError("hidden_states_half must be the fp16 / bf16 copy of hidden_states, got %s %r"
-                                        % (hidden_states_half.dtype, tuple(hidden_states_half.shape)))
-        return hidden_states_half
+        x = self._projection_rows(hidden_states, hidden_states_half)
+        return self._layer(x, hidden_states, _first_of_padded, lambda q0, k, v: attention_first_row(
+            q0, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
+            precision=self.attention_precision))
 
     def forward_packed(self, hidden_states, packed, hidden_states_half=None, return_half=False):
         """``forward`` over the R rows of a PackedTokens: hidden_states [R, H] fp32 -> [R, H] fp32 (precision="half": with
@@ -520,69 +482,21 @@ class BertLayer(torch.nn.Module):
         attention_padded: the Linears and the seams run over R rows instead of B * L.  The attention's dropout mask is forward's
         bit for bit; the tails' masks are those of an R-row call.  A slack row (one that no sequence covers) is computed like any
         other by the seams, from a zero context: finite, and never read by a kept sequence; its gradient is exactly zero."""
-        F = torch.nn.functional
-        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
-        half = self.precision == "half"
-        if return_half and not half:
-            raise _lib.AnceLibraryError("BertLayer: hidden_states_half and return_half need precision=\"half\"")
-        x = self._packed_inputs(hidden_states, packed, hidden_states_half, "forward_packed")
-        prec = dict(precision="half") if half else {}
-        q = F.linear(x, att.self.query.weight, att.self.query.bias)
-        k = F.linear(x, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
-        v = F.linear(x, att.self.value.weight, att.self.value.bias)
-        ctx = attention_packed(q, k, v, packed.seq_off, packed.max_seq_len, self.num_attention_heads, self.attention_probs_dropout_prob,
-                               self.training, precision=self.attention_precision)
-        ln = att.output.LayerNorm
-        h = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, hidden_states, ln.weight, ln.bias,
-                                   eps, p, self.training, return_half=half, **prec)
-        h, h_in = h if half else (h, h)
-        t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
-        ln = self.output.LayerNorm
-        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
-                                      self.training, return_half=return_half, **prec)
+        self._check_packed(hidden_states, packed, "forward_packed")
+        x = self._projection_rows(hidden_states, hidden_states_half, return_half)
+        return self._layer(x, hidden_states, _all_rows, lambda q, k, v: attention_packed(
+            q, k, v, packed.seq_off, packed.max_seq_len, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
+            precision=self.attention_precision), return_half)
 
     def forward_first_rows_packed(self, hidden_states, packed, hidden_states_half=None):
         """``forward_first_rows`` over the R rows of a PackedTokens -> [B, H] fp32: ``first_rows`` in place of ``x[:, 0]`` and
         attention_first_row_packed in place of attention_first_row.  An empty sequence's row is the tails of a zero residual and a
         zero context; a DROPPED sequence's row is NaN (first_rows), which is how an overflow of the capacity reaches the loss."""
-        F = torch.nn.functional
-        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
-        half = self.precision == "half"
-        x = self._packed_inputs(hidden_states, packed, hidden_states_half, "forward_first_rows_packed")
-        prec = dict(precision="half") if half else {}
-        q0 = F.linear(first_rows(x, packed), att.self.query.weight, att.self.query.bias)
-        k = F.linear(x, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
-        v = F.linear(x, att.self.value.weight, att.self.value.bias)
-        ctx0 = attention_first_row_packed(q0, k, v, packed.seq_off, packed.max_seq_len, self.num_attention_heads,
-                                          self.attention_probs_dropout_prob, self.training, precision=self.attention_precision)
-        ln = att.output.LayerNorm
-        h = dropout_add_layer_norm(F.linear(ctx0, att.output.dense.weight), att.output.dense.bias, first_rows(hidden_states, packed),
-                                   ln.weight, ln.bias, eps, p, self.training, return_half=half, **prec)
-        h, h_in = h if half else (h, h)
-        t = bias_gelu(F.linear(h_in, self.intermediate.dense.weight), self.intermediate.dense.bias, **prec)
-        ln = self.output.LayerNorm
-        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
-                                      self.training, **prec)
-
-    def forward(self, hidden_states, lens, hidden_states_half=None, return_half=False):
-        if self.precision == "half":
-            return self._forward_half(hidden_states, lens, hidden_states_half, return_half)
-        if hidden_states_half is not None or return_half:
-            raise _lib.AnceLibraryError("BertLayer: hidden_states_half and return_half need precision=\"half\"")
-        F = torch.nn.functional
-        att, eps, p = self.attention, self.layer_norm_eps, self.hidden_dropout_prob
-        q = F.linear(hidden_states, att.self.query.weight, att.self.query.bias)
-        k = F.linear(hidden_states, att.self.key.weight, _ZeroGradient.apply(att.self.key.bias))
-        v = F.linear(hidden_states, att.self.value.weight, att.self.value.bias)
-        ctx = attention_padded(q, k, v, lens, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
-                               precision=self.attention_precision)
-        ln = att.output.LayerNorm
-        h = dropout_add_layer_norm(F.linear(ctx, att.output.dense.weight), att.output.dense.bias, hidden_states, ln.weight, ln.bias,
-                                   eps, p, self.training)
-        t = bias_gelu(F.linear(h, self.intermediate.dense.weight), self.intermediate.dense.bias)
-        ln = self.output.LayerNorm
-        return dropout_add_layer_norm(F.linear(t, self.output.dense.weight), self.output.dense.bias, h, ln.weight, ln.bias, eps, p,
-                                      self.training)
+        self._check_packed(hidden_states, packed, "forward_first_rows_packed")
+        x = self._projection_rows(hidden_states, hidden_states_half)
+        return self._layer(x, hidden_states, lambda t: first_rows(t, packed), lambda q0, k, v: attention_first_row_packed(
+            q0, k, v, packed.seq_off, packed.max_seq_len, self.num_attention_heads, self.attention_probs_dropout_prob, self.training,
+            precision=self.attention_precision))
 
 
 class _Names(object):

@@ -99,17 +99,24 @@ def _check_packed_batch(embeddings, packed):
         raise _lib.AnceLibraryError("the packed batch is on %s, the tower on %s" % (packed.ids.device, dev))
 
 
-def _run_packed_rows(embeddings, layers, precision, packed):
-    """The embeddings, N - 1 layers and the last layer's first rows over the R rows of a PackedTokens."""
-    h = embeddings.forward_packed(packed)
+def _chain_layers(h, layers, precision, step, last_step, where):
+    """N - 1 layers and the last layer's first rows.  ``step(layer, h, where, ...)`` / ``last_step(layer, h, where, ...)`` are the
+    layers' methods of the form, padded or packed, as plain functions; ``where`` is what they take behind the hidden states (lens,
+    or the PackedTokens).  precision="half": chained through the 16-bit copy, one activation cast in the whole tower."""
     if precision == "half":
         h16 = None
         for layer in layers[:-1]:
-            h, h16 = layer.forward_packed(h, packed, hidden_states_half=h16, return_half=True)
-        return layers[-1].forward_first_rows_packed(h, packed, hidden_states_half=h16)
+            h, h16 = step(layer, h, where, hidden_states_half=h16, return_half=True)
+        return last_step(layers[-1], h, where, hidden_states_half=h16)
     for layer in layers[:-1]:
-        h = layer.forward_packed(h, packed)
-    return layers[-1].forward_first_rows_packed(h, packed)
+        h = step(layer, h, where)
+    return last_step(layers[-1], h, where)
+
+
+def _run_packed_rows(embeddings, layers, precision, packed):
+    """The embeddings, N - 1 layers and the last layer's first rows over the R rows of a PackedTokens."""
+    return _chain_layers(embeddings.forward_packed(packed), layers, precision, BertLayer.forward_packed,
+                         BertLayer.forward_first_rows_packed, packed)
 
 
 class _Tower(torch.nn.Module):
@@ -150,16 +157,8 @@ class _Tower(torch.nn.Module):
         lens = lens_from_mask(attention_mask)
         if packed_rows is not None:
             return self._forward_packed(input_ids, lens, token_type_ids, packed_rows, dropped)
-        h = self.embeddings(input_ids, token_type_ids)
-        layers = self.encoder.layer
-        if self.precision == "half":   # chained through the 16-bit copy: one activation cast in the whole tower
-            h16 = None
-            for layer in layers[:-1]:
-                h, h16 = layer(h, lens, hidden_states_half=h16, return_half=True)
-            return layers[-1].forward_first_rows(h, lens, hidden_states_half=h16)
-        for layer in layers[:-1]:
-            h = layer(h, lens)
-        return layers[-1].forward_first_rows(h, lens)
+        return _chain_layers(self.embeddings(input_ids, token_type_ids), self.encoder.layer, self.precision, BertLayer.__call__,
+                             BertLayer.forward_first_rows, lens)   # __call__: a layer's hooks run, as in layer(h, lens)
 
 
 def _never_used(key):
@@ -189,8 +188,8 @@ class _Checkpointed(torch.nn.Module):
         B * C chunks).  Returns self."""
         self._packed_rows = (_check_packed_rows(query, "query"), _check_packed_rows(body, "body"))
         dev = next(self.parameters()).device
-        if dev.type == "cuda" and (self.packed_dropped is None or self.packed_dropped.device != dev):
-            self.packed_dropped = torch.zeros((), dtype=torch.int64, device=dev)   # here, not inside a step: a captured step only adds
+        if dev.type == "cuda":
+            self._dropped_counter(dev)   # here, not inside a step: a captured step only adds
         return self
 
     def _dropped_counter(self, dev):
@@ -202,12 +201,16 @@ class _Checkpointed(torch.nn.Module):
         """(the query tower, the body tower)."""
         raise NotImplementedError
 
+    def _tower_packed(self, tower, packed, attention_mask):
+        """A PackedTokens through a tower as it is; the model's counter adds the batch's own count."""
+        tower._check_packed(packed)   # before the counter moves
+        out = tower(packed, attention_mask)
+        self._dropped_counter(packed.ids.device).add_(packed.dropped)
+        return out
+
     def _tower(self, tower, which, input_ids, attention_mask):
         if isinstance(input_ids, PackedTokens):
-            tower._check_packed(input_ids)   # before the counter moves
-            out = tower(input_ids, attention_mask)
-            self._dropped_counter(input_ids.ids.device).add_(input_ids.dropped)
-            return out
+            return self._tower_packed(tower, input_ids, attention_mask)
         rows = self._packed_rows[which]
         if rows is None:
             return tower(input_ids, attention_mask)
@@ -450,10 +453,7 @@ class SEEDEncoderDot_NLL_LN(RobertaDot_NLL_LN):
 
     def _tower(self, tower, which, input_ids, attention_mask):
         if isinstance(input_ids, PackedTokens):
-            tower._check_packed(input_ids)   # before the counter moves
-            out = tower(input_ids)
-            self._dropped_counter(input_ids.ids.device).add_(input_ids.dropped)
-            return out
+            return self._tower_packed(tower, input_ids, None)   # the mask is ignored: the keys are masked by id
         return tower(input_ids, None, packed_rows=self._packed_rows[which], dropped=self._dropped_counter(input_ids.device))
 
     def query_emb(self, input_ids, attention_mask=None):

@@ -227,6 +227,27 @@ def test_strided_views_give_the_contiguous_bits():
         out.append([_np(y)] + [_np(t) for t in torch.autograd.grad(y, [tx, tb], _dev(gdy))])
     for a, c in zip(*out):
         assert np.array_equal(_bits(a), _bits(c))
+    # fp32 rows whose stride is 4 mod 8 (a 16-byte piece is 4 floats; 8 is the 16-bit rows' rule), one row past a 16-row workgroup
+    n = 17
+    x, b, r, g, be, dy = U.tail_inputs("stride 772", n, H)
+    res = []
+    for tx in (_dev(x, True), _dev(np.concatenate([x, np.full((n, 4), np.nan, np.float32)], axis=1), True)[:, :H]):
+        tr, tb, tg, tbe = _dev(r, True), _dev(b, True), _dev(g, True), _dev(be, True)
+        T.manual_seed(SEED)
+        y = dropout_add_layer_norm(tx, tb, tr, tg, tbe, 1e-5, 0.5, True)
+        res.append([_np(y)] + [_np(t) for t in torch.autograd.grad(y, [tx, tr, tb, tg, tbe], _dev(dy))])
+    assert tx.stride(0) == 772 and tx.data_ptr() % 16 == 0
+    for a, c in zip(*res):
+        assert np.array_equal(_bits(a), _bits(c))
+    gx, gb, gdy = U.gelu_inputs("stride 3076", n, 3072)
+    out = []
+    for tx in (_dev(gx, True), _dev(np.concatenate([gx, np.full((n, 4), np.nan, np.float32)], axis=1), True)[:, :3072]):
+        tb = _dev(gb, True)
+        y = bias_gelu(tx, tb)
+        out.append([_np(y)] + [_np(t) for t in torch.autograd.grad(y, [tx, tb], _dev(gdy))])
+    assert tx.stride(0) == 3076 and tx.data_ptr() % 16 == 0
+    for a, c in zip(*out):
+        assert np.array_equal(_bits(a), _bits(c))
 
 
 class _Guarded:

@@ -150,7 +150,12 @@ TAIL_REFUSALS = [("width", dict(H=512)), ("width", dict(H=3072)), ("n_rows", dic
                  ("stride", dict(ld_x=772)), ("stride", dict(ld_x=760)), ("stride", dict(ld_res=770)), ("stride", dict(ld_res=0)),
                  ("stride", dict(H=1024)), ("dropout_p", dict(dropout_p=1.0)), ("dropout_p", dict(dropout_p=float("nan"))),
                  ("eps", dict(eps=0.0)), ("workspace", dict(d_workspace=None)), ("workspace", dict(d_workspace=FAKE + 8)),
-                 ("workspace", dict(workspace_bytes=0))]
+                 ("workspace", dict(workspace_bytes=0)),
+                 # the front end these calls share with the fp32 family: ANCE_DTYPE_F32 (0) stays refused here, after n_rows and
+                 # before x; a 16-bit x wants a multiple of 8 (772 passes the fp32 rule), res stays an fp32 matrix
+                 ("dtype neither ANCE_DTYPE_F16 nor ANCE_DTYPE_BF16", dict(dtype=0)), ("n_rows < 1", dict(dtype=0, n_rows=0)),
+                 ("dtype neither", dict(dtype=0, x=None)), ("dtype neither", dict(dtype=-1)), ("dtype neither", dict(dtype=32)),
+                 ("a 16-bit row stride is not a multiple of 8", dict(ld_x=772)), ("stride: not a multiple of 4", dict(ld_res=772 + 2))]
 TAIL_FORWARD_ONLY = [("null pointer", dict(y=None)), ("null pointer", dict(beta=None)), ("alignment", dict(y=FAKE + 4)),
                      ("alignment", dict(y16=FAKE + 8)), ("stride", dict(ld_y=766)), ("stride", dict(ld_y16=772))]
 TAIL_BAD_GRADS = [("neither dy nor dy16", dict(dy=None, dy16=None)), ("alignment", dict(dy=FAKE + 4)), ("alignment", dict(dy16=FAKE + 8)),
@@ -159,7 +164,9 @@ TAIL_BAD_GRADS = [("neither dy nor dy16", dict(dy=None, dy16=None)), ("alignment
                   ("stride", dict(ld_dy16=772)), ("stride", dict(ld_dx=772)), ("stride", dict(ld_dres=0))]
 GELU_REFUSALS = [("width", dict(N=768)), ("width", dict(N=4000)), ("n_rows", dict(n_rows=0)), ("dtype", dict(dtype=7)),
                  ("null pointer", dict(x=None)), ("null pointer", dict(bias=None)), ("alignment", dict(x=FAKE + 8)),
-                 ("alignment", dict(bias=FAKE + 8)), ("stride", dict(ld_x=3076)), ("stride", dict(ld_x=3064)), ("stride", dict(N=4096))]
+                 ("alignment", dict(bias=FAKE + 8)), ("stride", dict(ld_x=3076)), ("stride", dict(ld_x=3064)), ("stride", dict(N=4096)),
+                 ("dtype neither ANCE_DTYPE_F16 nor ANCE_DTYPE_BF16", dict(dtype=0)), ("n_rows < 1", dict(dtype=0, n_rows=0)),
+                 ("dtype neither", dict(dtype=0, x=None)), ("a 16-bit row stride is not a multiple of 8", dict(ld_x=3076))]
 GELU_FORWARD_ONLY = [("null pointer", dict(y=None)), ("alignment", dict(y=FAKE + 8)), ("stride", dict(ld_y=3076))]
 GELU_BACKWARD_ONLY = [("workspace", dict(d_workspace=None)), ("workspace", dict(d_workspace=FAKE + 4)), ("workspace", dict(workspace_bytes=0))]
 GELU_BAD_GRADS = [("null pointer", dict(dy=None)), ("alignment", dict(dy=FAKE + 8)), ("alignment", dict(dx=FAKE + 8)),

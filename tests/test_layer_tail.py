@@ -256,6 +256,11 @@ def test_c_abi_refuses_before_any_launch():
                     ("alignment", dict(dres=FAKE + 8)), ("alignment", dict(dgamma=FAKE + 4)), ("alignment", dict(dbeta=FAKE + 4)),
                     ("alignment", dict(dbias=FAKE + 4)), ("stride", dict(ld_dy=766)), ("stride", dict(ld_dx=704)), ("stride", dict(ld_dres=2))):
         refused(bwd, lambda: L.ance_layer_tail_backward(ctypes.byref(tail_args()), ctypes.byref(tail_grads(**kw)), None), why)
+    # the front end is shared with the 16-bit family: a missing dy keeps THIS family's text (not "neither dy nor dy16"), an fp32
+    # stride its own rule's, and the arguments are judged before the gradients
+    refused(bwd, lambda: L.ance_layer_tail_backward(ctypes.byref(tail_args()), ctypes.byref(tail_grads(dy=None)), None), "(null pointer)")
+    refused(bwd, lambda: L.ance_layer_tail_backward(ctypes.byref(tail_args(eps=0.0)), ctypes.byref(tail_grads(dy=None)), None), "(eps <= 0)")
+    refused(fwd, lambda: L.ance_layer_tail_forward(ctypes.byref(tail_args(ld_x=770)), None), "(stride: not a multiple of 4 or below the width)")
 
     fwd, bwd = "ance_bias_gelu_forward", "ance_bias_gelu_backward"
     for why, kw in GELU_REFUSALS + GELU_FORWARD_ONLY:
