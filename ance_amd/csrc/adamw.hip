@@ -17,6 +17,8 @@
 // Launches: TWO without clipping (prep, update: 28 B per element), THREE with it (gnorm, prep, update: 32 B per element), under
 // loss scaling too (unscale in registers, skip on the device: the arithmetic of ance_lamb_step_amp).  No atomics and a fixed
 // summation order: the same inputs give the same bits.  Division and sqrtf are the IEEE ones, as in lamb.hip.
+// ance_adamw_step_scaled (a loss scaler that hands no flag in): always the three launches; prep (adamw_prep_scaled_kernel) totals
+// first, stores the overflow flag from the fp64 total and only then decides whether the step counts advance.
 //
 // Here: AdamW's arithmetic, prep and update, its group rows and its entry point.  The walk of a workgroup over its chunk and the
 // device tensor row are multi_tensor.h's; the checks and the fill of the tables, the staging pool and gnorm are multi_tensor.hip's,
@@ -49,18 +51,9 @@ __device__ __forceinline__ float adamw_elem(float p, float g, float &m, float &v
     return p;
 }
 
-// CLIP: the gradient total and the clip factor first (one workgroup: multi_tensor.h).  Then one thread per tensor.
-template <bool CLIP>
-__global__ void __launch_bounds__(1024) adamw_prep_kernel(const AdamwDevGroup *groups, const DevTensor *tensors, int n_tensors,
-                                                          int correct_bias, AdamwScalars *scalars, const double *gpartial,
-                                                          int n_chunks, float max_norm, float *grad_norm, float *coef,
-                                                          const float *found_inf, int64_t *skipped) {
-    __shared__ double s[CLIP ? 1024 : 1];
-    if (CLIP) mt::grad_total(gpartial, n_chunks, max_norm, grad_norm, coef, s);
-    if (mt::skip(found_inf)) {
-        if (threadIdx.x == 0 && skipped) skipped[0] = skipped[0] + 1;
-        return;
-    }
+// prep, one thread per tensor of an applied step: t, ss and the decay factor -> scalars[t]; *step <- t
+__device__ __forceinline__ void adamw_prep_tensors(const AdamwDevGroup *groups, const DevTensor *tensors, int n_tensors, int correct_bias,
+                                                   AdamwScalars *scalars) {
     for (int t = threadIdx.x; t < n_tensors; t += 1024) {
         const DevTensor T = tensors[t];
         if (T.numel == 0) continue;  // its step is neither read nor written
@@ -75,6 +68,36 @@ __global__ void __launch_bounds__(1024) adamw_prep_kernel(const AdamwDevGroup *g
         scalars[t] = S;
         T.step[0] = t1;
     }
+}
+
+// CLIP: the gradient total and the clip factor first (one workgroup: multi_tensor.h).  Then one thread per tensor.
+template <bool CLIP>
+__global__ void __launch_bounds__(1024) adamw_prep_kernel(const AdamwDevGroup *groups, const DevTensor *tensors, int n_tensors,
+                                                          int correct_bias, AdamwScalars *scalars, const double *gpartial,
+                                                          int n_chunks, float max_norm, float *grad_norm, float *coef,
+                                                          const float *found_inf, int64_t *skipped) {
+    __shared__ double s[CLIP ? 1024 : 1];
+    if (CLIP) mt::grad_total(gpartial, n_chunks, max_norm, grad_norm, coef, s);
+    if (mt::skip(found_inf)) {
+        if (threadIdx.x == 0 && skipped) skipped[0] = skipped[0] + 1;
+        return;
+    }
+    adamw_prep_tensors(groups, tensors, n_tensors, correct_bias, scalars);
+}
+
+// prep of ance_adamw_step_scaled: the gradient total always comes first and the step's own overflow flag with it (multi_tensor.h:
+// grad_total_flag; thread 0 stores *found_inf), and only then is it decided whether the step counts advance.
+template <bool CLIP>
+__global__ void __launch_bounds__(1024) adamw_prep_scaled_kernel(const AdamwDevGroup *groups, const DevTensor *tensors, int n_tensors,
+                                                                 int correct_bias, AdamwScalars *scalars, const double *gpartial,
+                                                                 int n_chunks, float max_norm, float *grad_norm, float *coef,
+                                                                 float *found_inf, int64_t *skipped) {
+    __shared__ double s[1024];
+    if (mt::grad_total_flag<CLIP>(gpartial, n_chunks, max_norm, grad_norm, coef, found_inf, s)) {
+        if (threadIdx.x == 0 && skipped) skipped[0] = skipped[0] + 1;
+        return;
+    }
+    adamw_prep_tensors(groups, tensors, n_tensors, correct_bias, scalars);
 }
 
 // CLIP: every gradient element is multiplied by *coef before it enters m and v; UNSCALE: by the inverse of *grad_scale before that.
@@ -131,14 +154,29 @@ void launch_update(bool unscale, int64_t n_chunks, hipStream_t st, const AdamwDe
                            (const float *)nullptr, found_inf);
 }
 
-// the launches of a step whose tables stand at the head of ws (layout L): two, or three with the clip
+// the launches of a step whose tables stand at the head of ws (layout L): two, or three with the clip.  flag_out (ance_adamw_step_scaled;
+// then d_found_inf == flag_out and ws has the clipped layout): three, the step writes the flag itself
 int adamw_launch(const char *fn, int n_tensors, int64_t n_chunks, const mt::Staged &L, int correct_bias, bool clip, double max_grad_norm,
-                 const float *d_grad_scale, const float *d_found_inf, float *d_grad_norm, int64_t *d_skipped, char *ws, hipStream_t st) {
+                 const float *d_grad_scale, const float *d_found_inf, float *d_grad_norm, int64_t *d_skipped, char *ws, hipStream_t st,
+                 float *flag_out = nullptr) {
     const AdamwDevGroup *dG = (const AdamwDevGroup *)ws;
     const DevTensor *dT = (const DevTensor *)(ws + L.tensors);
     const int32_t *dC = (const int32_t *)(ws + L.chunk_tensor);
     AdamwScalars *dS = (AdamwScalars *)(ws + L.end);
-    if (clip) {
+    if (flag_out) {
+        double *dGP = (double *)(ws + L.end + align16(sizeof(AdamwScalars) * (size_t)n_tensors));
+        float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
+        mt::launch_gnorm(n_chunks, st, dT, dC, dGP, d_grad_scale);
+        if (clip) {
+            hipLaunchKernelGGL(adamw_prep_scaled_kernel<true>, dim3(1), dim3(1024), 0, st, dG, dT, n_tensors, correct_bias ? 1 : 0, dS,
+                               (const double *)dGP, (int)n_chunks, (float)max_grad_norm, d_grad_norm, dCoef, flag_out, d_skipped);
+            if (n_chunks > 0) launch_update<true>(true, n_chunks, st, dG, dT, dC, dS, dCoef, d_grad_scale, d_found_inf);
+        } else {
+            hipLaunchKernelGGL(adamw_prep_scaled_kernel<false>, dim3(1), dim3(1024), 0, st, dG, dT, n_tensors, correct_bias ? 1 : 0, dS,
+                               (const double *)dGP, (int)n_chunks, 0.0f, (float *)nullptr, (float *)nullptr, flag_out, d_skipped);
+            if (n_chunks > 0) launch_update<false>(true, n_chunks, st, dG, dT, dC, dS, nullptr, d_grad_scale, d_found_inf);
+        }
+    } else if (clip) {
         double *dGP = (double *)(ws + L.end + align16(sizeof(AdamwScalars) * (size_t)n_tensors));
         float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
         mt::launch_gnorm(n_chunks, st, dT, dC, dGP, d_grad_scale);
@@ -235,4 +273,24 @@ extern "C" int ance_adamw_step_planned(int n_tensors, int n_groups, int64_t n_ch
     const mt::Staged L = mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, n_chunks);
     return adamw_launch(fn, n_tensors, n_chunks, L, correct_bias, clip, max_grad_norm, d_grad_scale, d_found_inf, d_grad_norm, d_skipped,
                         (char *)d_workspace, (hipStream_t)stream);
+}
+
+// ance_adamw_step_planned for a caller that has no overflow flag to hand in: the step derives it (include/ance_amd.h)
+extern "C" int ance_adamw_step_scaled(int n_tensors, int n_groups, int64_t n_chunks, int correct_bias, double max_grad_norm,
+                                      const float *d_grad_scale, float *d_found_inf, float *d_grad_norm, int64_t *d_skipped,
+                                      void *d_workspace, size_t workspace_bytes, void *stream) {
+    using namespace ance;
+    const char *fn = "ance_adamw_step_scaled";
+    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return refuse(fn, "table sizes out of range");
+    if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
+        return refuse(fn, "max_grad_norm not 0 or a positive finite number");
+    const bool clip = max_grad_norm != 0.0;
+    if (clip && !d_grad_norm) return refuse(fn, "null d_grad_norm");
+    if (!d_grad_scale) return refuse(fn, "null d_grad_scale");
+    if (!d_found_inf) return refuse(fn, "null d_found_inf");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < workspace_bytes_for(n_tensors, n_groups, n_chunks, true)) return refuse(fn, "workspace too small");
+    const mt::Staged L = mt::staged(sizeof(AdamwDevGroup), n_tensors, n_groups, n_chunks);
+    return adamw_launch(fn, n_tensors, n_chunks, L, correct_bias, clip, max_grad_norm, d_grad_scale, d_found_inf, d_grad_norm, d_skipped,
+                        (char *)d_workspace, (hipStream_t)stream, d_found_inf);
 }

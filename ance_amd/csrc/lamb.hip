@@ -30,6 +30,10 @@
 //            and one thread adds 1 to *d_skipped with an ordinary load, add and store.
 // Without the two pointers the launches and the instantiations are those of ance_lamb_step / ance_lamb_step_clipped.
 //
+// ance_lamb_step_scaled: the planned step for a loss scaler that hands no flag in.  gnorm runs with and without the clip, and gtotal
+// (lamb_gtotal_flag_kernel) stores the overflow flag from its fp64 total -- 1 when it is not finite -- before pass 1 reads it: five
+// launches either way, and with a finite total the bits of the planned step with a flag of 0.
+//
 // Here: LAMB's arithmetic, pass 1, reduce, gtotal and pass 2, its group rows and its entry points.  The walk of a workgroup over its
 // chunk, the block sum and the device tensor row are multi_tensor.h's; the checks and the fill of the tables, the staging pool and
 // gnorm are multi_tensor.hip's, shared with adamw.hip.
@@ -91,6 +95,15 @@ __global__ void __launch_bounds__(1024) lamb_gtotal_kernel(const double *gpartia
                                                            float *coef) {
     __shared__ double s[1024];
     mt::grad_total(gpartial, n_chunks, max_norm, grad_norm, coef, s);
+}
+
+// gtotal of ance_lamb_step_scaled: the same total, and the step's own overflow flag from it (multi_tensor.h: grad_total_flag).
+// Without CLIP only the flag is written.
+template <bool CLIP>
+__global__ void __launch_bounds__(1024) lamb_gtotal_flag_kernel(const double *gpartial, int n_chunks, float max_norm, float *grad_norm,
+                                                                float *coef, float *found_inf) {
+    __shared__ double s[1024];
+    mt::grad_total_flag<CLIP>(gpartial, n_chunks, max_norm, grad_norm, coef, found_inf, s);
 }
 
 // one wave per tensor: chunk sums in chunk order (lane-strided, then an xor-shuffle tree) -> (wn, an, tr).  A skipped step
@@ -175,6 +188,7 @@ void lamb_group_row(void *row, const AnceLambGroup &a, const double *d_lr) {
 struct LambAmp {
     const float *grad_scale = nullptr, *found_inf = nullptr, *prev_out = nullptr;
     int64_t *skipped = nullptr;
+    float *flag_out = nullptr;  // ance_lamb_step_scaled: the step writes the flag itself (found_inf == flag_out) and always runs gnorm
 };
 
 template <bool CLIP, bool UNSCALE>
@@ -184,7 +198,7 @@ void launch_pass1(int64_t n_chunks, hipStream_t st, const LambDevGroup *dG, cons
                        amp.grad_scale, amp.found_inf);
 }
 
-// the launches of a step whose tables stand at the head of ws (layout L): three, or five with the clip
+// the launches of a step whose tables stand at the head of ws (layout L): three, or five with the clip or with a flag of its own
 int lamb_launch(const char *fn, int n_tensors, int64_t n_chunks, const mt::Staged &L, int adam, float *d_out, char *ws, hipStream_t st,
                 bool clip, double max_norm, float *d_grad_norm, const LambAmp &amp) {
     const LambDevGroup *dG = (const LambDevGroup *)ws;
@@ -192,12 +206,22 @@ int lamb_launch(const char *fn, int n_tensors, int64_t n_chunks, const mt::Stage
     const int32_t *dC = (const int32_t *)(ws + L.chunk_tensor);
     double2 *dP = (double2 *)(ws + L.end);
     const bool unscale = amp.grad_scale != nullptr;
-    if (clip) {
-        double *dGP = (double *)(ws + L.end + sizeof(double2) * (size_t)n_chunks);
-        float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
+    // behind the chunk sums of pass 1, in the clipped layout only: never dereferenced by a step without clip and flag
+    double *dGP = (double *)(ws + L.end + sizeof(double2) * (size_t)n_chunks);
+    float *dCoef = (float *)((char *)dGP + align16(sizeof(double) * (size_t)n_chunks));
+    if (clip || amp.flag_out) {
         mt::launch_gnorm(n_chunks, st, dT, dC, dGP, amp.grad_scale);
-        hipLaunchKernelGGL(lamb_gtotal_kernel, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks, (float)max_norm, d_grad_norm,
-                           dCoef);
+        if (!amp.flag_out)
+            hipLaunchKernelGGL(lamb_gtotal_kernel, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks, (float)max_norm,
+                               d_grad_norm, dCoef);
+        else if (clip)
+            hipLaunchKernelGGL(lamb_gtotal_flag_kernel<true>, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks,
+                               (float)max_norm, d_grad_norm, dCoef, amp.flag_out);
+        else
+            hipLaunchKernelGGL(lamb_gtotal_flag_kernel<false>, dim3(1), dim3(1024), 0, st, (const double *)dGP, (int)n_chunks, 0.0f,
+                               (float *)nullptr, (float *)nullptr, amp.flag_out);
+    }
+    if (clip) {
         if (n_chunks > 0) {
             if (unscale) launch_pass1<true, true>(n_chunks, st, dG, dT, dC, dP, dCoef, amp);
             else launch_pass1<true, false>(n_chunks, st, dG, dT, dC, dP, dCoef, amp);
@@ -349,6 +373,33 @@ extern "C" int ance_lamb_step_planned(int n_tensors, int n_groups, int64_t n_chu
     LambAmp amp;
     amp.grad_scale = d_grad_scale;
     amp.found_inf = d_found_inf;
+    amp.prev_out = d_prev_out;
+    amp.skipped = d_skipped;
+    const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);
+    return lamb_launch(fn, n_tensors, n_chunks, L, adam, d_out, (char *)d_workspace, (hipStream_t)stream, clip, max_grad_norm, d_grad_norm,
+                       amp);
+}
+
+// ance_lamb_step_planned for a caller that has no overflow flag to hand in: the step derives it (include/ance_amd.h)
+extern "C" int ance_lamb_step_scaled(int n_tensors, int n_groups, int64_t n_chunks, int adam, double max_grad_norm,
+                                     const float *d_grad_scale, float *d_found_inf, const float *d_prev_out, float *d_grad_norm,
+                                     int64_t *d_skipped, float *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
+    using namespace ance;
+    const char *fn = "ance_lamb_step_scaled";
+    if (n_tensors < 1 || n_groups < 1 || n_chunks < 0 || n_chunks > (int64_t)INT32_MAX) return refuse(fn, "table sizes out of range");
+    if (!(max_grad_norm >= 0.0) || !(max_grad_norm < (double)INFINITY))
+        return refuse(fn, "max_grad_norm not 0 or a positive finite number");
+    const bool clip = max_grad_norm != 0.0;
+    if (clip && !d_grad_norm) return refuse(fn, "null d_grad_norm");
+    if (!d_grad_scale) return refuse(fn, "null d_grad_scale");
+    if (!d_found_inf) return refuse(fn, "null d_found_inf");
+    if (!d_out) return refuse(fn, "null d_out");
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return refuse(fn, "null or unaligned workspace");
+    if (workspace_bytes < workspace_bytes_clipped(n_tensors, n_groups, n_chunks)) return refuse(fn, "workspace too small");
+    LambAmp amp;
+    amp.grad_scale = d_grad_scale;
+    amp.found_inf = d_found_inf;
+    amp.flag_out = d_found_inf;
     amp.prev_out = d_prev_out;
     amp.skipped = d_skipped;
     const mt::Staged L = mt::staged(sizeof(LambDevGroup), n_tensors, n_groups, n_chunks);

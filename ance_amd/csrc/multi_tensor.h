@@ -6,6 +6,7 @@
 #pragma once
 #include "common.h"
 
+#include <float.h>
 #include <math.h>
 
 namespace ance {
@@ -153,6 +154,37 @@ __device__ __forceinline__ void grad_total(const double *gpartial, int n_chunks,
         grad_norm[0] = total;
         coef[0] = c > 1.0f ? 1.0f : c;  // clamp(max=1) that lets a NaN through, as torch's clamp does
     }
+}
+
+// grad_total for a step that finds its own overflow (ance_*_step_scaled): the same sum in the same order, and thread 0 stores
+// *found_inf = 1 when the fp64 total is not finite, else 0 -- an ordinary store, the only write of the flag.  The total is a sum of
+// squares of fp32 values in fp64 (each at most 1.2e77, at most 2^31 * 16,384 of them: far inside the fp64 range), so it is finite
+// exactly when every squared product g * inv is.  CLIP: *grad_norm and *coef as grad_total forms them; else neither is touched.
+// Returns, to every thread of the workgroup, whether the step is skipped; ends with the workgroup synchronised.
+template <bool CLIP>
+__device__ __forceinline__ bool grad_total_flag(const double *gpartial, int n_chunks, float max_norm, float *grad_norm, float *coef,
+                                                float *found_inf, double *s) {
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    for (int c = tid; c < n_chunks; c += 1024) acc += gpartial[c];
+    s[tid] = acc;
+    __syncthreads();
+    for (int off = 512; off > 0; off >>= 1) {
+        if (tid < off) s[tid] += s[tid + off];
+        __syncthreads();
+    }
+    const double sum = s[0];
+    const bool overflow = !(fabs(sum) <= DBL_MAX);  // inf or NaN
+    if (tid == 0) {
+        found_inf[0] = overflow ? 1.0f : 0.0f;
+        if (CLIP) {
+            const float total = (float)sqrt(sum);
+            const float c = max_norm / (total + 1e-6f);
+            grad_norm[0] = total;
+            coef[0] = c > 1.0f ? 1.0f : c;
+        }
+    }
+    return overflow;
 }
 
 // ---- host side (multi_tensor.hip) ----

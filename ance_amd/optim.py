@@ -18,6 +18,10 @@ speaks the scaler's contract for fused optimizers: ``_step_supports_amp_scaling`
 scale and the overflow flag over as device tensors and calls ``step()`` unconditionally; ``ance_lamb_step_amp`` unscales in
 registers and skips on the device -- no host wait, no launch more, and the fused clip sees the unscaled gradients.
 
+``LossScaler`` (at the end) is the scaler with its whole state on the device: the fused step derives the overflow flag from the
+gradient total it forms anyway (``ance_lamb_step_scaled`` / ``ance_adamw_step_scaled``) and ``update()`` is one launch
+(``ance_loss_scale_update``), so ``scale`` / ``step`` / ``update`` can be captured in a graph with the rest of the step.
+
 No CPU fallback: every parameter, gradient and state tensor must be a contiguous fp32 tensor on one HIP device.
 """
 import ctypes
@@ -59,8 +63,9 @@ def _ptr(t):
 class _Call(object):
     """What ``_FusedOptimizer.step`` hands to a subclass's ``_launch``: the library, the resident plan (``plan``: its sizes are the
     leading arguments of every planned entry point, ``tab``), the workspace and the stream, the scaler's tensors and what is stepped
-    (``todo``: [(parameter, gradient, group index, state)]; ``group0``: the group of the first of them)."""
-    __slots__ = ("L", "tab", "n", "device", "ws", "stream", "clip", "amp", "grad_scale", "found_inf", "todo", "group0", "plan")
+    (``todo``: [(parameter, gradient, group index, state)]; ``group0``: the group of the first of them).  ``scaled``: the step runs
+    under a ``LossScaler`` -- ``grad_scale`` and ``found_inf`` are its tensors and the step writes the flag itself."""
+    __slots__ = ("L", "tab", "n", "device", "ws", "stream", "clip", "amp", "grad_scale", "found_inf", "todo", "group0", "plan", "scaled")
 
 
 class _Plan(object):
@@ -227,11 +232,18 @@ class _FusedOptimizer(Optimizer):
             loss = closure()
 
         todo, groups, lrs, device = self._walk()
+        scaler = getattr(self, "_loss_scaler", None)   # set by LossScaler.step around this call only
         if not todo:
+            if scaler is not None:
+                raise RuntimeError("%s: LossScaler.step found no parameter with a gradient: no overflow check was made" % self._name)
             return loss
         c = _Call()
         c.group0 = self.param_groups[todo[0][2]]
-        c.grad_scale, c.found_inf = self._amp_scalar("grad_scale", device), self._amp_scalar("found_inf", device)
+        c.scaled = scaler is not None
+        if c.scaled:
+            c.grad_scale, c.found_inf = scaler._tensors_on(device, self._name)
+        else:
+            c.grad_scale, c.found_inf = self._amp_scalar("grad_scale", device), self._amp_scalar("found_inf", device)
         c.amp = c.grad_scale is not None or c.found_inf is not None
         for k, (p, grad, gi, state) in enumerate(todo):   # everything is checked: only now is state created
             if not state:
@@ -243,7 +255,7 @@ class _FusedOptimizer(Optimizer):
 
         c.L = _lib.lib()
         c.n, c.device, c.clip = len(rows), device, self.max_grad_norm is not None
-        key = (rows, groups, [None if lr is None else lr.data_ptr() for lr in lrs], c.clip, c.amp, self._plan_flags(c), device)
+        key = (rows, groups, [None if lr is None else lr.data_ptr() for lr in lrs], c.clip, c.amp, self._plan_flags(c), device, c.scaled)
         capturing = torch.cuda.is_current_stream_capturing()
         with torch.cuda.device(device):
             plan = self._plan
@@ -313,6 +325,7 @@ class Lamb(_FusedOptimizer):
         self._workspace = {}
         self._plan_init()
         self._prev_out = None  # (out of the last step, the ids of the parameters its rows belong to)
+        self._scaled_out = None  # the same under a LossScaler: one persistent buffer
 
     def _plan_flags(self, c):
         return bool(self.adam)
@@ -334,13 +347,26 @@ class Lamb(_FusedOptimizer):
     def _launch(self, c):
         L, device, clip = c.L, c.device, c.clip
         stepped = [id(t[0]) for t in c.todo]
-        out = torch.empty((c.n, 3), dtype=torch.float32, device=device)
         norm = torch.empty((1,), dtype=torch.float32, device=device) if clip else None
-        prev = self._prev_out[0] if c.amp and self._prev_out is not None and self._prev_out[1] == stepped else None
-        _lib.check(L.ance_lamb_step_planned(*c.tab, 1 if self.adam else 0, self.max_grad_norm if clip else 0.0, _ptr(c.grad_scale),
-                                            _ptr(c.found_inf), _ptr(prev), _ptr(norm), _ptr(self.skipped_steps if c.amp else None),
-                                            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), c.stream),
-                   "ance_lamb_step_planned")
+        if c.scaled:
+            # one buffer as long as the same parameters are stepped, handed in as its own d_prev_out: a skipped step, eager or
+            # replayed from a graph, keeps the rows of the step before it ((0, 0, 1) before the first).  It outlives a rebuild of
+            # the plan (new gradient tensors at a capture), so the buffer a graph holds is the one the warm-up steps made
+            kept = self._scaled_out
+            if kept is None or kept[1] != stepped or kept[0].device != device:
+                out = torch.zeros((c.n, 3), dtype=torch.float32, device=device)
+                out[:, 2] = 1.0
+                self._scaled_out = (out, stepped)
+            else:
+                out = kept[0]
+            entry, prev = "ance_lamb_step_scaled", out
+        else:
+            out = torch.empty((c.n, 3), dtype=torch.float32, device=device)
+            prev = self._prev_out[0] if c.amp and self._prev_out is not None and self._prev_out[1] == stepped else None
+            entry = "ance_lamb_step_planned"
+        _lib.check(getattr(L, entry)(*c.tab, 1 if self.adam else 0, self.max_grad_norm if clip else 0.0, _ptr(c.grad_scale),
+                                     _ptr(c.found_inf), _ptr(prev), _ptr(norm), _ptr(self.skipped_steps if c.amp else None),
+                                     ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(c.ws.data_ptr()), c.ws.numel(), c.stream), entry)
         if clip:
             self.last_grad_norm = norm[0]
         self._prev_out = (out, stepped)
@@ -453,15 +479,16 @@ class AdamW(_FusedOptimizer):
                  p.numel(), gi, 0) for p, grad, gi, state in todo]
 
     def _workspace_bytes(self, c, n_groups, total):
-        return c.L.ance_adamw_workspace_bytes(c.n, n_groups, total, 1 if c.clip else 0)
+        return c.L.ance_adamw_workspace_bytes(c.n, n_groups, total, 1 if c.clip or c.scaled else 0)
 
     def _launch(self, c):
         """A skipped step is skipped on the device, its step counts included."""
         norm = torch.empty((1,), dtype=torch.float32, device=c.device) if c.clip else None
-        _lib.check(c.L.ance_adamw_step_planned(*c.tab, 1 if c.group0['correct_bias'] else 0, self.max_grad_norm if c.clip else 0.0,
-                                               _ptr(c.grad_scale), _ptr(c.found_inf), _ptr(norm),
-                                               _ptr(self.skipped_steps if c.amp else None), ctypes.c_void_p(c.ws.data_ptr()),
-                                               c.ws.numel(), c.stream), "ance_adamw_step_planned")
+        entry = "ance_adamw_step_scaled" if c.scaled else "ance_adamw_step_planned"
+        _lib.check(getattr(c.L, entry)(*c.tab, 1 if c.group0['correct_bias'] else 0, self.max_grad_norm if c.clip else 0.0,
+                                       _ptr(c.grad_scale), _ptr(c.found_inf), _ptr(norm),
+                                       _ptr(self.skipped_steps if c.amp else None), ctypes.c_void_p(c.ws.data_ptr()),
+                                       c.ws.numel(), c.stream), entry)
         if c.clip:
             self.last_grad_norm = norm[0]
 
@@ -532,3 +559,185 @@ class LinearWarmupSchedule(object):
         self._n.fill_(int(state_dict["last_epoch"]) - 1)
         self.step()
 
+
+
+def _positive_finite(name, x):
+    try:
+        ok = 0.0 < float(x) < float("inf")
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("Invalid {}: {} (a positive finite number)".format(name, x))
+    return float(x)
+
+
+class LossScaler(object):
+    r"""Dynamic loss scaling for ``Lamb`` / ``AdamW`` with the scaler's whole state on the device: ``torch.amp.GradScaler``'s recipe
+    (``scale`` -> ``backward`` -> ``step`` -> ``update``) without its pass over the gradients and without its walk over the parameters,
+    so that a captured training step carries its scaler::
+
+        scaler = LossScaler(init_scale=65536.0, growth_interval=2000)
+        scaler.scale(loss).backward()
+        scaler.step(optimizer)     # the fused step unscales in registers, finds its own overflow and skips on the device
+        scaler.update()            # one launch: torch._amp_update_scale_'s arithmetic, bit for bit
+
+    ``step`` calls the optimizer through ``ance_lamb_step_scaled`` / ``ance_adamw_step_scaled``: the gradient-norm pass (which the
+    fused clip makes anyway; it also runs without ``max_grad_norm``) totals the squares of the unscaled gradient elements ``g * inv``
+    in fp64, and the step is skipped exactly when that total is not finite.  For a scale >= 1 that is ``GradScaler``'s rule (some
+    gradient element is inf or NaN); for a scale below 1 it also catches a finite element whose unscaled product overflows.
+    ``optimizer.skipped_steps``, ``last_grad_norm`` and LAMB's recorded norms behave as under a ``GradScaler``; a skipped LAMB step
+    keeps the previous step's norms, also when replayed from a graph (one persistent buffer per plan).
+
+    State: ``scale`` (fp32 [1]), ``growth_tracker`` (int32 [1]) and ``found_inf`` (fp32 [1]) are created at the first ``scale()`` on
+    that tensor's device and kept for life -- a captured graph holds their addresses; everything later fills them in place.
+    Nothing in ``scale``, ``step`` or ``update`` waits for the device, and all three can be captured (after a first eager use).
+    ``get_scale()``, ``state_dict()`` and ``load_state_dict()`` read or fill the device tensors off the step path; the state dict has
+    ``GradScaler``'s keys, so a checkpoint moves between the two classes.
+
+    One optimizer per scaler; ``unscale_`` is refused (the fused clip already works on the unscaled gradients).  ``enabled=False``:
+    every method passes through and ``step`` calls ``optimizer.step()``."""
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True):
+        self._enabled = bool(enabled)
+        self._init_scale = _positive_finite("init_scale", init_scale)
+        self._growth_factor = _positive_finite("growth_factor", growth_factor)
+        self._backoff_factor = _positive_finite("backoff_factor", backoff_factor)
+        if int(growth_interval) != growth_interval or int(growth_interval) < 1:
+            raise ValueError("Invalid growth_interval: {} (an integer >= 1)".format(growth_interval))
+        self._growth_interval = int(growth_interval)
+        self._init_growth_tracker = 0
+        self.scale_tensor = self.growth_tracker = self.found_inf = None   # device tensors, from the first scale() on
+        self._scale0 = None   # a 0-dim view of scale_tensor: what outputs are multiplied by
+
+    def is_enabled(self):
+        return self._enabled
+
+    # ---- state
+    def _create(self, device):
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.AnceLibraryError("LossScaler: the first scale() creates the scaler's device state and cannot be captured: "
+                                        "run a step outside the capture first")
+        self.scale_tensor = torch.full((1,), self._init_scale, dtype=torch.float32, device=device)
+        self.growth_tracker = torch.full((1,), self._init_growth_tracker, dtype=torch.int32, device=device)
+        self.found_inf = torch.zeros((1,), dtype=torch.float32, device=device)
+        self._scale0 = self.scale_tensor[0]
+
+    def _tensors_on(self, device, who):
+        """(scale, found_inf) for a step of ``who`` on ``device``."""
+        if self.scale_tensor is None:
+            raise RuntimeError("LossScaler.step: no scale() came before it: there are no scaled gradients to step on")
+        if self.scale_tensor.device != device:
+            raise _lib.AnceLibraryError("%s: the LossScaler's state is on %s, the parameters of this step on %s (mixed devices)"
+                                        % (who, self.scale_tensor.device, device))
+        return self.scale_tensor, self.found_inf
+
+    # ---- the step path: no host wait, capturable
+    def scale(self, outputs):
+        """``outputs * scale`` by the device scalar, for a tensor or an iterable of tensors, as ``GradScaler.scale``."""
+        if not self._enabled:
+            return outputs
+        if isinstance(outputs, torch.Tensor):
+            if not outputs.is_cuda:
+                raise _lib.AnceLibraryError("LossScaler.scale: outputs must be on a HIP device, got %s" % outputs.device)
+            if self.scale_tensor is None:
+                self._create(outputs.device)
+            elif self.scale_tensor.device != outputs.device:
+                raise _lib.AnceLibraryError("LossScaler.scale: outputs are on %s, the scaler's state on %s (mixed devices)"
+                                            % (outputs.device, self.scale_tensor.device))
+            return outputs * self._scale0
+        if isinstance(outputs, (list, tuple)) or hasattr(outputs, "__iter__"):
+            mapped = [self.scale(o) for o in outputs]
+            return type(outputs)(mapped) if isinstance(outputs, (list, tuple)) else mapped
+        raise ValueError("outputs must be a Tensor or an iterable of Tensors")
+
+    def step(self, optimizer, *args, **kwargs):
+        """One step of ``optimizer`` -- a ``Lamb`` or ``AdamW`` of this module -- on the scaled gradients: unscaled in registers,
+        skipped on the device when an unscaled gradient element is not finite.  Returns what ``optimizer.step`` returns."""
+        if not self._enabled:
+            return optimizer.step(*args, **kwargs)
+        if not isinstance(optimizer, _FusedOptimizer):
+            raise TypeError("LossScaler.step takes an ance_amd.optim.Lamb or ance_amd.optim.AdamW, got %s.%s: use "
+                            "torch.amp.GradScaler for other optimizers"
+                            % (type(optimizer).__module__, type(optimizer).__name__))
+        if "closure" in kwargs or args:
+            raise RuntimeError("Closure use is not currently supported if LossScaler is enabled.")
+        if getattr(optimizer, "grad_scale", None) is not None or getattr(optimizer, "found_inf", None) is not None:
+            raise RuntimeError("LossScaler.step: %s.grad_scale / found_inf are set: the optimizer is being driven by another scaler"
+                               % optimizer._name)
+        optimizer._loss_scaler = self
+        try:
+            return optimizer.step()
+        finally:
+            optimizer._loss_scaler = None
+
+    def unscale_(self, optimizer):
+        raise RuntimeError("LossScaler.unscale_ is not supported: the fused clip (max_grad_norm) of Lamb / AdamW already works on the "
+                           "unscaled gradients, and the step unscales in registers")
+
+    def update(self, new_scale=None):
+        """After ``step``: back off on an overflow, grow after ``growth_interval`` clean steps -- one launch.  With ``new_scale`` (a
+        float or a one-element tensor) the scale is filled in place instead, as ``GradScaler.update`` does."""
+        if not self._enabled:
+            return
+        if self.scale_tensor is None:
+            raise RuntimeError("LossScaler.update: no scale() came before it")
+        if new_scale is not None:
+            if isinstance(new_scale, torch.Tensor):
+                if new_scale.numel() != 1 or new_scale.requires_grad:
+                    raise ValueError("new_scale must be a one-element tensor with requires_grad=False")
+                if not new_scale.is_cuda and torch.cuda.is_current_stream_capturing():
+                    raise _lib.AnceLibraryError("LossScaler.update: new_scale is a host tensor and a copy from the host cannot be "
+                                                "captured: pass a device tensor or a float")
+                self.scale_tensor.copy_(new_scale.detach().reshape(1))
+            else:
+                self.scale_tensor.fill_(_positive_finite("new_scale", new_scale))
+            return
+        with torch.cuda.device(self.scale_tensor.device):
+            _lib.check(_lib.lib().ance_loss_scale_update(ctypes.c_void_p(self.scale_tensor.data_ptr()),
+                                                         ctypes.c_void_p(self.growth_tracker.data_ptr()),
+                                                         ctypes.c_void_p(self.found_inf.data_ptr()), self._growth_factor,
+                                                         self._backoff_factor, self._growth_interval, _lib.current_stream_ptr()),
+                       "ance_loss_scale_update")
+
+    # ---- read-outs and checkpoints: off the step path
+    def get_scale(self):
+        """The scale as a Python float: one synchronising read (``init_scale`` before the first ``scale()``)."""
+        if not self._enabled:
+            return 1.0
+        return self._init_scale if self.scale_tensor is None else float(self.scale_tensor.item())
+
+    def get_growth_factor(self):
+        return self._growth_factor
+
+    def get_backoff_factor(self):
+        return self._backoff_factor
+
+    def get_growth_interval(self):
+        return self._growth_interval
+
+    def _get_growth_tracker(self):
+        if not self._enabled:
+            return 0
+        return self._init_growth_tracker if self.growth_tracker is None else int(self.growth_tracker.item())
+
+    def state_dict(self):
+        """``torch.amp.GradScaler.state_dict()``'s keys and meanings; ``{}`` when disabled."""
+        if not self._enabled:
+            return {}
+        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": self._get_growth_tracker()}
+
+    def load_state_dict(self, state_dict):
+        """Takes this class's and ``torch.amp.GradScaler``'s state dicts; device tensors that exist are filled in place."""
+        if not self._enabled:
+            return
+        if len(state_dict) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of GradScaler.")
+        self._init_scale = _positive_finite("scale", state_dict["scale"])
+        self._growth_factor = _positive_finite("growth_factor", state_dict["growth_factor"])
+        self._backoff_factor = _positive_finite("backoff_factor", state_dict["backoff_factor"])
+        self._growth_interval = int(state_dict["growth_interval"])
+        self._init_growth_tracker = int(state_dict["_growth_tracker"])
+        if self.scale_tensor is not None:
+            self.scale_tensor.fill_(self._init_scale)
+            self.growth_tracker.fill_(self._init_growth_tracker)

@@ -39,7 +39,7 @@ extern "C" {
 #define ANCE_E_LAUNCH (-3)    /* HIP reported a launch error */
 #define ANCE_E_NOMEM (-4)
 
-#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_*, ance_pack_tokens, ance_embed_rows_*, ance_first_rows_*, ance_record_lengths, ance_gather_batch_packed, ance_pack_tokens_by_id only ADD symbols, which
+#define ANCE_ABI_VERSION 7  /* still 7: ance_nll_backward, ance_inbatch_nll_*, ance_lamb_step_clipped, ance_lamb_step_amp, ance_adamw_step, ance_gather_batch, ance_attention_*, ance_layer_tail_*, ance_bias_gelu_*, ance_embed_*, ance_layer_tail16_*, ance_bias_gelu16_*, ance_*_dstream, ance_dropout_stream_advance, ance_*_plan_*, ance_*_step_planned, ance_linear_warmup_step, ance_attention_row0_*, ance_pack_tokens, ance_embed_rows_*, ance_first_rows_*, ance_record_lengths, ance_gather_batch_packed, ance_pack_tokens_by_id, ance_*_step_scaled, ance_loss_scale_update only ADD symbols, which
                                callers built against the earlier 7 never look up; nothing that existed changed;
                                7: + ance_debug_attention (AnceAttnDebugArgs); + ance_lamb_step (additive);
                                6: + ance_debug_gemm_hw (AnceGemmDebugArgs);
@@ -1007,6 +1007,39 @@ int ance_lamb_step_planned(int n_tensors, int n_groups, int64_t n_chunks, int ad
                            const float *d_found_inf, const float *d_prev_out, float *d_grad_norm, int64_t *d_skipped, float *d_out,
                            void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* A planned step that FINDS ITS OWN OVERFLOW (for a loss scaler whose state lives on the device: ance_amd.optim.LossScaler).  Same
+ * leading arguments, plan and workspace as ance_lamb_step_planned, but d_grad_scale is required and d_found_inf is a required
+ * OUTPUT that nobody hands in: the step writes it and is its only reader.
+ *   flag     the gradient-norm pass over the products g inv runs with and without max_grad_norm, and the one workgroup that adds its
+ *            per-chunk fp64 sums (in the fixed chunk order of the clipped step, no atomics) stores, by one thread and an ordinary
+ *            store, *d_found_inf = 1.0f when the total is not finite and 0.0f otherwise.  RULE: the flag is set iff some product
+ *            g inv is not finite.  (The total is a sum of squares of fp32 values in fp64: the square of the largest fp32 is 1.2e77
+ *            and 2^31 chunks of 16,384 such terms stay far inside the fp64 range, so the total is finite exactly when every term
+ *            is.)  For any scale >= 1 that is torch's rule -- some g is not finite -- since |inv| <= 1 cannot overflow a finite g.
+ *            For a scale below 1 it ALSO catches a finite g whose unscaled product overflows, which torch's check (of g itself)
+ *            lets through into the moments.
+ *   skip     every later kernel of the call reads the flag as ance_lamb_step_planned reads d_found_inf: on a non-finite total no
+ *            bit of any p, m, v changes, *d_skipped grows by one, d_out takes the rows of d_prev_out ((0, 0, 1) without it; it may
+ *            be d_out itself) and *d_grad_norm (when clipping) holds the inf / NaN norm.
+ *   no clip  max_grad_norm == 0: the clip factor is not applied, d_grad_norm may be null and only the flag is taken from the total.
+ * With a finite total the results have the bits of ance_lamb_step_planned called with the same d_grad_scale and a d_found_inf of 0.
+ * Five launches with or without the clip (gnorm, total + flag, pass 1, reduce, pass 2), capturable like the planned step.
+ * Workspace: ance_lamb_amp_workspace_bytes in both cases (the per-chunk fp64 area is used without the clip too).  Refuses
+ * (ANCE_E_INVALID, before any launch) what ance_lamb_step_planned refuses, a null d_grad_scale and a null d_found_inf. */
+int ance_lamb_step_scaled(int n_tensors, int n_groups, int64_t n_chunks, int adam, double max_grad_norm, const float *d_grad_scale,
+                          float *d_found_inf, const float *d_prev_out, float *d_grad_norm, int64_t *d_skipped, float *d_out,
+                          void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The dynamic loss scale's update (csrc/loss_scale.hip): the arithmetic of torch._amp_update_scale_, which
+ * torch.amp.GradScaler.update() runs, roundings included, on three DEVICE scalars -- *d_scale fp32, *d_growth_tracker int32,
+ * *d_found_inf fp32 (e.g. what ance_*_step_scaled left).  !(*d_found_inf == 0) (NaN included):
+ * scale <- float32(float64(scale) * backoff_factor), tracker <- 0.  Otherwise n = tracker + 1; at n == growth_interval
+ * scale <- float32(float64(scale) * growth_factor) unless that is not finite (the scale is then kept) and tracker <- 0; else
+ * tracker <- n.  One launch of one thread, no host synchronisation, capturable.  Refuses (ANCE_E_INVALID, before the launch) a null
+ * or unaligned (4 B) pointer, a factor that is not a positive finite number and growth_interval < 1. */
+int ance_loss_scale_update(float *d_scale, int32_t *d_growth_tracker, const float *d_found_inf, double growth_factor,
+                           double backoff_factor, int32_t growth_interval, void *stream);
+
 /* transformers' get_linear_schedule_with_warmup as one launch on device scalars (csrc/lr_schedule.hip): *d_n += 1, then
  * d_lrs[g] = d_base_lrs[g] * lambda(*d_n) in fp64 for every group, lambda(n) = n / max(1, warm) below warm, else
  * max(0, (total - n) / max(1, total - warm)): the values torch.optim.lr_scheduler.LambdaLR holds after its step(), bit for bit.
@@ -1070,6 +1103,15 @@ int ance_adamw_plan_build(const AnceAdamwTensor *h_tensors, int n_tensors, const
 int ance_adamw_step_planned(int n_tensors, int n_groups, int64_t n_chunks, int correct_bias, double max_grad_norm,
                             const float *d_grad_scale, const float *d_found_inf, float *d_grad_norm, int64_t *d_skipped,
                             void *d_workspace, size_t workspace_bytes, void *stream);
+/* The planned AdamW step that finds its own overflow: the flag, its rule, the skip and the refusals of ance_lamb_step_scaled (there
+ * is no d_out).  The per-tensor workgroup forms the gradient total and stores *d_found_inf BEFORE it decides whether the step counts
+ * advance: on a non-finite total no bit of any p, m, v or *step changes and *d_skipped grows by one.  With a finite total the
+ * results have the bits of ance_adamw_step_planned with the same d_grad_scale and a d_found_inf of 0.  Three launches with or
+ * without the clip (gnorm, total + flag + per-tensor scalars, update).  Workspace: ance_adamw_workspace_bytes(.., clip = 1) in both
+ * cases. */
+int ance_adamw_step_scaled(int n_tensors, int n_groups, int64_t n_chunks, int correct_bias, double max_grad_norm,
+                           const float *d_grad_scale, float *d_found_inf, float *d_grad_norm, int64_t *d_skipped,
+                           void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training batches gathered on the device (csrc/batch_gather.hip): what the reference's loaders build per item in Python
